@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: training tokens/s of the full MMTG configuration on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,7 +11,10 @@ released shape: forward (encoder + fuser + conditioning + 12-layer GPT-2) -> MyL
 three dropout sites active (model.train()).  Batches are resident in HBM before the timed
 region.  Weak scaling: 64 rows per GPU (global 512 at 8 GPUs).
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set up, warm up, time the K steps, and print
+`value` (tokens/s) and `ms_per_step`.  --dump-outputs DIR then also writes what the last timed step computed as DIR/<name>.npy
+(float32 / float64; the inputs are seeded, so two builds can be compared output for output).  With --full the line carries, besides
+the contract fields,
   roofline      dominant kernel (bf16 MFMA GEMM): algorithmic FLOPs / HIP-event time, measured
                 live with events on the launch stream during a second, instrumented pass over
                 the same steps (the first pass is timed without events and gives `value`)
@@ -23,6 +26,8 @@ Prints ONE JSON line (rank 0).  Besides the contract fields it carries
   decode        the second half of BASELINE.json's metric, measured in the same run after the training
                 region: batched greedy generation (batch 256, 128 positions) with its own roofline and
                 cpu_baseline objects (python bench.py --mode decode prints it as a line of its own)
+  bf16x3, bf16x3f, f32, medium, conditioning, ddp   the other compute modes, BASELINE configs[4], the conditioning
+                kernels against the HBM roofline, the data-parallel exchange figures
 """
 import argparse
 import json
@@ -45,7 +50,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from bench_parts import common as _common  # noqa: E402
-from bench_parts.common import _host_threads, _timed, gpu_rewarm  # noqa: E402
+from bench_parts.common import _host_threads, _timed, dump_outputs, flat_sample, gpu_rewarm  # noqa: E402
 from bench_parts.decode import bench_decode  # noqa: E402
 from bench_parts.launch import _claim_stdout, _dry_launch, _emit, _self_launch  # noqa: E402
 from bench_parts.objects import _pmc_traffic, allreduce_probe, conditioning_probe, f32_object, medium_object  # noqa: E402
@@ -60,6 +65,18 @@ def algorithmic_flops_per_token(S, T, D, L, V, H=512, E=2048):
     fwd = L * (layer + attn) + head + proj
     enc_per_sample = 2 * (E * H) + 2 * S * 2 * (E * 3 * H + H * 3 * H) + 2 * S * 2 * (H * 3 * H) + 2 * S * H * E
     return fwd, enc_per_sample
+
+
+def train_outputs(trainer, out):
+    """What a caller of the timed path holds after its last step: the scalars trainer.step returned (None: the stage filter left no
+    rows), the gradient norm the clip saw, and the updated fp32 parameters and that step's fp32 gradient at the same fixed sample
+    of positions of the flat buffers."""
+    flat, grad = trainer.model._flat, trainer.eng.grad
+    idx = torch.from_numpy(flat_sample(flat.numel())).to(flat.device)
+    arrays = {"params_sample": flat[idx], "grad_sample": grad[idx], "grad_norm": trainer.grad_norm().reshape(1)}
+    if out is not None:
+        arrays.update({k: v.reshape(1) for k, v in out.items()})
+    return arrays
 
 
 def cpu_baseline(mcfg, dcfg, gcfg, V, T, seconds_budget=100.0):
@@ -163,7 +180,7 @@ def main():
                     help="medium: BASELINE configs[4] (GPT-2-medium 24L/1024/16H, S=8, T=512, rating skew K=32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-decode", action="store_true", help="skip the decode object of the default line")
+    ap.add_argument("--no-decode", action="store_true", help="skip the decode object of the --full line")
     ap.add_argument("--no-check", action="store_true", help="skip the probe-loss evidence (profiling runs: keeps the kernel "
                                                             "statistics to the training steps only)")
     ap.add_argument("--bucket-mb", type=float, default=64.0)
@@ -175,14 +192,22 @@ def main():
         help="decode without graph capture (counter-collection passes: every dispatch visible)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launch contract only (no GPU): ranks rendezvous over gloo, rank 0 prints one JSON line")
-    ap.add_argument("--no-f32", action="store_true", help="skip the f32 (parity-gate mode) object of the default line")
-    ap.add_argument("--no-x3", action="store_true", help="skip the bf16x3 (split-precision parity mode) object of the default line")
-    ap.add_argument("--no-medium", action="store_true", help="skip the configs[4] (GPT-2-medium, T = 512) object of the default line")
+    ap.add_argument("--no-f32", action="store_true", help="skip the f32 (parity-gate mode) object of the --full line")
+    ap.add_argument("--no-x3", action="store_true", help="skip the bf16x3 (split-precision parity mode) object of the --full line")
+    ap.add_argument("--no-medium", action="store_true", help="skip the configs[4] (GPT-2-medium, T = 512) object of the --full line")
     ap.add_argument("--primary-only", action="store_true",
         help="the primary train measurement only: no decode / bf16x3 / f32 / medium objects (profiling passes)")
+    ap.add_argument("--full", action="store_true",
+        help="measure and check everything beyond the headline figure too: roofline and per-kernel figures, the probe-loss check, "
+             "the conditioning probe, the exchange figures, the CPU baselines, the decode / bf16x3 / bf16x3f / f32 / medium objects "
+             "(the --no-* options above then take parts out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+        help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
-    if args.primary_only:
+    if args.primary_only or not args.full:
         args.no_decode = args.no_x3 = args.no_f32 = args.no_medium = True
+    if not args.full:
+        args.no_roofline = args.no_cpu_baseline = True
     _common._PROFILING_RUN = bool(args.no_check)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -217,7 +242,8 @@ def main():
     from mmtg_amd.trainer import MMTGTrainer
 
     if args.mode == "decode":
-        out = bench_decode(args, world, rank, dev, args.steps, args.warmup, cpu_fn=cpu_decode_baseline)
+        dump = (lambda arrays: dump_outputs(args.dump_outputs, arrays)) if args.dump_outputs and rank == 0 else None
+        out = bench_decode(args, world, rank, dev, args.steps, args.warmup, cpu_fn=cpu_decode_baseline, dump=dump)
         if rank == 0 and out is not None:
             _emit(out)
         if dist.is_initialized():
@@ -262,9 +288,11 @@ def main():
     T = dcfg.topic_prompt_length + batches[0]["targets"].shape[1]
 
     # did-work evidence, outside the timed region: MyLoss of a held-out probe batch (eval mode, no dropout) before the
-    # first and after the last optimizer step
-    probe_nb = synth.make_batch(min(B, 16), mcfg, dcfg, V, seed=99 + rank)
-    probe = {k: torch.from_numpy(np.asarray(v)).to(dev) for k, v in probe_nb.items()}
+    # first and after the last optimizer step (--full)
+    check_probe = args.full and not args.no_check
+    if check_probe:
+        probe_nb = synth.make_batch(min(B, 16), mcfg, dcfg, V, seed=99 + rank)
+        probe = {k: torch.from_numpy(np.asarray(v)).to(dev) for k, v in probe_nb.items()}
 
     def probe_loss():
         eng = model.engine()
@@ -272,12 +300,13 @@ def main():
         sc = eng.loss(probe["rating"], 3)
         return float(sc[0].item())
 
-    loss_first = None if args.no_check else probe_loss()
-    p0 = model._flat.detach().clone()
+    loss_first = probe_loss() if check_probe else None
+    p0 = model._flat.detach().clone() if args.full else None
+    last = [None]       # what the last step returned
 
     def run(n):
         for i in range(n):
-            trainer.step(batches[i % 2], stage=stage)
+            last[0] = trainer.step(batches[i % 2], stage=stage)
 
     gpu_rewarm(dev)              # a fresh box's GPU has been idle: W short warm-up steps alone may still run at ramping clocks
     run(args.warmup)
@@ -289,6 +318,8 @@ def main():
     ms_step = 1e3 * el / args.steps
     tokens = B * world * T
     value = tokens * args.steps / el
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train_outputs(trainer, last[0]))
 
     roof = None
     launches_per_step = None
@@ -337,21 +368,23 @@ def main():
             step_flops = 3.0 * (fwd_tok * B * T + enc * B)
             roof["whole_step_tflops_per_gpu"] = round(step_flops / (ms_step * 1e-3) / 1e12, 2)
 
-    model.eval()
-    loss_last = None if args.no_check else probe_loss()
-    moved = float((model._flat.detach() - p0).abs().max().item())
-    check = {"probe_myloss_before": loss_first if loss_first is None else round(loss_first, 6),
-             "probe_myloss_after": loss_last if loss_last is None else round(loss_last, 6),
-             "optimizer_steps": trainer.sched_step, "params_finite": bool(torch.isfinite(model._flat).all().item()),
-             "max_param_change": moved, "launches_per_step": launches_per_step,
-             "note": "probe = MyLoss (stage 3) of a held-out synthetic batch in eval mode before the first and after the last "
-                     "optimizer step of this process (lr warms up from 0 over 10 steps to 1e-5)"}
+    check = None
+    if args.full:
+        model.eval()
+        loss_last = probe_loss() if check_probe else None
+        moved = float((model._flat.detach() - p0).abs().max().item())
+        check = {"probe_myloss_before": loss_first if loss_first is None else round(loss_first, 6),
+                 "probe_myloss_after": loss_last if loss_last is None else round(loss_last, 6),
+                 "optimizer_steps": trainer.sched_step, "params_finite": bool(torch.isfinite(model._flat).all().item()),
+                 "max_param_change": moved, "launches_per_step": launches_per_step,
+                 "note": "probe = MyLoss (stage 3) of a held-out synthetic batch in eval mode before the first and after the last "
+                         "optimizer step of this process (lr warms up from 0 over 10 steps to 1e-5)"}
 
     conditioning = None
     if rank == 0 and not args.no_roofline and args.dtype == "bf16" and args.config == "base":
         conditioning = conditioning_probe(model, batches[0])
     ddp_info = None
-    if ddp:
+    if ddp and args.full:
         # exposed exchange time: a few more steps with HIP events around the reducer's finish() (outside the timed region)
         trainer.measure_finish = True
         trainer.reducer.measure = True

@@ -71,6 +71,27 @@ def _timed(fn, world, dev):
     return el
 
 
+DUMP_SAMPLE = 1 << 22      # positions of a flat parameter / gradient buffer that --dump-outputs writes (16 MB each in float32)
+
+
+def flat_sample(n, seed=0):
+    """Sorted positions of a fixed, seeded sample of a flat buffer of n elements (all of them when n is small)."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, DUMP_SAMPLE, replace=False))
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array as outdir/<name>.npy, floating point as float32, integers as float64 (exact below 2**53)."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach().float().cpu() if a.is_floating_point() else a.detach().cpu()
+            a = a.numpy()
+        a = np.asarray(a)
+        np.save(os.path.join(outdir, name + ".npy"), a.astype(np.float32 if a.dtype.kind == "f" else np.float64))
+
+
 def _event_us(call, iters=20, warm=3):
     """Mean duration of call() in us: HIP events on the launch stream around `iters` back-to-back launches."""
     for _ in range(warm):

@@ -13,9 +13,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 from .common import _timed, gpu_rewarm
 
 
-def bench_decode(args, world, rank, dev, steps, warmup, with_cpu=True, cpu_fn=None):
+def bench_decode(args, world, rank, dev, steps, warmup, with_cpu=True, cpu_fn=None, dump=None):
     """Greedy decode tokens/s: every rank decodes its own batch (replicas only, no exchange).  Returns the result
-    object (rank 0) or None.  cpu_fn: bench.py's cpu_decode_baseline (the only code that touches the oracle stays in bench.py)."""
+    object (rank 0) or None.  cpu_fn: bench.py's cpu_decode_baseline (the only code that touches the oracle stays in bench.py).
+    dump: called with {"ids": ...} of the last timed generation (bench.py --dump-outputs)."""
     from mmtg_amd import MMTG, hip, synth
     from mmtg_amd.configs import data_config, gpt2_config, make_model_cfgs
     from mmtg_amd.decode import GreedyDecoder
@@ -52,6 +53,8 @@ def bench_decode(args, world, rank, dev, steps, warmup, with_cpu=True, cpu_fn=No
 
     el = _timed(run, world, dev)
     ids = out_ids[0]
+    if dump is not None:
+        dump({"ids": ids})
     free = [j for j in range(1, Ln + 1) if (j + 1) % 22 not in (0, 1)]
     check = {"ids_shape": list(ids.shape), "all_rows_start_with_START": bool((ids[:, 0] == 1).all().item()),
              "banned_ids_sampled": int(torch.isin(ids[:, free], torch.tensor([1, 2, 100, 102], device=ids.device)).sum().item()),

@@ -418,6 +418,25 @@ def test_bench_self_launch_reports_a_dead_rank():
     assert not [ln for ln in r.stdout.splitlines() if ln.strip()]     # no JSON line from a failed job
 
 
+def test_bench_dump_outputs_format(tmp_path):
+    """bench.py --dump-outputs: one DIR/<name>.npy per array, floating point as float32 and integers as float64, values kept; the
+    sample of a flat buffer is the same positions on every run, sorted, in range, and two full samples in fp32 stay within 64 MB."""
+    from bench_parts.common import DUMP_SAMPLE, dump_outputs, flat_sample
+    n = 109159232                                   # flat parameter count of the benchmarked configuration
+    idx = flat_sample(n)
+    assert len(idx) == DUMP_SAMPLE and np.array_equal(idx, flat_sample(n))
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+    assert 2 * 4 * DUMP_SAMPLE <= 64 * 2 ** 20
+    assert np.array_equal(flat_sample(10), np.arange(10))         # small buffers: every position
+    dump_outputs(str(tmp_path / "out"), {"loss": torch.tensor([1.5], dtype=torch.bfloat16),
+                                         "ids": torch.arange(6).reshape(2, 3), "norm": np.float64(2.25)})
+    assert sorted(os.listdir(tmp_path / "out")) == ["ids.npy", "loss.npy", "norm.npy"]
+    loss, ids, norm = (np.load(tmp_path / "out" / f) for f in ("loss.npy", "ids.npy", "norm.npy"))
+    assert loss.dtype == np.float32 and loss.tolist() == [1.5]
+    assert ids.dtype == np.float64 and ids.tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert norm.dtype == np.float32 and float(norm) == 2.25
+
+
 def test_grouped_weight_gradient_split_rule_and_workspace_sizes():
     """Engine-side rules of the grouped weight-gradient launch (no GPU): one round of the kernel's slots, no K slice shorter than
     1024 tokens; workspace / counter sizes per configuration as include/mmtg_hip.h states them."""

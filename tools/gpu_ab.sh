@@ -4,7 +4,7 @@ mkdir -p gpurun_out/ab
 i=0
 for v in "$@"; do
   for rep in 1 2; do
-    env $v python bench.py --no-cpu-baseline --no-decode --no-check --steps 20 --warmup 5 2>/dev/null | python -c "
+    env $v python bench.py --full --no-cpu-baseline --no-decode --no-check --steps 20 --warmup 5 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']

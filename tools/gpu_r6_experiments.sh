@@ -91,7 +91,7 @@ f)
 # Round 6, call F: the default bench line on the split bench.py (all objects), 3000-step memorisation curves of the three fast modes.
 mkdir -p gpurun_out/r6f
 E=gpurun_out/r6f
-timeout 1200 python bench.py > $E/bench_default.json 2> $E/bench_default.err; tail -c 600 $E/bench_default.err; python - <<'PY'
+timeout 1200 python bench.py --full > $E/bench_default.json 2> $E/bench_default.err; tail -c 600 $E/bench_default.err; python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r6f/bench_default.json").read().strip().splitlines()[-1])
 print(d["value"], d["ms_per_step"], {k: d["roofline"].get(k) for k in ("frac", "traffic", "decode_tokens_per_s", "decode_us_per_token_step", "decode_frac", "parity_train_tokens_per_s", "forward_parity_train_tokens_per_s", "conditioning_unfused_f32_frac_hbm")})
@@ -145,7 +145,7 @@ mkdir -p gpurun_out/r6k
 for rep in 1 2; do
 for cfg in "0 1" "0 2" "1 1" "1 2"; do
   set -- $cfg
-  MMTG_GELU_GRAD=$1 MMTG_GEMM_P8=$2 timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --primary-only 2>/dev/null | python -c "
+  MMTG_GELU_GRAD=$1 MMTG_GEMM_P8=$2 timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --primary-only 2>/dev/null | python -c "
 import sys, json
 for ln in sys.stdin:
     try: d = json.loads(ln)
@@ -196,7 +196,7 @@ E=gpurun_out/r6o
 timeout 1500 python -m pytest tests/test_ddp_gpu.py -m gpu -q --no-header -p no:cacheprovider -x 2>&1 | tail -8 | tee $E/pytest_ddp.txt
 for rep in 1 2; do
 for comm in torch abi; do
-  MMTG_FORCE_DDP=1 MMTG_DDP_COMM=$comm timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --primary-only --no-roofline 2>$E/err_$comm.log | python -c "
+  MMTG_FORCE_DDP=1 MMTG_DDP_COMM=$comm timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --primary-only --no-roofline 2>$E/err_$comm.log | python -c "
 import sys, json
 for ln in sys.stdin:
     try: d = json.loads(ln)
