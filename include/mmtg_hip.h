@@ -544,6 +544,31 @@ MMTG_API int mmtg_decode_sample(const float* logits, long ldl, int V, long long*
                        const float* uniforms, long ldu, int B, int* pos_next, void* stream);
 MMTG_API int mmtg_decode_advance(int* pos_ptr, void* stream);
 
+/* ---- beam search on the decode step (BeamDecoder, mmtg_amd/decode.py).  Rows b0 .. b0 + nb - 1 are the nb (1..16) beams of prompt
+ * b0 / nb.  rows: the ancestry table, int32 [B, ldrows >= Tmax]: rows[b, j] = the batch row whose cache slot j holds position j's
+ * K / V for beam b (only ever pointing backwards: a slot is written once, by the row that sits there at that step).
+ * mmtg_decode_attn_split_rows / mmtg_decode_attn_split_x3_rows: mmtg_decode_attn_split / mmtg_decode_attn_split_x3 with the keys
+ *   j < pos read from cache row rows[b, j] (the token's own K / V still go to row b, slot pos).
+ * mmtg_decode_beam_candidates: per row, the processed logits x of mmtg_decode_select (cut at V) and the row's nb best
+ *   (log_softmax(x)[v] in fp32, v) by x descending, then v ascending, into cand_val / cand_id [B, nb]; a row whose last token is
+ *   PAD offers (0, PAD) then -inf; nothing is written at forced positions.
+ * mmtg_decode_beam_merge: per prompt, candidate (p, k) scores scores[b0 + p] + cand_val[b0 + p, k]; the nb best by (score
+ *   descending, p ascending, k ascending) become beams 0 .. nb - 1: their rows of seq / keep / rows are reordered in place,
+ *   seq[b, pos + 1] = the token, scores[b] = the score, rows[b, pos + 1] = b; forced positions (or cand_val = null) keep every
+ *   beam and append the forced token.  pos_next as in mmtg_decode_select.  nb outside 1..16 fails before any device call.  */
+MMTG_API int mmtg_decode_attn_split_rows(int dtype, const float* part, int splits, const float* bias, void* kcache, void* vcache,
+                                const int* keep, long ldkeep, const int* rows, long ldrows, const int* pos_ptr, void* out,
+                                int B, int nH, int dh, int Tmax, void* stream);
+MMTG_API int mmtg_decode_attn_split_x3_rows(const float* part, int splits, const float* bias, float* kcache, float* vcache, const int* keep,
+                                   long ldkeep, const int* rows, long ldrows, const int* pos_ptr, void* out_planes, long plane, int B,
+                                   int nH, int dh, int Tmax, void* stream);
+MMTG_API int mmtg_decode_beam_candidates(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                int B, void* stream);
+MMTG_API int mmtg_decode_beam_merge(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
+                           long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
+                           int* pos_next, void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

@@ -845,16 +845,22 @@ template <typename V, bool NT> __device__ __forceinline__ V ld_kv(const V* p) {
 template <typename T> constexpr int da_lds_bytes() { return 1024 * 4 + 1024 * 4 + 64 * 4 + 2 * 64 * (int)sizeof(T); }
 
 // one 64-thread workgroup per (b, head)
-template <typename T, bool NT = false>
+// ROWS (beam search): the K / V rows of key j < pos are read from cache row rows[b * ldrows + j] (the ancestry table: which row of
+// the batch wrote position j of this beam's history) instead of row b; the token's own K / V still go to row b, slot pos.  The
+// table of the prefix is read into LDS (the first 4 KB, unused otherwise) in the pass that reads the key flags; the first two
+// chunks' row indices are requested before their K / V (one dependent round trip more than the plain form).
+template <typename T, bool NT = false, bool ROWS = false>
 __device__ __forceinline__ void da_body(const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
         const int* __restrict__ keep, long ldkeep, const int pos, T* __restrict__ out, const int B,
         int nH, int Tmax, const float* __restrict__ part, int splits, long slab, const float* __restrict__ bias,
-        const int h, const int b, const int lane, char* lds, bf16* __restrict__ oplanes = nullptr, long oplane = 0) {
+        const int h, const int b, const int lane, char* lds, bf16* __restrict__ oplanes = nullptr, long oplane = 0,
+        const int* __restrict__ rows = nullptr, long ldrows = 0) {
     typedef typename Vec16<T>::type V;
     constexpr int EPL = Vec16<T>::N, OCT = 64 / EPL, KPI = 64 / OCT;      // elements per lane, lanes per key, keys per instruction
     // (the SAME chunking in both forms: the first chunk's scores and the later chunks' come out of differently contracted
     //  loops, so moving the chunk boundary moves last bits -- the persistent step stays bit-equal to the per-launch one)
     constexpr int UN = 4, CH = UN * KPI;         // a chunk: UN keys per lane group = 32 keys (bf16) / 16 (f32)
+    int* const srows = reinterpret_cast<int*>(lds);
     int* const skeep = reinterpret_cast<int*>(lds + 4096);
     float* const sq = reinterpret_cast<float*>(lds + 8192);
     T* const sk = reinterpret_cast<T*>(lds + 8192 + 256);
@@ -870,24 +876,50 @@ __device__ __forceinline__ void da_body(const T* __restrict__ qkv, T* __restrict
     // chunks 0 and 1 (K and V rows) are requested at the very top: they depend on nothing this kernel computes.  Branch-free:
     // rows at or past `pos` are requested from the last valid row and replaced (key == pos: the token's own row, from LDS) or masked
     V kA[UN], vA[UN], kB[UN], vB[UN];
+    // ROWS: element offset of (cache row r, head h, key kr); r is clamped into the batch (a table is only ever read, never trusted)
+    const int* const rrow = ROWS ? rows + (long)b * ldrows : nullptr;
+    auto kv_off = [&](int r, int kr) -> long { return ((((long)min(max(r, 0), B - 1) * nH + h) * Tmax) + kr) * 64 + oc * EPL; };
+    int rA[UN], rB[UN];
+    if constexpr (ROWS) {
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const int kA_ = u * KPI + kg, kB_ = CH + u * KPI + kg;
+            rA[u] = rrow[kA_ < pos ? kA_ : last];
+            rB[u] = rrow[kB_ < pos ? kB_ : last];
+        }
+    }
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
         const int key = u * KPI + kg, kr = key < pos ? key : last;
-        kA[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(kbase + (long)kr * 64 + oc * EPL));
-        vA[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(vbase + (long)kr * 64 + oc * EPL));
+        if constexpr (ROWS) {
+            kA[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(kc + kv_off(rA[u], kr)));
+            vA[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(vc + kv_off(rA[u], kr)));
+        } else {
+            kA[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(kbase + (long)kr * 64 + oc * EPL));
+            vA[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(vbase + (long)kr * 64 + oc * EPL));
+        }
     }
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
         const int key = CH + u * KPI + kg, kr = key < pos ? key : last;
-        kB[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(kbase + (long)kr * 64 + oc * EPL));
-        vB[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(vbase + (long)kr * 64 + oc * EPL));
+        if constexpr (ROWS) {
+            kB[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(kc + kv_off(rB[u], kr)));
+            vB[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(vc + kv_off(rB[u], kr)));
+        } else {
+            kB[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(kbase + (long)kr * 64 + oc * EPL));
+            vB[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(vbase + (long)kr * 64 + oc * EPL));
+        }
     }
     // the key-padding flags of the whole prefix in one coalesced pass, into LDS (round 3: the score loop used to read keep[]
     // from global memory key group by key group -- up to 16 DEPENDENT 4-byte loads, each a full memory round trip)
     // (the first 256 flags as four independent loads, stored after the slab sums; longer prefixes: a plain loop)
-    int kp[4];
+    int kp[4], rp[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) kp[i] = keep[(long)b * ldkeep + min(lane + 64 * i, pos)];
+    if constexpr (ROWS) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rp[i] = rrow[min(lane + 64 * i, pos)];
+    }
     asm volatile("" ::: "memory");      // compiler barrier: the requests above are ISSUED here (nothing waits for them yet)
     if (part) {
         // the c_attn product arrives as split-K slabs (MMTG_EPI_SPLIT): sum them in order, add the bias
@@ -920,6 +952,11 @@ __device__ __forceinline__ void da_body(const T* __restrict__ qkv, T* __restrict
 #pragma unroll
     for (int i = 0; i < 4; ++i) skeep[lane + 64 * i] = kp[i];
     for (int key = lane + 256; key < nkeys; key += 64) skeep[key] = keep[(long)b * ldkeep + key];
+    if constexpr (ROWS) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) srows[lane + 64 * i] = rp[i];
+        for (int key = lane + 256; key < nkeys; key += 64) srows[key] = rrow[key];
+    }
     DA_SYNC();
     float qv[EPL];
 #pragma unroll
@@ -967,8 +1004,14 @@ __device__ __forceinline__ void da_body(const T* __restrict__ qkv, T* __restrict
     do {                                                                                                             \
         _Pragma("unroll") for (int u = 0; u < UN; ++u) {                                                             \
             const int key = (K0_) + u * KPI + kg, kr = key < pos ? key : last;                                       \
-            KB_[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(kbase + (long)kr * 64 + oc * EPL));                     \
-            VB_[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(vbase + (long)kr * 64 + oc * EPL));                     \
+            if constexpr (ROWS) {                                                                                    \
+                const long o_ = kv_off(srows[kr], kr);                                                               \
+                KB_[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(kc + o_));                                          \
+                VB_[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(vc + o_));                                          \
+            } else {                                                                                                 \
+                KB_[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(kbase + (long)kr * 64 + oc * EPL));                 \
+                VB_[u] = ld_kv<V, NT>(reinterpret_cast<const V*>(vbase + (long)kr * 64 + oc * EPL));                 \
+            }                                                                                                        \
         }                                                                                                            \
     } while (0)
 #pragma unroll 1
@@ -1020,6 +1063,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void de
                       (int)blockIdx.x, (int)blockIdx.y, (int)threadIdx.x, lds, oplanes, oplane);
 }
 
+// the same with the ancestry table of beam search (da_body ROWS): a kernel of its own, so the plain forms' code is unchanged
+template <typename T, bool NT = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void decode_attn_rows_kernel(T* __restrict__ kc, T* __restrict__ vc,
+        const int* __restrict__ keep, long ldkeep, const int* __restrict__ rows, long ldrows, const int* __restrict__ pos_ptr,
+        T* __restrict__ out, int nH, int Tmax, const float* __restrict__ part, int splits, long slab, const float* __restrict__ bias,
+        bf16* __restrict__ oplanes, long oplane) {
+    __shared__ __attribute__((aligned(16))) char lds[da_lds_bytes<T>()];
+    da_body<T, NT, true>(nullptr, kc, vc, keep, ldkeep, *pos_ptr, out, (int)gridDim.y, nH, Tmax, part, splits, slab, bias,
+                         (int)blockIdx.x, (int)blockIdx.y, (int)threadIdx.x, lds, oplanes, oplane, rows, ldrows);
+}
+
 // logits processor + arg-max + forced-token cadence + append (generate.py:117-142), device-driven.
 __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restrict__ logits, long ldl, int V,
         long long* __restrict__ seq, long ldseq, const int* __restrict__ pos_ptr, int P, int sent,
@@ -1067,6 +1121,174 @@ __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restr
 }
 
 __global__ void decode_advance_kernel(int* pos_ptr) { *pos_ptr += 1; }
+
+// ------------------------------------------------------------------ beam search (the selection step of BeamDecoder)
+// Rows b0 .. b0 + nb - 1 of the batch are the nb beams of prompt b0 / nb.  Two launches replace decode_select:
+//   candidates (one workgroup per row): the row's processed logits x exactly as decode_select computes them (per-occurrence
+//     penalty, temperature, bans; cut at V), log_softmax(x) in fp32, and the row's top nb (log-probability, id) pairs ordered by
+//     x descending, then id ascending.  A sticky-PAD row offers PAD at log-probability 0 (then -inf fillers).
+//   merge (one workgroup per prompt): candidate (parent p, rank k) scores scores[p] + logp; the prompt keeps its nb best by
+//     (score descending, parent ascending, rank ascending), reorders its rows of seq / keep / the ancestry table in place (staged
+//     through LDS), appends the tokens and points rows[b, pos + 1] at b.  Forced positions keep every beam (identity) and append
+//     the forced token; the scores are unchanged there.
+constexpr int BEAM_MAX = 16;
+constexpr int BEAM_TW = 64;        // columns of seq / keep / rows staged per pass of the reorder
+
+__device__ __forceinline__ bool beam_forced(int j, int sent) { return j > 1 && ((j + 1) % sent == 0 || (j + 1) % sent == 1); }
+
+__global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __restrict__ logits, long ldl, int V,
+        const long long* __restrict__ seq, long ldseq, const int* __restrict__ pos_ptr, int P, int sent,
+        float temperature, float rep_penalty, int nb, float* __restrict__ cand_val, int* __restrict__ cand_id) {
+    extern __shared__ unsigned cnt[];          // (V + 1) / 2 count words | V processed logits
+    float* const px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
+    __shared__ float sval[4], sx[BEAM_MAX];
+    __shared__ int sidx[4], si[BEAM_MAX];
+    const int b = blockIdx.x, tid = threadIdx.x, pos = *pos_ptr;
+    const int j = pos + 1 - P;
+    if (j < 1 || beam_forced(j, sent)) return;             // the merge appends the forced token without candidates
+    float* const cv = cand_val + (long)b * nb;
+    int* const ci = cand_id + (long)b * nb;
+    const long long* gen = seq + (long)b * ldseq + P;
+    const int n = min(j, MAXGEN);
+    if (gen[n - 1] == 0) {                                 // sticky PAD: PAD with the score unchanged
+        if (tid < nb) { cv[tid] = tid == 0 ? 0.f : -INFINITY; ci[tid] = 0; }
+        return;
+    }
+    count_ids(cnt, V, gen, n, tid);
+    const float* row = logits + (long)b * ldl;
+    float mx = -INFINITY;
+    for (int v = tid; v < V; v += 256) {
+        float x = row[v];
+        if (v != 0 && v != 102) {
+            const int c = (cnt[v >> 1] >> (16 * (v & 1))) & 0xFFFF;
+            for (int i = 0; i < c; ++i) x = x / rep_penalty;
+        }
+        x = x / temperature;
+        if (v == 1 || v == 2 || v == 100 || v == 102) x = -INFINITY;
+        px[v] = x;
+        mx = fmaxf(mx, x);
+    }
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) sval[tid >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(sval[0], sval[1]), fmaxf(sval[2], sval[3]));
+    float sum = 0.f;
+    for (int v = tid; v < V; v += 256) sum += expf(px[v] - mx);
+    sum = wave_sum(sum);
+    __syncthreads();
+    if ((tid & 63) == 0) sval[tid >> 6] = sum;
+    __syncthreads();
+    const float lsum = logf(sval[0] + sval[1] + sval[2] + sval[3]);
+    // nb rounds of the block arg-max (lowest id wins ties); a taken id is marked NaN, which no comparison selects again
+    for (int r = 0; r < nb; ++r) {
+        __syncthreads();
+        float best = -INFINITY;
+        int besti = 0x7fffffff;
+        for (int v = tid; v < V; v += 256) {
+            const float x = px[v];
+            if (x > best || (x == best && v < besti)) { best = x; besti = v; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(best, o, 64);
+            const int oi = __shfl_xor(besti, o, 64);
+            if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        }
+        if ((tid & 63) == 0) { sval[tid >> 6] = best; sidx[tid >> 6] = besti; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < 4; ++w)
+                if (sval[w] > best || (sval[w] == best && sidx[w] < besti)) { best = sval[w]; besti = sidx[w]; }
+            sx[r] = best;
+            si[r] = besti;
+            if (besti >= 0 && besti < V) px[besti] = __int_as_float(0x7fc00000);
+        }
+    }
+    __syncthreads();
+    if (tid < nb) {
+        const float x = sx[tid];
+        const bool ok = si[tid] >= 0 && si[tid] < V && x > -INFINITY && mx > -INFINITY;
+        cv[tid] = ok ? (x - mx) - lsum : -INFINITY;        // log_softmax(x)[v] = (x - max) - log(sum exp(x - max))
+        ci[tid] = ok ? si[tid] : 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_id,
+        float* __restrict__ scores, long long* __restrict__ seq, long ldseq, int* __restrict__ keep, long ldkeep,
+        int* __restrict__ rows, long ldrows, const int* __restrict__ pos_ptr, int P, int sent, int nb, int* __restrict__ pos_next) {
+    __shared__ float sc[BEAM_MAX * BEAM_MAX];
+    __shared__ float s_sc[BEAM_MAX];
+    __shared__ int s_par[BEAM_MAX], s_tok[BEAM_MAX];
+    __shared__ long long st_seq[BEAM_MAX][BEAM_TW];
+    __shared__ int st_keep[BEAM_MAX][BEAM_TW], st_rows[BEAM_MAX][BEAM_TW];
+    const int g = blockIdx.x, tid = threadIdx.x, pos = *pos_ptr, b0 = g * nb;
+    if (pos_next && g == 0 && tid == 0) *pos_next = pos + 1;
+    const int j = pos + 1 - P;
+    const bool next_ok = pos + 1 < ldrows;
+    if (j < 1 || beam_forced(j, sent) || !cand_val) {      // identity: the forced token (if any), every beam keeps its own row
+        if (tid < nb) {
+            const long b = b0 + tid;
+            if (j >= 1 && beam_forced(j, sent)) seq[b * ldseq + pos + 1] = (j + 1) % sent == 0 ? 2 : 1;
+            if (next_ok) rows[b * ldrows + pos + 1] = (int)b;
+        }
+        return;
+    }
+    const int nc = nb * nb;
+    float my = -INFINITY;
+    int mp = 0, mk = 0;
+    if (tid < nc) {
+        mp = tid / nb;
+        mk = tid - mp * nb;
+        my = scores[b0 + mp] + cand_val[(long)(b0 + mp) * nb + mk];
+        if (my != my) my = -INFINITY;                      // (a strict total order: every place below is taken once)
+        sc[tid] = my;
+    }
+    __syncthreads();
+    if (tid < nc) {
+        // candidate o = (parent o / nb, rank o % nb): (parent, rank) ascending is o ascending
+        int place = 0;
+        for (int o = 0; o < nc; ++o) {
+            const float so = sc[o];
+            place += (so > my) || (so == my && o < tid);
+        }
+        if (place < nb) { s_par[place] = mp; s_tok[place] = cand_id[(long)(b0 + mp) * nb + mk]; s_sc[place] = my; }
+    }
+    __syncthreads();
+    bool ident = true;
+    for (int r = 0; r < nb; ++r) ident = ident && s_par[r] == r;
+    if (!ident) {
+        for (int c0 = 0; c0 <= pos; c0 += BEAM_TW) {
+            const int w = min(BEAM_TW, pos + 1 - c0);
+            for (int e = tid; e < nb * BEAM_TW; e += 256) {
+                const int r = e / BEAM_TW, c = e - r * BEAM_TW;
+                if (c < w) {
+                    const long b = b0 + r;
+                    st_seq[r][c] = seq[b * ldseq + c0 + c];
+                    st_keep[r][c] = keep[b * ldkeep + c0 + c];
+                    st_rows[r][c] = rows[b * ldrows + c0 + c];
+                }
+            }
+            __syncthreads();
+            for (int e = tid; e < nb * BEAM_TW; e += 256) {
+                const int r = e / BEAM_TW, c = e - r * BEAM_TW;
+                if (c < w) {
+                    const long b = b0 + r;
+                    const int p = s_par[r];
+                    seq[b * ldseq + c0 + c] = st_seq[p][c];
+                    keep[b * ldkeep + c0 + c] = st_keep[p][c];
+                    rows[b * ldrows + c0 + c] = st_rows[p][c];
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (tid < nb) {
+        const long b = b0 + tid;
+        scores[b] = s_sc[tid];
+        seq[b * ldseq + pos + 1] = s_tok[tid];
+        if (next_ok) rows[b * ldrows + pos + 1] = (int)b;
+    }
+}
 
 }  // namespace
 
@@ -1136,6 +1358,69 @@ extern "C" int mmtg_decode_attn_split(int dtype, const float* part, int splits, 
         else hipLaunchKernelGGL(decode_attn_kernel<bf16>, grid, block, 0, s, (const bf16*)nullptr, (bf16*)kcache, (bf16*)vcache, keep, ldkeep, pos_ptr, (bf16*)out, nH, Tmax, part, splits, slab, bias);
     } else MMTG_FAIL(MMTG_ERR_BAD_ARG, "decode_attn_split: bad dtype");
     MMTG_LAUNCH_CHECK("decode_attn_split");
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_attn_split_rows(int dtype, const float* part, int splits, const float* bias, void* kcache, void* vcache,
+                                           const int* keep, long ldkeep, const int* rows, long ldrows, const int* pos_ptr, void* out,
+                                           int B, int nH, int dh, int Tmax, void* stream) {
+    MMTG_REQUIRE(part && bias && splits > 0 && kcache && vcache && keep && rows && pos_ptr && out, "decode_attn_split_rows: null pointer");
+    MMTG_REQUIRE(dh == 64 && B > 0 && nH > 0 && Tmax > 0 && Tmax <= 1024 && ldrows >= Tmax,
+                 "decode_attn_split_rows: head dim 64, Tmax <= 1024, the ancestry table [B, ldrows >= Tmax]");
+    hipStream_t s = (hipStream_t)stream;
+    const double esz = dtype == MMTG_F32 ? 4 : 2;
+    ProfScope prof(MMTG_PROF_DECODE, s, 4.0 * B * nH * (double)Tmax * dh, esz * 2.0 * B * nH * (double)Tmax * dh);
+    dim3 grid(nH, B), block(64);
+    const long slab = (long)B * 3 * nH * 64;
+    if (dtype == MMTG_F32)
+        hipLaunchKernelGGL(decode_attn_rows_kernel<float>, grid, block, 0, s, (float*)kcache, (float*)vcache, keep, ldkeep, rows, ldrows, pos_ptr,
+                           (float*)out, nH, Tmax, part, splits, slab, bias, (bf16*)nullptr, 0L);
+    else if (dtype == MMTG_BF16) {
+        static const bool kv_nt = !getenv("MMTG_DECODE_KV_NT") || atoi(getenv("MMTG_DECODE_KV_NT")) != 0;      // as mmtg_decode_attn_split
+        if (kv_nt) hipLaunchKernelGGL((decode_attn_rows_kernel<bf16, true>), grid, block, 0, s, (bf16*)kcache, (bf16*)vcache, keep, ldkeep, rows, ldrows,
+                                      pos_ptr, (bf16*)out, nH, Tmax, part, splits, slab, bias, (bf16*)nullptr, 0L);
+        else hipLaunchKernelGGL((decode_attn_rows_kernel<bf16, false>), grid, block, 0, s, (bf16*)kcache, (bf16*)vcache, keep, ldkeep, rows, ldrows,
+                                pos_ptr, (bf16*)out, nH, Tmax, part, splits, slab, bias, (bf16*)nullptr, 0L);
+    } else MMTG_FAIL(MMTG_ERR_BAD_ARG, "decode_attn_split_rows: bad dtype");
+    MMTG_LAUNCH_CHECK("decode_attn_split_rows");
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_beam_candidates(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                           int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                           int B, void* stream) {
+    MMTG_REQUIRE(nb >= 1 && nb <= BEAM_MAX, "decode_beam_candidates: %d beams per prompt (1..%d)", nb, BEAM_MAX);
+    MMTG_REQUIRE(logits && seq && pos_ptr && cand_val && cand_id && B > 0 && sent > 1 && V > 0 && ldl >= V,
+                 "decode_beam_candidates: bad args");
+    MMTG_REQUIRE(temperature > 0.f && rep_penalty > 0.f, "decode_beam_candidates: temperature / penalty must be > 0");
+    MMTG_REQUIRE(V <= 24000, "decode_beam_candidates: vocabulary of %d exceeds the LDS row image (24000)", V);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, 4.0 * B * V, 4.0 * B * V);
+    const size_t shm = (size_t)((V + 1) / 2) * 4 + (size_t)V * 4;
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute((const void*)beam_candidates_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
+            MMTG_FAIL(MMTG_ERR_HIP, "decode_beam_candidates: cannot raise dynamic LDS");
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(beam_candidates_kernel, dim3(B), dim3(256), shm, s, logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature,
+                       rep_penalty, nb, cand_val, cand_id);
+    MMTG_LAUNCH_CHECK("decode_beam_candidates");
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_beam_merge(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
+                                      long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
+                                      int* pos_next, void* stream) {
+    MMTG_REQUIRE(nb >= 1 && nb <= BEAM_MAX, "decode_beam_merge: %d beams per prompt (1..%d)", nb, BEAM_MAX);
+    MMTG_REQUIRE(scores && seq && keep && rows && pos_ptr && n_prompts > 0 && sent > 1 && ldrows > 0 && (!cand_val || cand_id),
+                 "decode_beam_merge: bad args");
+    MMTG_REQUIRE(pos_next != pos_ptr, "decode_beam_merge: pos_next must not alias pos_ptr");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, (double)n_prompts * nb * nb, 32.0 * n_prompts * nb * (double)ldrows);
+    hipLaunchKernelGGL(beam_merge_kernel, dim3(n_prompts), dim3(256), 0, s, cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows, ldrows,
+                       pos_ptr, P, sent, nb, pos_next);
+    MMTG_LAUNCH_CHECK("decode_beam_merge");
     return MMTG_OK;
 }
 
@@ -1385,5 +1670,24 @@ extern "C" int mmtg_decode_embed_x3(const float* table, const long long* seq, lo
     hipLaunchKernelGGL(decode_embed_kernel<float>, dim3(B), dim3(256), 0, s, table, seq, ldseq, c, (float*)nullptr, pos_ptr, tpw_type, tpw_mask, type_out, keep,
                        ldkeep, P, S, E, two_sents, V, sent, max_sent_num, (bf16*)x_planes, plane);
     MMTG_LAUNCH_CHECK("decode_embed_x3");
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_attn_split_x3_rows(const float* part, int splits, const float* bias, float* kcache, float* vcache, const int* keep,
+                                              long ldkeep, const int* rows, long ldrows, const int* pos_ptr, void* out_planes, long plane, int B,
+                                              int nH, int dh, int Tmax, void* stream) {
+    MMTG_REQUIRE(part && bias && splits > 0 && kcache && vcache && keep && rows && pos_ptr && out_planes, "decode_attn_split_x3_rows: null pointer");
+    MMTG_REQUIRE(dh == 64 && B > 0 && nH > 0 && Tmax > 0 && Tmax <= 1024 && ldrows >= Tmax && plane % 4 == 0 && plane >= (long)B * nH * 64 &&
+                 (((uintptr_t)out_planes) & 7) == 0,
+                 "decode_attn_split_x3_rows: head dim 64, Tmax <= 1024, the ancestry table [B, ldrows >= Tmax], the lo plane behind the hi plane");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, 4.0 * B * nH * (double)Tmax * dh, 8.0 * B * nH * (double)Tmax * dh);
+    const long slab = (long)B * 3 * nH * 64;
+    static const bool kv_nt = !getenv("MMTG_DECODE_KV_NT") || atoi(getenv("MMTG_DECODE_KV_NT")) != 0;
+    if (kv_nt) hipLaunchKernelGGL((decode_attn_rows_kernel<float, true>), dim3(nH, B), dim3(64), 0, s, kcache, vcache, keep, ldkeep, rows, ldrows, pos_ptr,
+                                  (float*)nullptr, nH, Tmax, part, splits, slab, bias, (bf16*)out_planes, plane);
+    else hipLaunchKernelGGL((decode_attn_rows_kernel<float, false>), dim3(nH, B), dim3(64), 0, s, kcache, vcache, keep, ldkeep, rows, ldrows, pos_ptr,
+                            (float*)nullptr, nH, Tmax, part, splits, slab, bias, (bf16*)out_planes, plane);
+    MMTG_LAUNCH_CHECK("decode_attn_split_x3_rows");
     return MMTG_OK;
 }

@@ -181,6 +181,7 @@ class GreedyDecoder:
         self.uniforms = None
         self.graphs = {}
         self.params = None
+        self.rows = None            # the ancestry table of beam search (BeamDecoder); None: row b attends over its own cache row
 
     def _conv1d(self, x, wkey, out, **kw):
         # bf16: Engine._fwd routes Conv1D weights through their [out,in] copies (NT layout), which is
@@ -282,7 +283,8 @@ class GreedyDecoder:
             p = f"{pre}h.{l}."
             wf, c, bq = self.fq[l]
             hip.decode_gemm_x3(1, xp, wf, B, 3 * D, D, C_=self.part, colsum=c, stats_in=st, np_in=NP, eps=sh.eps, splits=sq)
-            hip.decode_attn_split_x3(self.part, nslab, bq, self.kc[l], self.vc[l], self.keep, self.pos, self.ctxp, B, sh.nH, 64, self.Tmax)
+            hip.decode_attn_split_x3(self.part, nslab, bq, self.kc[l], self.vc[l], self.keep, self.pos, self.ctxp, B, sh.nH, 64, self.Tmax,
+                                     rows=self.rows)
             hip.decode_gemm_x3(2, self.ctxp, eng.Wtx(p + "attn.c_proj.weight"), B, D, D, C_=xo, Cp=xop, bias=eng.P(p + "attn.c_proj.bias"),
                                resid=x, stats_out=sto, splits=sp, ws=self.rws, counters=self.rcnt)
             wf, c, bfc = self.ffc[l]
@@ -346,7 +348,7 @@ class GreedyDecoder:
                 # c_attn: the attention kernel sums the split-K slabs itself (no finish launch)
                 self._slabs(self.a, p + "attn.c_attn.weight", sq)
                 hip.decode_attn_split(self.part, sq, eng.P(p + "attn.c_attn.bias"), self.kc[l], self.vc[l], self.keep, self.pos,
-                                      self.ctx, B, sh.nH, 64, self.Tmax)
+                                      self.ctx, B, sh.nH, 64, self.Tmax, rows=self.rows)
             else:
                 self._split(self.a, p + "attn.c_attn.weight", self.qkv, sq, eng.P(p + "attn.c_attn.bias"))
                 hip.decode_attn(self.qkv, self.kc[l], self.vc[l], self.keep, self.pos, self.ctx, B, sh.nH, 64, self.Tmax)
@@ -417,7 +419,7 @@ class GreedyDecoder:
             wf, c, bq = self.fq[l]
             hip.decode_gemm(1, x, wf, self.part, B, 3 * D, D, colsum=c, stats_in=st, np_in=npx, eps=sh.eps, out_f32=True, splits=sq)
             hip.decode_attn_split(self.part, nslab, bq, self.kc[l], self.vc[l], self.keep, self.pos,
-                                  self.ctx, B, sh.nH, 64, self.Tmax)
+                                  self.ctx, B, sh.nH, 64, self.Tmax, rows=self.rows)
             hip.decode_gemm(2, self.ctx, eng.Wt(p + "attn.c_proj.weight"), xo, B, D, D, bias=eng.P(p + "attn.c_proj.bias"), resid=x,
                             stats_out=sto, splits=sp, ws=self.rws, counters=self.rcnt)
             wf, c, bfc = self.ffc[l]
@@ -443,16 +445,23 @@ class GreedyDecoder:
         g = self.graphs.get(key)
         if g is None:
             # warm-up outside capture (lazy LDS-attribute / module loading), then rewind the position
-            saved = (self.pos_all.clone(), self.seq.clone(), self.keep.clone())
+            state = self._step_state()
+            saved = [t.clone() for t in state]
             self._step(with_head, parity)
             torch.cuda.synchronize()
-            self.pos_all.copy_(saved[0]); self.seq.copy_(saved[1]); self.keep.copy_(saved[2])
+            for t, v in zip(state, saved):
+                t.copy_(v)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 self._step(with_head, parity)
             self.graphs[key] = g
-            self.pos_all.copy_(saved[0]); self.seq.copy_(saved[1]); self.keep.copy_(saved[2])
+            for t, v in zip(state, saved):
+                t.copy_(v)
         g.replay()
+
+    def _step_state(self):
+        """What a token step changes besides the caches' slot `pos` (rewound around the warm-up step of a graph capture)."""
+        return [self.pos_all, self.seq, self.keep]
 
     # ------------------------------------------------------------------ public
     def describe(self):
@@ -605,3 +614,80 @@ class GreedyDecoder:
         before the append of the last iteration that called the model (generate.py:126,144)."""
         last_call = max(i for i in range(length) if not (i > 0 and (i + 2) % sent in (0, 1)))
         return list(ids_row[:1 + last_call])
+
+
+class BeamDecoder(GreedyDecoder):
+    """Beam search on the KV-cached, graph-replayed token step: `num_beams` rows per prompt advance in lock step, and the step's
+    last two launches (mmtg_decode_beam_candidates, mmtg_decode_beam_merge) replace decode_select.
+
+    Per model call, candidate (beam, v) scores cum[beam] + log_softmax(x)[v] in fp32, x the beam's processed logits exactly as the
+    greedy step computes them (per-occurrence repetition penalty, temperature, bans; cut at 13317); each prompt keeps its best
+    `num_beams` by (score descending, parent beam ascending, rank inside the parent: x descending, id ascending), so one beam
+    picks what greedy picks.  Forced [#EOS#] / [#START#] positions and sticky PAD keep the score; a PAD-terminated beam keeps its
+    frozen score (no length penalty, no early stop: every beam has the same length).  Beam scores start at [0, -inf, ...], so the
+    replicated beams of a prompt never yield duplicate hypotheses.
+
+    The KV cache is never copied: a row writes its new K / V into its own slot `pos`, and the ancestry table `rows` [B, Tmax]
+    (rows[b, j] = the cache row holding position j of beam b's history) is reordered with seq / keep by the merge; the attention
+    reads the prefix through it (mmtg_decode_attn_split_rows / mmtg_decode_attn_split_x3_rows)."""
+
+    def __init__(self, model, max_prompts, num_beams, max_len=None, use_graph=True, lanes=1):
+        nb = int(num_beams)
+        if not 1 <= nb <= 16:
+            raise ValueError("num_beams %d outside 1..16" % nb)
+        if lanes != 1:
+            raise ValueError("beam search runs on one lane (got lanes=%r)" % (lanes,))
+        super().__init__(model, int(max_prompts) * nb, max_len=max_len, use_graph=use_graph, lanes=1)
+        if not self.fast:
+            raise ValueError("beam search needs the split decode step (MMTG_DECODE_PLAIN has no table-aware attention)")
+        if not (self.x3 or getattr(self, "fused", False)) and os.environ.get("MMTG_DECODE_ATTN_SPLIT", "1") != "1":
+            raise ValueError("beam search needs the split attention (MMTG_DECODE_ATTN_SPLIT=0 has no table-aware attention)")
+        dev = self.eng.dev
+        self.nb, self.n_prompts = nb, int(max_prompts)
+        self.rows = torch.zeros(self.B, self.Tmax, dtype=torch.int32, device=dev)
+        self.scores = torch.zeros(self.B, dtype=torch.float32, device=dev)
+        self.cand_val = torch.zeros(self.B, nb, dtype=torch.float32, device=dev)
+        self.cand_id = torch.zeros(self.B, nb, dtype=torch.int32, device=dev)
+
+    def _select(self, with_head):
+        eng, sh, B = self.eng, self.eng.sh, self.B
+        temperature, rep, _, _ = self.params
+        sent = sh.msl + 2
+        if with_head:
+            hip.decode_beam_candidates(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep,
+                                       self.nb, self.cand_val, self.cand_id, B)
+        hip.decode_beam_merge(self.cand_val if with_head else None, self.cand_id if with_head else None, self.scores, self.seq, self.keep,
+                              self.rows, self.pos, sh.P, sent, self.nb, self.n_prompts, pos_next=self.pos_next)
+
+    def _step_state(self):
+        return super()._step_state() + [self.rows, self.scores]
+
+    def describe(self):
+        return "%d beams per prompt, " % self.nb + super().describe()
+
+    @torch.no_grad()
+    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None):
+        """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs and prompt prefill), the ancestry table as
+        the identity and the beam scores at [0, -inf, ...] per prompt."""
+        n = batch["img_embs"].shape[0]
+        if n != self.n_prompts:
+            raise ValueError("decoder was built for %d prompts, got %d" % (self.n_prompts, n))
+        rep = {k: (v.repeat_interleave(self.nb, 0) if torch.is_tensor(v) else v) for k, v in batch.items()}
+        n_steps = super().begin(rep, length, temperature, repitition_penalty, 1, 0.0)
+        B, dev = self.B, self.eng.dev
+        self.rows.copy_(torch.arange(B, dtype=torch.int32, device=dev)[:, None].expand(B, self.Tmax))
+        sc = torch.full((n, self.nb), float("-inf"), dtype=torch.float32, device=dev)
+        sc[:, 0] = 0.0
+        self.scores.copy_(sc.view(-1))
+        return n_steps
+
+    @torch.no_grad()
+    def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None):
+        """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_beams, 1 + length] in
+        GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row."""
+        ids = super().generate(batch, length, temperature=temperature, repitition_penalty=repitition_penalty, use_graph=use_graph)
+        n, nb = self.n_prompts, self.nb
+        ids = ids.view(n, nb, -1)
+        sc = self.scores.view(n, nb).clone()
+        order = torch.sort(sc, dim=1, descending=True, stable=True).indices
+        return torch.gather(ids, 1, order[:, :, None].expand_as(ids)), torch.gather(sc, 1, order)

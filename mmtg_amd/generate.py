@@ -181,3 +181,41 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
             seq = GreedyDecoder.reference_return(ids[r].tolist(), length, sent=sh.msl + 2)
             texts.append(postprocess_tokens(tokenizer.convert_ids_to_tokens(seq)))
     return [texts[i * n_samples:(i + 1) * n_samples] for i in range(n_prompts)]
+
+
+def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature=1.1, repetition_penalty=1.5, max_batch=256,
+                   return_all=False):
+    """Beam search per prompt on the batched, graph-replayed decoder (BeamDecoder): prompts are decoded max_batch // num_beams at
+    a time, every beam is cut back to what sample_sequence would have returned (GreedyDecoder.reference_return) and
+    post-processed as generate_samples does.  rows: as generate_samples.  Returns one string per prompt (its best beam), or with
+    return_all=True one list per prompt of num_beams (text, score) pairs, best first (score: the sum of the fp32 log-probabilities
+    of the processed logits at the positions the model chose; see BeamDecoder)."""
+    from .decode import BeamDecoder, GreedyDecoder
+    eng = model.engine()
+    sh = eng.sh
+    length = sh.max_seq_length if length is None else length
+    keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
+    if isinstance(rows, dict):
+        stacked = {k: torch.as_tensor(np.asarray(rows[k])) for k in keys}
+    else:
+        stacked = {k: torch.as_tensor(np.stack([np.asarray(r[k]) for r in rows])) for k in keys}
+    n_prompts = stacked["topic_ids"].shape[0]
+    per = max(1, min(max_batch // num_beams, n_prompts))
+    dec = BeamDecoder(model, per, num_beams, max_len=length)
+    out = []
+    for lo in range(0, n_prompts, per):
+        hi = min(n_prompts, lo + per)
+        chunk = {k: v[lo:hi] for k, v in stacked.items()}
+        if hi - lo < per:          # the decoder's prompt count is fixed: pad the last chunk by repeating its first prompt
+            pad = per - (hi - lo)
+            chunk = {k: torch.cat([v, v[:1].expand(pad, *v.shape[1:])], 0) for k, v in chunk.items()}
+        chunk = {k: v.to(eng.dev) for k, v in chunk.items()}
+        ids, scores = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty)
+        ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
+        for r in range(hi - lo):
+            beams = []
+            for k in range(num_beams):
+                seq = GreedyDecoder.reference_return(ids[r, k].tolist(), length, sent=sh.msl + 2)
+                beams.append((postprocess_tokens(tokenizer.convert_ids_to_tokens(seq)), float(scores[r, k])))
+            out.append(beams if return_all else beams[0][0])
+    return out

@@ -102,6 +102,10 @@ _SIGS = {
     "mmtg_decode_sample": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp], _i),
     "mmtg_decode_select": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp], _i),
     "mmtg_decode_advance": ([_vp, _vp], _i),
+    "mmtg_decode_attn_split_rows": ([_i, _vp, _i, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "mmtg_decode_attn_split_x3_rows": ([_vp, _i, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _i, _i, _vp], _i),
+    "mmtg_decode_beam_candidates": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp], _i),
+    "mmtg_decode_beam_merge": ([_vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
     "mmtg_decode_mlp_sync_words": ([], _i),
     "mmtg_decode_mlp_census": ([_vp, _vp], _i),
@@ -778,7 +782,13 @@ def ln_fold_weights_x3(W, gamma, beta, bias, Wf, colsum, bias_f, N, K):
                                          N, K, _stream()), "ln_fold_weights_x3")
 
 
-def decode_attn_split_x3(part, splits, bias, kcache, vcache, keep, pos, out, B, nH, dh, Tmax):
+def decode_attn_split_x3(part, splits, bias, kcache, vcache, keep, pos, out, B, nH, dh, Tmax, rows=None):
+    """rows (int32 [B, >= Tmax], beam search): the ancestry table -- the keys j < pos of row b come from cache row rows[b, j]."""
+    if rows is not None:
+        _check(lib().mmtg_decode_attn_split_x3_rows(_p(part), splits, _p(bias), _p(kcache), _p(vcache), _p(keep), keep.stride(0), _p(rows),
+                                                    rows.stride(0), _p(pos), _p(out.t), out.plane, B, nH, dh, Tmax, _stream()),
+               "decode_attn_split_x3_rows")
+        return
     _check(lib().mmtg_decode_attn_split_x3(_p(part), splits, _p(bias), _p(kcache), _p(vcache), _p(keep), keep.stride(0), _p(pos), _p(out.t),
                                            out.plane, B, nH, dh, Tmax, _stream()), "decode_attn_split_x3")
 
@@ -799,7 +809,13 @@ def decode_attn(qkv, kcache, vcache, keep, pos, out, B, nH, dh, Tmax):
                                   B, nH, dh, Tmax, _stream()), "decode_attn")
 
 
-def decode_attn_split(part, splits, bias, kcache, vcache, keep, pos, out, B, nH, dh, Tmax):
+def decode_attn_split(part, splits, bias, kcache, vcache, keep, pos, out, B, nH, dh, Tmax, rows=None):
+    """rows (int32 [B, >= Tmax], beam search): the ancestry table -- the keys j < pos of row b come from cache row rows[b, j]."""
+    if rows is not None:
+        _check(lib().mmtg_decode_attn_split_rows(dt(out), _p(part), splits, _p(bias), _p(kcache), _p(vcache), _p(keep), keep.stride(0),
+                                                 _p(rows), rows.stride(0), _p(pos), _p(out), B, nH, dh, Tmax, _stream()),
+               "decode_attn_split_rows")
+        return
     _check(lib().mmtg_decode_attn_split(dt(out), _p(part), splits, _p(bias), _p(kcache), _p(vcache), _p(keep), keep.stride(0),
                                         _p(pos), _p(out), B, nH, dh, Tmax, _stream()), "decode_attn_split")
 
@@ -813,6 +829,19 @@ def decode_sample(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, t
     _check(lib().mmtg_decode_sample(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
                                     float(rep_penalty), int(top_k), float(top_p), _p(uniforms), uniforms.stride(0), B, _p(pos_next),
                                     _stream()), "decode_sample")
+
+
+def decode_beam_candidates(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B):
+    """Per row: the nb best (log-probability, id) continuations of the processed logits (include/mmtg_hip.h)."""
+    _check(lib().mmtg_decode_beam_candidates(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                             float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B, _stream()), "decode_beam_candidates")
+
+
+def decode_beam_merge(cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next=None):
+    """Per prompt: keep the nb best candidates, reorder seq / keep / rows in place, append (include/mmtg_hip.h)."""
+    _check(lib().mmtg_decode_beam_merge(_p(cand_val), _p(cand_id), _p(scores), _p(seq), seq.stride(0), _p(keep), keep.stride(0), _p(rows),
+                                        rows.stride(0), _p(pos), P, sent, int(nb), int(n_prompts), _p(pos_next), _stream()),
+           "decode_beam_merge")
 
 
 def decode_advance(pos):
