@@ -569,6 +569,30 @@ MMTG_API int mmtg_decode_beam_merge(const float* cand_val, const int* cand_id, f
                            long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
                            int* pos_next, void* stream);
 
+/* ---- prefixed generation (GreedyDecoder / BeamDecoder with prefix=..., mmtg_amd/decode.py): the caller gives each row the first
+ * lyric ids -- the reference's sample_sequence conditioned on a longer `targets` (src/generate.py:97-145, the commented-out --prefix of
+ * src/predict.py) -- and writes them into seq before the steps.  fixed_end: int32 [B], the absolute position up to which row b's seq
+ * is host-written.  At a step with pos + 1 < fixed_end[b] the row's column pos + 1 is left alone; pos_next is written as ever.
+ * The check rides in the step's existing last launch (no extra graph node).  Each entry is its plain namesake plus fixed_end
+ * (null fails before any device call):
+ * mmtg_decode_select_fixed / mmtg_decode_sample_fixed: as mmtg_decode_select / mmtg_decode_sample (generate.py:127-142);
+ * mmtg_decode_beam_candidates_fixed: a fixed row offers no candidates;
+ * mmtg_decode_beam_merge_fixed: a prompt whose rows are fixed (one prefix per prompt: its beams share fixed_end, the merge reads
+ *   fixed_end[b0] of its first beam) keeps every beam, its scores and its tokens, and sets rows[b, pos + 1] = b.  The kernels of
+ *   the plain entries compile to the same code as before these were added.                                                   */
+MMTG_API int mmtg_decode_select_fixed(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                             int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, const int* fixed_end,
+                             void* stream);
+MMTG_API int mmtg_decode_sample_fixed(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                             int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                             const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, void* stream);
+MMTG_API int mmtg_decode_beam_candidates_fixed(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                      int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                      int B, const int* fixed_end, void* stream);
+MMTG_API int mmtg_decode_beam_merge_fixed(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
+                                 long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
+                                 int* pos_next, const int* fixed_end, void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

@@ -1074,11 +1074,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void de
                          (int)blockIdx.x, (int)blockIdx.y, (int)threadIdx.x, lds, oplanes, oplane, rows, ldrows);
 }
 
+// Prefixed generation: the selection kernels below take an optional trailing `const int* fixed_end` (the kernel templates' pack
+// Fixed: empty for the plain forms, so their parameter lists and code are what they were; one pointer for the *_fixed forms).  Row b
+// with pos + 1 < fixed_end[b] sits on a column the host has written (a prefix token): the row leaves seq[b, pos + 1] alone and
+// offers no beam candidates; the position is still published.
+template <typename... Fixed>
+__device__ __forceinline__ bool prefix_column(int b, int pos, Fixed... fixed_end) {
+    if constexpr (sizeof...(Fixed) == 0) return false;
+    else return pos + 1 < (fixed_end[b], ...);
+}
+
 // logits processor + arg-max + forced-token cadence + append (generate.py:117-142), device-driven.
+template <typename... Fixed>
 __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restrict__ logits, long ldl, int V,
         long long* __restrict__ seq, long ldseq, const int* __restrict__ pos_ptr, int P, int sent,
         float temperature, float rep_penalty, int have_logits, int top_k, float top_p,
-        const float* __restrict__ uniforms, long ldu, int* __restrict__ pos_next) {
+        const float* __restrict__ uniforms, long ldu, int* __restrict__ pos_next, Fixed... fixed_end) {
     extern __shared__ unsigned cnt[];
     __shared__ float sval[4];
     __shared__ int sidx[4];
@@ -1086,6 +1097,7 @@ __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restr
     // the step's last kernel also publishes the next position -- into the OTHER slot of the decoder's position pair (every
     // kernel of this step reads *pos_ptr; nobody reads *pos_next before the next step), which replaces a one-thread launch
     if (pos_next && b == 0 && tid == 0) *pos_next = pos + 1;
+    if (prefix_column(b, pos, fixed_end...)) return;
     const int j = pos + 1 - P;                 // lyric index of the token to append
     if (j < 1) return;                         // still inside the prompt / the initial [#START#]
     long long* gen = seq + (long)b * ldseq + P;
@@ -1136,9 +1148,10 @@ constexpr int BEAM_TW = 64;        // columns of seq / keep / rows staged per pa
 
 __device__ __forceinline__ bool beam_forced(int j, int sent) { return j > 1 && ((j + 1) % sent == 0 || (j + 1) % sent == 1); }
 
+template <typename... Fixed>
 __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __restrict__ logits, long ldl, int V,
         const long long* __restrict__ seq, long ldseq, const int* __restrict__ pos_ptr, int P, int sent,
-        float temperature, float rep_penalty, int nb, float* __restrict__ cand_val, int* __restrict__ cand_id) {
+        float temperature, float rep_penalty, int nb, float* __restrict__ cand_val, int* __restrict__ cand_id, Fixed... fixed_end) {
     extern __shared__ unsigned cnt[];          // (V + 1) / 2 count words | V processed logits
     float* const px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
     __shared__ float sval[4], sx[BEAM_MAX];
@@ -1146,6 +1159,7 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __res
     const int b = blockIdx.x, tid = threadIdx.x, pos = *pos_ptr;
     const int j = pos + 1 - P;
     if (j < 1 || beam_forced(j, sent)) return;             // the merge appends the forced token without candidates
+    if (prefix_column(b, pos, fixed_end...)) return;       // a prefix column: nothing to offer (the merge keeps the prompt)
     float* const cv = cand_val + (long)b * nb;
     int* const ci = cand_id + (long)b * nb;
     const long long* gen = seq + (long)b * ldseq + P;
@@ -1213,9 +1227,11 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __res
     }
 }
 
+template <typename... Fixed>
 __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_id,
         float* __restrict__ scores, long long* __restrict__ seq, long ldseq, int* __restrict__ keep, long ldkeep,
-        int* __restrict__ rows, long ldrows, const int* __restrict__ pos_ptr, int P, int sent, int nb, int* __restrict__ pos_next) {
+        int* __restrict__ rows, long ldrows, const int* __restrict__ pos_ptr, int P, int sent, int nb, int* __restrict__ pos_next,
+        Fixed... fixed_end) {
     __shared__ float sc[BEAM_MAX * BEAM_MAX];
     __shared__ float s_sc[BEAM_MAX];
     __shared__ int s_par[BEAM_MAX], s_tok[BEAM_MAX];
@@ -1225,6 +1241,10 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
     if (pos_next && g == 0 && tid == 0) *pos_next = pos + 1;
     const int j = pos + 1 - P;
     const bool next_ok = pos + 1 < ldrows;
+    if (prefix_column(b0, pos, fixed_end...)) {             // the prompt's prefix column (one prefix per prompt): keep every beam,
+        if (tid < nb && next_ok) rows[(long)(b0 + tid) * ldrows + pos + 1] = b0 + tid;       // its score and its host-written token
+        return;
+    }
     if (j < 1 || beam_forced(j, sent) || !cand_val) {      // identity: the forced token (if any), every beam keeps its own row
         if (tid < nb) {
             const long b = b0 + tid;
@@ -1386,81 +1406,131 @@ extern "C" int mmtg_decode_attn_split_rows(int dtype, const float* part, int spl
     return MMTG_OK;
 }
 
-extern "C" int mmtg_decode_beam_candidates(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
-                                           int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
-                                           int B, void* stream) {
-    MMTG_REQUIRE(nb >= 1 && nb <= BEAM_MAX, "decode_beam_candidates: %d beams per prompt (1..%d)", nb, BEAM_MAX);
+// (the launches of the plain and the *_fixed selection entries: `fe` is empty for the plain ones, the prefix ends for the others)
+template <typename... Fixed>
+static int beam_candidates_launch(const char* what, const float* logits, long ldl, int V, const long long* seq, long ldseq,
+                                  const int* pos_ptr, int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val,
+                                  int* cand_id, int B, void* stream, Fixed... fe) {
+    MMTG_REQUIRE(nb >= 1 && nb <= BEAM_MAX, "%s: %d beams per prompt (1..%d)", what, nb, BEAM_MAX);
     MMTG_REQUIRE(logits && seq && pos_ptr && cand_val && cand_id && B > 0 && sent > 1 && V > 0 && ldl >= V,
-                 "decode_beam_candidates: bad args");
-    MMTG_REQUIRE(temperature > 0.f && rep_penalty > 0.f, "decode_beam_candidates: temperature / penalty must be > 0");
-    MMTG_REQUIRE(V <= 24000, "decode_beam_candidates: vocabulary of %d exceeds the LDS row image (24000)", V);
+                 "%s: bad args", what);
+    MMTG_REQUIRE(temperature > 0.f && rep_penalty > 0.f, "%s: temperature / penalty must be > 0", what);
+    MMTG_REQUIRE(V <= 24000, "%s: vocabulary of %d exceeds the LDS row image (24000)", what, V);
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(MMTG_PROF_DECODE, s, 4.0 * B * V, 4.0 * B * V);
     const size_t shm = (size_t)((V + 1) / 2) * 4 + (size_t)V * 4;
     static bool attr_done = false;
     if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)beam_candidates_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
-            MMTG_FAIL(MMTG_ERR_HIP, "decode_beam_candidates: cannot raise dynamic LDS");
+        if (hipFuncSetAttribute((const void*)beam_candidates_kernel<Fixed...>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
+            MMTG_FAIL(MMTG_ERR_HIP, "%s: cannot raise dynamic LDS", what);
         attr_done = true;
     }
-    hipLaunchKernelGGL(beam_candidates_kernel, dim3(B), dim3(256), shm, s, logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature,
-                       rep_penalty, nb, cand_val, cand_id);
-    MMTG_LAUNCH_CHECK("decode_beam_candidates");
+    hipLaunchKernelGGL(beam_candidates_kernel<Fixed...>, dim3(B), dim3(256), shm, s, logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature,
+                       rep_penalty, nb, cand_val, cand_id, fe...);
+    MMTG_LAUNCH_CHECK(what);
     return MMTG_OK;
+}
+
+template <typename... Fixed>
+static int beam_merge_launch(const char* what, const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
+                             long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
+                             int* pos_next, void* stream, Fixed... fe) {
+    MMTG_REQUIRE(nb >= 1 && nb <= BEAM_MAX, "%s: %d beams per prompt (1..%d)", what, nb, BEAM_MAX);
+    MMTG_REQUIRE(scores && seq && keep && rows && pos_ptr && n_prompts > 0 && sent > 1 && ldrows > 0 && (!cand_val || cand_id),
+                 "%s: bad args", what);
+    MMTG_REQUIRE(pos_next != pos_ptr, "%s: pos_next must not alias pos_ptr", what);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, (double)n_prompts * nb * nb, 32.0 * n_prompts * nb * (double)ldrows);
+    hipLaunchKernelGGL(beam_merge_kernel<Fixed...>, dim3(n_prompts), dim3(256), 0, s, cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows,
+                       ldrows, pos_ptr, P, sent, nb, pos_next, fe...);
+    MMTG_LAUNCH_CHECK(what);
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_beam_candidates(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                           int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                           int B, void* stream) {
+    return beam_candidates_launch("decode_beam_candidates", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, nb,
+                                  cand_val, cand_id, B, stream);
+}
+
+extern "C" int mmtg_decode_beam_candidates_fixed(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                                 int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                                 int B, const int* fixed_end, void* stream) {
+    MMTG_REQUIRE(fixed_end, "decode_beam_candidates_fixed: null fixed_end");
+    return beam_candidates_launch("decode_beam_candidates_fixed", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
+                                  nb, cand_val, cand_id, B, stream, fixed_end);
 }
 
 extern "C" int mmtg_decode_beam_merge(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
                                       long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
                                       int* pos_next, void* stream) {
-    MMTG_REQUIRE(nb >= 1 && nb <= BEAM_MAX, "decode_beam_merge: %d beams per prompt (1..%d)", nb, BEAM_MAX);
-    MMTG_REQUIRE(scores && seq && keep && rows && pos_ptr && n_prompts > 0 && sent > 1 && ldrows > 0 && (!cand_val || cand_id),
-                 "decode_beam_merge: bad args");
-    MMTG_REQUIRE(pos_next != pos_ptr, "decode_beam_merge: pos_next must not alias pos_ptr");
+    return beam_merge_launch("decode_beam_merge", cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows, ldrows, pos_ptr, P, sent, nb,
+                             n_prompts, pos_next, stream);
+}
+
+extern "C" int mmtg_decode_beam_merge_fixed(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
+                                            long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
+                                            int* pos_next, const int* fixed_end, void* stream) {
+    MMTG_REQUIRE(fixed_end, "decode_beam_merge_fixed: null fixed_end");
+    return beam_merge_launch("decode_beam_merge_fixed", cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows, ldrows, pos_ptr, P, sent,
+                             nb, n_prompts, pos_next, stream, fixed_end);
+}
+
+template <typename... Fixed>
+static int decode_select_launch(const char* what, const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                                const float* uniforms, long ldu, int B, int* pos_next, void* stream, Fixed... fe) {
+    MMTG_REQUIRE(seq && pos_ptr && B > 0 && sent > 1, "%s: bad args", what);
+    MMTG_REQUIRE(pos_next != pos_ptr, "%s: pos_next must not alias pos_ptr (blocks read the position while block 0 writes the next)", what);
+    MMTG_REQUIRE(!logits || (V > 0 && ldl >= V && temperature > 0.f && rep_penalty > 0.f), "%s: bad logits args", what);
     hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(MMTG_PROF_DECODE, s, (double)n_prompts * nb * nb, 32.0 * n_prompts * nb * (double)ldrows);
-    hipLaunchKernelGGL(beam_merge_kernel, dim3(n_prompts), dim3(256), 0, s, cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows, ldrows,
-                       pos_ptr, P, sent, nb, pos_next);
-    MMTG_LAUNCH_CHECK("decode_beam_merge");
+    ProfScope prof(MMTG_PROF_DECODE, s, 4.0 * B * V, 4.0 * B * V);
+    MMTG_REQUIRE(!logits || V <= (uniforms ? 24000 : 30000), "%s: vocabulary of %d exceeds the LDS tables", what, V);
+    size_t shm = logits ? (size_t)((V + 1) / 2) * 4 : 0;
+    if (logits && uniforms) shm += (size_t)V * 4;
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute((const void*)decode_select_kernel<Fixed...>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
+            MMTG_FAIL(MMTG_ERR_HIP, "%s: cannot raise dynamic LDS", what);
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(decode_select_kernel<Fixed...>, dim3(B), dim3(256), shm, s, logits, ldl, V, seq, ldseq,
+                       pos_ptr, P, sent, temperature, rep_penalty, logits != nullptr, top_k, top_p, logits ? uniforms : nullptr, ldu, pos_next, fe...);
+    MMTG_LAUNCH_CHECK(what);
     return MMTG_OK;
 }
 
-static int decode_select_launch(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
-                                int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
-                                const float* uniforms, long ldu, int B, int* pos_next, void* stream);
-
 extern "C" int mmtg_decode_select(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
                                   int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, void* stream) {
-    return decode_select_launch(logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, 1, 0.f, nullptr, 0, B, pos_next, stream);
+    return decode_select_launch("decode_select", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, 1, 0.f, nullptr, 0, B,
+                                pos_next, stream);
 }
 
 extern "C" int mmtg_decode_sample(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
                                   int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
                                   const float* uniforms, long ldu, int B, int* pos_next, void* stream) {
     MMTG_REQUIRE(uniforms && ldu >= B && top_k >= 0 && top_p >= 0.f, "decode_sample: uniforms [positions, ldu >= B], top_k >= 0, top_p >= 0");
-    return decode_select_launch(logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, ldu, B, pos_next, stream);
+    return decode_select_launch("decode_select", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p, uniforms,
+                                ldu, B, pos_next, stream);
 }
 
-static int decode_select_launch(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
-                                int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
-                                const float* uniforms, long ldu, int B, int* pos_next, void* stream) {
-    MMTG_REQUIRE(seq && pos_ptr && B > 0 && sent > 1, "decode_select: bad args");
-    MMTG_REQUIRE(pos_next != pos_ptr, "decode_select: pos_next must not alias pos_ptr (blocks read the position while block 0 writes the next)");
-    MMTG_REQUIRE(!logits || (V > 0 && ldl >= V && temperature > 0.f && rep_penalty > 0.f), "decode_select: bad logits args");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(MMTG_PROF_DECODE, s, 4.0 * B * V, 4.0 * B * V);
-    MMTG_REQUIRE(!logits || V <= (uniforms ? 24000 : 30000), "decode_select: vocabulary of %d exceeds the LDS tables", V);
-    size_t shm = logits ? (size_t)((V + 1) / 2) * 4 : 0;
-    if (logits && uniforms) shm += (size_t)V * 4;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)decode_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
-            MMTG_FAIL(MMTG_ERR_HIP, "decode_select: cannot raise dynamic LDS");
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(decode_select_kernel, dim3(B), dim3(256), shm, s, logits, ldl, V, seq, ldseq,
-                       pos_ptr, P, sent, temperature, rep_penalty, logits != nullptr, top_k, top_p, logits ? uniforms : nullptr, ldu, pos_next);
-    MMTG_LAUNCH_CHECK("decode_select");
-    return MMTG_OK;
+extern "C" int mmtg_decode_select_fixed(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                        int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, const int* fixed_end,
+                                        void* stream) {
+    MMTG_REQUIRE(fixed_end, "decode_select_fixed: null fixed_end");
+    return decode_select_launch("decode_select_fixed", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, 1, 0.f, nullptr,
+                                0, B, pos_next, stream, fixed_end);
+}
+
+extern "C" int mmtg_decode_sample_fixed(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                        int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                                        const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, void* stream) {
+    MMTG_REQUIRE(fixed_end, "decode_sample_fixed: null fixed_end");
+    MMTG_REQUIRE(uniforms && ldu >= B && top_k >= 0 && top_p >= 0.f,
+                 "decode_sample_fixed: uniforms [positions, ldu >= B], top_k >= 0, top_p >= 0");
+    return decode_select_launch("decode_select_fixed", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p,
+                                uniforms, ldu, B, pos_next, stream, fixed_end);
 }
 
 extern "C" int mmtg_decode_advance(int* pos_ptr, void* stream) {

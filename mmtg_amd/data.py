@@ -38,6 +38,38 @@ def _steps_of(record):
     return n
 
 
+def _line_words(tok, msl, sent):
+    """One lyric line's words: whitespace stripped, tokenized, cut at max_sent_length (MyDataset.py:92-95)."""
+    for ch in _STRIP:
+        sent = sent.replace(ch, "")
+    return tok.tokenize(sent)[:msl]
+
+
+def _lyric_slots(tok, msl, lyrics):
+    """The lyric layout of MyDataset.convert_lyrics2ids without the closing [SEP]: per line [#START#] words PAD.. [#EOS#] in a
+    fixed slot of msl + 2 tokens, with the attention mask and type ids."""
+    tokens, mask, types = [], [], []
+    for s, sent in enumerate(lyrics):
+        words = _line_words(tok, msl, sent)
+        pair = s // 2
+        tid = 1 if pair == 4 else pair + 1
+        n, pad = len(words), msl - len(words)
+        tokens += [START_TOKEN] + words + [tok.pad_token] * pad + [EOS_TOKEN]
+        mask += [1] + [1] * n + [0] * pad + [1]
+        types += [0] + [tid] * n + [0] * pad + [0]
+    return tokens, mask, types
+
+
+def encode_prefix(tokenizer, lines, partial=None, max_sent_length=20):
+    """The opening lyric ids of a prefixed generation (decode.check_prefix): the whole `lines` laid out exactly as MyDataset lays out
+    `targets` (each in its slot of max_sent_length + 2), the next line's [#START#], then the optional `partial` line's words
+    (stripped, tokenized, cut at max_sent_length, unpadded).  A list of ids starting with [#START#]."""
+    tokens = _lyric_slots(tokenizer, max_sent_length, list(lines))[0] + [START_TOKEN]
+    if partial is not None:
+        tokens += _line_words(tokenizer, max_sent_length, partial)
+    return list(tokenizer.convert_tokens_to_ids(tokens))
+
+
 class MyDataset(torch.utils.data.Dataset):
     """Same contract as src/MyDataset.py: ``MyDataset(file_path, tokenizer, data_config, if_train=True)``;
     ``file_path`` is the reference's pickle (a list of dicts) or an already loaded list."""
@@ -68,18 +100,8 @@ class MyDataset(torch.utils.data.Dataset):
     # ---- lyrics: per sentence [#START#] w_1..w_n PAD.. [#EOS#] in a fixed slot of max_sent_length + 2,
     #      sentence pair k carries type k+1 (the fifth pair type 1 again, MyDataset.py:99-102), [SEP] closes
     def convert_lyrics2ids(self, lyrics):
-        tok, msl = self._tokenizer, self._max_sent_length
-        tokens, mask, types = [], [], []
-        for s, sent in enumerate(lyrics):
-            for ch in _STRIP:
-                sent = sent.replace(ch, "")
-            words = tok.tokenize(sent)[:msl]
-            pair = s // 2
-            tid = 1 if pair == 4 else pair + 1
-            n, pad = len(words), msl - len(words)
-            tokens += [START_TOKEN] + words + [tok.pad_token] * pad + [EOS_TOKEN]
-            mask += [1] + [1] * n + [0] * pad + [1]
-            types += [0] + [tid] * n + [0] * pad + [0]
+        tok = self._tokenizer
+        tokens, mask, types = _lyric_slots(tok, self._max_sent_length, lyrics)
         tokens.append(tok.sep_token)
         mask.append(1)
         types.append(0)

@@ -23,6 +23,45 @@ from . import hip
 
 _PLACEMENT = {}
 
+BANNED = (1, 2, 100, 102)           # never a content id: [#START#] [#EOS#] [UNK] [SEP] (src/generate.py:135)
+
+
+def check_prefix(prefix, rows, length, sent=22, V=None):
+    """Validate a prefixed generation's opening lyric ids on the host, before any device work; returns one list of ids per row.
+
+    prefix: a [rows, Lmax] integer tensor / array padded with -1, or a list of `rows` id lists.  Row b's prefix p (L >= 1 ids) is
+    lyric columns 0 .. L - 1 in the slot layout of the training data (data.MyDataset): column c holds [#START#] (1) where
+    c % sent == 0, [#EOS#] (2) where c % sent == sent - 1, and a content id or PAD (0) elsewhere -- never one of the banned ids
+    1, 2, 100, 102.  So p is whole lines (L % sent == 1: it ends on the next line's [#START#]) or whole lines plus a partial line.
+    L <= length + 1: the output has 1 + length columns."""
+    if isinstance(prefix, (list, tuple)):
+        ids = [[int(v) for v in np.asarray(r).reshape(-1).tolist()] for r in prefix]
+    else:
+        a = prefix.detach().cpu().numpy() if torch.is_tensor(prefix) else np.asarray(prefix)
+        if a.ndim != 2:
+            raise ValueError("prefix must be a [rows, Lmax] array padded with -1 or a list of id lists (got shape %s)" % (a.shape,))
+        ids = []
+        for r in a.tolist():
+            n = r.index(-1) if -1 in r else len(r)
+            if any(v != -1 for v in r[n:]):
+                raise ValueError("prefix row %d: ids after the -1 padding" % len(ids))
+            ids.append([int(v) for v in r[:n]])
+    if len(ids) != rows:
+        raise ValueError("prefix has %d rows, the generation %d" % (len(ids), rows))
+    for b, p in enumerate(ids):
+        if not p:
+            raise ValueError("prefix row %d is empty (it starts with [#START#])" % b)
+        if len(p) > length + 1:
+            raise ValueError("prefix row %d has %d ids, more than length + 1 = %d" % (b, len(p), length + 1))
+        for c, v in enumerate(p):
+            if c % sent == 0 and v != 1:
+                raise ValueError("prefix row %d, column %d: [#START#] (1) expected, got %d" % (b, c, v))
+            if c % sent == sent - 1 and v != 2:
+                raise ValueError("prefix row %d, column %d: [#EOS#] (2) expected, got %d" % (b, c, v))
+            if 0 < c % sent < sent - 1 and (v in BANNED or v < 0 or (V is not None and v >= V)):
+                raise ValueError("prefix row %d, column %d: id %d is not a content id or PAD" % (b, c, v))
+    return ids
+
 
 def _placement_ok(dev):
     """True when a 256-workgroup, one-per-CU launch puts workgroups b and b + 8 k on one XCD, 32 per XCD (census kernel, once per
@@ -70,6 +109,8 @@ class GreedyDecoder:
             # the position lives in a PAIR of slots per lane: the kernels of step k read slot k % 2, the step's last kernel
             # (decode_select) writes k + 1 into the other one -- no separate "advance" launch, two captured graphs per setting
             self.pos_all = torch.zeros(2, lanes, dtype=torch.int32, device=dev)
+            # prefixed generation: row b's seq is host-written up to position fixed_end[b] (the *_fixed selection entries)
+            self.fixed_end = torch.zeros(B, dtype=torch.int32, device=dev)
             self.keep = torch.zeros(B, self.Tmax, dtype=torch.int32, device=dev)
             self.types = torch.zeros(B, dtype=torch.long, device=dev)
             self.tpw_type = torch.zeros(B, sh.P, dtype=torch.long, device=dev)
@@ -81,6 +122,7 @@ class GreedyDecoder:
         else:       # a lane: row block [_lane*B, (_lane+1)*B) of the parent's state, private scratch
             lo, hi = _lane * B, (_lane + 1) * B
             self.seq, self.keep, self.types = _parent.seq[lo:hi], _parent.keep[lo:hi], _parent.types[lo:hi]
+            self.fixed_end = _parent.fixed_end[lo:hi]
             self.tpw_type, self.tpw_mask = _parent.tpw_type[lo:hi], _parent.tpw_mask[lo:hi]
             self.c = _parent.c[lo * sh.S:hi * sh.S]
             self.kc = [_parent.kc[l, lo:hi] for l in range(sh.L)]
@@ -182,6 +224,8 @@ class GreedyDecoder:
         self.graphs = {}
         self.params = None
         self.rows = None            # the ancestry table of beam search (BeamDecoder); None: row b attends over its own cache row
+        self.use_fixed = False      # this generation has a prefix: the step ends in the *_fixed selection entries
+        self.min_fixed = 0          # min over rows of fixed_end (a step below it appends nothing: no head needed)
 
     def _conv1d(self, x, wkey, out, **kw):
         # bf16: Engine._fwd routes Conv1D weights through their [out,in] copies (NT layout), which is
@@ -245,6 +289,9 @@ class GreedyDecoder:
         eng, sh, B = self.eng, self.eng.sh, self.B
         temperature, rep, top_k, top_p = self.params
         sent = sh.msl + 2
+        if self.use_fixed:
+            self._select_fixed(with_head)
+            return
         if with_head:
             Vp = eng.layout.Vpad
             if top_k == 1 and top_p == 0.0:
@@ -255,6 +302,23 @@ class GreedyDecoder:
                                   top_k, top_p, self.uniforms, B, pos_next=self.pos_next)
         else:
             hip.decode_select(None, 0, 0, self.seq, self.pos, sh.P, sent, temperature, rep, B, pos_next=self.pos_next)
+
+    def _select_fixed(self, with_head):
+        """_select of a prefixed generation: the same launch through the *_fixed entries, which leave row b's column pos + 1 alone
+        while pos + 1 < fixed_end[b] (the host wrote it)."""
+        eng, sh, B = self.eng, self.eng.sh, self.B
+        temperature, rep, top_k, top_p = self.params
+        sent = sh.msl + 2
+        if with_head:
+            Vp = eng.layout.Vpad
+            if top_k == 1 and top_p == 0.0:
+                hip.decode_select_fixed(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep, B,
+                                        self.fixed_end, pos_next=self.pos_next)
+            else:
+                hip.decode_sample_fixed(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep,
+                                        top_k, top_p, self.uniforms, B, self.fixed_end, pos_next=self.pos_next)
+        else:
+            hip.decode_select_fixed(None, 0, 0, self.seq, self.pos, sh.P, sent, temperature, rep, B, self.fixed_end, pos_next=self.pos_next)
 
     def _step_x3(self, with_head):
         """The split-precision token step: embedding -> projector -> 12 blocks -> head, every product through mmtg_decode_gemm_x3
@@ -441,7 +505,7 @@ class GreedyDecoder:
         if not self.use_graph:
             self._step(with_head, parity)
             return
-        key = (with_head, parity, self.params)
+        key = (with_head, parity, self.params) + (("prefix",) if self.use_fixed else ())
         g = self.graphs.get(key)
         if g is None:
             # warm-up outside capture (lazy LDS-attribute / module loading), then rewind the position
@@ -484,17 +548,23 @@ class GreedyDecoder:
                 if self.fast else "decode token step: training-side kernels per layer")
 
     @torch.no_grad()
-    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None):
+    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None):
         """Everything of a generation that happens once: the settings, the uniforms of a stochastic run, fresh weight copies /
         LayerNorm folds, the experience encoder, the prompt (prefilled in one batched pass: ``first_pos`` = P afterwards) and the
         reset position.  Returns the end position n; ``step_at(pos)`` for pos = first_pos .. n - 1 then runs the token steps (``generate`` does both; tools/decode_lanes_threads.py drives
-        several decoders' steps from their own threads and streams)."""
+        several decoders' steps from their own threads and streams).
+
+        prefix (optional; check_prefix states the rules): row b's first L_b lyric ids, written into seq[b, P:P + L_b] with
+        fixed_end[b] = P + L_b -- the steps leave those columns alone.  The prefill then covers [prompt, p[:, :Lmin]] (Lmin = min_b
+        L_b, first_pos = P + Lmin - 1); longer prefixes go through token steps held by fixed_end.  prefix=None runs exactly the
+        launches and graphs of an unprefixed generation."""
         eng, sh = self.eng, self.eng.sh
         B = batch["img_embs"].shape[0]
         if B != self.B:
             raise ValueError("decoder was built for batch %d, got %d" % (self.B, B))
         if length > self.max_len:
             raise ValueError("length %d exceeds max_len %d" % (length, self.max_len))
+        pre = None if prefix is None else check_prefix(prefix, B, length, sent=sh.msl + 2, V=sh.V)
         self.params = (float(temperature), float(repitition_penalty), int(top_k), float(top_p))
         if not (int(top_k) == 1 and float(top_p) == 0.0):
             if self.uniforms is None:
@@ -516,30 +586,47 @@ class GreedyDecoder:
         self.seq.zero_()
         self.seq[:, :sh.P] = batch["topic_ids"].to(eng.dev).long()
         self.seq[:, sh.P] = 1                                   # [#START#]
+        lmin = 1
+        for d in [self] + self.children:            # (a lane's _select reads its own flag and its slice of fixed_end)
+            d.use_fixed = pre is not None
+        self.min_fixed = 0
+        if pre is not None:
+            lens = [len(p) for p in pre]
+            lmin = min(lens)
+            host = torch.zeros(B, max(lens), dtype=torch.long)
+            for b, p in enumerate(pre):
+                host[b, :len(p)] = torch.tensor(p, dtype=torch.long)
+            self.seq[:, sh.P:sh.P + host.shape[1]] = host.to(eng.dev)
+            self.fixed_end.copy_(torch.tensor(lens, dtype=torch.int32) + sh.P)
+            self.min_fixed = sh.P + lmin
         self.tpw_type.copy_(batch["tpw_type_ids"].to(eng.dev).long())
         self.tpw_mask.copy_(batch["tpw_attention_mask"].to(eng.dev).long())
         self.keep.zero_()
         self.pos_all.zero_()
         self.first_pos = 0
         if self.prefill and sh.P > 0:
-            self._prefill(batch)
+            self._prefill(batch, lmin)
         else:
             a = eng.forward(batch, train_flag=False, training=False, encode_only=True)
             self.c.copy_(a["c"])
         return sh.P + length                                    # positions first_pos .. P+length-1 are consumed by token steps
 
-    def _prefill(self, batch):
+    def _prefill(self, batch, lmin=1):
         """The P prompt positions in ONE batched pass instead of P token steps (a token step costs the same whatever it appends; the
         reference has no such distinction -- its every call re-runs the whole prefix, generate.py:124).  The engine's inference-branch
         forward (model.py:290-326) over [prompt, [#START#]] computes every block's K / V rows for all prompt positions at once
         (B x (P + 1) rows through the training-side kernels of the compute mode, nothing of the last block beyond its c_attn; causal,
         so the rows of the P prompt positions do not depend on the extra one -- the conditioning kernel wants at least one lyric
         position); they go into the caches, the key mask of the prompt is the prompt's attention mask, and the token
-        steps start at position P."""
+        steps start at position P.
+        With a prefix the pass runs over [prompt, p[:, :lmin]] (the prefix every row has): the caches take the first P + lmin - 1
+        positions, a lyric position's key mask is tok != 0 (the inference-branch rule of decode_embed) and the steps start at
+        P + lmin - 1."""
         eng, sh = self.eng, self.eng.sh
         P = sh.P
+        n = P + lmin - 1                                        # positions whose K / V the pass provides
         pb = dict(batch)
-        pb["targets"] = self.seq[:, P:P + 1]
+        pb["targets"] = self.seq[:, P:P + lmin]
         a = eng.forward(pb, train_flag=False, training=False, per_row_infer=True, need_logits=False)
         self.c.copy_(a["c"])
         B, T, nH = a["B"], a["T"], sh.nH
@@ -547,28 +634,32 @@ class GreedyDecoder:
             qkv = rec[4]
             if isinstance(qkv, hip.Planes):        # bf16x3: c_attn writes a (hi | lo) plane pair [2, M, 3D]; the cache holds fp32 rows
                 hi, lo = qkv.t[0].view(B, T, 3, nH, 64), qkv.t[1].view(B, T, 3, nH, 64)
-                kv = hi[:, :P, 1:3].float() + lo[:, :P, 1:3].float()           # [B, P, 2, nH, 64]: only what the cache takes
+                kv = hi[:, :n, 1:3].float() + lo[:, :n, 1:3].float()           # [B, n, 2, nH, 64]: only what the cache takes
                 k, v = kv[:, :, 0], kv[:, :, 1]
             else:
                 qkv = qkv.view(B, T, 3, nH, 64)
-                k, v = qkv[:, :P, 1], qkv[:, :P, 2]
-            self.kc[l][:, :, :P].copy_(k.permute(0, 2, 1, 3))
-            self.vc[l][:, :, :P].copy_(v.permute(0, 2, 1, 3))
+                k, v = qkv[:, :n, 1], qkv[:, :n, 2]
+            self.kc[l][:, :, :n].copy_(k.permute(0, 2, 1, 3))
+            self.vc[l][:, :, :n].copy_(v.permute(0, 2, 1, 3))
         self.keep[:, :P] = (self.tpw_mask != 0).to(torch.int32)
-        self.pos_all.fill_(P)
-        self.first_pos = P
+        if n > P:
+            self.keep[:, P:n] = (self.seq[:, P:n] != 0).to(torch.int32)
+        self.pos_all.fill_(n)
+        self.first_pos = n
 
     def step_at(self, pos):
         """Token step `pos` of the generation ``begin`` prepared; returns whether the step called the model's head."""
         sh = self.eng.sh
         j = pos + 1 - sh.P                                      # lyric index appended after this step
         forced = j < 1 or (j > 1 and (j + 1) % (sh.msl + 2) in (0, 1))
+        if self.use_fixed and pos + 1 < self.min_fixed:
+            forced = True                                       # every row's column pos + 1 is a prefix id: no model call
         self._run_step(with_head=not forced, parity=pos & 1)
         return not forced
 
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None,
-                 use_graph=None, teacher=None, tap=None):
+                 use_graph=None, teacher=None, tap=None, prefix=None):
         """batch: dict with topic_ids/tpw_* [B,P], topic_emb, img_embs, r_embs (no targets needed).
         Runs `length` iterations of the reference loop and returns the lyric ids
         [B, 1 + length] (column 0 is the initial [#START#]).  top_k = 1, top_p = 0 is the greedy setting;
@@ -576,8 +667,10 @@ class GreedyDecoder:
         from `generator` (a CUDA torch.Generator; default: the global one) before the steps are replayed.
         Parity hooks (tests/test_decode_gpu.py): `teacher` [B, 1 + length] long -- after every step the token the step
         appended is replaced by teacher[:, j] wherever that is >= 0 (teacher forcing on a reference id list; the step's own
-        pick is handed to `tap` first); `tap(j, with_head, picked [B], logits [B, Vpad] or None)` is called after every step."""
-        n_steps = self.begin(batch, length, temperature, repitition_penalty, top_k, top_p, generator)
+        pick is handed to `tap` first); `tap(j, with_head, picked [B], logits [B, Vpad] or None)` is called after every step.
+        prefix: the opening lyric ids of every row (``begin``, ``check_prefix``); columns 0 .. L_b - 1 of row b's result are its
+        prefix, the rest follows the rules above (the penalty counts the prefix)."""
+        n_steps = self.begin(batch, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix)
         eng, sh = self.eng, self.eng.sh
         saved_mode = self.use_graph
         if use_graph is not None:
@@ -653,6 +746,14 @@ class BeamDecoder(GreedyDecoder):
         eng, sh, B = self.eng, self.eng.sh, self.B
         temperature, rep, _, _ = self.params
         sent = sh.msl + 2
+        if self.use_fixed:
+            if with_head:
+                hip.decode_beam_candidates_fixed(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature,
+                                                 rep, self.nb, self.cand_val, self.cand_id, B, self.fixed_end)
+            hip.decode_beam_merge_fixed(self.cand_val if with_head else None, self.cand_id if with_head else None, self.scores, self.seq,
+                                        self.keep, self.rows, self.pos, sh.P, sent, self.nb, self.n_prompts, self.fixed_end,
+                                        pos_next=self.pos_next)
+            return
         if with_head:
             hip.decode_beam_candidates(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep,
                                        self.nb, self.cand_val, self.cand_id, B)
@@ -666,14 +767,18 @@ class BeamDecoder(GreedyDecoder):
         return "%d beams per prompt, " % self.nb + super().describe()
 
     @torch.no_grad()
-    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None):
-        """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs and prompt prefill), the ancestry table as
-        the identity and the beam scores at [0, -inf, ...] per prompt."""
+    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None):
+        """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill and the prefix: one per
+        prompt), the ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at
+        the free positions after a prompt's prefix."""
         n = batch["img_embs"].shape[0]
         if n != self.n_prompts:
             raise ValueError("decoder was built for %d prompts, got %d" % (self.n_prompts, n))
+        if prefix is not None:
+            sh = self.eng.sh
+            prefix = [p for p in check_prefix(prefix, n, length, sent=sh.msl + 2, V=sh.V) for _ in range(self.nb)]
         rep = {k: (v.repeat_interleave(self.nb, 0) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        n_steps = super().begin(rep, length, temperature, repitition_penalty, 1, 0.0)
+        n_steps = super().begin(rep, length, temperature, repitition_penalty, 1, 0.0, prefix=prefix)
         B, dev = self.B, self.eng.dev
         self.rows.copy_(torch.arange(B, dtype=torch.int32, device=dev)[:, None].expand(B, self.Tmax))
         sc = torch.full((n, self.nb), float("-inf"), dtype=torch.float32, device=dev)
@@ -682,10 +787,12 @@ class BeamDecoder(GreedyDecoder):
         return n_steps
 
     @torch.no_grad()
-    def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None):
+    def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_beams, 1 + length] in
-        GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row."""
-        ids = super().generate(batch, length, temperature=temperature, repitition_penalty=repitition_penalty, use_graph=use_graph)
+        GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row.
+        prefix: one per prompt (check_prefix), shared by its beams."""
+        ids = super().generate(batch, length, temperature=temperature, repitition_penalty=repitition_penalty, use_graph=use_graph,
+                               prefix=prefix)
         n, nb = self.n_prompts, self.nb
         ids = ids.view(n, nb, -1)
         sc = self.scores.view(n, nb).clone()

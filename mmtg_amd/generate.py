@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
+from .data import encode_prefix  # noqa: F401  (public: the opening lines of a prefixed generate_samples / generate_beams)
 
 SENT_SLOT = 22  # generate.py:118-121
 BANNED = (1, 2, 100, 102)  # [#START#] [#EOS#] [UNK] [SEP] in src/vocab/vocab.txt
@@ -144,15 +145,25 @@ def postprocess_tokens(preds):
     return text
 
 
+def _prompt_prefixes(prefixes, n_prompts, length, sh):
+    """One validated prefix (a list of lyric ids, e.g. encode_prefix's) per prompt, or None: decode.check_prefix before any device work."""
+    if prefixes is None:
+        return None
+    from .decode import check_prefix
+    return check_prefix(prefixes, n_prompts, length, sent=sh.msl + 2, V=sh.V)
+
+
 def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperature=1.1, top_k=10, top_p=0.7,
-                     repetition_penalty=1.5, max_batch=256, generator=None, decoder=None):
+                     repetition_penalty=1.5, max_batch=256, generator=None, decoder=None, prefixes=None):
     """n_samples texts per prompt (generate.sh's loop, generate.py:205-235) on the batched, graph-replayed decoder:
     every prompt is replicated over n_samples rows, rows are decoded max_batch at a time with the device-side
     top-k / top-p sampler (one uniform per row and position from `generator`), each row is cut back to what
     sample_sequence would have returned (the sequence before the last model call's append) and post-processed.
 
     rows: list of dataset items (dicts with topic_ids / tpw_* / topic_emb / img_embs / r_embs, numpy or tensors) or a dict of
-    stacked arrays.  Returns a list (one entry per prompt) of lists of n_samples strings."""
+    stacked arrays.  Returns a list (one entry per prompt) of lists of n_samples strings.
+    prefixes (optional): one list of opening lyric ids per prompt (encode_prefix, decode.check_prefix); every sample of the prompt
+    continues it, and its text includes the given lines."""
     from .decode import GreedyDecoder
     eng = model.engine()
     sh = eng.sh
@@ -163,6 +174,7 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     else:
         stacked = {k: torch.as_tensor(np.stack([np.asarray(r[k]) for r in rows])) for k in keys}
     n_prompts = stacked["topic_ids"].shape[0]
+    pre = _prompt_prefixes(prefixes, n_prompts, length, sh)
     rep = {k: v.repeat_interleave(n_samples, dim=0) for k, v in stacked.items()}
     total = n_prompts * n_samples
     bsz = min(max_batch, total)
@@ -174,9 +186,13 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
         if hi - lo < bsz:          # the decoder's batch is fixed: pad the last chunk by repeating its first row
             pad = bsz - (hi - lo)
             chunk = {k: torch.cat([v, v[:1].expand(pad, *v.shape[1:])], 0) for k, v in chunk.items()}
+        cpre = None
+        if pre is not None:
+            cpre = [pre[r // n_samples] for r in range(lo, hi)]
+            cpre += [cpre[0]] * (bsz - len(cpre))
         chunk = {k: v.to(eng.dev) for k, v in chunk.items()}
         ids = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty,
-                           top_k=top_k, top_p=top_p, generator=generator).cpu().numpy()
+                           top_k=top_k, top_p=top_p, generator=generator, prefix=cpre).cpu().numpy()
         for r in range(hi - lo):
             seq = GreedyDecoder.reference_return(ids[r].tolist(), length, sent=sh.msl + 2)
             texts.append(postprocess_tokens(tokenizer.convert_ids_to_tokens(seq)))
@@ -184,12 +200,13 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
 
 
 def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature=1.1, repetition_penalty=1.5, max_batch=256,
-                   return_all=False):
+                   return_all=False, prefixes=None):
     """Beam search per prompt on the batched, graph-replayed decoder (BeamDecoder): prompts are decoded max_batch // num_beams at
     a time, every beam is cut back to what sample_sequence would have returned (GreedyDecoder.reference_return) and
     post-processed as generate_samples does.  rows: as generate_samples.  Returns one string per prompt (its best beam), or with
     return_all=True one list per prompt of num_beams (text, score) pairs, best first (score: the sum of the fp32 log-probabilities
-    of the processed logits at the positions the model chose; see BeamDecoder)."""
+    of the processed logits at the positions the model chose; see BeamDecoder).  prefixes: as generate_samples (the prefix
+    positions add nothing to a score)."""
     from .decode import BeamDecoder, GreedyDecoder
     eng = model.engine()
     sh = eng.sh
@@ -200,6 +217,7 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
     else:
         stacked = {k: torch.as_tensor(np.stack([np.asarray(r[k]) for r in rows])) for k in keys}
     n_prompts = stacked["topic_ids"].shape[0]
+    pre = _prompt_prefixes(prefixes, n_prompts, length, sh)
     per = max(1, min(max_batch // num_beams, n_prompts))
     dec = BeamDecoder(model, per, num_beams, max_len=length)
     out = []
@@ -209,8 +227,11 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
         if hi - lo < per:          # the decoder's prompt count is fixed: pad the last chunk by repeating its first prompt
             pad = per - (hi - lo)
             chunk = {k: torch.cat([v, v[:1].expand(pad, *v.shape[1:])], 0) for k, v in chunk.items()}
+        cpre = None
+        if pre is not None:
+            cpre = pre[lo:hi] + [pre[lo]] * (per - (hi - lo))
         chunk = {k: v.to(eng.dev) for k, v in chunk.items()}
-        ids, scores = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty)
+        ids, scores = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty, prefix=cpre)
         ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
         for r in range(hi - lo):
             beams = []

@@ -106,6 +106,10 @@ _SIGS = {
     "mmtg_decode_attn_split_x3_rows": ([_vp, _i, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _i, _i, _vp], _i),
     "mmtg_decode_beam_candidates": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_beam_merge": ([_vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp], _i),
+    "mmtg_decode_select_fixed": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _vp], _i),
+    "mmtg_decode_sample_fixed": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp, _vp], _i),
+    "mmtg_decode_beam_candidates_fixed": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _vp], _i),
+    "mmtg_decode_beam_merge_fixed": ([_vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
     "mmtg_decode_mlp_sync_words": ([], _i),
     "mmtg_decode_mlp_census": ([_vp, _vp], _i),
@@ -842,6 +846,41 @@ def decode_beam_merge(cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, 
     _check(lib().mmtg_decode_beam_merge(_p(cand_val), _p(cand_id), _p(scores), _p(seq), seq.stride(0), _p(keep), keep.stride(0), _p(rows),
                                         rows.stride(0), _p(pos), P, sent, int(nb), int(n_prompts), _p(pos_next), _stream()),
            "decode_beam_merge")
+
+
+def _fixed(fixed_end, B):
+    """The int32 [>= B] prefix-end array of the *_fixed entries (None is passed on: the library rejects it)."""
+    if fixed_end is not None:
+        import torch
+        if fixed_end.dtype != torch.int32 or fixed_end.dim() != 1 or fixed_end.numel() < B or not fixed_end.is_contiguous():
+            raise ValueError("fixed_end must be a contiguous int32 vector of at least %d entries" % B)
+    return _p(fixed_end)
+
+
+def decode_select_fixed(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, fixed_end, pos_next=None):
+    """decode_select that leaves row b's column pos + 1 alone while pos + 1 < fixed_end[b] (a host-written prefix, include/mmtg_hip.h)."""
+    _check(lib().mmtg_decode_select_fixed(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                          float(rep_penalty), B, _p(pos_next), _fixed(fixed_end, B), _stream()), "decode_select_fixed")
+
+
+def decode_sample_fixed(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, fixed_end, pos_next=None):
+    _check(lib().mmtg_decode_sample_fixed(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                          float(rep_penalty), int(top_k), float(top_p), _p(uniforms), uniforms.stride(0), B, _p(pos_next),
+                                          _fixed(fixed_end, B), _stream()), "decode_sample_fixed")
+
+
+def decode_beam_candidates_fixed(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end):
+    """decode_beam_candidates; a row on a prefix column (pos + 1 < fixed_end[b]) offers nothing."""
+    _check(lib().mmtg_decode_beam_candidates_fixed(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                                   float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B, _fixed(fixed_end, B),
+                                                   _stream()), "decode_beam_candidates_fixed")
+
+
+def decode_beam_merge_fixed(cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, fixed_end, pos_next=None):
+    """decode_beam_merge; a prompt on a prefix column keeps every beam, score and token (include/mmtg_hip.h)."""
+    _check(lib().mmtg_decode_beam_merge_fixed(_p(cand_val), _p(cand_id), _p(scores), _p(seq), seq.stride(0), _p(keep), keep.stride(0),
+                                              _p(rows), rows.stride(0), _p(pos), P, sent, int(nb), int(n_prompts), _p(pos_next),
+                                              _fixed(fixed_end, n_prompts * nb), _stream()), "decode_beam_merge_fixed")
 
 
 def decode_advance(pos):
