@@ -593,6 +593,27 @@ MMTG_API int mmtg_decode_beam_merge_fixed(const float* cand_val, const int* cand
                                  long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
                                  int* pos_next, const int* fixed_end, void* stream);
 
+/* ---- n-gram blocking (GreedyDecoder / BeamDecoder with no_repeat_ngram_size=n, mmtg_amd/decode.py): a row never writes a content
+ * n-gram it already holds.  Row b about to fill a free lyric column j (not forced, not sticky PAD, not a held prefix column) has the
+ * history g[0..j-1], its own lyric columns (prefix columns included, the topic prompt not).  Content ids: all but 0, 1, 2, 100, 102
+ * (PAD, [#START#], [#EOS#], [UNK], [SEP]), so those break n-grams.  Key: g[j-n+1 .. j-1] (empty for n = 1).  If j >= n - 1 and the
+ * key is all content, every v = g[i+n-1] (0 <= i <= j-n) with g[i .. i+n-1] all content and g[i .. i+n-2] equal to the key is
+ * banned: its processed logit becomes -inf after the penalty, temperature and fixed bans, before the arg-max / the top-k, top-p
+ * filters and the draw / the beam's log_softmax and top-nb.  Everything else is as in the plain entries.  The ban set is built
+ * per row in the step's existing last launch.  Each entry is its plain namesake plus fixed_end (null: no prefix; else as the
+ * *_fixed entries) and ngram, 1 <= ngram <= sent - 2 (a longer n-gram cannot be all content); outside that range, or without
+ * logits, the entry fails before any device call.  The beam merge is unchanged: bans act in the candidates.  The kernels of the
+ * plain and *_fixed entries compile to the same code as before these were added.                                              */
+MMTG_API int mmtg_decode_select_ngram(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                             int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, const int* fixed_end,
+                             int ngram, void* stream);
+MMTG_API int mmtg_decode_sample_ngram(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                             int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                             const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, int ngram, void* stream);
+MMTG_API int mmtg_decode_beam_candidates_ngram(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                      int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                      int B, const int* fixed_end, int ngram, void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

@@ -22,11 +22,21 @@ __device__ __forceinline__ void count_ids(unsigned* cnt, int V, const long long*
     __syncthreads();
 }
 
+// the per-occurrence penalty of a logit whose id occurred c times.  NG (the n-gram forms of the selection kernels, ban_ngrams):
+// the sentinel count 0xFFFF marks a banned id, whose processed logit is -inf (it stays -inf through the temperature and the bans)
+template <bool NG>
+__device__ __forceinline__ float penalize(float x, int c, float rep_penalty) {
+    if (NG && c == 0xFFFF) return -INFINITY;
+    for (int i = 0; i < c; ++i) x = x / rep_penalty;
+    return x;
+}
+
 // one logit through the reference's processor (generate.py:127-136), folded into the running arg-max (lowest index wins ties)
+template <bool NG = false>
 __device__ __forceinline__ void scan_one(float x, int v, const unsigned* cnt, float temperature, float rep_penalty, float& best, int& besti) {
     if (v != 0 && v != 102) {
         const int c = (cnt[v >> 1] >> (16 * (v & 1))) & 0xFFFF;
-        for (int i = 0; i < c; ++i) x = x / rep_penalty;
+        x = penalize<NG>(x, c, rep_penalty);
     }
     x = x / temperature;
     if (v == 1 || v == 2 || v == 100 || v == 102) x = -INFINITY;
@@ -35,6 +45,7 @@ __device__ __forceinline__ void scan_one(float x, int v, const unsigned* cnt, fl
 // this thread's share of the processed-logit arg-max.  16-byte aligned rows are read as float4 with all of a pass's loads
 // (up to 16 per thread = 16 K logits per block) requested before the first is used: one memory round trip per row instead of a
 // dependent 4-byte load per 256 logits (round 3: 21.5 -> see profiles/ us for 256 rows of V = 13317).
+template <bool NG = false>
 __device__ __forceinline__ void scan_row(const float* row, int V, const unsigned* cnt, float temperature, float rep_penalty,
                                          int tid, float& best, int& besti) {
     best = -INFINITY;
@@ -56,13 +67,13 @@ __device__ __forceinline__ void scan_row(const float* row, int V, const unsigned
                 const int idx = base + i * 256 + tid;
                 if (idx < nvec) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) scan_one(r[i][e], 4 * idx + e, cnt, temperature, rep_penalty, best, besti);
+                    for (int e = 0; e < 4; ++e) scan_one<NG>(r[i][e], 4 * idx + e, cnt, temperature, rep_penalty, best, besti);
                 }
             }
         }
         done = nvec << 2;
     }
-    for (int v = done + tid; v < V; v += 256) scan_one(row[v], v, cnt, temperature, rep_penalty, best, besti);
+    for (int v = done + tid; v < V; v += 256) scan_one<NG>(row[v], v, cnt, temperature, rep_penalty, best, besti);
 }
 
 __global__ __launch_bounds__(256) void logits_argmax_kernel(const float* __restrict__ logits, long ldl, int V,
@@ -109,6 +120,7 @@ __device__ __forceinline__ unsigned fkey(float x) {
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
+template <bool NG = false>
 __device__ int sample_row(const float* row, int V, const unsigned* cnt, float* px, float temperature, float rep_penalty,
                           int top_k, float top_p, float u, int tid, float* filtered) {
     __shared__ unsigned hcnt[256];
@@ -121,7 +133,7 @@ __device__ int sample_row(const float* row, int V, const unsigned* cnt, float* p
         float x = row[v];
         if (v != 0 && v != 102) {
             const int c = (cnt[v >> 1] >> (16 * (v & 1))) & 0xFFFF;
-            for (int i = 0; i < c; ++i) x = x / rep_penalty;
+            x = penalize<NG>(x, c, rep_penalty);
         }
         x = x / temperature;
         if (v == 1 || v == 2 || v == 100 || v == 102) x = -INFINITY;
@@ -1084,6 +1096,44 @@ __device__ __forceinline__ bool prefix_column(int b, int pos, Fixed... fixed_end
     else return pos + 1 < (fixed_end[b], ...);
 }
 
+// n-gram blocking (the *_ngram entries, include/mmtg_hip.h): the pack is one NgramBan instead.  Its fixed_end is optional (null: no
+// prefix).  After count_ids, ban_ngrams marks every id that would complete a content n-gram the row already holds with the sentinel
+// count 0xFFFF (a banned id has occurred, so its slot is non-zero; no real count reaches 0xFFFF since MAXGEN < 65535), and the
+// processing reads the sentinel as -inf (penalize<true>) with no extra LDS read per logit.
+struct NgramBan {
+    const int* fixed_end;   // int32 [B] or null
+    int n;                  // 1 .. sent - 2
+    int hist_cap;           // ints of dynamic LDS for the staged history (>= the longest history, min(ldseq - P, MAXGEN))
+};
+
+template <typename... Fixed> constexpr bool is_ngram = (std::is_same<Fixed, NgramBan>::value || ... || false);
+template <typename... Fixed> __host__ __device__ __forceinline__ NgramBan ngram_of(Fixed... e) { return (e, ...); }
+
+__device__ __forceinline__ bool prefix_column(int b, int pos, NgramBan ng) { return ng.fixed_end && pos + 1 < ng.fixed_end[b]; }
+
+// PAD, [#START#], [#EOS#], [UNK], [SEP] are not content: they break n-grams
+__device__ __forceinline__ bool ngram_content(int v) { return v != 0 && v != 1 && v != 2 && v != 100 && v != 102; }
+
+// The ban rule for history g = gen[0..n) (the row's lyric columns before the one it fills) and n-gram size ng: with key
+// g[n-ng+1 .. n-1] (empty for ng = 1), if n >= ng - 1 and the key is all content, every v = g[i+ng-1] (0 <= i <= n-ng) with
+// g[i .. i+ng-1] all content and g[i .. i+ng-2] equal to the key is banned.  h: n ints of LDS; all threads of the block call.
+__device__ __forceinline__ void ban_ngrams(unsigned* cnt, int* h, int V, const long long* gen, int n, int ng, int tid) {
+    for (int i = tid; i < n; i += 256) h[i] = (int)gen[i];
+    __syncthreads();
+    const int k0 = n - ng + 1;                             // first key column
+    bool key_ok = k0 >= 0;
+    for (int k = k0; key_ok && k < n; ++k) key_ok = ngram_content(h[k]);
+    if (key_ok) {
+        for (int i = tid; i <= n - ng; i += 256) {        // window g[i .. i+ng-1]: a key match makes its columns content
+            const int v = h[i + ng - 1];
+            bool hit = ngram_content(v) && v > 0 && v < V;
+            for (int k = 0; hit && k < ng - 1; ++k) hit = h[i + k] == h[k0 + k];
+            if (hit) atomicOr(cnt + (v >> 1), 0xFFFFu << (16 * (v & 1)));
+        }
+    }
+    __syncthreads();
+}
+
 // logits processor + arg-max + forced-token cadence + append (generate.py:117-142), device-driven.
 template <typename... Fixed>
 __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restrict__ logits, long ldl, int V,
@@ -1107,16 +1157,21 @@ __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restr
     const int n = min(j, MAXGEN);
     if (gen[n - 1] == 0) { if (tid == 0) gen[j] = 0; return; }                   // sticky PAD
     count_ids(cnt, V, gen, n, tid);
+    constexpr bool NG = is_ngram<Fixed...>;
+    if constexpr (NG) {        // after the (V + 1) / 2 count words and, when sampling, the V-float row image
+        const NgramBan ng = ngram_of(fixed_end...);
+        ban_ngrams(cnt, reinterpret_cast<int*>(cnt + (V + 1) / 2 + (uniforms ? V : 0)), V, gen, min(n, ng.hist_cap), ng.n, tid);
+    }
     if (uniforms) {            // stochastic: uniforms[pos, b] drives the draw (top_k == 1 and top_p == 0 is the greedy path)
         float* px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
-        const int pick = sample_row(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k, top_p,
-                                    uniforms[(long)pos * ldu + b], tid, nullptr);
+        const int pick = sample_row<NG>(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k, top_p,
+                                        uniforms[(long)pos * ldu + b], tid, nullptr);
         if (tid == 0) gen[j] = pick;
         return;
     }
     float best;
     int besti;
-    scan_row(logits + (long)b * ldl, V, cnt, temperature, rep_penalty, tid, best, besti);
+    scan_row<NG>(logits + (long)b * ldl, V, cnt, temperature, rep_penalty, tid, best, besti);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(best, o, 64);
@@ -1169,13 +1224,18 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __res
         return;
     }
     count_ids(cnt, V, gen, n, tid);
+    constexpr bool NG = is_ngram<Fixed...>;
+    if constexpr (NG) {        // after the count words and the V processed logits
+        const NgramBan ng = ngram_of(fixed_end...);
+        ban_ngrams(cnt, reinterpret_cast<int*>(px + V), V, gen, min(n, ng.hist_cap), ng.n, tid);
+    }
     const float* row = logits + (long)b * ldl;
     float mx = -INFINITY;
     for (int v = tid; v < V; v += 256) {
         float x = row[v];
         if (v != 0 && v != 102) {
             const int c = (cnt[v >> 1] >> (16 * (v & 1))) & 0xFFFF;
-            for (int i = 0; i < c; ++i) x = x / rep_penalty;
+            x = penalize<NG>(x, c, rep_penalty);
         }
         x = x / temperature;
         if (v == 1 || v == 2 || v == 100 || v == 102) x = -INFINITY;
@@ -1418,7 +1478,8 @@ static int beam_candidates_launch(const char* what, const float* logits, long ld
     MMTG_REQUIRE(V <= 24000, "%s: vocabulary of %d exceeds the LDS row image (24000)", what, V);
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(MMTG_PROF_DECODE, s, 4.0 * B * V, 4.0 * B * V);
-    const size_t shm = (size_t)((V + 1) / 2) * 4 + (size_t)V * 4;
+    size_t shm = (size_t)((V + 1) / 2) * 4 + (size_t)V * 4;
+    if constexpr (is_ngram<Fixed...>) shm += (size_t)ngram_of(fe...).hist_cap * 4;          // the staged history
     static bool attr_done = false;
     if (!attr_done) {
         if (hipFuncSetAttribute((const void*)beam_candidates_kernel<Fixed...>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
@@ -1462,6 +1523,24 @@ extern "C" int mmtg_decode_beam_candidates_fixed(const float* logits, long ldl, 
                                   nb, cand_val, cand_id, B, stream, fixed_end);
 }
 
+// (the checks every *_ngram entry makes before its launch; the history fits MAXGEN ints of LDS, which the V limits leave room for)
+static int ngram_check(const char* what, const float* logits, long ldseq, int P, int sent, int ngram, int* hist_cap) {
+    MMTG_REQUIRE(logits, "%s: the n-gram form needs logits", what);
+    MMTG_REQUIRE(sent > 2 && ngram >= 1 && ngram <= sent - 2, "%s: n-gram size %d outside 1..%d (sent - 2)", what, ngram, sent - 2);
+    MMTG_REQUIRE(ldseq > P && P >= 0, "%s: bad sequence layout (ldseq %ld, P %d)", what, ldseq, P);
+    *hist_cap = (int)(ldseq - P < MAXGEN ? ldseq - P : MAXGEN);
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_beam_candidates_ngram(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                                 int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                                 int B, const int* fixed_end, int ngram, void* stream) {
+    int cap = 0;
+    if (int e = ngram_check("decode_beam_candidates_ngram", logits, ldseq, P, sent, ngram, &cap)) return e;
+    return beam_candidates_launch("decode_beam_candidates_ngram", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
+                                  nb, cand_val, cand_id, B, stream, NgramBan{fixed_end, ngram, cap});
+}
+
 extern "C" int mmtg_decode_beam_merge(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
                                       long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
                                       int* pos_next, void* stream) {
@@ -1489,6 +1568,7 @@ static int decode_select_launch(const char* what, const float* logits, long ldl,
     MMTG_REQUIRE(!logits || V <= (uniforms ? 24000 : 30000), "%s: vocabulary of %d exceeds the LDS tables", what, V);
     size_t shm = logits ? (size_t)((V + 1) / 2) * 4 : 0;
     if (logits && uniforms) shm += (size_t)V * 4;
+    if constexpr (is_ngram<Fixed...>) shm += (size_t)ngram_of(fe...).hist_cap * 4;          // the staged history
     static bool attr_done = false;
     if (!attr_done) {
         if (hipFuncSetAttribute((const void*)decode_select_kernel<Fixed...>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
@@ -1531,6 +1611,27 @@ extern "C" int mmtg_decode_sample_fixed(const float* logits, long ldl, int V, lo
                  "decode_sample_fixed: uniforms [positions, ldu >= B], top_k >= 0, top_p >= 0");
     return decode_select_launch("decode_select_fixed", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p,
                                 uniforms, ldu, B, pos_next, stream, fixed_end);
+}
+
+extern "C" int mmtg_decode_select_ngram(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                        int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, const int* fixed_end,
+                                        int ngram, void* stream) {
+    int cap = 0;
+    if (int e = ngram_check("decode_select_ngram", logits, ldseq, P, sent, ngram, &cap)) return e;
+    return decode_select_launch("decode_select_ngram", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, 1, 0.f, nullptr,
+                                0, B, pos_next, stream, NgramBan{fixed_end, ngram, cap});
+}
+
+extern "C" int mmtg_decode_sample_ngram(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                        int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                                        const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, int ngram,
+                                        void* stream) {
+    int cap = 0;
+    if (int e = ngram_check("decode_sample_ngram", logits, ldseq, P, sent, ngram, &cap)) return e;
+    MMTG_REQUIRE(uniforms && ldu >= B && top_k >= 0 && top_p >= 0.f,
+                 "decode_sample_ngram: uniforms [positions, ldu >= B], top_k >= 0, top_p >= 0");
+    return decode_select_launch("decode_sample_ngram", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p,
+                                uniforms, ldu, B, pos_next, stream, NgramBan{fixed_end, ngram, cap});
 }
 
 extern "C" int mmtg_decode_advance(int* pos_ptr, void* stream) {

@@ -63,6 +63,18 @@ def check_prefix(prefix, rows, length, sent=22, V=None):
     return ids
 
 
+def check_ngram(n, sent=22):
+    """Validate no_repeat_ngram_size on the host, before any device work; returns it as an int.  0 is off; 1 .. sent - 2 blocks
+    every content n-gram a row already holds (include/mmtg_hip.h states the rule; a longer n-gram can never be all content).
+    Bools and non-integers raise ValueError, as do values out of range."""
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)):
+        raise ValueError("no_repeat_ngram_size must be an integer, got %r" % (n,))
+    n = int(n)
+    if not 0 <= n <= sent - 2:
+        raise ValueError("no_repeat_ngram_size %d outside 0..%d (sent - 2)" % (n, sent - 2))
+    return n
+
+
 def _placement_ok(dev):
     """True when a 256-workgroup, one-per-CU launch puts workgroups b and b + 8 k on one XCD, 32 per XCD (census kernel, once per
     device and process): what the plain hand-off of mmtg_decode_mlp relies on (the launch itself re-checks every group)."""
@@ -226,6 +238,7 @@ class GreedyDecoder:
         self.rows = None            # the ancestry table of beam search (BeamDecoder); None: row b attends over its own cache row
         self.use_fixed = False      # this generation has a prefix: the step ends in the *_fixed selection entries
         self.min_fixed = 0          # min over rows of fixed_end (a step below it appends nothing: no head needed)
+        self.ngram = 0              # no_repeat_ngram_size: > 0 ends every step that calls the head in the *_ngram selection entries
 
     def _conv1d(self, x, wkey, out, **kw):
         # bf16: Engine._fwd routes Conv1D weights through their [out,in] copies (NT layout), which is
@@ -289,6 +302,9 @@ class GreedyDecoder:
         eng, sh, B = self.eng, self.eng.sh, self.B
         temperature, rep, top_k, top_p = self.params
         sent = sh.msl + 2
+        if self.ngram and with_head:
+            self._select_ngram()
+            return
         if self.use_fixed:
             self._select_fixed(with_head)
             return
@@ -319,6 +335,20 @@ class GreedyDecoder:
                                         top_k, top_p, self.uniforms, B, self.fixed_end, pos_next=self.pos_next)
         else:
             hip.decode_select_fixed(None, 0, 0, self.seq, self.pos, sh.P, sent, temperature, rep, B, self.fixed_end, pos_next=self.pos_next)
+
+    def _select_ngram(self):
+        """_select of a step that calls the head with no_repeat_ngram_size = self.ngram: the same launch through the *_ngram entries,
+        which also ban every id that would complete a content n-gram the row already holds (and hold prefix columns, if any)."""
+        eng, sh, B = self.eng, self.eng.sh, self.B
+        temperature, rep, top_k, top_p = self.params
+        sent, Vp = sh.msl + 2, eng.layout.Vpad
+        fe = self.fixed_end if self.use_fixed else None
+        if top_k == 1 and top_p == 0.0:
+            hip.decode_select_ngram(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep, B, self.ngram,
+                                    fixed_end=fe, pos_next=self.pos_next)
+        else:
+            hip.decode_sample_ngram(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep, top_k, top_p,
+                                    self.uniforms, B, self.ngram, fixed_end=fe, pos_next=self.pos_next)
 
     def _step_x3(self, with_head):
         """The split-precision token step: embedding -> projector -> 12 blocks -> head, every product through mmtg_decode_gemm_x3
@@ -505,7 +535,7 @@ class GreedyDecoder:
         if not self.use_graph:
             self._step(with_head, parity)
             return
-        key = (with_head, parity, self.params) + (("prefix",) if self.use_fixed else ())
+        key = (with_head, parity, self.params) + (("prefix",) if self.use_fixed else ()) + (("ngram", self.ngram) if self.ngram else ())
         g = self.graphs.get(key)
         if g is None:
             # warm-up outside capture (lazy LDS-attribute / module loading), then rewind the position
@@ -548,7 +578,8 @@ class GreedyDecoder:
                 if self.fast else "decode token step: training-side kernels per layer")
 
     @torch.no_grad()
-    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None):
+    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
+              no_repeat_ngram_size=0):
         """Everything of a generation that happens once: the settings, the uniforms of a stochastic run, fresh weight copies /
         LayerNorm folds, the experience encoder, the prompt (prefilled in one batched pass: ``first_pos`` = P afterwards) and the
         reset position.  Returns the end position n; ``step_at(pos)`` for pos = first_pos .. n - 1 then runs the token steps (``generate`` does both; tools/decode_lanes_threads.py drives
@@ -557,13 +588,18 @@ class GreedyDecoder:
         prefix (optional; check_prefix states the rules): row b's first L_b lyric ids, written into seq[b, P:P + L_b] with
         fixed_end[b] = P + L_b -- the steps leave those columns alone.  The prefill then covers [prompt, p[:, :Lmin]] (Lmin = min_b
         L_b, first_pos = P + Lmin - 1); longer prefixes go through token steps held by fixed_end.  prefix=None runs exactly the
-        launches and graphs of an unprefixed generation."""
+        launches and graphs of an unprefixed generation.
+
+        no_repeat_ngram_size (check_ngram): n > 0 makes every step that calls the head end in the *_ngram selection entries, so no
+        row writes a content n-gram it already holds (prefix columns count as history).  0 runs exactly the launches and graphs of a
+        generation without the argument."""
         eng, sh = self.eng, self.eng.sh
         B = batch["img_embs"].shape[0]
         if B != self.B:
             raise ValueError("decoder was built for batch %d, got %d" % (self.B, B))
         if length > self.max_len:
             raise ValueError("length %d exceeds max_len %d" % (length, self.max_len))
+        ngram = check_ngram(no_repeat_ngram_size, sh.msl + 2)
         pre = None if prefix is None else check_prefix(prefix, B, length, sent=sh.msl + 2, V=sh.V)
         self.params = (float(temperature), float(repitition_penalty), int(top_k), float(top_p))
         if not (int(top_k) == 1 and float(top_p) == 0.0):
@@ -587,8 +623,9 @@ class GreedyDecoder:
         self.seq[:, :sh.P] = batch["topic_ids"].to(eng.dev).long()
         self.seq[:, sh.P] = 1                                   # [#START#]
         lmin = 1
-        for d in [self] + self.children:            # (a lane's _select reads its own flag and its slice of fixed_end)
+        for d in [self] + self.children:            # (a lane's _select reads its own flags and its slice of fixed_end)
             d.use_fixed = pre is not None
+            d.ngram = ngram
         self.min_fixed = 0
         if pre is not None:
             lens = [len(p) for p in pre]
@@ -659,7 +696,7 @@ class GreedyDecoder:
 
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None,
-                 use_graph=None, teacher=None, tap=None, prefix=None):
+                 use_graph=None, teacher=None, tap=None, prefix=None, no_repeat_ngram_size=0):
         """batch: dict with topic_ids/tpw_* [B,P], topic_emb, img_embs, r_embs (no targets needed).
         Runs `length` iterations of the reference loop and returns the lyric ids
         [B, 1 + length] (column 0 is the initial [#START#]).  top_k = 1, top_p = 0 is the greedy setting;
@@ -669,8 +706,11 @@ class GreedyDecoder:
         appended is replaced by teacher[:, j] wherever that is >= 0 (teacher forcing on a reference id list; the step's own
         pick is handed to `tap` first); `tap(j, with_head, picked [B], logits [B, Vpad] or None)` is called after every step.
         prefix: the opening lyric ids of every row (``begin``, ``check_prefix``); columns 0 .. L_b - 1 of row b's result are its
-        prefix, the rest follows the rules above (the penalty counts the prefix)."""
-        n_steps = self.begin(batch, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix)
+        prefix, the rest follows the rules above (the penalty counts the prefix).
+        no_repeat_ngram_size: n > 0 bans, at every model-chosen column, each id that would repeat a content n-gram of the row
+        (``begin``, include/mmtg_hip.h); 0 (the default) is off."""
+        n_steps = self.begin(batch, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix,
+                             no_repeat_ngram_size=no_repeat_ngram_size)
         eng, sh = self.eng, self.eng.sh
         saved_mode = self.use_graph
         if use_graph is not None:
@@ -746,6 +786,17 @@ class BeamDecoder(GreedyDecoder):
         eng, sh, B = self.eng, self.eng.sh, self.B
         temperature, rep, _, _ = self.params
         sent = sh.msl + 2
+        if self.ngram and with_head:             # the bans act in the candidates; the merge is the prefix-aware one or the plain one
+            hip.decode_beam_candidates_ngram(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature,
+                                             rep, self.nb, self.cand_val, self.cand_id, B, self.ngram,
+                                             fixed_end=self.fixed_end if self.use_fixed else None)
+            if self.use_fixed:
+                hip.decode_beam_merge_fixed(self.cand_val, self.cand_id, self.scores, self.seq, self.keep, self.rows, self.pos, sh.P, sent,
+                                            self.nb, self.n_prompts, self.fixed_end, pos_next=self.pos_next)
+            else:
+                hip.decode_beam_merge(self.cand_val, self.cand_id, self.scores, self.seq, self.keep, self.rows, self.pos, sh.P, sent,
+                                      self.nb, self.n_prompts, pos_next=self.pos_next)
+            return
         if self.use_fixed:
             if with_head:
                 hip.decode_beam_candidates_fixed(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature,
@@ -767,18 +818,21 @@ class BeamDecoder(GreedyDecoder):
         return "%d beams per prompt, " % self.nb + super().describe()
 
     @torch.no_grad()
-    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None):
+    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
+              no_repeat_ngram_size=0):
         """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill and the prefix: one per
         prompt), the ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at
         the free positions after a prompt's prefix."""
         n = batch["img_embs"].shape[0]
         if n != self.n_prompts:
             raise ValueError("decoder was built for %d prompts, got %d" % (self.n_prompts, n))
+        check_ngram(no_repeat_ngram_size, self.eng.sh.msl + 2)
         if prefix is not None:
             sh = self.eng.sh
             prefix = [p for p in check_prefix(prefix, n, length, sent=sh.msl + 2, V=sh.V) for _ in range(self.nb)]
         rep = {k: (v.repeat_interleave(self.nb, 0) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        n_steps = super().begin(rep, length, temperature, repitition_penalty, 1, 0.0, prefix=prefix)
+        n_steps = super().begin(rep, length, temperature, repitition_penalty, 1, 0.0, prefix=prefix,
+                                no_repeat_ngram_size=no_repeat_ngram_size)
         B, dev = self.B, self.eng.dev
         self.rows.copy_(torch.arange(B, dtype=torch.int32, device=dev)[:, None].expand(B, self.Tmax))
         sc = torch.full((n, self.nb), float("-inf"), dtype=torch.float32, device=dev)
@@ -787,12 +841,13 @@ class BeamDecoder(GreedyDecoder):
         return n_steps
 
     @torch.no_grad()
-    def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None):
+    def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None, no_repeat_ngram_size=0):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_beams, 1 + length] in
         GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row.
-        prefix: one per prompt (check_prefix), shared by its beams."""
+        prefix: one per prompt (check_prefix), shared by its beams.  no_repeat_ngram_size: as GreedyDecoder.generate, per beam
+        on its own (reordered) history."""
         ids = super().generate(batch, length, temperature=temperature, repitition_penalty=repitition_penalty, use_graph=use_graph,
-                               prefix=prefix)
+                               prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size)
         n, nb = self.n_prompts, self.nb
         ids = ids.view(n, nb, -1)
         sc = self.scores.view(n, nb).clone()

@@ -154,7 +154,7 @@ def _prompt_prefixes(prefixes, n_prompts, length, sh):
 
 
 def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperature=1.1, top_k=10, top_p=0.7,
-                     repetition_penalty=1.5, max_batch=256, generator=None, decoder=None, prefixes=None):
+                     repetition_penalty=1.5, max_batch=256, generator=None, decoder=None, prefixes=None, no_repeat_ngram_size=0):
     """n_samples texts per prompt (generate.sh's loop, generate.py:205-235) on the batched, graph-replayed decoder:
     every prompt is replicated over n_samples rows, rows are decoded max_batch at a time with the device-side
     top-k / top-p sampler (one uniform per row and position from `generator`), each row is cut back to what
@@ -163,10 +163,12 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     rows: list of dataset items (dicts with topic_ids / tpw_* / topic_emb / img_embs / r_embs, numpy or tensors) or a dict of
     stacked arrays.  Returns a list (one entry per prompt) of lists of n_samples strings.
     prefixes (optional): one list of opening lyric ids per prompt (encode_prefix, decode.check_prefix); every sample of the prompt
-    continues it, and its text includes the given lines."""
-    from .decode import GreedyDecoder
+    continues it, and its text includes the given lines.
+    no_repeat_ngram_size (optional, decode.check_ngram): n > 0 keeps every row from writing a content n-gram it already holds."""
+    from .decode import GreedyDecoder, check_ngram
     eng = model.engine()
     sh = eng.sh
+    ngram = check_ngram(no_repeat_ngram_size, sh.msl + 2)
     length = sh.max_seq_length if length is None else length
     keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
     if isinstance(rows, dict):
@@ -192,7 +194,7 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
             cpre += [cpre[0]] * (bsz - len(cpre))
         chunk = {k: v.to(eng.dev) for k, v in chunk.items()}
         ids = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty,
-                           top_k=top_k, top_p=top_p, generator=generator, prefix=cpre).cpu().numpy()
+                           top_k=top_k, top_p=top_p, generator=generator, prefix=cpre, no_repeat_ngram_size=ngram).cpu().numpy()
         for r in range(hi - lo):
             seq = GreedyDecoder.reference_return(ids[r].tolist(), length, sent=sh.msl + 2)
             texts.append(postprocess_tokens(tokenizer.convert_ids_to_tokens(seq)))
@@ -200,16 +202,17 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
 
 
 def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature=1.1, repetition_penalty=1.5, max_batch=256,
-                   return_all=False, prefixes=None):
+                   return_all=False, prefixes=None, no_repeat_ngram_size=0):
     """Beam search per prompt on the batched, graph-replayed decoder (BeamDecoder): prompts are decoded max_batch // num_beams at
     a time, every beam is cut back to what sample_sequence would have returned (GreedyDecoder.reference_return) and
     post-processed as generate_samples does.  rows: as generate_samples.  Returns one string per prompt (its best beam), or with
     return_all=True one list per prompt of num_beams (text, score) pairs, best first (score: the sum of the fp32 log-probabilities
     of the processed logits at the positions the model chose; see BeamDecoder).  prefixes: as generate_samples (the prefix
-    positions add nothing to a score)."""
-    from .decode import BeamDecoder, GreedyDecoder
+    positions add nothing to a score).  no_repeat_ngram_size: as generate_samples, on every beam's own history."""
+    from .decode import BeamDecoder, GreedyDecoder, check_ngram
     eng = model.engine()
     sh = eng.sh
+    ngram = check_ngram(no_repeat_ngram_size, sh.msl + 2)
     length = sh.max_seq_length if length is None else length
     keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
     if isinstance(rows, dict):
@@ -231,7 +234,8 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
         if pre is not None:
             cpre = pre[lo:hi] + [pre[lo]] * (per - (hi - lo))
         chunk = {k: v.to(eng.dev) for k, v in chunk.items()}
-        ids, scores = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty, prefix=cpre)
+        ids, scores = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty, prefix=cpre,
+                                   no_repeat_ngram_size=ngram)
         ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
         for r in range(hi - lo):
             beams = []

@@ -110,6 +110,9 @@ _SIGS = {
     "mmtg_decode_sample_fixed": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp, _vp], _i),
     "mmtg_decode_beam_candidates_fixed": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _vp], _i),
     "mmtg_decode_beam_merge_fixed": ([_vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "mmtg_decode_select_ngram": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp], _i),
+    "mmtg_decode_sample_ngram": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp, _i, _vp], _i),
+    "mmtg_decode_beam_candidates_ngram": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
     "mmtg_decode_mlp_sync_words": ([], _i),
     "mmtg_decode_mlp_census": ([_vp, _vp], _i),
@@ -881,6 +884,29 @@ def decode_beam_merge_fixed(cand_val, cand_id, scores, seq, keep, rows, pos, P, 
     _check(lib().mmtg_decode_beam_merge_fixed(_p(cand_val), _p(cand_id), _p(scores), _p(seq), seq.stride(0), _p(keep), keep.stride(0),
                                               _p(rows), rows.stride(0), _p(pos), P, sent, int(nb), int(n_prompts), _p(pos_next),
                                               _fixed(fixed_end, n_prompts * nb), _stream()), "decode_beam_merge_fixed")
+
+
+def decode_select_ngram(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, ngram, fixed_end=None, pos_next=None):
+    """decode_select that never writes a content n-gram (n = ngram) the row already holds (include/mmtg_hip.h); fixed_end: as
+    decode_select_fixed, or None (no prefix)."""
+    _check(lib().mmtg_decode_select_ngram(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                          float(rep_penalty), B, _p(pos_next), _fixed(fixed_end, B), int(ngram), _stream()),
+           "decode_select_ngram")
+
+
+def decode_sample_ngram(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, ngram, fixed_end=None,
+                        pos_next=None):
+    _check(lib().mmtg_decode_sample_ngram(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                          float(rep_penalty), int(top_k), float(top_p), _p(uniforms), uniforms.stride(0), B, _p(pos_next),
+                                          _fixed(fixed_end, B), int(ngram), _stream()), "decode_sample_ngram")
+
+
+def decode_beam_candidates_ngram(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, ngram,
+                                 fixed_end=None):
+    """decode_beam_candidates with the n-gram bans of decode_select_ngram applied before the log_softmax and the top nb."""
+    _check(lib().mmtg_decode_beam_candidates_ngram(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                                   float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B, _fixed(fixed_end, B),
+                                                   int(ngram), _stream()), "decode_beam_candidates_ngram")
 
 
 def decode_advance(pos):
