@@ -614,6 +614,38 @@ MMTG_API int mmtg_decode_beam_candidates_ngram(const float* logits, long ldl, in
                                       int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
                                       int B, const int* fixed_end, int ngram, void* stream);
 
+/* ---- line-length bounds and line-end token sets (GreedyDecoder / BeamDecoder with line_lengths= / line_end_ids=,
+ * mmtg_amd/decode.py): the form of the lyric.  The reference ends a line where the model happens to pick PAD and pads the slot from
+ * there (generate.py:137-138, its sticky PAD; the slots are those of generate.py:117-123); these entries decide PAD by rule.
+ * Lyric index j is line l = j / sent, content column c = j % sent - 1 (0 .. sent - 3).  Row b carries per line lo[b, l] <= hi[b, l]
+ * <= sent - 2 (bytes, [B, n_lines]; a line l >= n_lines is unconstrained) and optionally an end set: set_of[b, l] (int16, -1: none)
+ * names a row of `sets`, n_sets bit rows of ceil(V / 32) words (bit v & 31 of word v >> 5: content id v is a member).  (0, sent - 2,
+ * no set) is unconstrained and gives the *_ngram entry's output bit for bit.  At a column the row's model chooses (not a held prefix
+ * column, not forced, the row not in sticky PAD):
+ *   c >= hi: the row writes PAD without consulting the logits (beams: PAD at log-probability 0, -inf fillers, as sticky PAD);
+ *   else PAD's processed logit is -inf when c < lo, or when the line has an end set and seq[j - 1] is not a member ([#START#] at
+ *   c = 0 is none: such a line is never empty); and at c == hi - 1 of a line with an end set every id outside the set is -inf.
+ * The bans act where the n-gram bans act (after the penalty, temperature and fixed bans; before the arg-max / the top-k, top-p
+ * filters and the draw / the beam's log_softmax and top-nb) and compose with them.  A row whose every logit is -inf writes PAD
+ * (arg-max and draw) / offers id 0 at -inf for every rank (beams), as the plain kernels do.  Each entry is its *_ngram namesake
+ * (fixed_end may be null; ngram 0 .. sent - 2, 0: no n-gram bans) plus the tables; sets, set_of and n_sets are null / 0 together.
+ * Without logits, or with tables missing, the entry fails before any device call.  The beam merge is unchanged: a full line is
+ * offered by the candidates the way sticky PAD is.  The kernels of the plain, *_fixed and *_ngram entries compile to the same code
+ * as before these were added.                                                                                                  */
+MMTG_API int mmtg_decode_select_lines(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                             int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, const int* fixed_end,
+                             int ngram, const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets,
+                             int n_sets, const short* set_of, void* stream);
+MMTG_API int mmtg_decode_sample_lines(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                             int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                             const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, int ngram,
+                             const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
+                             const short* set_of, void* stream);
+MMTG_API int mmtg_decode_beam_candidates_lines(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                      int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                      int B, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
+                                      int n_lines, const unsigned* sets, int n_sets, const short* set_of, void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

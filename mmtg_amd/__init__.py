@@ -30,7 +30,7 @@ def __getattr__(name):
     if name in ("sample_sequence", "top_k_top_p_filtering", "generate_samples", "generate_beams", "postprocess_tokens"):
         from . import generate
         return getattr(generate, name)
-    if name in ("MyDataset", "BinaryDataset", "DeviceLoader", "pack_binary", "encode_prefix"):
+    if name in ("MyDataset", "BinaryDataset", "DeviceLoader", "pack_binary", "encode_prefix", "encode_line_end"):
         from . import data
         return getattr(data, name)
     if name in ("MMTGTrainer",):

@@ -32,9 +32,10 @@ __device__ __forceinline__ float penalize(float x, int c, float rep_penalty) {
 }
 
 // one logit through the reference's processor (generate.py:127-136), folded into the running arg-max (lowest index wins ties)
-template <bool NG = false>
+// LN (the line forms, ban_line): PAD reads its slot too, which ban_line has set to 0 (no penalty, as ever) or to the sentinel
+template <bool NG = false, bool LN = false>
 __device__ __forceinline__ void scan_one(float x, int v, const unsigned* cnt, float temperature, float rep_penalty, float& best, int& besti) {
-    if (v != 0 && v != 102) {
+    if ((LN || v != 0) && v != 102) {
         const int c = (cnt[v >> 1] >> (16 * (v & 1))) & 0xFFFF;
         x = penalize<NG>(x, c, rep_penalty);
     }
@@ -45,7 +46,7 @@ __device__ __forceinline__ void scan_one(float x, int v, const unsigned* cnt, fl
 // this thread's share of the processed-logit arg-max.  16-byte aligned rows are read as float4 with all of a pass's loads
 // (up to 16 per thread = 16 K logits per block) requested before the first is used: one memory round trip per row instead of a
 // dependent 4-byte load per 256 logits (round 3: 21.5 -> see profiles/ us for 256 rows of V = 13317).
-template <bool NG = false>
+template <bool NG = false, bool LN = false>
 __device__ __forceinline__ void scan_row(const float* row, int V, const unsigned* cnt, float temperature, float rep_penalty,
                                          int tid, float& best, int& besti) {
     best = -INFINITY;
@@ -67,13 +68,13 @@ __device__ __forceinline__ void scan_row(const float* row, int V, const unsigned
                 const int idx = base + i * 256 + tid;
                 if (idx < nvec) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) scan_one<NG>(r[i][e], 4 * idx + e, cnt, temperature, rep_penalty, best, besti);
+                    for (int e = 0; e < 4; ++e) scan_one<NG, LN>(r[i][e], 4 * idx + e, cnt, temperature, rep_penalty, best, besti);
                 }
             }
         }
         done = nvec << 2;
     }
-    for (int v = done + tid; v < V; v += 256) scan_one<NG>(row[v], v, cnt, temperature, rep_penalty, best, besti);
+    for (int v = done + tid; v < V; v += 256) scan_one<NG, LN>(row[v], v, cnt, temperature, rep_penalty, best, besti);
 }
 
 __global__ __launch_bounds__(256) void logits_argmax_kernel(const float* __restrict__ logits, long ldl, int V,
@@ -120,7 +121,7 @@ __device__ __forceinline__ unsigned fkey(float x) {
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
-template <bool NG = false>
+template <bool NG = false, bool LN = false>
 __device__ int sample_row(const float* row, int V, const unsigned* cnt, float* px, float temperature, float rep_penalty,
                           int top_k, float top_p, float u, int tid, float* filtered) {
     __shared__ unsigned hcnt[256];
@@ -131,7 +132,7 @@ __device__ int sample_row(const float* row, int V, const unsigned* cnt, float* p
     __shared__ int s_pick;
     for (int v = tid; v < V; v += 256) {
         float x = row[v];
-        if (v != 0 && v != 102) {
+        if ((LN || v != 0) && v != 102) {
             const int c = (cnt[v >> 1] >> (16 * (v & 1))) & 0xFFFF;
             x = penalize<NG>(x, c, rep_penalty);
         }
@@ -1134,6 +1135,62 @@ __device__ __forceinline__ void ban_ngrams(unsigned* cnt, int* h, int V, const l
     __syncthreads();
 }
 
+// Line-length bounds and line-end sets (the *_lines entries, include/mmtg_hip.h): the pack is one LineRule -- an NgramBan whose n may
+// be 0 (no n-gram bans) plus the per-row, per-line tables.  Lyric index j sits on line l = j / sent at content column
+// c = j % sent - 1; a line past n_lines is unconstrained (lo 0, hi sent - 2, no set).
+struct LineRule {
+    NgramBan ng;                   // fixed_end optional; n = 0: no n-gram bans (hist_cap 0)
+    const unsigned char* lo;       // [B, n_lines]
+    const unsigned char* hi;       // [B, n_lines], lo <= hi <= sent - 2
+    const short* set_of;           // [B, n_lines] row of `sets` (-1: no end set), or null
+    const unsigned* sets;          // [n_sets, words] bit v of a row: content id v is in the set
+    int n_lines, n_sets, words;    // words >= ceil(V / 32)
+};
+
+template <typename... Fixed> constexpr bool is_lines = (std::is_same<Fixed, LineRule>::value || ... || false);
+template <typename... Fixed> __host__ __device__ __forceinline__ LineRule lines_of(Fixed... e) { return (e, ...); }
+__host__ __device__ __forceinline__ NgramBan ngram_of(LineRule lr) { return lr.ng; }
+__device__ __forceinline__ bool prefix_column(int b, int pos, LineRule lr) { return prefix_column(b, pos, lr.ng); }
+
+// what the rule says of row b's free column j (uniform over the workgroup: every thread computes the same)
+struct LineCol {
+    bool force_pad;          // c >= hi: the row writes PAD, no logits consulted
+    bool pad_ban;            // c < lo, or an end set whose members do not include the previous token
+    const unsigned* mask;    // c == hi - 1 of a line with an end set: the set's bit row (else null)
+};
+__device__ __forceinline__ LineCol line_col(const LineRule& lr, int b, int j, int sent, const long long* gen) {
+    LineCol lc = {false, false, nullptr};
+    const int l = j / sent, c = j % sent - 1;
+    if (l >= lr.n_lines) return lc;
+    const long at = (long)b * lr.n_lines + l;
+    const int lo = lr.lo[at], hi = lr.hi[at];
+    const int s = lr.set_of ? (int)lr.set_of[at] : -1;
+    lc.force_pad = c >= hi;
+    lc.pad_ban = c < lo;
+    if (s >= 0 && s < lr.n_sets && !lc.force_pad) {
+        const unsigned* m = lr.sets + (long)s * lr.words;
+        const long long prev = gen[j - 1];
+        const bool in = prev >= 0 && prev < 32LL * lr.words && ((m[prev >> 5] >> (prev & 31)) & 1u);
+        lc.pad_ban = lc.pad_ban || !in;
+        if (c == hi - 1) lc.mask = m;
+    }
+    return lc;
+}
+
+// The line bans as edits of the occurrence table, after count_ids / ban_ngrams (all threads of the block call): at the end-set
+// column every id outside the set gets the sentinel 0xFFFF (the specials among them are -inf anyway); PAD's slot, which the plain
+// forms never read, is set to 0 (no penalty, as ever) or to the sentinel (PAD banned).  The logit loops of the LN forms read PAD's
+// slot like any other, so the rule costs them nothing per logit.  (Thread 0 owns word 0 in both loops: no barrier between them.)
+__device__ __forceinline__ void ban_line(unsigned* cnt, int V, const LineCol& lc, int tid) {
+    if (lc.mask)
+        for (int i = tid; i < (V + 1) / 2; i += 256) {          // word i: ids 2 i and 2 i + 1 = bits 2 (i & 15), + 1 of mask word i / 16
+            const unsigned two = (lc.mask[i >> 4] >> (2 * (i & 15))) & 3u;
+            cnt[i] |= ((two & 1u) ? 0u : 0xFFFFu) | ((two & 2u) ? 0u : 0xFFFF0000u);
+        }
+    if (tid == 0) cnt[0] = (cnt[0] & 0xFFFF0000u) | (lc.pad_ban ? 0xFFFFu : 0u);
+    __syncthreads();
+}
+
 // logits processor + arg-max + forced-token cadence + append (generate.py:117-142), device-driven.
 template <typename... Fixed>
 __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restrict__ logits, long ldl, int V,
@@ -1156,22 +1213,30 @@ __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restr
     if (!have_logits) return;
     const int n = min(j, MAXGEN);
     if (gen[n - 1] == 0) { if (tid == 0) gen[j] = 0; return; }                   // sticky PAD
+    constexpr bool LN = is_lines<Fixed...>;
+    constexpr bool NG = is_ngram<Fixed...> || LN;          // (the line bans use the n-gram sentinel)
+    LineCol lc = {false, false, nullptr};
+    if constexpr (LN) {
+        lc = line_col(lines_of(fixed_end...), b, j, sent, gen);
+        if (lc.force_pad) { if (tid == 0) gen[j] = 0; return; }                  // the line is full: PAD, as sticky PAD writes it
+    }
     count_ids(cnt, V, gen, n, tid);
-    constexpr bool NG = is_ngram<Fixed...>;
     if constexpr (NG) {        // after the (V + 1) / 2 count words and, when sampling, the V-float row image
         const NgramBan ng = ngram_of(fixed_end...);
-        ban_ngrams(cnt, reinterpret_cast<int*>(cnt + (V + 1) / 2 + (uniforms ? V : 0)), V, gen, min(n, ng.hist_cap), ng.n, tid);
+        if (!LN || ng.n > 0)
+            ban_ngrams(cnt, reinterpret_cast<int*>(cnt + (V + 1) / 2 + (uniforms ? V : 0)), V, gen, min(n, ng.hist_cap), ng.n, tid);
     }
+    if constexpr (LN) ban_line(cnt, V, lc, tid);
     if (uniforms) {            // stochastic: uniforms[pos, b] drives the draw (top_k == 1 and top_p == 0 is the greedy path)
         float* px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
-        const int pick = sample_row<NG>(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k, top_p,
+        const int pick = sample_row<NG, LN>(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k, top_p,
                                         uniforms[(long)pos * ldu + b], tid, nullptr);
         if (tid == 0) gen[j] = pick;
         return;
     }
     float best;
     int besti;
-    scan_row<NG>(logits + (long)b * ldl, V, cnt, temperature, rep_penalty, tid, best, besti);
+    scan_row<NG, LN>(logits + (long)b * ldl, V, cnt, temperature, rep_penalty, tid, best, besti);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(best, o, 64);
@@ -1223,17 +1288,27 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __res
         if (tid < nb) { cv[tid] = tid == 0 ? 0.f : -INFINITY; ci[tid] = 0; }
         return;
     }
+    constexpr bool LN = is_lines<Fixed...>;
+    constexpr bool NG = is_ngram<Fixed...> || LN;
+    LineCol lc = {false, false, nullptr};
+    if constexpr (LN) {
+        lc = line_col(lines_of(fixed_end...), b, j, sent, gen);
+        if (lc.force_pad) {                                // the line is full: PAD with the score unchanged, as sticky PAD offers it
+            if (tid < nb) { cv[tid] = tid == 0 ? 0.f : -INFINITY; ci[tid] = 0; }
+            return;
+        }
+    }
     count_ids(cnt, V, gen, n, tid);
-    constexpr bool NG = is_ngram<Fixed...>;
     if constexpr (NG) {        // after the count words and the V processed logits
         const NgramBan ng = ngram_of(fixed_end...);
-        ban_ngrams(cnt, reinterpret_cast<int*>(px + V), V, gen, min(n, ng.hist_cap), ng.n, tid);
+        if (!LN || ng.n > 0) ban_ngrams(cnt, reinterpret_cast<int*>(px + V), V, gen, min(n, ng.hist_cap), ng.n, tid);
     }
+    if constexpr (LN) ban_line(cnt, V, lc, tid);
     const float* row = logits + (long)b * ldl;
     float mx = -INFINITY;
     for (int v = tid; v < V; v += 256) {
         float x = row[v];
-        if (v != 0 && v != 102) {
+        if ((LN || v != 0) && v != 102) {
             const int c = (cnt[v >> 1] >> (16 * (v & 1))) & 0xFFFF;
             x = penalize<NG>(x, c, rep_penalty);
         }
@@ -1479,7 +1554,7 @@ static int beam_candidates_launch(const char* what, const float* logits, long ld
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(MMTG_PROF_DECODE, s, 4.0 * B * V, 4.0 * B * V);
     size_t shm = (size_t)((V + 1) / 2) * 4 + (size_t)V * 4;
-    if constexpr (is_ngram<Fixed...>) shm += (size_t)ngram_of(fe...).hist_cap * 4;          // the staged history
+    if constexpr (is_ngram<Fixed...> || is_lines<Fixed...>) shm += (size_t)ngram_of(fe...).hist_cap * 4;     // the staged history
     static bool attr_done = false;
     if (!attr_done) {
         if (hipFuncSetAttribute((const void*)beam_candidates_kernel<Fixed...>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
@@ -1568,7 +1643,7 @@ static int decode_select_launch(const char* what, const float* logits, long ldl,
     MMTG_REQUIRE(!logits || V <= (uniforms ? 24000 : 30000), "%s: vocabulary of %d exceeds the LDS tables", what, V);
     size_t shm = logits ? (size_t)((V + 1) / 2) * 4 : 0;
     if (logits && uniforms) shm += (size_t)V * 4;
-    if constexpr (is_ngram<Fixed...>) shm += (size_t)ngram_of(fe...).hist_cap * 4;          // the staged history
+    if constexpr (is_ngram<Fixed...> || is_lines<Fixed...>) shm += (size_t)ngram_of(fe...).hist_cap * 4;     // the staged history
     static bool attr_done = false;
     if (!attr_done) {
         if (hipFuncSetAttribute((const void*)decode_select_kernel<Fixed...>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
@@ -1632,6 +1707,60 @@ extern "C" int mmtg_decode_sample_ngram(const float* logits, long ldl, int V, lo
                  "decode_sample_ngram: uniforms [positions, ldu >= B], top_k >= 0, top_p >= 0");
     return decode_select_launch("decode_sample_ngram", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p,
                                 uniforms, ldu, B, pos_next, stream, NgramBan{fixed_end, ngram, cap});
+}
+
+// (the checks every *_lines entry makes before its launch, and its pack; ngram 0 stages no history)
+static int lines_check(const char* what, const float* logits, int V, long ldseq, int P, int sent, const int* fixed_end, int ngram,
+                       const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
+                       const short* set_of, LineRule* lr) {
+    MMTG_REQUIRE(logits, "%s: the line form needs logits", what);
+    MMTG_REQUIRE(sent > 2 && ngram >= 0 && ngram <= sent - 2, "%s: n-gram size %d outside 0..%d (sent - 2)", what, ngram, sent - 2);
+    MMTG_REQUIRE(lo && hi && n_lines >= 1, "%s: lo / hi [B, n_lines >= 1] needed (n_lines %d)", what, n_lines);
+    MMTG_REQUIRE(n_sets >= 0 && (n_sets > 0) == (sets != nullptr) && (n_sets > 0) == (set_of != nullptr),
+                 "%s: end sets need sets, set_of and n_sets > 0 together (n_sets %d)", what, n_sets);
+    int cap = 0;
+    if (ngram > 0) {
+        if (int e = ngram_check(what, logits, ldseq, P, sent, ngram, &cap)) return e;
+    } else MMTG_REQUIRE(ldseq > P && P >= 0, "%s: bad sequence layout (ldseq %ld, P %d)", what, ldseq, P);
+    *lr = LineRule{NgramBan{fixed_end, ngram, cap}, lo, hi, set_of, sets, n_lines, n_sets, (V + 31) / 32};
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_select_lines(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                        int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, const int* fixed_end,
+                                        int ngram, const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets,
+                                        int n_sets, const short* set_of, void* stream) {
+    LineRule lr;
+    if (int e = lines_check("decode_select_lines", logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, &lr))
+        return e;
+    return decode_select_launch("decode_select_lines", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, 1, 0.f, nullptr,
+                                0, B, pos_next, stream, lr);
+}
+
+extern "C" int mmtg_decode_sample_lines(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                        int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                                        const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, int ngram,
+                                        const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
+                                        const short* set_of, void* stream) {
+    LineRule lr;
+    if (int e = lines_check("decode_sample_lines", logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, &lr))
+        return e;
+    MMTG_REQUIRE(uniforms && ldu >= B && top_k >= 0 && top_p >= 0.f,
+                 "decode_sample_lines: uniforms [positions, ldu >= B], top_k >= 0, top_p >= 0");
+    return decode_select_launch("decode_sample_lines", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p,
+                                uniforms, ldu, B, pos_next, stream, lr);
+}
+
+extern "C" int mmtg_decode_beam_candidates_lines(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                                 int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                                 int B, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
+                                                 int n_lines, const unsigned* sets, int n_sets, const short* set_of, void* stream) {
+    LineRule lr;
+    if (int e = lines_check("decode_beam_candidates_lines", logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets,
+                            set_of, &lr))
+        return e;
+    return beam_candidates_launch("decode_beam_candidates_lines", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
+                                  nb, cand_val, cand_id, B, stream, lr);
 }
 
 extern "C" int mmtg_decode_advance(int* pos_ptr, void* stream) {

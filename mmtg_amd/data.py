@@ -70,6 +70,23 @@ def encode_prefix(tokenizer, lines, partial=None, max_sent_length=20):
     return list(tokenizer.convert_tokens_to_ids(tokens))
 
 
+def encode_line_end(tokenizer, chars, vocab_cut=13317):
+    """The id set of a line-end constraint (decode.check_lines' line_end_ids) from a string of characters -- one character is one
+    token in this vocabulary, so e.g. the characters of one rhyme.  Whitespace is skipped; a character the tokenizer does not know
+    ([UNK]), a special token, PAD or an id at or above the generation's vocabulary cut raises ValueError, as does an empty string."""
+    ids = set()
+    for ch in chars:
+        if ch.isspace():
+            continue
+        v = int(tokenizer.convert_tokens_to_ids(ch))
+        if v in (0, 1, 2, 100, 102) or not 0 <= v < vocab_cut:
+            raise ValueError("line-end character %r maps to id %d, not a content id below %d" % (ch, v, vocab_cut))
+        ids.add(v)
+    if not ids:
+        raise ValueError("line-end characters %r hold no content token" % (chars,))
+    return frozenset(ids)
+
+
 class MyDataset(torch.utils.data.Dataset):
     """Same contract as src/MyDataset.py: ``MyDataset(file_path, tokenizer, data_config, if_train=True)``;
     ``file_path`` is the reference's pickle (a list of dicts) or an already loaded list."""

@@ -75,6 +75,151 @@ def check_ngram(n, sent=22):
     return n
 
 
+class LineTables:
+    """The packed line constraints check_lines returns: lo, hi uint8 [rows, n_lines]; set_of int16 [rows, n_lines] (-1: no end set)
+    and sets uint32 [n_sets, ceil(V / 32)] (bit v & 31 of word v >> 5: id v is a member), or both None when no line has a set."""
+
+    def __init__(self, lo, hi, set_of, sets, sent, V):
+        self.lo, self.hi, self.set_of, self.sets, self.sent, self.V = lo, hi, set_of, sets, sent, V
+
+    @property
+    def rows(self):
+        return self.lo.shape[0]
+
+    def repeat(self, k):
+        """Every row k times in place of itself (the beams of a prompt share its constraints)."""
+        rep = lambda a: None if a is None else np.repeat(a, k, axis=0)      # noqa: E731
+        return LineTables(rep(self.lo), rep(self.hi), rep(self.set_of), self.sets, self.sent, self.V)
+
+    def bounds(self, b, l):
+        """(lo, hi, end set as a frozenset or None) of row b's line l; a line past the table is unconstrained."""
+        if l >= self.lo.shape[1]:
+            return 0, self.sent - 2, None
+        s = -1 if self.set_of is None else int(self.set_of[b, l])
+        return int(self.lo[b, l]), int(self.hi[b, l]), self.members(s) if s >= 0 else None
+
+    def members(self, s):
+        """Set s of the table as a frozenset of ids."""
+        cache = self.__dict__.setdefault("_members", {})
+        if s not in cache:
+            w = self.sets[s]
+            cache[s] = frozenset(v for v in range(32 * len(w)) if (int(w[v >> 5]) >> (v & 31)) & 1)
+        return cache[s]
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _is_ids(e):
+    return isinstance(e, (set, frozenset)) or (isinstance(e, (list, tuple, np.ndarray)) and all(_is_int(v) for v in e))
+
+
+def _per_row(spec, rows, what, whole, per_row_form):
+    """spec as one list of per-line entries per row (or the marker ("all", entry): that entry on every line).  spec is None (no
+    entries), one entry for every line (`whole(spec)`), one list for all rows, or one list, entry or None per row
+    (`per_row_form(spec)`)."""
+    if spec is None:
+        return [[] for _ in range(rows)]
+    if whole(spec):
+        return [("all", spec)] * rows
+    if not isinstance(spec, (list, tuple)):
+        raise ValueError("%s: a list of per-line entries (or one list per row) expected, got %r" % (what, spec))
+    if per_row_form(spec):
+        if len(spec) != rows:
+            raise ValueError("%s has %d rows, the generation %d" % (what, len(spec), rows))
+        out = []
+        for r in spec:
+            if r is not None and not whole(r) and not isinstance(r, (list, tuple)):
+                raise ValueError("%s: a row is None, one entry or a list of per-line entries, got %r" % (what, r))
+            out.append([] if r is None else ("all", r) if whole(r) else list(r))
+        return out
+    return [list(spec)] * rows
+
+
+def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefix=None):
+    """Validate line-length bounds and line-end id sets on the host, before any device work; returns the packed LineTables, or
+    None when both arguments are None (no constraints: the decoders then run the launches of a generation without them).
+
+    A generation of `length` holds n_lines = (length - 1) // sent + 1 lines (those with a content column); line l of row b is
+    lyric columns l * sent .. l * sent + sent - 1 and holds up to sent - 2 content tokens.
+    line_lengths: a line's entry is an int (exactly that many content tokens), a (lo, hi) tuple or None (unconstrained, the
+    same as (0, sent - 2)).  Given as one entry (every line of every row), one list of entries (line by line, for every row; a
+    shorter list leaves the later lines unconstrained) or a list with one such list, entry or None per row (the lists, not tuples,
+    mark this form).
+    line_end_ids: a line's entry is None or a non-empty collection of content ids below the vocabulary cut V (no PAD, none of
+    1, 2, 100, 102): the line's last content token is one of them, so the line is not empty and its hi must be >= 1.  Given as
+    one set / frozenset (every line), one list of entries, or one list of entries (or None) per row.
+    prefix (check_prefix's result, optional): a row whose prefix stops inside a line continues that line under its bounds; given
+    content beyond the line's hi raises.  Whole given lines are the caller's text and are not checked.
+    Raises ValueError for bounds outside 0 .. sent - 2, lo > hi, more entries than lines, and any end set that breaks the above."""
+    if line_lengths is None and line_end_ids is None:
+        return None
+    if length < 1 or not 3 <= sent <= 257:
+        raise ValueError("line constraints need length >= 1 and 3 <= sent <= 257 (got length %d, sent %d)" % (length, sent))
+    n_lines, cap = (length - 1) // sent + 1, sent - 2
+    is_len = lambda e: _is_int(e) or (isinstance(e, tuple) and len(e) == 2)                     # noqa: E731
+    lens = _per_row(line_lengths, rows, "line_lengths", is_len,
+                    lambda s: any(isinstance(e, list) for e in s))
+    ends = _per_row(line_end_ids, rows, "line_end_ids", lambda e: isinstance(e, (set, frozenset)),
+                    lambda s: any(isinstance(e, (list, tuple)) and not _is_ids(e) for e in s))
+    lo = np.zeros((rows, n_lines), np.uint8)
+    hi = np.full((rows, n_lines), cap, np.uint8)
+    set_of = np.full((rows, n_lines), -1, np.int16)
+    table, seen = [], {}
+    for b in range(rows):
+        for what, spec in (("line_lengths", lens[b]), ("line_end_ids", ends[b])):
+            if isinstance(spec, tuple) and spec and spec[0] == "all":
+                spec = [spec[1]] * n_lines
+            if len(spec) > n_lines:
+                raise ValueError("%s row %d has %d lines, a generation of length %d holds %d" % (what, b, len(spec), length, n_lines))
+            for l, e in enumerate(spec):
+                if e is None:
+                    continue
+                if what == "line_lengths":
+                    pair = (e, e) if _is_int(e) else e
+                    if not (isinstance(pair, tuple) and len(pair) == 2 and all(_is_int(v) for v in pair)):
+                        raise ValueError("line_lengths row %d, line %d: an int, a (lo, hi) tuple or None expected, got %r" % (b, l, e))
+                    a, z = int(pair[0]), int(pair[1])
+                    if not 0 <= a <= z <= cap:
+                        raise ValueError("line_lengths row %d, line %d: (%d, %d) is not 0 <= lo <= hi <= %d (sent - 2)" % (b, l, a, z, cap))
+                    lo[b, l], hi[b, l] = a, z
+                else:
+                    if not _is_ids(e) or (isinstance(e, np.ndarray) and e.ndim != 1) or not all(_is_int(v) for v in e):
+                        raise ValueError("line_end_ids row %d, line %d: a collection of ids or None expected, got %r" % (b, l, e))
+                    ids = frozenset(int(v) for v in e)
+                    if not ids:
+                        raise ValueError("line_end_ids row %d, line %d: the end set is empty" % (b, l))
+                    for v in sorted(ids):
+                        if v == 0 or v in BANNED or v < 0 or (V is not None and v >= V):
+                            raise ValueError("line_end_ids row %d, line %d: id %d is not a content id below the vocabulary cut" % (b, l, v))
+                    if ids not in seen:
+                        seen[ids] = len(table)
+                        table.append(ids)
+                    if seen[ids] > 32767:
+                        raise ValueError("line_end_ids: more than 32768 distinct end sets")
+                    set_of[b, l] = seen[ids]
+        for l in range(n_lines):
+            if set_of[b, l] >= 0 and hi[b, l] == 0:
+                raise ValueError("line_end_ids row %d, line %d: an end set on a line with hi = 0" % (b, l))
+        if prefix is not None:
+            p = prefix[b]
+            l, q = (len(p) - 1) // sent, (len(p) - 1) % sent
+            if 1 <= q <= cap and l < n_lines:                        # the prefix stops inside line l: q content columns are given
+                given = sum(1 for v in p[l * sent + 1:] if v != 0)
+                if given > hi[b, l]:
+                    raise ValueError("prefix row %d gives %d content tokens of line %d, more than its hi = %d" % (b, given, l, hi[b, l]))
+    sets = None
+    if table:
+        if V is None:
+            V = max(max(t) for t in table) + 1
+        sets = np.zeros((len(table), (V + 31) // 32), np.uint32)
+        for i, t in enumerate(table):
+            for v in t:
+                sets[i, v >> 5] |= np.uint32(1 << (v & 31))
+    return LineTables(lo, hi, set_of if table else None, sets, sent, V)
+
+
 def _placement_ok(dev):
     """True when a 256-workgroup, one-per-CU launch puts workgroups b and b + 8 k on one XCD, 32 per XCD (census kernel, once per
     device and process): what the plain hand-off of mmtg_decode_mlp relies on (the launch itself re-checks every group)."""
@@ -239,6 +384,10 @@ class GreedyDecoder:
         self.use_fixed = False      # this generation has a prefix: the step ends in the *_fixed selection entries
         self.min_fixed = 0          # min over rows of fixed_end (a step below it appends nothing: no head needed)
         self.ngram = 0              # no_repeat_ngram_size: > 0 ends every step that calls the head in the *_ngram selection entries
+        # line constraints (line_lengths= / line_end_ids=): the device tables (lo, hi, sets or None, set_of or None) of this
+        # decoder's rows; not None ends every step that calls the head in the *_lines selection entries
+        self.lines = None
+        self._line_buf = None       # (lo, hi, set_of) [B, lines of max_len] and the growing `sets` buffer: fixed addresses for the graphs
 
     def _conv1d(self, x, wkey, out, **kw):
         # bf16: Engine._fwd routes Conv1D weights through their [out,in] copies (NT layout), which is
@@ -302,6 +451,9 @@ class GreedyDecoder:
         eng, sh, B = self.eng, self.eng.sh, self.B
         temperature, rep, top_k, top_p = self.params
         sent = sh.msl + 2
+        if self.lines is not None and with_head:
+            self._select_lines()
+            return
         if self.ngram and with_head:
             self._select_ngram()
             return
@@ -349,6 +501,59 @@ class GreedyDecoder:
         else:
             hip.decode_sample_ngram(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep, top_k, top_p,
                                     self.uniforms, B, self.ngram, fixed_end=fe, pos_next=self.pos_next)
+
+    def _select_lines(self):
+        """_select of a step that calls the head under line constraints: the same launch through the *_lines entries (the *_ngram
+        entries, n possibly 0, plus the line-length bounds and line-end sets of include/mmtg_hip.h)."""
+        eng, sh, B = self.eng, self.eng.sh, self.B
+        temperature, rep, top_k, top_p = self.params
+        sent, Vp = sh.msl + 2, eng.layout.Vpad
+        fe = self.fixed_end if self.use_fixed else None
+        if top_k == 1 and top_p == 0.0:
+            hip.decode_select_lines(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep, B, self.lines,
+                                    ngram=self.ngram, fixed_end=fe, pos_next=self.pos_next)
+        else:
+            hip.decode_sample_lines(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep, top_k, top_p,
+                                    self.uniforms, B, self.lines, ngram=self.ngram, fixed_end=fe, pos_next=self.pos_next)
+
+    def _upload_lines(self, tables):
+        """The line tables into this decoder's device buffers (allocated once, so captured graphs keep their addresses; a `sets`
+        buffer that has to grow drops the graphs captured on the old one) and every lane's view of its own rows."""
+        if tables is None:
+            for d in [self] + self.children:
+                d.lines = None
+            return
+        sh, dev, B = self.eng.sh, self.eng.dev, self.B
+        sent = sh.msl + 2
+        ml = (self.max_len - 1) // sent + 1
+        if self._line_buf is None:
+            self._line_buf = [torch.zeros(B, ml, dtype=torch.uint8, device=dev), torch.zeros(B, ml, dtype=torch.uint8, device=dev),
+                              torch.zeros(B, ml, dtype=torch.int16, device=dev), None]
+        lo, hi, set_of, sets = self._line_buf
+        n = tables.lo.shape[1]
+
+        def padded(a, fill, dtype):
+            full = np.full((B, ml), fill, dtype)
+            full[:, :n] = a
+            return torch.from_numpy(full)
+        lo.copy_(padded(tables.lo, 0, np.uint8))
+        hi.copy_(padded(tables.hi, sent - 2, np.uint8))
+        if tables.sets is not None:
+            need = tables.sets.shape[0]
+            if sets is None or sets.shape[0] < need:
+                cap = 16
+                while cap < need:
+                    cap *= 2
+                sets = self._line_buf[3] = torch.zeros(cap, tables.sets.shape[1], dtype=torch.int32, device=dev)
+                self.graphs = {k: g for k, g in self.graphs.items() if "lines" not in k}
+            sets.zero_()
+            sets[:need].copy_(torch.from_numpy(tables.sets.view(np.int32)))
+            set_of.copy_(padded(tables.set_of, -1, np.int16))
+        for i, d in enumerate([self] if not self.children else self.children):
+            a, z = i * d.B, (i + 1) * d.B
+            d.lines = (lo[a:z], hi[a:z], sets, set_of[a:z]) if tables.sets is not None else (lo[a:z], hi[a:z], None, None)
+        if self.children:
+            self.lines = (lo, hi, sets, set_of) if tables.sets is not None else (lo, hi, None, None)
 
     def _step_x3(self, with_head):
         """The split-precision token step: embedding -> projector -> 12 blocks -> head, every product through mmtg_decode_gemm_x3
@@ -536,6 +741,8 @@ class GreedyDecoder:
             self._step(with_head, parity)
             return
         key = (with_head, parity, self.params) + (("prefix",) if self.use_fixed else ()) + (("ngram", self.ngram) if self.ngram else ())
+        if self.lines is not None and with_head:            # (a step without the head runs the launches it always ran)
+            key += ("lines", "sets" if self.lines[2] is not None else "bounds")
         g = self.graphs.get(key)
         if g is None:
             # warm-up outside capture (lazy LDS-attribute / module loading), then rewind the position
@@ -579,7 +786,7 @@ class GreedyDecoder:
 
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
-              no_repeat_ngram_size=0):
+              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None):
         """Everything of a generation that happens once: the settings, the uniforms of a stochastic run, fresh weight copies /
         LayerNorm folds, the experience encoder, the prompt (prefilled in one batched pass: ``first_pos`` = P afterwards) and the
         reset position.  Returns the end position n; ``step_at(pos)`` for pos = first_pos .. n - 1 then runs the token steps (``generate`` does both; tools/decode_lanes_threads.py drives
@@ -592,7 +799,12 @@ class GreedyDecoder:
 
         no_repeat_ngram_size (check_ngram): n > 0 makes every step that calls the head end in the *_ngram selection entries, so no
         row writes a content n-gram it already holds (prefix columns count as history).  0 runs exactly the launches and graphs of a
-        generation without the argument."""
+        generation without the argument.
+
+        line_lengths / line_end_ids (check_lines states the forms and the rule's home is include/mmtg_hip.h): per-row, per-line
+        bounds on the number of content tokens and sets the last content token of a line comes from.  With either given, every
+        step that calls the head ends in the *_lines selection entries; the tables are uploaded here, once.  None for both runs
+        exactly the launches and graphs of a generation without them.  (line_lengths may also be a LineTables, taken as checked.)"""
         eng, sh = self.eng, self.eng.sh
         B = batch["img_embs"].shape[0]
         if B != self.B:
@@ -601,6 +813,12 @@ class GreedyDecoder:
             raise ValueError("length %d exceeds max_len %d" % (length, self.max_len))
         ngram = check_ngram(no_repeat_ngram_size, sh.msl + 2)
         pre = None if prefix is None else check_prefix(prefix, B, length, sent=sh.msl + 2, V=sh.V)
+        if isinstance(line_lengths, LineTables):
+            if line_lengths.rows != B or line_end_ids is not None:
+                raise ValueError("line tables of %d rows for a batch of %d (and no line_end_ids beside them)" % (line_lengths.rows, B))
+            tables = line_lengths
+        else:
+            tables = check_lines(line_lengths, line_end_ids, B, length, sent=sh.msl + 2, V=min(sh.V, 13317), prefix=pre)
         self.params = (float(temperature), float(repitition_penalty), int(top_k), float(top_p))
         if not (int(top_k) == 1 and float(top_p) == 0.0):
             if self.uniforms is None:
@@ -626,6 +844,7 @@ class GreedyDecoder:
         for d in [self] + self.children:            # (a lane's _select reads its own flags and its slice of fixed_end)
             d.use_fixed = pre is not None
             d.ngram = ngram
+        self._upload_lines(tables)
         self.min_fixed = 0
         if pre is not None:
             lens = [len(p) for p in pre]
@@ -696,7 +915,7 @@ class GreedyDecoder:
 
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None,
-                 use_graph=None, teacher=None, tap=None, prefix=None, no_repeat_ngram_size=0):
+                 use_graph=None, teacher=None, tap=None, prefix=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None):
         """batch: dict with topic_ids/tpw_* [B,P], topic_emb, img_embs, r_embs (no targets needed).
         Runs `length` iterations of the reference loop and returns the lyric ids
         [B, 1 + length] (column 0 is the initial [#START#]).  top_k = 1, top_p = 0 is the greedy setting;
@@ -708,9 +927,12 @@ class GreedyDecoder:
         prefix: the opening lyric ids of every row (``begin``, ``check_prefix``); columns 0 .. L_b - 1 of row b's result are its
         prefix, the rest follows the rules above (the penalty counts the prefix).
         no_repeat_ngram_size: n > 0 bans, at every model-chosen column, each id that would repeat a content n-gram of the row
-        (``begin``, include/mmtg_hip.h); 0 (the default) is off."""
+        (``begin``, include/mmtg_hip.h); 0 (the default) is off.
+        line_lengths / line_end_ids: the form of the lyric (``check_lines``): line_lengths=7 makes every line seven content
+        tokens long, line_lengths=(1, 20) forbids empty lines, line_end_ids=[None, ids, None, ids] ends lines 1 and 3 on one of
+        ids.  A line is full at its hi (the row pads from there), cannot end below its lo, and with an end set ends on a member."""
         n_steps = self.begin(batch, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix,
-                             no_repeat_ngram_size=no_repeat_ngram_size)
+                             no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths, line_end_ids=line_end_ids)
         eng, sh = self.eng, self.eng.sh
         saved_mode = self.use_graph
         if use_graph is not None:
@@ -786,10 +1008,15 @@ class BeamDecoder(GreedyDecoder):
         eng, sh, B = self.eng, self.eng.sh, self.B
         temperature, rep, _, _ = self.params
         sent = sh.msl + 2
-        if self.ngram and with_head:             # the bans act in the candidates; the merge is the prefix-aware one or the plain one
-            hip.decode_beam_candidates_ngram(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature,
-                                             rep, self.nb, self.cand_val, self.cand_id, B, self.ngram,
-                                             fixed_end=self.fixed_end if self.use_fixed else None)
+        if (self.ngram or self.lines is not None) and with_head:
+            # the bans (and a full line's PAD, offered as sticky PAD is) act in the candidates; the merge is the prefix-aware one or the plain one
+            fe = self.fixed_end if self.use_fixed else None
+            if self.lines is not None:
+                hip.decode_beam_candidates_lines(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature,
+                                                 rep, self.nb, self.cand_val, self.cand_id, B, self.lines, ngram=self.ngram, fixed_end=fe)
+            else:
+                hip.decode_beam_candidates_ngram(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature,
+                                                 rep, self.nb, self.cand_val, self.cand_id, B, self.ngram, fixed_end=fe)
             if self.use_fixed:
                 hip.decode_beam_merge_fixed(self.cand_val, self.cand_id, self.scores, self.seq, self.keep, self.rows, self.pos, sh.P, sent,
                                             self.nb, self.n_prompts, self.fixed_end, pos_next=self.pos_next)
@@ -819,20 +1046,29 @@ class BeamDecoder(GreedyDecoder):
 
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
-              no_repeat_ngram_size=0):
-        """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill and the prefix: one per
-        prompt), the ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at
+              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None):
+        """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill, the prefix and the line
+        constraints: one per prompt), the ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at
         the free positions after a prompt's prefix."""
         n = batch["img_embs"].shape[0]
         if n != self.n_prompts:
             raise ValueError("decoder was built for %d prompts, got %d" % (self.n_prompts, n))
         check_ngram(no_repeat_ngram_size, self.eng.sh.msl + 2)
+        sh = self.eng.sh
         if prefix is not None:
-            sh = self.eng.sh
-            prefix = [p for p in check_prefix(prefix, n, length, sent=sh.msl + 2, V=sh.V) for _ in range(self.nb)]
+            prefix = check_prefix(prefix, n, length, sent=sh.msl + 2, V=sh.V)
+        if not isinstance(line_lengths, LineTables):
+            line_lengths = check_lines(line_lengths, line_end_ids, n, length, sent=sh.msl + 2, V=min(sh.V, 13317), prefix=prefix)
+            line_end_ids = None
+        elif line_lengths.rows != n or line_end_ids is not None:
+            raise ValueError("line tables of %d rows for %d prompts (and no line_end_ids beside them)" % (line_lengths.rows, n))
+        if line_lengths is not None:
+            line_lengths = line_lengths.repeat(self.nb)
+        if prefix is not None:
+            prefix = [p for p in prefix for _ in range(self.nb)]
         rep = {k: (v.repeat_interleave(self.nb, 0) if torch.is_tensor(v) else v) for k, v in batch.items()}
         n_steps = super().begin(rep, length, temperature, repitition_penalty, 1, 0.0, prefix=prefix,
-                                no_repeat_ngram_size=no_repeat_ngram_size)
+                                no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths, line_end_ids=line_end_ids)
         B, dev = self.B, self.eng.dev
         self.rows.copy_(torch.arange(B, dtype=torch.int32, device=dev)[:, None].expand(B, self.Tmax))
         sc = torch.full((n, self.nb), float("-inf"), dtype=torch.float32, device=dev)
@@ -841,13 +1077,15 @@ class BeamDecoder(GreedyDecoder):
         return n_steps
 
     @torch.no_grad()
-    def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None, no_repeat_ngram_size=0):
+    def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None, no_repeat_ngram_size=0,
+                 line_lengths=None, line_end_ids=None):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_beams, 1 + length] in
         GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row.
         prefix: one per prompt (check_prefix), shared by its beams.  no_repeat_ngram_size: as GreedyDecoder.generate, per beam
-        on its own (reordered) history."""
+        on its own (reordered) history.  line_lengths / line_end_ids: as GreedyDecoder.generate, one per prompt, shared by its beams."""
         ids = super().generate(batch, length, temperature=temperature, repitition_penalty=repitition_penalty, use_graph=use_graph,
-                               prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size)
+                               prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths,
+                               line_end_ids=line_end_ids)
         n, nb = self.n_prompts, self.nb
         ids = ids.view(n, nb, -1)
         sc = self.scores.view(n, nb).clone()

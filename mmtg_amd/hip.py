@@ -113,6 +113,11 @@ _SIGS = {
     "mmtg_decode_select_ngram": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_sample_ngram": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_beam_candidates_ngram": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp], _i),
+    "mmtg_decode_select_lines": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp], _i),
+    "mmtg_decode_sample_lines": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i,
+                                 _vp, _vp], _i),
+    "mmtg_decode_beam_candidates_lines": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
+                                          _vp, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
     "mmtg_decode_mlp_sync_words": ([], _i),
     "mmtg_decode_mlp_census": ([_vp, _vp], _i),
@@ -907,6 +912,47 @@ def decode_beam_candidates_ngram(logits, ldl, V, seq, pos, P, sent, temperature,
     _check(lib().mmtg_decode_beam_candidates_ngram(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
                                                    float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B, _fixed(fixed_end, B),
                                                    int(ngram), _stream()), "decode_beam_candidates_ngram")
+
+
+def _lines(tables, B, V):
+    """The line tables of decode.check_lines on the device, (lo, hi, sets or None, set_of or None), as the *_lines entries' trailing
+    arguments (lo, hi, n_lines, sets, n_sets, set_of); shapes and dtypes are checked here, the values by check_lines."""
+    lo, hi, sets, set_of = tables
+    if not (lo.dtype == torch.uint8 and hi.dtype == torch.uint8 and lo.dim() == 2 and lo.shape == hi.shape and lo.shape[0] >= B
+            and lo.is_contiguous() and hi.is_contiguous()):
+        raise ValueError("line tables: lo / hi must be contiguous uint8 [rows >= %d, n_lines]" % B)
+    if (sets is None) != (set_of is None):
+        raise ValueError("line tables: sets and set_of come together")
+    n_sets = 0
+    if sets is not None:
+        if not (sets.dtype == torch.int32 and sets.dim() == 2 and sets.shape[1] == (V + 31) // 32 and sets.is_contiguous()):
+            raise ValueError("line tables: sets must be contiguous int32 [n_sets, ceil(V / 32) = %d]" % ((V + 31) // 32))
+        if not (set_of.dtype == torch.int16 and set_of.shape == lo.shape and set_of.is_contiguous()):
+            raise ValueError("line tables: set_of must be contiguous int16 of lo's shape")
+        n_sets = sets.shape[0]
+    return _p(lo), _p(hi), lo.shape[1], _p(sets), n_sets, _p(set_of)
+
+
+def decode_select_lines(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, tables, ngram=0, fixed_end=None, pos_next=None):
+    """decode_select_ngram (ngram may be 0) under the line-length bounds and line-end sets of `tables` (include/mmtg_hip.h)."""
+    _check(lib().mmtg_decode_select_lines(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                          float(rep_penalty), B, _p(pos_next), _fixed(fixed_end, B), int(ngram), *_lines(tables, B, V),
+                                          _stream()), "decode_select_lines")
+
+
+def decode_sample_lines(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, tables, ngram=0,
+                        fixed_end=None, pos_next=None):
+    _check(lib().mmtg_decode_sample_lines(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                          float(rep_penalty), int(top_k), float(top_p), _p(uniforms), uniforms.stride(0), B, _p(pos_next),
+                                          _fixed(fixed_end, B), int(ngram), *_lines(tables, B, V), _stream()), "decode_sample_lines")
+
+
+def decode_beam_candidates_lines(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, tables, ngram=0,
+                                 fixed_end=None):
+    """decode_beam_candidates_ngram (ngram may be 0) under the line rule: a full line offers PAD the way sticky PAD does."""
+    _check(lib().mmtg_decode_beam_candidates_lines(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                                   float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B, _fixed(fixed_end, B),
+                                                   int(ngram), *_lines(tables, B, V), _stream()), "decode_beam_candidates_lines")
 
 
 def decode_advance(pos):
