@@ -33,6 +33,8 @@ __device__ __forceinline__ float penalize(float x, int c, float rep_penalty) {
 
 // one logit through the reference's processor (generate.py:127-136), folded into the running arg-max (lowest index wins ties)
 // LN (the line forms, ban_line): PAD reads its slot too, which ban_line has set to 0 (no penalty, as ever) or to the sentinel
+// (sample_row and beam_candidates_kernel restate the processing in their own loops, and the kernels below the block arg-max and
+// the count / ban sequence: as shared functions they compile to other code, profiles/r11_select_rule_disassembly_diff.txt)
 template <bool NG = false, bool LN = false>
 __device__ __forceinline__ void scan_one(float x, int v, const unsigned* cnt, float temperature, float rep_penalty, float& best, int& besti) {
     if ((LN || v != 0) && v != 102) {
@@ -1087,30 +1089,44 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void de
                          (int)blockIdx.x, (int)blockIdx.y, (int)threadIdx.x, lds, oplanes, oplane, rows, ldrows);
 }
 
-// Prefixed generation: the selection kernels below take an optional trailing `const int* fixed_end` (the kernel templates' pack
-// Fixed: empty for the plain forms, so their parameter lists and code are what they were; one pointer for the *_fixed forms).  Row b
-// with pos + 1 < fixed_end[b] sits on a column the host has written (a prefix token): the row leaves seq[b, pos + 1] alone and
-// offers no beam candidates; the position is still published.
-template <typename... Fixed>
-__device__ __forceinline__ bool prefix_column(int b, int pos, Fixed... fixed_end) {
-    if constexpr (sizeof...(Fixed) == 0) return false;
-    else return pos + 1 < (fixed_end[b], ...);
-}
+// The selection kernels below end in one argument, the step's rule R: NoRule (the plain entries), FixedEnd (*_fixed), NgramBan
+// (*_ngram) or LineRule (*_lines).  A rule says which rows it holds (held) and, with R::ngram (the sentinel of penalize<true> is
+// in use; bans() gives the NgramBan) and R::lines (PAD's slot is read; col() says what the line wants of a free column), which
+// edits of the occurrence table the kernel makes after count_ids.
+//
+// Prefixed generation: row b with pos + 1 < fixed_end[b] sits on a column the host has written (a prefix token).  The rule holds
+// the row: it leaves seq[b, pos + 1] alone and offers no beam candidates; the position is still published.
 
-// n-gram blocking (the *_ngram entries, include/mmtg_hip.h): the pack is one NgramBan instead.  Its fixed_end is optional (null: no
-// prefix).  After count_ids, ban_ngrams marks every id that would complete a content n-gram the row already holds with the sentinel
-// count 0xFFFF (a banned id has occurred, so its slot is non-zero; no real count reaches 0xFFFF since MAXGEN < 65535), and the
-// processing reads the sentinel as -inf (penalize<true>) with no extra LDS read per logit.
+// what a line rule says of row b's free column j (uniform over the workgroup: every thread computes the same)
+struct LineCol {
+    bool force_pad;          // c >= hi: the row writes PAD, no logits consulted
+    bool pad_ban;            // c < lo, or an end set whose members do not include the previous token
+    const unsigned* mask;    // c == hi - 1 of a line with an end set: the set's bit row (else null)
+};
+
+struct NoRule {
+    static constexpr bool ngram = false, lines = false;
+    __device__ __forceinline__ bool held(int, int) const { return false; }
+};
+
+struct FixedEnd {
+    const int* fixed_end;   // int32 [B]
+    static constexpr bool ngram = false, lines = false;
+    __device__ __forceinline__ bool held(int b, int pos) const { return pos + 1 < fixed_end[b]; }
+};
+
+// n-gram blocking (the *_ngram entries, include/mmtg_hip.h).  Its fixed_end is optional (null: no prefix).  After count_ids,
+// ban_ngrams marks every id that would complete a content n-gram the row already holds with the sentinel count 0xFFFF (a banned id
+// has occurred, so its slot is non-zero; no real count reaches 0xFFFF since MAXGEN < 65535), and the processing reads the sentinel
+// as -inf (penalize<true>) with no extra LDS read per logit.
 struct NgramBan {
     const int* fixed_end;   // int32 [B] or null
     int n;                  // 1 .. sent - 2
     int hist_cap;           // ints of dynamic LDS for the staged history (>= the longest history, min(ldseq - P, MAXGEN))
+    static constexpr bool ngram = true, lines = false;
+    __device__ __forceinline__ bool held(int b, int pos) const { return fixed_end && pos + 1 < fixed_end[b]; }
+    __host__ __device__ __forceinline__ const NgramBan& bans() const { return *this; }
 };
-
-template <typename... Fixed> constexpr bool is_ngram = (std::is_same<Fixed, NgramBan>::value || ... || false);
-template <typename... Fixed> __host__ __device__ __forceinline__ NgramBan ngram_of(Fixed... e) { return (e, ...); }
-
-__device__ __forceinline__ bool prefix_column(int b, int pos, NgramBan ng) { return ng.fixed_end && pos + 1 < ng.fixed_end[b]; }
 
 // PAD, [#START#], [#EOS#], [UNK], [SEP] are not content: they break n-grams
 __device__ __forceinline__ bool ngram_content(int v) { return v != 0 && v != 1 && v != 2 && v != 100 && v != 102; }
@@ -1135,8 +1151,8 @@ __device__ __forceinline__ void ban_ngrams(unsigned* cnt, int* h, int V, const l
     __syncthreads();
 }
 
-// Line-length bounds and line-end sets (the *_lines entries, include/mmtg_hip.h): the pack is one LineRule -- an NgramBan whose n may
-// be 0 (no n-gram bans) plus the per-row, per-line tables.  Lyric index j sits on line l = j / sent at content column
+// Line-length bounds and line-end sets (the *_lines entries, include/mmtg_hip.h): an NgramBan whose n may be 0 (no n-gram bans;
+// the line bans use its sentinel) plus the per-row, per-line tables.  Lyric index j sits on line l = j / sent at content column
 // c = j % sent - 1; a line past n_lines is unconstrained (lo 0, hi sent - 2, no set).
 struct LineRule {
     NgramBan ng;                   // fixed_end optional; n = 0: no n-gram bans (hist_cap 0)
@@ -1145,37 +1161,29 @@ struct LineRule {
     const short* set_of;           // [B, n_lines] row of `sets` (-1: no end set), or null
     const unsigned* sets;          // [n_sets, words] bit v of a row: content id v is in the set
     int n_lines, n_sets, words;    // words >= ceil(V / 32)
-};
+    static constexpr bool ngram = true, lines = true;
+    __device__ __forceinline__ bool held(int b, int pos) const { return ng.held(b, pos); }
+    __host__ __device__ __forceinline__ const NgramBan& bans() const { return ng; }
 
-template <typename... Fixed> constexpr bool is_lines = (std::is_same<Fixed, LineRule>::value || ... || false);
-template <typename... Fixed> __host__ __device__ __forceinline__ LineRule lines_of(Fixed... e) { return (e, ...); }
-__host__ __device__ __forceinline__ NgramBan ngram_of(LineRule lr) { return lr.ng; }
-__device__ __forceinline__ bool prefix_column(int b, int pos, LineRule lr) { return prefix_column(b, pos, lr.ng); }
-
-// what the rule says of row b's free column j (uniform over the workgroup: every thread computes the same)
-struct LineCol {
-    bool force_pad;          // c >= hi: the row writes PAD, no logits consulted
-    bool pad_ban;            // c < lo, or an end set whose members do not include the previous token
-    const unsigned* mask;    // c == hi - 1 of a line with an end set: the set's bit row (else null)
-};
-__device__ __forceinline__ LineCol line_col(const LineRule& lr, int b, int j, int sent, const long long* gen) {
-    LineCol lc = {false, false, nullptr};
-    const int l = j / sent, c = j % sent - 1;
-    if (l >= lr.n_lines) return lc;
-    const long at = (long)b * lr.n_lines + l;
-    const int lo = lr.lo[at], hi = lr.hi[at];
-    const int s = lr.set_of ? (int)lr.set_of[at] : -1;
-    lc.force_pad = c >= hi;
-    lc.pad_ban = c < lo;
-    if (s >= 0 && s < lr.n_sets && !lc.force_pad) {
-        const unsigned* m = lr.sets + (long)s * lr.words;
-        const long long prev = gen[j - 1];
-        const bool in = prev >= 0 && prev < 32LL * lr.words && ((m[prev >> 5] >> (prev & 31)) & 1u);
-        lc.pad_ban = lc.pad_ban || !in;
-        if (c == hi - 1) lc.mask = m;
+    __device__ __forceinline__ LineCol col(int b, int j, int sent, const long long* gen) const {
+        LineCol lc = {false, false, nullptr};
+        const int l = j / sent, c = j % sent - 1;
+        if (l >= n_lines) return lc;
+        const long at = (long)b * n_lines + l;
+        const int lo_ = lo[at], hi_ = hi[at];
+        const int s = set_of ? (int)set_of[at] : -1;
+        lc.force_pad = c >= hi_;
+        lc.pad_ban = c < lo_;
+        if (s >= 0 && s < n_sets && !lc.force_pad) {
+            const unsigned* m = sets + (long)s * words;
+            const long long prev = gen[j - 1];
+            const bool in = prev >= 0 && prev < 32LL * words && ((m[prev >> 5] >> (prev & 31)) & 1u);
+            lc.pad_ban = lc.pad_ban || !in;
+            if (c == hi_ - 1) lc.mask = m;
+        }
+        return lc;
     }
-    return lc;
-}
+};
 
 // The line bans as edits of the occurrence table, after count_ids / ban_ngrams (all threads of the block call): at the end-set
 // column every id outside the set gets the sentinel 0xFFFF (the specials among them are -inf anyway); PAD's slot, which the plain
@@ -1192,11 +1200,11 @@ __device__ __forceinline__ void ban_line(unsigned* cnt, int V, const LineCol& lc
 }
 
 // logits processor + arg-max + forced-token cadence + append (generate.py:117-142), device-driven.
-template <typename... Fixed>
+template <typename R>
 __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restrict__ logits, long ldl, int V,
         long long* __restrict__ seq, long ldseq, const int* __restrict__ pos_ptr, int P, int sent,
         float temperature, float rep_penalty, int have_logits, int top_k, float top_p,
-        const float* __restrict__ uniforms, long ldu, int* __restrict__ pos_next, Fixed... fixed_end) {
+        const float* __restrict__ uniforms, long ldu, int* __restrict__ pos_next, R rule) {
     extern __shared__ unsigned cnt[];
     __shared__ float sval[4];
     __shared__ int sidx[4];
@@ -1204,7 +1212,7 @@ __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restr
     // the step's last kernel also publishes the next position -- into the OTHER slot of the decoder's position pair (every
     // kernel of this step reads *pos_ptr; nobody reads *pos_next before the next step), which replaces a one-thread launch
     if (pos_next && b == 0 && tid == 0) *pos_next = pos + 1;
-    if (prefix_column(b, pos, fixed_end...)) return;
+    if (rule.held(b, pos)) return;
     const int j = pos + 1 - P;                 // lyric index of the token to append
     if (j < 1) return;                         // still inside the prompt / the initial [#START#]
     long long* gen = seq + (long)b * ldseq + P;
@@ -1213,30 +1221,28 @@ __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restr
     if (!have_logits) return;
     const int n = min(j, MAXGEN);
     if (gen[n - 1] == 0) { if (tid == 0) gen[j] = 0; return; }                   // sticky PAD
-    constexpr bool LN = is_lines<Fixed...>;
-    constexpr bool NG = is_ngram<Fixed...> || LN;          // (the line bans use the n-gram sentinel)
     LineCol lc = {false, false, nullptr};
-    if constexpr (LN) {
-        lc = line_col(lines_of(fixed_end...), b, j, sent, gen);
+    if constexpr (R::lines) {
+        lc = rule.col(b, j, sent, gen);
         if (lc.force_pad) { if (tid == 0) gen[j] = 0; return; }                  // the line is full: PAD, as sticky PAD writes it
     }
     count_ids(cnt, V, gen, n, tid);
-    if constexpr (NG) {        // after the (V + 1) / 2 count words and, when sampling, the V-float row image
-        const NgramBan ng = ngram_of(fixed_end...);
-        if (!LN || ng.n > 0)
+    if constexpr (R::ngram) {  // after the (V + 1) / 2 count words and, when sampling, the V-float row image
+        const NgramBan ng = rule.bans();
+        if (!R::lines || ng.n > 0)
             ban_ngrams(cnt, reinterpret_cast<int*>(cnt + (V + 1) / 2 + (uniforms ? V : 0)), V, gen, min(n, ng.hist_cap), ng.n, tid);
     }
-    if constexpr (LN) ban_line(cnt, V, lc, tid);
+    if constexpr (R::lines) ban_line(cnt, V, lc, tid);
     if (uniforms) {            // stochastic: uniforms[pos, b] drives the draw (top_k == 1 and top_p == 0 is the greedy path)
         float* px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
-        const int pick = sample_row<NG, LN>(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k, top_p,
-                                        uniforms[(long)pos * ldu + b], tid, nullptr);
+        const int pick = sample_row<R::ngram, R::lines>(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k, top_p,
+                                                        uniforms[(long)pos * ldu + b], tid, nullptr);
         if (tid == 0) gen[j] = pick;
         return;
     }
     float best;
     int besti;
-    scan_row<NG, LN>(logits + (long)b * ldl, V, cnt, temperature, rep_penalty, tid, best, besti);
+    scan_row<R::ngram, R::lines>(logits + (long)b * ldl, V, cnt, temperature, rep_penalty, tid, best, besti);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(best, o, 64);
@@ -1268,10 +1274,10 @@ constexpr int BEAM_TW = 64;        // columns of seq / keep / rows staged per pa
 
 __device__ __forceinline__ bool beam_forced(int j, int sent) { return j > 1 && ((j + 1) % sent == 0 || (j + 1) % sent == 1); }
 
-template <typename... Fixed>
+template <typename R>
 __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __restrict__ logits, long ldl, int V,
         const long long* __restrict__ seq, long ldseq, const int* __restrict__ pos_ptr, int P, int sent,
-        float temperature, float rep_penalty, int nb, float* __restrict__ cand_val, int* __restrict__ cand_id, Fixed... fixed_end) {
+        float temperature, float rep_penalty, int nb, float* __restrict__ cand_val, int* __restrict__ cand_id, R rule) {
     extern __shared__ unsigned cnt[];          // (V + 1) / 2 count words | V processed logits
     float* const px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
     __shared__ float sval[4], sx[BEAM_MAX];
@@ -1279,7 +1285,7 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __res
     const int b = blockIdx.x, tid = threadIdx.x, pos = *pos_ptr;
     const int j = pos + 1 - P;
     if (j < 1 || beam_forced(j, sent)) return;             // the merge appends the forced token without candidates
-    if (prefix_column(b, pos, fixed_end...)) return;       // a prefix column: nothing to offer (the merge keeps the prompt)
+    if (rule.held(b, pos)) return;                         // a prefix column: nothing to offer (the merge keeps the prompt)
     float* const cv = cand_val + (long)b * nb;
     int* const ci = cand_id + (long)b * nb;
     const long long* gen = seq + (long)b * ldseq + P;
@@ -1288,29 +1294,27 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __res
         if (tid < nb) { cv[tid] = tid == 0 ? 0.f : -INFINITY; ci[tid] = 0; }
         return;
     }
-    constexpr bool LN = is_lines<Fixed...>;
-    constexpr bool NG = is_ngram<Fixed...> || LN;
     LineCol lc = {false, false, nullptr};
-    if constexpr (LN) {
-        lc = line_col(lines_of(fixed_end...), b, j, sent, gen);
+    if constexpr (R::lines) {
+        lc = rule.col(b, j, sent, gen);
         if (lc.force_pad) {                                // the line is full: PAD with the score unchanged, as sticky PAD offers it
             if (tid < nb) { cv[tid] = tid == 0 ? 0.f : -INFINITY; ci[tid] = 0; }
             return;
         }
     }
     count_ids(cnt, V, gen, n, tid);
-    if constexpr (NG) {        // after the count words and the V processed logits
-        const NgramBan ng = ngram_of(fixed_end...);
-        if (!LN || ng.n > 0) ban_ngrams(cnt, reinterpret_cast<int*>(px + V), V, gen, min(n, ng.hist_cap), ng.n, tid);
+    if constexpr (R::ngram) {  // after the count words and the V processed logits
+        const NgramBan ng = rule.bans();
+        if (!R::lines || ng.n > 0) ban_ngrams(cnt, reinterpret_cast<int*>(px + V), V, gen, min(n, ng.hist_cap), ng.n, tid);
     }
-    if constexpr (LN) ban_line(cnt, V, lc, tid);
+    if constexpr (R::lines) ban_line(cnt, V, lc, tid);
     const float* row = logits + (long)b * ldl;
     float mx = -INFINITY;
     for (int v = tid; v < V; v += 256) {
         float x = row[v];
-        if ((LN || v != 0) && v != 102) {
+        if ((R::lines || v != 0) && v != 102) {
             const int c = (cnt[v >> 1] >> (16 * (v & 1))) & 0xFFFF;
-            x = penalize<NG>(x, c, rep_penalty);
+            x = penalize<R::ngram>(x, c, rep_penalty);
         }
         x = x / temperature;
         if (v == 1 || v == 2 || v == 100 || v == 102) x = -INFINITY;
@@ -1362,11 +1366,11 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __res
     }
 }
 
-template <typename... Fixed>
+template <typename R>
 __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_id,
         float* __restrict__ scores, long long* __restrict__ seq, long ldseq, int* __restrict__ keep, long ldkeep,
         int* __restrict__ rows, long ldrows, const int* __restrict__ pos_ptr, int P, int sent, int nb, int* __restrict__ pos_next,
-        Fixed... fixed_end) {
+        R rule) {
     __shared__ float sc[BEAM_MAX * BEAM_MAX];
     __shared__ float s_sc[BEAM_MAX];
     __shared__ int s_par[BEAM_MAX], s_tok[BEAM_MAX];
@@ -1376,7 +1380,7 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
     if (pos_next && g == 0 && tid == 0) *pos_next = pos + 1;
     const int j = pos + 1 - P;
     const bool next_ok = pos + 1 < ldrows;
-    if (prefix_column(b0, pos, fixed_end...)) {             // the prompt's prefix column (one prefix per prompt): keep every beam,
+    if (rule.held(b0, pos)) {                               // the prompt's prefix column (one prefix per prompt): keep every beam,
         if (tid < nb && next_ok) rows[(long)(b0 + tid) * ldrows + pos + 1] = b0 + tid;       // its score and its host-written token
         return;
     }
@@ -1541,11 +1545,43 @@ extern "C" int mmtg_decode_attn_split_rows(int dtype, const float* part, int spl
     return MMTG_OK;
 }
 
-// (the launches of the plain and the *_fixed selection entries: `fe` is empty for the plain ones, the prefix ends for the others)
-template <typename... Fixed>
+// ---- the selection entries: one launch helper per kernel, taking the entry's rule (NoRule{} for the plain ones)
+
+// dynamic LDS of a selection launch: the count words, the V-float row image (sampling, beam candidates), the rule's staged history
+template <typename R>
+static size_t select_lds(int V, bool row_image, const R& rule) {
+    size_t shm = (size_t)((V + 1) / 2) * 4 + (row_image ? (size_t)V * 4 : 0);
+    if constexpr (R::ngram) shm += (size_t)rule.bans().hist_cap * 4;
+    return shm;
+}
+
+template <typename R>
+static int decode_select_launch(const char* what, const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                                const float* uniforms, long ldu, int B, int* pos_next, void* stream, R rule) {
+    MMTG_REQUIRE(seq && pos_ptr && B > 0 && sent > 1, "%s: bad args", what);
+    MMTG_REQUIRE(pos_next != pos_ptr, "%s: pos_next must not alias pos_ptr (blocks read the position while block 0 writes the next)", what);
+    MMTG_REQUIRE(!logits || (V > 0 && ldl >= V && temperature > 0.f && rep_penalty > 0.f), "%s: bad logits args", what);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, 4.0 * B * V, 4.0 * B * V);
+    MMTG_REQUIRE(!logits || V <= (uniforms ? 24000 : 30000), "%s: vocabulary of %d exceeds the LDS tables", what, V);
+    const size_t shm = logits ? select_lds(V, uniforms != nullptr, rule) : 0;
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute((const void*)decode_select_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
+            MMTG_FAIL(MMTG_ERR_HIP, "%s: cannot raise dynamic LDS", what);
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(decode_select_kernel<R>, dim3(B), dim3(256), shm, s, logits, ldl, V, seq, ldseq,
+                       pos_ptr, P, sent, temperature, rep_penalty, logits != nullptr, top_k, top_p, logits ? uniforms : nullptr, ldu, pos_next, rule);
+    MMTG_LAUNCH_CHECK(what);
+    return MMTG_OK;
+}
+
+template <typename R>
 static int beam_candidates_launch(const char* what, const float* logits, long ldl, int V, const long long* seq, long ldseq,
                                   const int* pos_ptr, int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val,
-                                  int* cand_id, int B, void* stream, Fixed... fe) {
+                                  int* cand_id, int B, void* stream, R rule) {
     MMTG_REQUIRE(nb >= 1 && nb <= BEAM_MAX, "%s: %d beams per prompt (1..%d)", what, nb, BEAM_MAX);
     MMTG_REQUIRE(logits && seq && pos_ptr && cand_val && cand_id && B > 0 && sent > 1 && V > 0 && ldl >= V,
                  "%s: bad args", what);
@@ -1553,49 +1589,38 @@ static int beam_candidates_launch(const char* what, const float* logits, long ld
     MMTG_REQUIRE(V <= 24000, "%s: vocabulary of %d exceeds the LDS row image (24000)", what, V);
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(MMTG_PROF_DECODE, s, 4.0 * B * V, 4.0 * B * V);
-    size_t shm = (size_t)((V + 1) / 2) * 4 + (size_t)V * 4;
-    if constexpr (is_ngram<Fixed...> || is_lines<Fixed...>) shm += (size_t)ngram_of(fe...).hist_cap * 4;     // the staged history
     static bool attr_done = false;
     if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)beam_candidates_kernel<Fixed...>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
+        if (hipFuncSetAttribute((const void*)beam_candidates_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
             MMTG_FAIL(MMTG_ERR_HIP, "%s: cannot raise dynamic LDS", what);
         attr_done = true;
     }
-    hipLaunchKernelGGL(beam_candidates_kernel<Fixed...>, dim3(B), dim3(256), shm, s, logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature,
-                       rep_penalty, nb, cand_val, cand_id, fe...);
+    hipLaunchKernelGGL(beam_candidates_kernel<R>, dim3(B), dim3(256), select_lds(V, true, rule), s, logits, ldl, V, seq, ldseq, pos_ptr, P, sent,
+                       temperature, rep_penalty, nb, cand_val, cand_id, rule);
     MMTG_LAUNCH_CHECK(what);
     return MMTG_OK;
 }
 
-template <typename... Fixed>
+template <typename R>
 static int beam_merge_launch(const char* what, const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
                              long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
-                             int* pos_next, void* stream, Fixed... fe) {
+                             int* pos_next, void* stream, R rule) {
     MMTG_REQUIRE(nb >= 1 && nb <= BEAM_MAX, "%s: %d beams per prompt (1..%d)", what, nb, BEAM_MAX);
     MMTG_REQUIRE(scores && seq && keep && rows && pos_ptr && n_prompts > 0 && sent > 1 && ldrows > 0 && (!cand_val || cand_id),
                  "%s: bad args", what);
     MMTG_REQUIRE(pos_next != pos_ptr, "%s: pos_next must not alias pos_ptr", what);
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(MMTG_PROF_DECODE, s, (double)n_prompts * nb * nb, 32.0 * n_prompts * nb * (double)ldrows);
-    hipLaunchKernelGGL(beam_merge_kernel<Fixed...>, dim3(n_prompts), dim3(256), 0, s, cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows,
-                       ldrows, pos_ptr, P, sent, nb, pos_next, fe...);
+    hipLaunchKernelGGL(beam_merge_kernel<R>, dim3(n_prompts), dim3(256), 0, s, cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows,
+                       ldrows, pos_ptr, P, sent, nb, pos_next, rule);
     MMTG_LAUNCH_CHECK(what);
     return MMTG_OK;
 }
 
-extern "C" int mmtg_decode_beam_candidates(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
-                                           int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
-                                           int B, void* stream) {
-    return beam_candidates_launch("decode_beam_candidates", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, nb,
-                                  cand_val, cand_id, B, stream);
-}
-
-extern "C" int mmtg_decode_beam_candidates_fixed(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
-                                                 int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
-                                                 int B, const int* fixed_end, void* stream) {
-    MMTG_REQUIRE(fixed_end, "decode_beam_candidates_fixed: null fixed_end");
-    return beam_candidates_launch("decode_beam_candidates_fixed", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
-                                  nb, cand_val, cand_id, B, stream, fixed_end);
+// (what every sample_* entry asks of its own arguments)
+static int sample_args_check(const char* what, const float* uniforms, long ldu, int B, int top_k, float top_p) {
+    MMTG_REQUIRE(uniforms && ldu >= B && top_k >= 0 && top_p >= 0.f, "%s: uniforms [positions, ldu >= B], top_k >= 0, top_p >= 0", what);
+    return MMTG_OK;
 }
 
 // (the checks every *_ngram entry makes before its launch; the history fits MAXGEN ints of LDS, which the V limits leave room for)
@@ -1607,67 +1632,56 @@ static int ngram_check(const char* what, const float* logits, long ldseq, int P,
     return MMTG_OK;
 }
 
-extern "C" int mmtg_decode_beam_candidates_ngram(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
-                                                 int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
-                                                 int B, const int* fixed_end, int ngram, void* stream) {
+// (the checks every *_lines entry makes before its launch, and its rule; ngram 0 stages no history)
+static int lines_check(const char* what, const float* logits, int V, long ldseq, int P, int sent, const int* fixed_end, int ngram,
+                       const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
+                       const short* set_of, LineRule* lr) {
+    MMTG_REQUIRE(logits, "%s: the line form needs logits", what);
+    MMTG_REQUIRE(sent > 2 && ngram >= 0 && ngram <= sent - 2, "%s: n-gram size %d outside 0..%d (sent - 2)", what, ngram, sent - 2);
+    MMTG_REQUIRE(lo && hi && n_lines >= 1, "%s: lo / hi [B, n_lines >= 1] needed (n_lines %d)", what, n_lines);
+    MMTG_REQUIRE(n_sets >= 0 && (n_sets > 0) == (sets != nullptr) && (n_sets > 0) == (set_of != nullptr),
+                 "%s: end sets need sets, set_of and n_sets > 0 together (n_sets %d)", what, n_sets);
     int cap = 0;
-    if (int e = ngram_check("decode_beam_candidates_ngram", logits, ldseq, P, sent, ngram, &cap)) return e;
-    return beam_candidates_launch("decode_beam_candidates_ngram", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
-                                  nb, cand_val, cand_id, B, stream, NgramBan{fixed_end, ngram, cap});
-}
-
-extern "C" int mmtg_decode_beam_merge(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
-                                      long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
-                                      int* pos_next, void* stream) {
-    return beam_merge_launch("decode_beam_merge", cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows, ldrows, pos_ptr, P, sent, nb,
-                             n_prompts, pos_next, stream);
-}
-
-extern "C" int mmtg_decode_beam_merge_fixed(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
-                                            long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
-                                            int* pos_next, const int* fixed_end, void* stream) {
-    MMTG_REQUIRE(fixed_end, "decode_beam_merge_fixed: null fixed_end");
-    return beam_merge_launch("decode_beam_merge_fixed", cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows, ldrows, pos_ptr, P, sent,
-                             nb, n_prompts, pos_next, stream, fixed_end);
-}
-
-template <typename... Fixed>
-static int decode_select_launch(const char* what, const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
-                                int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
-                                const float* uniforms, long ldu, int B, int* pos_next, void* stream, Fixed... fe) {
-    MMTG_REQUIRE(seq && pos_ptr && B > 0 && sent > 1, "%s: bad args", what);
-    MMTG_REQUIRE(pos_next != pos_ptr, "%s: pos_next must not alias pos_ptr (blocks read the position while block 0 writes the next)", what);
-    MMTG_REQUIRE(!logits || (V > 0 && ldl >= V && temperature > 0.f && rep_penalty > 0.f), "%s: bad logits args", what);
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(MMTG_PROF_DECODE, s, 4.0 * B * V, 4.0 * B * V);
-    MMTG_REQUIRE(!logits || V <= (uniforms ? 24000 : 30000), "%s: vocabulary of %d exceeds the LDS tables", what, V);
-    size_t shm = logits ? (size_t)((V + 1) / 2) * 4 : 0;
-    if (logits && uniforms) shm += (size_t)V * 4;
-    if constexpr (is_ngram<Fixed...> || is_lines<Fixed...>) shm += (size_t)ngram_of(fe...).hist_cap * 4;     // the staged history
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute((const void*)decode_select_kernel<Fixed...>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
-            MMTG_FAIL(MMTG_ERR_HIP, "%s: cannot raise dynamic LDS", what);
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(decode_select_kernel<Fixed...>, dim3(B), dim3(256), shm, s, logits, ldl, V, seq, ldseq,
-                       pos_ptr, P, sent, temperature, rep_penalty, logits != nullptr, top_k, top_p, logits ? uniforms : nullptr, ldu, pos_next, fe...);
-    MMTG_LAUNCH_CHECK(what);
+    if (ngram > 0) {
+        if (int e = ngram_check(what, logits, ldseq, P, sent, ngram, &cap)) return e;
+    } else MMTG_REQUIRE(ldseq > P && P >= 0, "%s: bad sequence layout (ldseq %ld, P %d)", what, ldseq, P);
+    *lr = LineRule{NgramBan{fixed_end, ngram, cap}, lo, hi, set_of, sets, n_lines, n_sets, (V + 31) / 32};
     return MMTG_OK;
 }
 
 extern "C" int mmtg_decode_select(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
                                   int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, void* stream) {
     return decode_select_launch("decode_select", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, 1, 0.f, nullptr, 0, B,
-                                pos_next, stream);
+                                pos_next, stream, NoRule{});
 }
 
 extern "C" int mmtg_decode_sample(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
                                   int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
                                   const float* uniforms, long ldu, int B, int* pos_next, void* stream) {
-    MMTG_REQUIRE(uniforms && ldu >= B && top_k >= 0 && top_p >= 0.f, "decode_sample: uniforms [positions, ldu >= B], top_k >= 0, top_p >= 0");
+    if (int e = sample_args_check("decode_sample", uniforms, ldu, B, top_k, top_p)) return e;
     return decode_select_launch("decode_select", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p, uniforms,
-                                ldu, B, pos_next, stream);
+                                ldu, B, pos_next, stream, NoRule{});
+}
+
+extern "C" int mmtg_decode_advance(int* pos_ptr, void* stream) {
+    MMTG_REQUIRE(pos_ptr, "decode_advance: null pointer");
+    hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos_ptr);
+    MMTG_LAUNCH_CHECK("decode_advance");
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_beam_candidates(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                           int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                           int B, void* stream) {
+    return beam_candidates_launch("decode_beam_candidates", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, nb,
+                                  cand_val, cand_id, B, stream, NoRule{});
+}
+
+extern "C" int mmtg_decode_beam_merge(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
+                                      long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
+                                      int* pos_next, void* stream) {
+    return beam_merge_launch("decode_beam_merge", cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows, ldrows, pos_ptr, P, sent, nb,
+                             n_prompts, pos_next, stream, NoRule{});
 }
 
 extern "C" int mmtg_decode_select_fixed(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
@@ -1675,17 +1689,32 @@ extern "C" int mmtg_decode_select_fixed(const float* logits, long ldl, int V, lo
                                         void* stream) {
     MMTG_REQUIRE(fixed_end, "decode_select_fixed: null fixed_end");
     return decode_select_launch("decode_select_fixed", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, 1, 0.f, nullptr,
-                                0, B, pos_next, stream, fixed_end);
+                                0, B, pos_next, stream, FixedEnd{fixed_end});
 }
 
 extern "C" int mmtg_decode_sample_fixed(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
                                         int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
                                         const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, void* stream) {
     MMTG_REQUIRE(fixed_end, "decode_sample_fixed: null fixed_end");
-    MMTG_REQUIRE(uniforms && ldu >= B && top_k >= 0 && top_p >= 0.f,
-                 "decode_sample_fixed: uniforms [positions, ldu >= B], top_k >= 0, top_p >= 0");
+    if (int e = sample_args_check("decode_sample_fixed", uniforms, ldu, B, top_k, top_p)) return e;
     return decode_select_launch("decode_select_fixed", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p,
-                                uniforms, ldu, B, pos_next, stream, fixed_end);
+                                uniforms, ldu, B, pos_next, stream, FixedEnd{fixed_end});
+}
+
+extern "C" int mmtg_decode_beam_candidates_fixed(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                                 int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                                 int B, const int* fixed_end, void* stream) {
+    MMTG_REQUIRE(fixed_end, "decode_beam_candidates_fixed: null fixed_end");
+    return beam_candidates_launch("decode_beam_candidates_fixed", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
+                                  nb, cand_val, cand_id, B, stream, FixedEnd{fixed_end});
+}
+
+extern "C" int mmtg_decode_beam_merge_fixed(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
+                                            long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
+                                            int* pos_next, const int* fixed_end, void* stream) {
+    MMTG_REQUIRE(fixed_end, "decode_beam_merge_fixed: null fixed_end");
+    return beam_merge_launch("decode_beam_merge_fixed", cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows, ldrows, pos_ptr, P, sent,
+                             nb, n_prompts, pos_next, stream, FixedEnd{fixed_end});
 }
 
 extern "C" int mmtg_decode_select_ngram(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
@@ -1703,27 +1732,18 @@ extern "C" int mmtg_decode_sample_ngram(const float* logits, long ldl, int V, lo
                                         void* stream) {
     int cap = 0;
     if (int e = ngram_check("decode_sample_ngram", logits, ldseq, P, sent, ngram, &cap)) return e;
-    MMTG_REQUIRE(uniforms && ldu >= B && top_k >= 0 && top_p >= 0.f,
-                 "decode_sample_ngram: uniforms [positions, ldu >= B], top_k >= 0, top_p >= 0");
+    if (int e = sample_args_check("decode_sample_ngram", uniforms, ldu, B, top_k, top_p)) return e;
     return decode_select_launch("decode_sample_ngram", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p,
                                 uniforms, ldu, B, pos_next, stream, NgramBan{fixed_end, ngram, cap});
 }
 
-// (the checks every *_lines entry makes before its launch, and its pack; ngram 0 stages no history)
-static int lines_check(const char* what, const float* logits, int V, long ldseq, int P, int sent, const int* fixed_end, int ngram,
-                       const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
-                       const short* set_of, LineRule* lr) {
-    MMTG_REQUIRE(logits, "%s: the line form needs logits", what);
-    MMTG_REQUIRE(sent > 2 && ngram >= 0 && ngram <= sent - 2, "%s: n-gram size %d outside 0..%d (sent - 2)", what, ngram, sent - 2);
-    MMTG_REQUIRE(lo && hi && n_lines >= 1, "%s: lo / hi [B, n_lines >= 1] needed (n_lines %d)", what, n_lines);
-    MMTG_REQUIRE(n_sets >= 0 && (n_sets > 0) == (sets != nullptr) && (n_sets > 0) == (set_of != nullptr),
-                 "%s: end sets need sets, set_of and n_sets > 0 together (n_sets %d)", what, n_sets);
+extern "C" int mmtg_decode_beam_candidates_ngram(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                                 int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                                 int B, const int* fixed_end, int ngram, void* stream) {
     int cap = 0;
-    if (ngram > 0) {
-        if (int e = ngram_check(what, logits, ldseq, P, sent, ngram, &cap)) return e;
-    } else MMTG_REQUIRE(ldseq > P && P >= 0, "%s: bad sequence layout (ldseq %ld, P %d)", what, ldseq, P);
-    *lr = LineRule{NgramBan{fixed_end, ngram, cap}, lo, hi, set_of, sets, n_lines, n_sets, (V + 31) / 32};
-    return MMTG_OK;
+    if (int e = ngram_check("decode_beam_candidates_ngram", logits, ldseq, P, sent, ngram, &cap)) return e;
+    return beam_candidates_launch("decode_beam_candidates_ngram", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
+                                  nb, cand_val, cand_id, B, stream, NgramBan{fixed_end, ngram, cap});
 }
 
 extern "C" int mmtg_decode_select_lines(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
@@ -1745,8 +1765,7 @@ extern "C" int mmtg_decode_sample_lines(const float* logits, long ldl, int V, lo
     LineRule lr;
     if (int e = lines_check("decode_sample_lines", logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, &lr))
         return e;
-    MMTG_REQUIRE(uniforms && ldu >= B && top_k >= 0 && top_p >= 0.f,
-                 "decode_sample_lines: uniforms [positions, ldu >= B], top_k >= 0, top_p >= 0");
+    if (int e = sample_args_check("decode_sample_lines", uniforms, ldu, B, top_k, top_p)) return e;
     return decode_select_launch("decode_sample_lines", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p,
                                 uniforms, ldu, B, pos_next, stream, lr);
 }
@@ -1761,13 +1780,6 @@ extern "C" int mmtg_decode_beam_candidates_lines(const float* logits, long ldl, 
         return e;
     return beam_candidates_launch("decode_beam_candidates_lines", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
                                   nb, cand_val, cand_id, B, stream, lr);
-}
-
-extern "C" int mmtg_decode_advance(int* pos_ptr, void* stream) {
-    MMTG_REQUIRE(pos_ptr, "decode_advance: null pointer");
-    hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos_ptr);
-    MMTG_LAUNCH_CHECK("decode_advance");
-    return MMTG_OK;
 }
 
 extern "C" int mmtg_ln_fold_weights(const void* W, long ldw, const float* gamma, const float* beta, const float* bias, void* Wf,

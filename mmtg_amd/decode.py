@@ -220,6 +220,31 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
     return LineTables(lo, hi, set_of if table else None, sets, sent, V)
 
 
+def select_forms(with_head, prefix, ngram, lines):
+    """Which selection entries a token step ends in: (form of mmtg_decode_select / _sample or mmtg_decode_beam_candidates, form of
+    mmtg_decode_beam_merge), each "" (plain), "_fixed", "_ngram" or "_lines".  with_head: the step calls the model's head; prefix:
+    the generation has one; ngram: no_repeat_ngram_size; lines: line constraints are given.  The bans act where logits are read, so
+    a step without the head (select with null logits; no candidates launch, merge with null candidates) and every merge only know
+    the prefix -- a generation without constraints runs the plain entries throughout."""
+    held = "_fixed" if prefix else ""
+    if not with_head:
+        return held, held
+    return ("_lines" if lines else "_ngram" if ngram else held), held
+
+
+def _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, rows, length, sh, what):
+    """The constraint arguments of ``begin`` for `rows` rows (`what` names them in messages): (n-gram size, checked prefix or None,
+    LineTables or None).  A LineTables given as line_lengths is taken as checked."""
+    sent = sh.msl + 2
+    ngram = check_ngram(no_repeat_ngram_size, sent)
+    pre = None if prefix is None else check_prefix(prefix, rows, length, sent=sent, V=sh.V)
+    if not isinstance(line_lengths, LineTables):
+        return ngram, pre, check_lines(line_lengths, line_end_ids, rows, length, sent=sent, V=min(sh.V, 13317), prefix=pre)
+    if line_lengths.rows != rows or line_end_ids is not None:
+        raise ValueError("line tables of %d rows for %s (and no line_end_ids beside them)" % (line_lengths.rows, what))
+    return ngram, pre, line_lengths
+
+
 def _placement_ok(dev):
     """True when a 256-workgroup, one-per-CU launch puts workgroups b and b + 8 k on one XCD, 32 per XCD (census kernel, once per
     device and process): what the plain hand-off of mmtg_decode_mlp relies on (the launch itself re-checks every group)."""
@@ -447,82 +472,25 @@ class GreedyDecoder:
         self._select(with_head)
 
     def _select(self, with_head):
-        """The step's last launch: logits processing + arg-max / draw + the forced cadence + the next position (generate.py:117-142)."""
-        eng, sh, B = self.eng, self.eng.sh, self.B
+        """The step's last launch: logits processing + arg-max / draw + the forced cadence + the next position (generate.py:117-142),
+        through the entry select_forms names: the *_fixed ones leave row b's column pos + 1 alone while pos + 1 < fixed_end[b] (the
+        host wrote it), the *_ngram ones also ban every id that would complete a content n-gram the row already holds, the *_lines
+        ones (n possibly 0) add the line-length bounds and line-end sets of include/mmtg_hip.h."""
+        sh = self.eng.sh
         temperature, rep, top_k, top_p = self.params
-        sent = sh.msl + 2
-        if self.lines is not None and with_head:
-            self._select_lines()
-            return
-        if self.ngram and with_head:
-            self._select_ngram()
-            return
-        if self.use_fixed:
-            self._select_fixed(with_head)
-            return
-        if with_head:
-            Vp = eng.layout.Vpad
-            if top_k == 1 and top_p == 0.0:
-                hip.decode_select(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep, B,
-                                  pos_next=self.pos_next)
-            else:        # stochastic: the draw of each position reads its row of the pre-filled uniforms
-                hip.decode_sample(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep,
-                                  top_k, top_p, self.uniforms, B, pos_next=self.pos_next)
-        else:
-            hip.decode_select(None, 0, 0, self.seq, self.pos, sh.P, sent, temperature, rep, B, pos_next=self.pos_next)
-
-    def _select_fixed(self, with_head):
-        """_select of a prefixed generation: the same launch through the *_fixed entries, which leave row b's column pos + 1 alone
-        while pos + 1 < fixed_end[b] (the host wrote it)."""
-        eng, sh, B = self.eng, self.eng.sh, self.B
-        temperature, rep, top_k, top_p = self.params
-        sent = sh.msl + 2
-        if with_head:
-            Vp = eng.layout.Vpad
-            if top_k == 1 and top_p == 0.0:
-                hip.decode_select_fixed(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep, B,
-                                        self.fixed_end, pos_next=self.pos_next)
-            else:
-                hip.decode_sample_fixed(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep,
-                                        top_k, top_p, self.uniforms, B, self.fixed_end, pos_next=self.pos_next)
-        else:
-            hip.decode_select_fixed(None, 0, 0, self.seq, self.pos, sh.P, sent, temperature, rep, B, self.fixed_end, pos_next=self.pos_next)
-
-    def _select_ngram(self):
-        """_select of a step that calls the head with no_repeat_ngram_size = self.ngram: the same launch through the *_ngram entries,
-        which also ban every id that would complete a content n-gram the row already holds (and hold prefix columns, if any)."""
-        eng, sh, B = self.eng, self.eng.sh, self.B
-        temperature, rep, top_k, top_p = self.params
-        sent, Vp = sh.msl + 2, eng.layout.Vpad
-        fe = self.fixed_end if self.use_fixed else None
-        if top_k == 1 and top_p == 0.0:
-            hip.decode_select_ngram(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep, B, self.ngram,
-                                    fixed_end=fe, pos_next=self.pos_next)
-        else:
-            hip.decode_sample_ngram(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep, top_k, top_p,
-                                    self.uniforms, B, self.ngram, fixed_end=fe, pos_next=self.pos_next)
-
-    def _select_lines(self):
-        """_select of a step that calls the head under line constraints: the same launch through the *_lines entries (the *_ngram
-        entries, n possibly 0, plus the line-length bounds and line-end sets of include/mmtg_hip.h)."""
-        eng, sh, B = self.eng, self.eng.sh, self.B
-        temperature, rep, top_k, top_p = self.params
-        sent, Vp = sh.msl + 2, eng.layout.Vpad
-        fe = self.fixed_end if self.use_fixed else None
-        if top_k == 1 and top_p == 0.0:
-            hip.decode_select_lines(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep, B, self.lines,
-                                    ngram=self.ngram, fixed_end=fe, pos_next=self.pos_next)
-        else:
-            hip.decode_sample_lines(self.logits, Vp, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep, top_k, top_p,
-                                    self.uniforms, B, self.lines, ngram=self.ngram, fixed_end=fe, pos_next=self.pos_next)
+        form, _ = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None)
+        logits, ldl, V = (self.logits, self.eng.layout.Vpad, min(sh.V, 13317)) if with_head else (None, 0, 0)
+        # stochastic: the draw of each position reads its row of the pre-filled uniforms
+        sampling = (top_k, top_p, self.uniforms) if with_head and not (top_k == 1 and top_p == 0.0) else None
+        hip._select(form, logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, self.B, self.pos_next, sampling,
+                    fixed_end=self.fixed_end if self.use_fixed else None, ngram=self.ngram, tables=self.lines)
 
     def _upload_lines(self, tables):
         """The line tables into this decoder's device buffers (allocated once, so captured graphs keep their addresses; a `sets`
-        buffer that has to grow drops the graphs captured on the old one) and every lane's view of its own rows."""
+        buffer that has to grow drops the graphs captured on the old one).  Returns them as the *_lines entries take them, (lo, hi,
+        sets or None, set_of or None) over all rows, or None without tables."""
         if tables is None:
-            for d in [self] + self.children:
-                d.lines = None
-            return
+            return None
         sh, dev, B = self.eng.sh, self.eng.dev, self.B
         sent = sh.msl + 2
         ml = (self.max_len - 1) // sent + 1
@@ -549,11 +517,7 @@ class GreedyDecoder:
             sets.zero_()
             sets[:need].copy_(torch.from_numpy(tables.sets.view(np.int32)))
             set_of.copy_(padded(tables.set_of, -1, np.int16))
-        for i, d in enumerate([self] if not self.children else self.children):
-            a, z = i * d.B, (i + 1) * d.B
-            d.lines = (lo[a:z], hi[a:z], sets, set_of[a:z]) if tables.sets is not None else (lo[a:z], hi[a:z], None, None)
-        if self.children:
-            self.lines = (lo, hi, sets, set_of) if tables.sets is not None else (lo, hi, None, None)
+        return (lo, hi, sets, set_of) if tables.sets is not None else (lo, hi, None, None)
 
     def _step_x3(self, with_head):
         """The split-precision token step: embedding -> projector -> 12 blocks -> head, every product through mmtg_decode_gemm_x3
@@ -740,9 +704,7 @@ class GreedyDecoder:
         if not self.use_graph:
             self._step(with_head, parity)
             return
-        key = (with_head, parity, self.params) + (("prefix",) if self.use_fixed else ()) + (("ngram", self.ngram) if self.ngram else ())
-        if self.lines is not None and with_head:            # (a step without the head runs the launches it always ran)
-            key += ("lines", "sets" if self.lines[2] is not None else "bounds")
+        key = self._graph_key(with_head, parity)
         g = self.graphs.get(key)
         if g is None:
             # warm-up outside capture (lazy LDS-attribute / module loading), then rewind the position
@@ -759,6 +721,14 @@ class GreedyDecoder:
             for t, v in zip(state, saved):
                 t.copy_(v)
         g.replay()
+
+    def _graph_key(self, with_head, parity):
+        """What the step's launches depend on: the settings, and the constraints as far as select_forms lets them reach this step
+        (a step without the head runs the launches it always ran)."""
+        key = (with_head, parity, self.params) + (("prefix",) if self.use_fixed else ()) + (("ngram", self.ngram) if self.ngram else ())
+        if "_lines" in select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None):
+            key += ("lines", "sets" if self.lines[2] is not None else "bounds")
+        return key
 
     def _step_state(self):
         """What a token step changes besides the caches' slot `pos` (rewound around the warm-up step of a graph capture)."""
@@ -811,14 +781,8 @@ class GreedyDecoder:
             raise ValueError("decoder was built for batch %d, got %d" % (self.B, B))
         if length > self.max_len:
             raise ValueError("length %d exceeds max_len %d" % (length, self.max_len))
-        ngram = check_ngram(no_repeat_ngram_size, sh.msl + 2)
-        pre = None if prefix is None else check_prefix(prefix, B, length, sent=sh.msl + 2, V=sh.V)
-        if isinstance(line_lengths, LineTables):
-            if line_lengths.rows != B or line_end_ids is not None:
-                raise ValueError("line tables of %d rows for a batch of %d (and no line_end_ids beside them)" % (line_lengths.rows, B))
-            tables = line_lengths
-        else:
-            tables = check_lines(line_lengths, line_end_ids, B, length, sent=sh.msl + 2, V=min(sh.V, 13317), prefix=pre)
+        ngram, pre, tables = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, B, length, sh,
+                                                "a batch of %d" % B)
         self.params = (float(temperature), float(repitition_penalty), int(top_k), float(top_p))
         if not (int(top_k) == 1 and float(top_p) == 0.0):
             if self.uniforms is None:
@@ -841,10 +805,13 @@ class GreedyDecoder:
         self.seq[:, :sh.P] = batch["topic_ids"].to(eng.dev).long()
         self.seq[:, sh.P] = 1                                   # [#START#]
         lmin = 1
-        for d in [self] + self.children:            # (a lane's _select reads its own flags and its slice of fixed_end)
-            d.use_fixed = pre is not None
-            d.ngram = ngram
-        self._upload_lines(tables)
+        # the generation's constraints, on the decoder and its lanes: a lane's _select reads its own flags, its slice of fixed_end
+        # (a view since construction) and its rows of the line tables (the sets are shared)
+        lines = self._upload_lines(tables)
+        for i, d in enumerate([self] + self.children):
+            a, z = (0, B) if d is self else ((i - 1) * d.B, i * d.B)
+            d.use_fixed, d.ngram = pre is not None, ngram
+            d.lines = None if lines is None else tuple(t if t is None or t is lines[2] else t[a:z] for t in lines)
         self.min_fixed = 0
         if pre is not None:
             lens = [len(p) for p in pre]
@@ -1005,38 +972,17 @@ class BeamDecoder(GreedyDecoder):
         self.cand_id = torch.zeros(self.B, nb, dtype=torch.int32, device=dev)
 
     def _select(self, with_head):
-        eng, sh, B = self.eng, self.eng.sh, self.B
+        """The step's last two launches, through the entries select_forms names: the bans (and a full line's PAD, offered as sticky
+        PAD is) act in the candidates; the merge is the prefix-aware one or the plain one."""
+        sh = self.eng.sh
         temperature, rep, _, _ = self.params
-        sent = sh.msl + 2
-        if (self.ngram or self.lines is not None) and with_head:
-            # the bans (and a full line's PAD, offered as sticky PAD is) act in the candidates; the merge is the prefix-aware one or the plain one
-            fe = self.fixed_end if self.use_fixed else None
-            if self.lines is not None:
-                hip.decode_beam_candidates_lines(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature,
-                                                 rep, self.nb, self.cand_val, self.cand_id, B, self.lines, ngram=self.ngram, fixed_end=fe)
-            else:
-                hip.decode_beam_candidates_ngram(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature,
-                                                 rep, self.nb, self.cand_val, self.cand_id, B, self.ngram, fixed_end=fe)
-            if self.use_fixed:
-                hip.decode_beam_merge_fixed(self.cand_val, self.cand_id, self.scores, self.seq, self.keep, self.rows, self.pos, sh.P, sent,
-                                            self.nb, self.n_prompts, self.fixed_end, pos_next=self.pos_next)
-            else:
-                hip.decode_beam_merge(self.cand_val, self.cand_id, self.scores, self.seq, self.keep, self.rows, self.pos, sh.P, sent,
-                                      self.nb, self.n_prompts, pos_next=self.pos_next)
-            return
-        if self.use_fixed:
-            if with_head:
-                hip.decode_beam_candidates_fixed(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature,
-                                                 rep, self.nb, self.cand_val, self.cand_id, B, self.fixed_end)
-            hip.decode_beam_merge_fixed(self.cand_val if with_head else None, self.cand_id if with_head else None, self.scores, self.seq,
-                                        self.keep, self.rows, self.pos, sh.P, sent, self.nb, self.n_prompts, self.fixed_end,
-                                        pos_next=self.pos_next)
-            return
+        cand, merge = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None)
+        fe = self.fixed_end if self.use_fixed else None
         if with_head:
-            hip.decode_beam_candidates(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sent, temperature, rep,
-                                       self.nb, self.cand_val, self.cand_id, B)
-        hip.decode_beam_merge(self.cand_val if with_head else None, self.cand_id if with_head else None, self.scores, self.seq, self.keep,
-                              self.rows, self.pos, sh.P, sent, self.nb, self.n_prompts, pos_next=self.pos_next)
+            hip._beam_candidates(cand, self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2, temperature,
+                                 rep, self.nb, self.cand_val, self.cand_id, self.B, fixed_end=fe, ngram=self.ngram, tables=self.lines)
+        hip._beam_merge(merge, self.cand_val if with_head else None, self.cand_id if with_head else None, self.scores, self.seq, self.keep,
+                        self.rows, self.pos, sh.P, sh.msl + 2, self.nb, self.n_prompts, self.pos_next, fixed_end=fe)
 
     def _step_state(self):
         return super()._step_state() + [self.rows, self.scores]
@@ -1053,22 +999,15 @@ class BeamDecoder(GreedyDecoder):
         n = batch["img_embs"].shape[0]
         if n != self.n_prompts:
             raise ValueError("decoder was built for %d prompts, got %d" % (self.n_prompts, n))
-        check_ngram(no_repeat_ngram_size, self.eng.sh.msl + 2)
-        sh = self.eng.sh
-        if prefix is not None:
-            prefix = check_prefix(prefix, n, length, sent=sh.msl + 2, V=sh.V)
-        if not isinstance(line_lengths, LineTables):
-            line_lengths = check_lines(line_lengths, line_end_ids, n, length, sent=sh.msl + 2, V=min(sh.V, 13317), prefix=prefix)
-            line_end_ids = None
-        elif line_lengths.rows != n or line_end_ids is not None:
-            raise ValueError("line tables of %d rows for %d prompts (and no line_end_ids beside them)" % (line_lengths.rows, n))
-        if line_lengths is not None:
-            line_lengths = line_lengths.repeat(self.nb)
+        _, prefix, tables = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, n, length, self.eng.sh,
+                                               "%d prompts" % n)
+        if tables is not None:
+            tables = tables.repeat(self.nb)
         if prefix is not None:
             prefix = [p for p in prefix for _ in range(self.nb)]
         rep = {k: (v.repeat_interleave(self.nb, 0) if torch.is_tensor(v) else v) for k, v in batch.items()}
         n_steps = super().begin(rep, length, temperature, repitition_penalty, 1, 0.0, prefix=prefix,
-                                no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths, line_end_ids=line_end_ids)
+                                no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=tables)
         B, dev = self.B, self.eng.dev
         self.rows.copy_(torch.arange(B, dtype=torch.int32, device=dev)[:, None].expand(B, self.Tmax))
         sc = torch.full((n, self.nb), float("-inf"), dtype=torch.float32, device=dev)

@@ -832,86 +832,12 @@ def decode_attn_split(part, splits, bias, kcache, vcache, keep, pos, out, B, nH,
                                         _p(pos), _p(out), B, nH, dh, Tmax, _stream()), "decode_attn_split")
 
 
-def decode_select(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next=None):
-    _check(lib().mmtg_decode_select(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                    float(rep_penalty), B, _p(pos_next), _stream()), "decode_select")
-
-
-def decode_sample(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, pos_next=None):
-    _check(lib().mmtg_decode_sample(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                    float(rep_penalty), int(top_k), float(top_p), _p(uniforms), uniforms.stride(0), B, _p(pos_next),
-                                    _stream()), "decode_sample")
-
-
-def decode_beam_candidates(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B):
-    """Per row: the nb best (log-probability, id) continuations of the processed logits (include/mmtg_hip.h)."""
-    _check(lib().mmtg_decode_beam_candidates(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                             float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B, _stream()), "decode_beam_candidates")
-
-
-def decode_beam_merge(cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next=None):
-    """Per prompt: keep the nb best candidates, reorder seq / keep / rows in place, append (include/mmtg_hip.h)."""
-    _check(lib().mmtg_decode_beam_merge(_p(cand_val), _p(cand_id), _p(scores), _p(seq), seq.stride(0), _p(keep), keep.stride(0), _p(rows),
-                                        rows.stride(0), _p(pos), P, sent, int(nb), int(n_prompts), _p(pos_next), _stream()),
-           "decode_beam_merge")
-
-
 def _fixed(fixed_end, B):
     """The int32 [>= B] prefix-end array of the *_fixed entries (None is passed on: the library rejects it)."""
     if fixed_end is not None:
-        import torch
         if fixed_end.dtype != torch.int32 or fixed_end.dim() != 1 or fixed_end.numel() < B or not fixed_end.is_contiguous():
             raise ValueError("fixed_end must be a contiguous int32 vector of at least %d entries" % B)
     return _p(fixed_end)
-
-
-def decode_select_fixed(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, fixed_end, pos_next=None):
-    """decode_select that leaves row b's column pos + 1 alone while pos + 1 < fixed_end[b] (a host-written prefix, include/mmtg_hip.h)."""
-    _check(lib().mmtg_decode_select_fixed(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                          float(rep_penalty), B, _p(pos_next), _fixed(fixed_end, B), _stream()), "decode_select_fixed")
-
-
-def decode_sample_fixed(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, fixed_end, pos_next=None):
-    _check(lib().mmtg_decode_sample_fixed(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                          float(rep_penalty), int(top_k), float(top_p), _p(uniforms), uniforms.stride(0), B, _p(pos_next),
-                                          _fixed(fixed_end, B), _stream()), "decode_sample_fixed")
-
-
-def decode_beam_candidates_fixed(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end):
-    """decode_beam_candidates; a row on a prefix column (pos + 1 < fixed_end[b]) offers nothing."""
-    _check(lib().mmtg_decode_beam_candidates_fixed(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                                   float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B, _fixed(fixed_end, B),
-                                                   _stream()), "decode_beam_candidates_fixed")
-
-
-def decode_beam_merge_fixed(cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, fixed_end, pos_next=None):
-    """decode_beam_merge; a prompt on a prefix column keeps every beam, score and token (include/mmtg_hip.h)."""
-    _check(lib().mmtg_decode_beam_merge_fixed(_p(cand_val), _p(cand_id), _p(scores), _p(seq), seq.stride(0), _p(keep), keep.stride(0),
-                                              _p(rows), rows.stride(0), _p(pos), P, sent, int(nb), int(n_prompts), _p(pos_next),
-                                              _fixed(fixed_end, n_prompts * nb), _stream()), "decode_beam_merge_fixed")
-
-
-def decode_select_ngram(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, ngram, fixed_end=None, pos_next=None):
-    """decode_select that never writes a content n-gram (n = ngram) the row already holds (include/mmtg_hip.h); fixed_end: as
-    decode_select_fixed, or None (no prefix)."""
-    _check(lib().mmtg_decode_select_ngram(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                          float(rep_penalty), B, _p(pos_next), _fixed(fixed_end, B), int(ngram), _stream()),
-           "decode_select_ngram")
-
-
-def decode_sample_ngram(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, ngram, fixed_end=None,
-                        pos_next=None):
-    _check(lib().mmtg_decode_sample_ngram(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                          float(rep_penalty), int(top_k), float(top_p), _p(uniforms), uniforms.stride(0), B, _p(pos_next),
-                                          _fixed(fixed_end, B), int(ngram), _stream()), "decode_sample_ngram")
-
-
-def decode_beam_candidates_ngram(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, ngram,
-                                 fixed_end=None):
-    """decode_beam_candidates with the n-gram bans of decode_select_ngram applied before the log_softmax and the top nb."""
-    _check(lib().mmtg_decode_beam_candidates_ngram(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                                   float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B, _fixed(fixed_end, B),
-                                                   int(ngram), _stream()), "decode_beam_candidates_ngram")
 
 
 def _lines(tables, B, V):
@@ -933,26 +859,116 @@ def _lines(tables, B, V):
     return _p(lo), _p(hi), lo.shape[1], _p(sets), n_sets, _p(set_of)
 
 
+def _rule_tail(form, B, V, fixed_end, ngram, tables):
+    """What the selection entry of `form` ("" plain, "_fixed", "_ngram", "_lines") takes between its own arguments and the stream."""
+    if form == "":
+        return ()
+    tail = (_fixed(fixed_end, B),)
+    if form != "_fixed":
+        tail += (int(ngram),)
+    if form == "_lines":
+        tail += _lines(tables, B, V)
+    return tail
+
+
+def _select(form, logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, sampling=None, fixed_end=None, ngram=0,
+            tables=None):
+    """mmtg_decode_select<form>, or with sampling = (top_k, top_p, uniforms) mmtg_decode_sample<form>."""
+    name = ("decode_select" if sampling is None else "decode_sample") + form
+    draw = () if sampling is None else (int(sampling[0]), float(sampling[1]), _p(sampling[2]), sampling[2].stride(0))
+    _check(getattr(lib(), "mmtg_" + name)(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                          float(rep_penalty), *draw, B, _p(pos_next), *_rule_tail(form, B, V, fixed_end, ngram, tables),
+                                          _stream()), name)
+
+
+def _beam_candidates(form, logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=None, ngram=0,
+                     tables=None):
+    name = "decode_beam_candidates" + form
+    _check(getattr(lib(), "mmtg_" + name)(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                          float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B,
+                                          *_rule_tail(form, B, V, fixed_end, ngram, tables), _stream()), name)
+
+
+def _beam_merge(form, cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next, fixed_end=None):
+    name = "decode_beam_merge" + form
+    _check(getattr(lib(), "mmtg_" + name)(_p(cand_val), _p(cand_id), _p(scores), _p(seq), seq.stride(0), _p(keep), keep.stride(0),
+                                          _p(rows), rows.stride(0), _p(pos), P, sent, int(nb), int(n_prompts), _p(pos_next),
+                                          *_rule_tail(form, n_prompts * nb, 0, fixed_end, 0, None), _stream()), name)
+
+
+def decode_select(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next=None):
+    _select("", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next)
+
+
+def decode_sample(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, pos_next=None):
+    _select("", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, (top_k, top_p, uniforms))
+
+
+def decode_beam_candidates(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B):
+    """Per row: the nb best (log-probability, id) continuations of the processed logits (include/mmtg_hip.h)."""
+    _beam_candidates("", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B)
+
+
+def decode_beam_merge(cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next=None):
+    """Per prompt: keep the nb best candidates, reorder seq / keep / rows in place, append (include/mmtg_hip.h)."""
+    _beam_merge("", cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next)
+
+
+def decode_select_fixed(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, fixed_end, pos_next=None):
+    """decode_select that leaves row b's column pos + 1 alone while pos + 1 < fixed_end[b] (a host-written prefix, include/mmtg_hip.h)."""
+    _select("_fixed", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, fixed_end=fixed_end)
+
+
+def decode_sample_fixed(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, fixed_end, pos_next=None):
+    _select("_fixed", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, (top_k, top_p, uniforms), fixed_end=fixed_end)
+
+
+def decode_beam_candidates_fixed(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end):
+    """decode_beam_candidates; a row on a prefix column (pos + 1 < fixed_end[b]) offers nothing."""
+    _beam_candidates("_fixed", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=fixed_end)
+
+
+def decode_beam_merge_fixed(cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, fixed_end, pos_next=None):
+    """decode_beam_merge; a prompt on a prefix column keeps every beam, score and token (include/mmtg_hip.h)."""
+    _beam_merge("_fixed", cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next, fixed_end=fixed_end)
+
+
+def decode_select_ngram(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, ngram, fixed_end=None, pos_next=None):
+    """decode_select that never writes a content n-gram (n = ngram) the row already holds (include/mmtg_hip.h); fixed_end: as
+    decode_select_fixed, or None (no prefix)."""
+    _select("_ngram", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, fixed_end=fixed_end, ngram=ngram)
+
+
+def decode_sample_ngram(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, ngram, fixed_end=None,
+                        pos_next=None):
+    _select("_ngram", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, (top_k, top_p, uniforms),
+            fixed_end=fixed_end, ngram=ngram)
+
+
+def decode_beam_candidates_ngram(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, ngram,
+                                 fixed_end=None):
+    """decode_beam_candidates with the n-gram bans of decode_select_ngram applied before the log_softmax and the top nb."""
+    _beam_candidates("_ngram", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=fixed_end,
+                     ngram=ngram)
+
+
 def decode_select_lines(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, tables, ngram=0, fixed_end=None, pos_next=None):
     """decode_select_ngram (ngram may be 0) under the line-length bounds and line-end sets of `tables` (include/mmtg_hip.h)."""
-    _check(lib().mmtg_decode_select_lines(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                          float(rep_penalty), B, _p(pos_next), _fixed(fixed_end, B), int(ngram), *_lines(tables, B, V),
-                                          _stream()), "decode_select_lines")
+    _select("_lines", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, fixed_end=fixed_end, ngram=ngram,
+            tables=tables)
 
 
 def decode_sample_lines(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, tables, ngram=0,
                         fixed_end=None, pos_next=None):
-    _check(lib().mmtg_decode_sample_lines(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                          float(rep_penalty), int(top_k), float(top_p), _p(uniforms), uniforms.stride(0), B, _p(pos_next),
-                                          _fixed(fixed_end, B), int(ngram), *_lines(tables, B, V), _stream()), "decode_sample_lines")
+    _select("_lines", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, (top_k, top_p, uniforms),
+            fixed_end=fixed_end, ngram=ngram, tables=tables)
 
 
 def decode_beam_candidates_lines(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, tables, ngram=0,
                                  fixed_end=None):
     """decode_beam_candidates_ngram (ngram may be 0) under the line rule: a full line offers PAD the way sticky PAD does."""
-    _check(lib().mmtg_decode_beam_candidates_lines(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                                   float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B, _fixed(fixed_end, B),
-                                                   int(ngram), *_lines(tables, B, V), _stream()), "decode_beam_candidates_lines")
+    _beam_candidates("_lines", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=fixed_end,
+                     ngram=ngram, tables=tables)
 
 
 def decode_advance(pos):
@@ -970,7 +986,6 @@ def decode_mlp_sync_words():
 def decode_mlp_census(device):
     """Workgroup placement of a 256-workgroup, one-per-CU launch: an [8, 8] int tensor, [v, x] = workgroups with id % 8 == v found on
     physical XCD x (include/mmtg_hip.h, mmtg_decode_mlp_census).  Synchronises."""
-    import torch
     out = torch.zeros(64, dtype=torch.int32, device=device)
     _check(lib().mmtg_decode_mlp_census(_p(out), _stream()), "decode_mlp_census")
     return out.view(8, 8).cpu()

@@ -421,3 +421,79 @@ def test_beam_restatement_obeys_the_rule_and_one_beam_is_greedy():
     for r in ids.tolist():
         assert r[:len(prefix)] == prefix and rule_violations(r, t, 0, start=len(prefix)) == []
         assert line_lengths_of(r)[1] == 4
+
+
+# ------------------------------------------------------------------ which entry a step ends in
+def test_every_step_ends_in_the_entry_the_dispatch_table_names(monkeypatch):
+    """All sixteen (with_head, prefix, n-gram, lines) inputs, for greedy / sampled steps and for beam steps: select_forms, and the
+    entries GreedyDecoder._select and BeamDecoder._select then call (recorded in place of the library, with their argument counts
+    held to the ABI's), against the table written out here."""
+    from types import SimpleNamespace as NS
+
+    from mmtg_amd.decode import select_forms
+    #        with_head prefix ngram lines   select / sample / candidates   merge
+    table = [(True, False, 0, False,        "",                            ""),
+             (True, True, 0, False,         "_fixed",                      "_fixed"),
+             (True, False, 3, False,        "_ngram",                      ""),
+             (True, True, 3, False,         "_ngram",                      "_fixed"),
+             (True, False, 0, True,         "_lines",                      ""),
+             (True, True, 0, True,          "_lines",                      "_fixed"),
+             (True, False, 3, True,         "_lines",                      ""),
+             (True, True, 3, True,          "_lines",                      "_fixed"),
+             (False, False, 0, False,       "",                            ""),
+             (False, True, 0, False,        "_fixed",                      "_fixed"),
+             (False, False, 3, False,       "",                            ""),
+             (False, True, 3, False,        "_fixed",                      "_fixed"),
+             (False, False, 0, True,        "",                            ""),
+             (False, True, 0, True,         "_fixed",                      "_fixed"),
+             (False, False, 3, True,        "",                            ""),
+             (False, True, 3, True,         "_fixed",                      "_fixed")]
+    assert len({r[:4] for r in table}) == 16
+    calls = []
+
+    class Lib:
+        def __getattr__(self, name):
+            def entry(*a):
+                assert len(a) == len(hip._SIGS[name][0]), name
+                calls.append((name, a))
+                return 0
+            return entry
+    monkeypatch.setattr(hip, "lib", lambda: Lib())
+    monkeypatch.setattr(hip, "_stream", lambda: 0)
+    B, nb, V = 4, 2, 160
+    i32 = lambda *s: torch.zeros(*s, dtype=torch.int32)
+    lines = (torch.zeros(B, 3, dtype=torch.uint8), torch.full((B, 3), CAP, dtype=torch.uint8), None, None)
+    for with_head, prefix, ngram, with_lines, want, want_merge in table:
+        assert select_forms(with_head, prefix, ngram, with_lines) == (want, want_merge)
+        fe = i32(B)
+        dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb, use_fixed=prefix, ngram=ngram,
+                 lines=lines if with_lines else None, fixed_end=fe, logits=torch.zeros(B, V), seq=torch.zeros(B, 64, dtype=torch.long),
+                 pos=i32(1), pos_next=i32(1), uniforms=torch.zeros(70, B), keep=i32(B, 64), rows=i32(B, 64), scores=torch.zeros(B),
+                 cand_val=torch.zeros(B, nb), cand_id=i32(B, nb))
+        # the graph key comes from the same answer: "prefix", then ("ngram", n), then "lines" exactly on a head step under line constraints
+        dec.params = (1.1, 1.5, 1, 0.0)
+        assert GreedyDecoder._graph_key(dec, with_head, 1) == (
+            (with_head, 1, dec.params) + (("prefix",) if prefix else ()) + (("ngram", ngram) if ngram else ())
+            + (("lines", "bounds") if with_head and with_lines else ()))
+        for params, kind in (((1.1, 1.5, 1, 0.0), "select"), ((1.1, 1.5, 5, 0.9), "sample" if with_head else "select")):
+            del calls[:]
+            dec.params = params
+            GreedyDecoder._select(dec, with_head)
+            assert [c[0] for c in calls] == ["mmtg_decode_" + kind + want]
+            a = calls[0][1]
+            assert (a[0] != 0) == with_head                                       # logits null exactly when no head was called
+            if want:                                                              # fixed_end follows pos_next: given with a prefix only
+                at = 15 if kind == "sample" else 11
+                assert a[at] == dec.pos_next.data_ptr() and a[at + 1] == (fe.data_ptr() if prefix else 0)
+            if want in ("_ngram", "_lines"):
+                assert a[at + 2] == ngram
+        del calls[:]
+        dec.params = (1.1, 1.5, 1, 0.0)
+        BeamDecoder._select(dec, with_head)
+        assert [c[0] for c in calls] == (["mmtg_decode_beam_candidates" + want] if with_head else []) + ["mmtg_decode_beam_merge" + want_merge]
+        merge = calls[-1][1]
+        assert (merge[0] != 0) == with_head and (merge[1] != 0) == with_head      # candidates null when no head was called
+        if want_merge:
+            assert merge[15] == fe.data_ptr()
+        if with_head and want:
+            assert calls[0][1][14] == (fe.data_ptr() if prefix else 0)
