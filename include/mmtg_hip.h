@@ -646,6 +646,40 @@ MMTG_API int mmtg_decode_beam_candidates_lines(const float* logits, long ldl, in
                                       int B, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
                                       int n_lines, const unsigned* sets, int n_sets, const short* set_of, void* stream);
 
+/* ---- line templates (GreedyDecoder / BeamDecoder with templates=, mmtg_amd/decode.py): given characters and id classes inside a
+ * line -- an acrostic, a fill-in, a tone or rhyme pattern.  The reference leaves every content column to the model
+ * (generate.py:117-142); these entries extend the line rule above by one symbol per row, line and content column:
+ * tmpl int32 [B, n_lines, sent - 2], tmpl[b, l, c] >= 0 a given id, -1 free, <= -2 the class -2 - value, a row of the SAME `sets` bit
+ * table the end sets use (a value that names no row of it is read as free).  A template of k symbols fixes the line's opening; the
+ * host folds its length into the bounds -- closed: (lo, hi) = (k, k); open: lo = max(lo, k), hi >= k -- so a column with a symbol
+ * has c < lo <= hi, PAD is banned there by the line rule and the tables need no further field.  At a column the row's model chooses
+ * (not a held prefix column, not forced, the row not in sticky PAD, the line not full):
+ *   given v: the row writes v without consulting the logits, the way a full line writes PAD (beams: v at log-probability 0 and -inf
+ *     fillers, so the merge keeps every live beam and its score); v is subject to no ban or mask, and counts as history for the
+ *     penalty, for later n-gram keys and as the end set's "previous token" like any written token;
+ *   class S: every id outside S is -inf where the end-set mask acts, composing with the n-gram bans and, at c == hi - 1 of a line
+ *     with an end set, with that set (an id survives only if every rule admits it);
+ *   free: the line rule alone.
+ * Sticky PAD wins over a template: once an all-banned column (n-gram bans can empty a class) has made the row write PAD, the
+ * line has ended and its later given columns are PAD too; the all -inf behaviour is that of the *_lines entries.  Both masks are
+ * read from global memory in the one pass the line rule makes over the count words: the dynamic LDS request is the *_lines
+ * entry's.  Each entry is its *_lines namesake plus the table; without logits or with a null table it fails before any device call.
+ * The beam merge is unchanged.  The kernels of every earlier entry compile to the same code as before these were added.       */
+MMTG_API int mmtg_decode_select_tmpl(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                            int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, const int* fixed_end,
+                            int ngram, const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets,
+                            int n_sets, const short* set_of, const int* tmpl, void* stream);
+MMTG_API int mmtg_decode_sample_tmpl(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                            int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                            const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, int ngram,
+                            const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
+                            const short* set_of, const int* tmpl, void* stream);
+MMTG_API int mmtg_decode_beam_candidates_tmpl(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                     int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                     int B, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
+                                     int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
+                                     void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

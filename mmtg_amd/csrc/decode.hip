@@ -123,7 +123,10 @@ __device__ __forceinline__ unsigned fkey(float x) {
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
-template <bool NG = false, bool LN = false>
+// (TM changes nothing in the body: it gives the template form an instantiation of its own, which its one caller inlines by force.
+// As a second user of <true, true> it takes the line form's copy out of line, and left out of line itself it is a second LDS-using
+// function of the module: either way the earlier sampling kernels compile to other code, profiles/r12_template_decode_disassembly_diff.txt)
+template <bool NG = false, bool LN = false, bool TM = false>
 __device__ int sample_row(const float* row, int V, const unsigned* cnt, float* px, float temperature, float rep_penalty,
                           int top_k, float top_p, float u, int tid, float* filtered) {
     __shared__ unsigned hcnt[256];
@@ -1090,7 +1093,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void de
 }
 
 // The selection kernels below end in one argument, the step's rule R: NoRule (the plain entries), FixedEnd (*_fixed), NgramBan
-// (*_ngram) or LineRule (*_lines).  A rule says which rows it holds (held) and, with R::ngram (the sentinel of penalize<true> is
+// (*_ngram), LineRule (*_lines) or TemplateRule (*_tmpl).  A rule says which rows it holds (held) and, with R::ngram (the sentinel of penalize<true> is
 // in use; bans() gives the NgramBan) and R::lines (PAD's slot is read; col() says what the line wants of a free column), which
 // edits of the occurrence table the kernel makes after count_ids.
 //
@@ -1105,13 +1108,13 @@ struct LineCol {
 };
 
 struct NoRule {
-    static constexpr bool ngram = false, lines = false;
+    static constexpr bool ngram = false, lines = false, tmpl = false;
     __device__ __forceinline__ bool held(int, int) const { return false; }
 };
 
 struct FixedEnd {
     const int* fixed_end;   // int32 [B]
-    static constexpr bool ngram = false, lines = false;
+    static constexpr bool ngram = false, lines = false, tmpl = false;
     __device__ __forceinline__ bool held(int b, int pos) const { return pos + 1 < fixed_end[b]; }
 };
 
@@ -1123,7 +1126,7 @@ struct NgramBan {
     const int* fixed_end;   // int32 [B] or null
     int n;                  // 1 .. sent - 2
     int hist_cap;           // ints of dynamic LDS for the staged history (>= the longest history, min(ldseq - P, MAXGEN))
-    static constexpr bool ngram = true, lines = false;
+    static constexpr bool ngram = true, lines = false, tmpl = false;
     __device__ __forceinline__ bool held(int b, int pos) const { return fixed_end && pos + 1 < fixed_end[b]; }
     __host__ __device__ __forceinline__ const NgramBan& bans() const { return *this; }
 };
@@ -1161,7 +1164,7 @@ struct LineRule {
     const short* set_of;           // [B, n_lines] row of `sets` (-1: no end set), or null
     const unsigned* sets;          // [n_sets, words] bit v of a row: content id v is in the set
     int n_lines, n_sets, words;    // words >= ceil(V / 32)
-    static constexpr bool ngram = true, lines = true;
+    static constexpr bool ngram = true, lines = true, tmpl = false;
     __device__ __forceinline__ bool held(int b, int pos) const { return ng.held(b, pos); }
     __host__ __device__ __forceinline__ const NgramBan& bans() const { return ng; }
 
@@ -1199,6 +1202,49 @@ __device__ __forceinline__ void ban_line(unsigned* cnt, int V, const LineCol& lc
     __syncthreads();
 }
 
+// Line templates (the *_tmpl entries, include/mmtg_hip.h): a LineRule plus one symbol per row, line and content column.  tmpl is
+// int32 [B, n_lines, sent - 2]: v >= 0 a given id (the row writes it, no logits consulted), -1 free, v <= -2 the class -2 - v, a row
+// of the line rule's own `sets` (every id outside it gets the sentinel).  Closed / open templates need no field: the host folds
+// them into lo / hi, so a column with a symbol always has c < lo <= hi (never a full line's PAD).
+struct TmplCol {
+    int given;               // >= 0: the row writes this id (else -1)
+    const unsigned* cls;     // a class column: the class's bit row (else null)
+};
+
+struct TemplateRule {
+    LineRule ln;
+    const int* table;              // [B, n_lines, sent - 2]
+    static constexpr bool ngram = true, lines = true, tmpl = true;
+    __device__ __forceinline__ bool held(int b, int pos) const { return ln.held(b, pos); }
+    __host__ __device__ __forceinline__ const NgramBan& bans() const { return ln.ng; }
+    __device__ __forceinline__ LineCol col(int b, int j, int sent, const long long* gen) const { return ln.col(b, j, sent, gen); }
+
+    __device__ __forceinline__ TmplCol sym(int b, int j, int sent) const {
+        TmplCol tc = {-1, nullptr};
+        const int l = j / sent, c = j % sent - 1;
+        if (l >= ln.n_lines || c < 0 || c >= sent - 2) return tc;
+        const int v = table[((long)b * ln.n_lines + l) * (sent - 2) + c];
+        if (v >= 0) tc.given = v;
+        else if (v <= -2 && -2 - v < ln.n_sets) tc.cls = ln.sets + (long)(-2 - v) * ln.words;
+        return tc;
+    }
+};
+
+// ban_line with a class column's mask beside the end set's (either may be null; both: an id survives only if both admit it).  The
+// masks are read from global memory in the one pass over the count words; nothing is staged.
+__device__ __forceinline__ void ban_line_tmpl(unsigned* cnt, int V, const LineCol& lc, const unsigned* cls, int tid) {
+    if (lc.mask || cls)
+        for (int i = tid; i < (V + 1) / 2; i += 256) {
+            unsigned m = 0xFFFFFFFFu;
+            if (lc.mask) m &= lc.mask[i >> 4];
+            if (cls) m &= cls[i >> 4];
+            const unsigned two = (m >> (2 * (i & 15))) & 3u;
+            cnt[i] |= ((two & 1u) ? 0u : 0xFFFFu) | ((two & 2u) ? 0u : 0xFFFF0000u);
+        }
+    if (tid == 0) cnt[0] = (cnt[0] & 0xFFFF0000u) | (lc.pad_ban ? 0xFFFFu : 0u);
+    __syncthreads();
+}
+
 // logits processor + arg-max + forced-token cadence + append (generate.py:117-142), device-driven.
 template <typename R>
 __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restrict__ logits, long ldl, int V,
@@ -1226,17 +1272,28 @@ __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restr
         lc = rule.col(b, j, sent, gen);
         if (lc.force_pad) { if (tid == 0) gen[j] = 0; return; }                  // the line is full: PAD, as sticky PAD writes it
     }
+    TmplCol tc = {-1, nullptr};
+    if constexpr (R::tmpl) {
+        tc = rule.sym(b, j, sent);
+        if (tc.given >= 0) { if (tid == 0) gen[j] = tc.given; return; }          // a given column: its id, as a full line writes PAD
+    }
     count_ids(cnt, V, gen, n, tid);
     if constexpr (R::ngram) {  // after the (V + 1) / 2 count words and, when sampling, the V-float row image
         const NgramBan ng = rule.bans();
         if (!R::lines || ng.n > 0)
             ban_ngrams(cnt, reinterpret_cast<int*>(cnt + (V + 1) / 2 + (uniforms ? V : 0)), V, gen, min(n, ng.hist_cap), ng.n, tid);
     }
-    if constexpr (R::lines) ban_line(cnt, V, lc, tid);
+    if constexpr (R::tmpl) ban_line_tmpl(cnt, V, lc, tc.cls, tid);
+    else if constexpr (R::lines) ban_line(cnt, V, lc, tid);
     if (uniforms) {            // stochastic: uniforms[pos, b] drives the draw (top_k == 1 and top_p == 0 is the greedy path)
         float* px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
-        const int pick = sample_row<R::ngram, R::lines>(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k, top_p,
-                                                        uniforms[(long)pos * ldu + b], tid, nullptr);
+        int pick;
+        if constexpr (R::tmpl)     // (sample_row's comment: an instantiation of its own, inlined by force)
+            [[clang::always_inline]] pick = sample_row<true, true, true>(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k,
+                                                                         top_p, uniforms[(long)pos * ldu + b], tid, nullptr);
+        else
+            pick = sample_row<R::ngram, R::lines>(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k, top_p,
+                                                  uniforms[(long)pos * ldu + b], tid, nullptr);
         if (tid == 0) gen[j] = pick;
         return;
     }
@@ -1302,12 +1359,21 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __res
             return;
         }
     }
+    TmplCol tc = {-1, nullptr};
+    if constexpr (R::tmpl) {
+        tc = rule.sym(b, j, sent);
+        if (tc.given >= 0) {                               // a given column: its id with the score unchanged
+            if (tid < nb) { cv[tid] = tid == 0 ? 0.f : -INFINITY; ci[tid] = tid == 0 ? tc.given : 0; }
+            return;
+        }
+    }
     count_ids(cnt, V, gen, n, tid);
     if constexpr (R::ngram) {  // after the count words and the V processed logits
         const NgramBan ng = rule.bans();
         if (!R::lines || ng.n > 0) ban_ngrams(cnt, reinterpret_cast<int*>(px + V), V, gen, min(n, ng.hist_cap), ng.n, tid);
     }
-    if constexpr (R::lines) ban_line(cnt, V, lc, tid);
+    if constexpr (R::tmpl) ban_line_tmpl(cnt, V, lc, tc.cls, tid);
+    else if constexpr (R::lines) ban_line(cnt, V, lc, tid);
     const float* row = logits + (long)b * ldl;
     float mx = -INFINITY;
     for (int v = tid; v < V; v += 256) {
@@ -1780,6 +1846,54 @@ extern "C" int mmtg_decode_beam_candidates_lines(const float* logits, long ldl, 
         return e;
     return beam_candidates_launch("decode_beam_candidates_lines", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
                                   nb, cand_val, cand_id, B, stream, lr);
+}
+
+// (a *_tmpl entry's checks: its *_lines namesake's, and the table)
+static int tmpl_check(const char* what, const float* logits, int V, long ldseq, int P, int sent, const int* fixed_end, int ngram,
+                      const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
+                      const short* set_of, const int* tmpl, TemplateRule* tr) {
+    LineRule lr;
+    if (int e = lines_check(what, logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, &lr)) return e;
+    MMTG_REQUIRE(tmpl, "%s: the template table [B, n_lines, sent - 2] is needed", what);
+    *tr = TemplateRule{lr, tmpl};
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_select_tmpl(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                       int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, const int* fixed_end,
+                                       int ngram, const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets,
+                                       int n_sets, const short* set_of, const int* tmpl, void* stream) {
+    TemplateRule tr;
+    if (int e = tmpl_check("decode_select_tmpl", logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, tmpl, &tr))
+        return e;
+    return decode_select_launch("decode_select_tmpl", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, 1, 0.f, nullptr,
+                                0, B, pos_next, stream, tr);
+}
+
+extern "C" int mmtg_decode_sample_tmpl(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                       int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                                       const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, int ngram,
+                                       const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
+                                       const short* set_of, const int* tmpl, void* stream) {
+    TemplateRule tr;
+    if (int e = tmpl_check("decode_sample_tmpl", logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, tmpl, &tr))
+        return e;
+    if (int e = sample_args_check("decode_sample_tmpl", uniforms, ldu, B, top_k, top_p)) return e;
+    return decode_select_launch("decode_sample_tmpl", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p,
+                                uniforms, ldu, B, pos_next, stream, tr);
+}
+
+extern "C" int mmtg_decode_beam_candidates_tmpl(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                                int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                                int B, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
+                                                int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
+                                                void* stream) {
+    TemplateRule tr;
+    if (int e = tmpl_check("decode_beam_candidates_tmpl", logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets,
+                           set_of, tmpl, &tr))
+        return e;
+    return beam_candidates_launch("decode_beam_candidates_tmpl", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
+                                  nb, cand_val, cand_id, B, stream, tr);
 }
 
 extern "C" int mmtg_ln_fold_weights(const void* W, long ldw, const float* gamma, const float* beta, const float* bias, void* Wf,

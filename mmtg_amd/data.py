@@ -87,6 +87,37 @@ def encode_line_end(tokenizer, chars, vocab_cut=13317):
     return frozenset(ids)
 
 
+def encode_template(tokenizer, text, classes=None, vocab_cut=13317):
+    """One line's template (decode.check_lines' templates) from a string, one character per content column: `?` / `？` is a free
+    column, a character that is a key of `classes` (a dict from one character to an id set, e.g. encode_line_end's) stands for that
+    class, any other character is given -- it must be a content character the tokenizer knows, below the generation's vocabulary
+    cut (else ValueError, as encode_line_end raises).  A trailing `…` or `...` makes the template open (the line goes on as the
+    model likes); without it the line is exactly as long as the template.  Returns the tuple check_lines takes, e.g.
+    encode_template(tok, "春…") == (id of 春, Ellipsis)."""
+    classes = {} if classes is None else classes
+    open_ = False
+    if text.endswith("…"):
+        text, open_ = text[:-1], True
+    elif text.endswith("..."):
+        text, open_ = text[:-3], True
+    syms = []
+    for ch in text:
+        if ch in ("?", "？"):
+            syms.append(None)
+        elif ch in classes:
+            syms.append(frozenset(int(v) for v in classes[ch]))
+        else:
+            if ch.isspace():
+                raise ValueError("template %r: whitespace is no column (use ? for a free one)" % (text,))
+            v = int(tokenizer.convert_tokens_to_ids(ch))
+            if v in (0, 1, 2, 100, 102) or not 0 <= v < vocab_cut:
+                raise ValueError("template character %r maps to id %d, not a content id below %d" % (ch, v, vocab_cut))
+            syms.append(v)
+    if not syms:
+        raise ValueError("template %r holds no column" % (text,))
+    return tuple(syms) + ((Ellipsis,) if open_ else ())
+
+
 class MyDataset(torch.utils.data.Dataset):
     """Same contract as src/MyDataset.py: ``MyDataset(file_path, tokenizer, data_config, if_train=True)``;
     ``file_path`` is the reference's pickle (a list of dicts) or an already loaded list."""

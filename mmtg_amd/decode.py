@@ -77,10 +77,12 @@ def check_ngram(n, sent=22):
 
 class LineTables:
     """The packed line constraints check_lines returns: lo, hi uint8 [rows, n_lines]; set_of int16 [rows, n_lines] (-1: no end set)
-    and sets uint32 [n_sets, ceil(V / 32)] (bit v & 31 of word v >> 5: id v is a member), or both None when no line has a set."""
+    and sets uint32 [n_sets, ceil(V / 32)] (bit v & 31 of word v >> 5: id v is a member), or both None when no line has a set.
+    tmpl (templates= only, else None): int32 [rows, n_lines, sent - 2], one symbol per content column -- v >= 0 a given id, -1 free,
+    v <= -2 the class `sets[-2 - v]` (classes and end sets share the table); a template's length is folded into lo / hi."""
 
-    def __init__(self, lo, hi, set_of, sets, sent, V):
-        self.lo, self.hi, self.set_of, self.sets, self.sent, self.V = lo, hi, set_of, sets, sent, V
+    def __init__(self, lo, hi, set_of, sets, sent, V, tmpl=None):
+        self.lo, self.hi, self.set_of, self.sets, self.sent, self.V, self.tmpl = lo, hi, set_of, sets, sent, V, tmpl
 
     @property
     def rows(self):
@@ -89,7 +91,20 @@ class LineTables:
     def repeat(self, k):
         """Every row k times in place of itself (the beams of a prompt share its constraints)."""
         rep = lambda a: None if a is None else np.repeat(a, k, axis=0)      # noqa: E731
-        return LineTables(rep(self.lo), rep(self.hi), rep(self.set_of), self.sets, self.sent, self.V)
+        return LineTables(rep(self.lo), rep(self.hi), rep(self.set_of), self.sets, self.sent, self.V, rep(self.tmpl))
+
+    def take(self, idx):
+        """Rows idx (a list of row indices) as tables of their own; the sets are shared."""
+        sub = lambda a: None if a is None else np.ascontiguousarray(a[idx])      # noqa: E731
+        return LineTables(sub(self.lo), sub(self.hi), sub(self.set_of), self.sets, self.sent, self.V, sub(self.tmpl))
+
+    def symbol(self, b, l, c):
+        """What row b's template says of content column c of line l: an int (a given id), a frozenset (a class) or None (free, no
+        template, or a column / line past it)."""
+        if self.tmpl is None or l >= self.tmpl.shape[1] or not 0 <= c < self.tmpl.shape[2]:
+            return None
+        v = int(self.tmpl[b, l, c])
+        return v if v >= 0 else None if v == -1 else self.members(-2 - v)
 
     def bounds(self, b, l):
         """(lo, hi, end set as a frozenset or None) of row b's line l; a line past the table is unconstrained."""
@@ -137,7 +152,28 @@ def _per_row(spec, rows, what, whole, per_row_form):
     return [list(spec)] * rows
 
 
-def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefix=None):
+def _template_rows(spec, rows):
+    """templates as one list of per-line entries per row: one list for all rows, or (a list among the entries marks it) one list or
+    None per row."""
+    if spec is None:
+        return [[] for _ in range(rows)]
+    if not isinstance(spec, list):
+        raise ValueError("templates: a list of per-line templates (or one such list per row) expected, got %r" % (spec,))
+    if any(isinstance(e, list) for e in spec):
+        if len(spec) != rows:
+            raise ValueError("templates has %d rows, the generation %d" % (len(spec), rows))
+        for b, r in enumerate(spec):
+            if r is not None and not isinstance(r, list):
+                raise ValueError("templates row %d: a list of per-line templates or None expected, got %r" % (b, r))
+        return [[] if r is None else r for r in spec]
+    return [spec] * rows
+
+
+def _content_id(v, V):
+    return not (v == 0 or v in BANNED or v < 0 or (V is not None and v >= V))
+
+
+def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefix=None, templates=None):
     """Validate line-length bounds and line-end id sets on the host, before any device work; returns the packed LineTables, or
     None when both arguments are None (no constraints: the decoders then run the launches of a generation without them).
 
@@ -152,8 +188,17 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
     one set / frozenset (every line), one list of entries, or one list of entries (or None) per row.
     prefix (check_prefix's result, optional): a row whose prefix stops inside a line continues that line under its bounds; given
     content beyond the line's hi raises.  Whole given lines are the caller's text and are not checked.
-    Raises ValueError for bounds outside 0 .. sent - 2, lo > hi, more entries than lines, and any end set that breaks the above."""
-    if line_lengths is None and line_end_ids is None:
+    templates: a line's entry is None or a tuple of k symbols (1 <= k <= sent - 2), one per content column from column 0 -- an int
+    (given: the row writes this content id), None (free) or a set / frozenset of content ids (a class: the column's id is a
+    member) -- optionally ending in `...` (Ellipsis: an open template).  A closed template fixes the line's length, its bounds
+    become (k, k) and k must lie inside the line's line_lengths bounds; an open one makes lo = max(lo, k) and needs hi >= k.  Given
+    as one list of entries (for every row; a shorter list leaves the later lines without a template) or a list with one such list
+    or None per row.  Given ids and class members are content ids below V; on a line with an end set whose length the template
+    fixes (hi == k) the last symbol must leave a member of the set possible.  A partial prefix line must agree with its line's
+    template.  So a column that only classes and end sets constrain always has a live id; only n-gram bans can empty one.
+    Raises ValueError for bounds outside 0 .. sent - 2, lo > hi, more entries than lines, and any end set or template that breaks
+    the above."""
+    if line_lengths is None and line_end_ids is None and templates is None:
         return None
     if length < 1 or not 3 <= sent <= 257:
         raise ValueError("line constraints need length >= 1 and 3 <= sent <= 257 (got length %d, sent %d)" % (length, sent))
@@ -166,7 +211,17 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
     lo = np.zeros((rows, n_lines), np.uint8)
     hi = np.full((rows, n_lines), cap, np.uint8)
     set_of = np.full((rows, n_lines), -1, np.int16)
+    tmpls = _template_rows(templates, rows)
+    tmpl = None if templates is None else np.full((rows, n_lines, cap), -1, np.int32)
     table, seen = [], {}
+
+    def set_index(ids):
+        if ids not in seen:
+            seen[ids] = len(table)
+            table.append(ids)
+        if seen[ids] > 32767:
+            raise ValueError("line_end_ids / templates: more than 32768 distinct id sets")
+        return seen[ids]
     for b in range(rows):
         for what, spec in (("line_lengths", lens[b]), ("line_end_ids", ends[b])):
             if isinstance(spec, tuple) and spec and spec[0] == "all":
@@ -193,18 +248,65 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
                     for v in sorted(ids):
                         if v == 0 or v in BANNED or v < 0 or (V is not None and v >= V):
                             raise ValueError("line_end_ids row %d, line %d: id %d is not a content id below the vocabulary cut" % (b, l, v))
-                    if ids not in seen:
-                        seen[ids] = len(table)
-                        table.append(ids)
-                    if seen[ids] > 32767:
-                        raise ValueError("line_end_ids: more than 32768 distinct end sets")
-                    set_of[b, l] = seen[ids]
+                    set_of[b, l] = set_index(ids)
         for l in range(n_lines):
             if set_of[b, l] >= 0 and hi[b, l] == 0:
                 raise ValueError("line_end_ids row %d, line %d: an end set on a line with hi = 0" % (b, l))
+        if len(tmpls[b]) > n_lines:
+            raise ValueError("templates row %d has %d lines, a generation of length %d holds %d" % (b, len(tmpls[b]), length, n_lines))
+        for l, e in enumerate(tmpls[b]):
+            if e is None:
+                continue
+            at = "templates row %d, line %d" % (b, l)
+            if not isinstance(e, tuple):
+                raise ValueError("%s: a tuple of symbols or None expected, got %r" % (at, e))
+            open_ = len(e) > 0 and e[-1] is Ellipsis
+            syms = e[:-1] if open_ else e
+            k = len(syms)
+            if not 1 <= k <= cap:
+                raise ValueError("%s: %d symbols, not 1 .. %d (sent - 2)" % (at, k, cap))
+            for c, y in enumerate(syms):
+                if y is None:
+                    continue
+                if _is_int(y):
+                    if not _content_id(int(y), V):
+                        raise ValueError("%s, column %d: id %d is not a content id below the vocabulary cut" % (at, c, int(y)))
+                    tmpl[b, l, c] = int(y)
+                elif isinstance(y, (set, frozenset)) and all(_is_int(v) for v in y):
+                    ids = frozenset(int(v) for v in y)
+                    if not ids:
+                        raise ValueError("%s, column %d: the class is empty" % (at, c))
+                    for v in sorted(ids):
+                        if not _content_id(v, V):
+                            raise ValueError("%s, column %d: id %d is not a content id below the vocabulary cut" % (at, c, v))
+                    tmpl[b, l, c] = -2 - set_index(ids)
+                else:
+                    raise ValueError("%s, column %d: an int, None or a set of ids expected, got %r" % (at, c, y))
+            a, z = int(lo[b, l]), int(hi[b, l])
+            if open_:
+                if z < k:
+                    raise ValueError("%s: an open template of %d symbols on a line with hi = %d" % (at, k, z))
+                lo[b, l] = max(a, k)
+            else:
+                if not a <= k <= z:
+                    raise ValueError("%s: a closed template of %d symbols outside the line's bounds (%d, %d)" % (at, k, a, z))
+                lo[b, l] = hi[b, l] = k
+            if set_of[b, l] >= 0 and hi[b, l] == k:              # the template's last column is the line's last: the end set's
+                members, y = table[set_of[b, l]], syms[-1]
+                if _is_int(y) and int(y) not in members:
+                    raise ValueError("%s: the line ends on the given id %d, which is not in its end set" % (at, int(y)))
+                if isinstance(y, (set, frozenset)) and not members & frozenset(int(v) for v in y):
+                    raise ValueError("%s: the last column's class and the line's end set share no id" % at)
         if prefix is not None:
             p = prefix[b]
             l, q = (len(p) - 1) // sent, (len(p) - 1) % sent
+            if 1 <= q <= cap and l < n_lines and tmpl is not None:   # the given columns of line l against its template
+                for c in range(min(q, cap)):
+                    v, y = int(p[l * sent + 1 + c]), int(tmpl[b, l, c])
+                    if y >= 0 and v != y:
+                        raise ValueError("prefix row %d gives id %d at column %d of line %d, its template %d" % (b, v, c, l, y))
+                    if y <= -2 and v not in table[-2 - y]:
+                        raise ValueError("prefix row %d gives id %d at column %d of line %d, outside its template's class" % (b, v, c, l))
             if 1 <= q <= cap and l < n_lines:                        # the prefix stops inside line l: q content columns are given
                 given = sum(1 for v in p[l * sent + 1:] if v != 0)
                 if given > hi[b, l]:
@@ -217,31 +319,33 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
         for i, t in enumerate(table):
             for v in t:
                 sets[i, v >> 5] |= np.uint32(1 << (v & 31))
-    return LineTables(lo, hi, set_of if table else None, sets, sent, V)
+    return LineTables(lo, hi, set_of if table else None, sets, sent, V, tmpl)
 
 
-def select_forms(with_head, prefix, ngram, lines):
+def select_forms(with_head, prefix, ngram, lines, templates=False):
     """Which selection entries a token step ends in: (form of mmtg_decode_select / _sample or mmtg_decode_beam_candidates, form of
-    mmtg_decode_beam_merge), each "" (plain), "_fixed", "_ngram" or "_lines".  with_head: the step calls the model's head; prefix:
-    the generation has one; ngram: no_repeat_ngram_size; lines: line constraints are given.  The bans act where logits are read, so
+    mmtg_decode_beam_merge), each "" (plain), "_fixed", "_ngram", "_lines" or "_tmpl".  with_head: the step calls the model's head;
+    prefix: the generation has one; ngram: no_repeat_ngram_size; lines: line constraints are given; templates: line templates are
+    given (every step that calls the head then ends in "_tmpl").  The bans act where logits are read, so
     a step without the head (select with null logits; no candidates launch, merge with null candidates) and every merge only know
     the prefix -- a generation without constraints runs the plain entries throughout."""
     held = "_fixed" if prefix else ""
     if not with_head:
         return held, held
-    return ("_lines" if lines else "_ngram" if ngram else held), held
+    return ("_tmpl" if templates else "_lines" if lines else "_ngram" if ngram else held), held
 
 
-def _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, rows, length, sh, what):
+def _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, rows, length, sh, what, templates=None):
     """The constraint arguments of ``begin`` for `rows` rows (`what` names them in messages): (n-gram size, checked prefix or None,
     LineTables or None).  A LineTables given as line_lengths is taken as checked."""
     sent = sh.msl + 2
     ngram = check_ngram(no_repeat_ngram_size, sent)
     pre = None if prefix is None else check_prefix(prefix, rows, length, sent=sent, V=sh.V)
     if not isinstance(line_lengths, LineTables):
-        return ngram, pre, check_lines(line_lengths, line_end_ids, rows, length, sent=sent, V=min(sh.V, 13317), prefix=pre)
-    if line_lengths.rows != rows or line_end_ids is not None:
-        raise ValueError("line tables of %d rows for %s (and no line_end_ids beside them)" % (line_lengths.rows, what))
+        return ngram, pre, check_lines(line_lengths, line_end_ids, rows, length, sent=sent, V=min(sh.V, 13317), prefix=pre,
+                                       templates=templates)
+    if line_lengths.rows != rows or line_end_ids is not None or templates is not None:
+        raise ValueError("line tables of %d rows for %s (and no line_end_ids / templates beside them)" % (line_lengths.rows, what))
     return ngram, pre, line_lengths
 
 
@@ -413,6 +517,10 @@ class GreedyDecoder:
         # decoder's rows; not None ends every step that calls the head in the *_lines selection entries
         self.lines = None
         self._line_buf = None       # (lo, hi, set_of) [B, lines of max_len] and the growing `sets` buffer: fixed addresses for the graphs
+        # line templates (templates=): this decoder's rows of the int32 symbol table [B, lines of max_len, sent - 2]; not None ends
+        # every step that calls the head in the *_tmpl selection entries
+        self.tmpl = None
+        self._tmpl_buf = None
 
     def _conv1d(self, x, wkey, out, **kw):
         # bf16: Engine._fwd routes Conv1D weights through their [out,in] copies (NT layout), which is
@@ -475,15 +583,16 @@ class GreedyDecoder:
         """The step's last launch: logits processing + arg-max / draw + the forced cadence + the next position (generate.py:117-142),
         through the entry select_forms names: the *_fixed ones leave row b's column pos + 1 alone while pos + 1 < fixed_end[b] (the
         host wrote it), the *_ngram ones also ban every id that would complete a content n-gram the row already holds, the *_lines
-        ones (n possibly 0) add the line-length bounds and line-end sets of include/mmtg_hip.h."""
+        ones (n possibly 0) add the line-length bounds and line-end sets of include/mmtg_hip.h, the *_tmpl ones the line templates."""
         sh = self.eng.sh
         temperature, rep, top_k, top_p = self.params
-        form, _ = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None)
+        tmpl = getattr(self, "tmpl", None)
+        form, _ = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=tmpl is not None)
         logits, ldl, V = (self.logits, self.eng.layout.Vpad, min(sh.V, 13317)) if with_head else (None, 0, 0)
         # stochastic: the draw of each position reads its row of the pre-filled uniforms
         sampling = (top_k, top_p, self.uniforms) if with_head and not (top_k == 1 and top_p == 0.0) else None
         hip._select(form, logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, self.B, self.pos_next, sampling,
-                    fixed_end=self.fixed_end if self.use_fixed else None, ngram=self.ngram, tables=self.lines)
+                    fixed_end=self.fixed_end if self.use_fixed else None, ngram=self.ngram, tables=self.lines, tmpl=tmpl)
 
     def _upload_lines(self, tables):
         """The line tables into this decoder's device buffers (allocated once, so captured graphs keep their addresses; a `sets`
@@ -513,11 +622,24 @@ class GreedyDecoder:
                 while cap < need:
                     cap *= 2
                 sets = self._line_buf[3] = torch.zeros(cap, tables.sets.shape[1], dtype=torch.int32, device=dev)
-                self.graphs = {k: g for k, g in self.graphs.items() if "lines" not in k}
+                self.graphs = {k: g for k, g in self.graphs.items() if "lines" not in k and "tmpl" not in k}
             sets.zero_()
             sets[:need].copy_(torch.from_numpy(tables.sets.view(np.int32)))
             set_of.copy_(padded(tables.set_of, -1, np.int16))
         return (lo, hi, sets, set_of) if tables.sets is not None else (lo, hi, None, None)
+
+    def _upload_templates(self, tables):
+        """The symbol table of a templated generation into this decoder's buffer (allocated once: captured graphs hold its address),
+        lines past the generation's free (-1); None without templates."""
+        if tables is None or tables.tmpl is None:
+            return None
+        sent = self.eng.sh.msl + 2
+        if self._tmpl_buf is None:
+            self._tmpl_buf = torch.zeros(self.B, (self.max_len - 1) // sent + 1, sent - 2, dtype=torch.int32, device=self.eng.dev)
+        full = np.full(tuple(self._tmpl_buf.shape), -1, np.int32)
+        full[:, :tables.tmpl.shape[1]] = tables.tmpl
+        self._tmpl_buf.copy_(torch.from_numpy(full))
+        return self._tmpl_buf
 
     def _step_x3(self, with_head):
         """The split-precision token step: embedding -> projector -> 12 blocks -> head, every product through mmtg_decode_gemm_x3
@@ -726,8 +848,9 @@ class GreedyDecoder:
         """What the step's launches depend on: the settings, and the constraints as far as select_forms lets them reach this step
         (a step without the head runs the launches it always ran)."""
         key = (with_head, parity, self.params) + (("prefix",) if self.use_fixed else ()) + (("ngram", self.ngram) if self.ngram else ())
-        if "_lines" in select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None):
-            key += ("lines", "sets" if self.lines[2] is not None else "bounds")
+        form = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=getattr(self, "tmpl", None) is not None)[0]
+        if form in ("_lines", "_tmpl"):
+            key += (form[1:], "sets" if self.lines[2] is not None else "bounds")
         return key
 
     def _step_state(self):
@@ -756,7 +879,7 @@ class GreedyDecoder:
 
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
-              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None):
+              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None):
         """Everything of a generation that happens once: the settings, the uniforms of a stochastic run, fresh weight copies /
         LayerNorm folds, the experience encoder, the prompt (prefilled in one batched pass: ``first_pos`` = P afterwards) and the
         reset position.  Returns the end position n; ``step_at(pos)`` for pos = first_pos .. n - 1 then runs the token steps (``generate`` does both; tools/decode_lanes_threads.py drives
@@ -774,7 +897,11 @@ class GreedyDecoder:
         line_lengths / line_end_ids (check_lines states the forms and the rule's home is include/mmtg_hip.h): per-row, per-line
         bounds on the number of content tokens and sets the last content token of a line comes from.  With either given, every
         step that calls the head ends in the *_lines selection entries; the tables are uploaded here, once.  None for both runs
-        exactly the launches and graphs of a generation without them.  (line_lengths may also be a LineTables, taken as checked.)"""
+        exactly the launches and graphs of a generation without them.  (line_lengths may also be a LineTables, taken as checked.)
+
+        templates (check_lines states the forms, include/mmtg_hip.h the rule): given ids, free columns and id classes for the opening
+        columns of a line.  With templates every step that calls the head ends in the *_tmpl selection entries; the symbol table is
+        uploaded here, once, beside the line tables.  None runs exactly the launches and graphs of a generation without them."""
         eng, sh = self.eng, self.eng.sh
         B = batch["img_embs"].shape[0]
         if B != self.B:
@@ -782,7 +909,7 @@ class GreedyDecoder:
         if length > self.max_len:
             raise ValueError("length %d exceeds max_len %d" % (length, self.max_len))
         ngram, pre, tables = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, B, length, sh,
-                                                "a batch of %d" % B)
+                                                "a batch of %d" % B, templates=templates)
         self.params = (float(temperature), float(repitition_penalty), int(top_k), float(top_p))
         if not (int(top_k) == 1 and float(top_p) == 0.0):
             if self.uniforms is None:
@@ -808,10 +935,12 @@ class GreedyDecoder:
         # the generation's constraints, on the decoder and its lanes: a lane's _select reads its own flags, its slice of fixed_end
         # (a view since construction) and its rows of the line tables (the sets are shared)
         lines = self._upload_lines(tables)
+        tmpl = self._upload_templates(tables)
         for i, d in enumerate([self] + self.children):
             a, z = (0, B) if d is self else ((i - 1) * d.B, i * d.B)
             d.use_fixed, d.ngram = pre is not None, ngram
             d.lines = None if lines is None else tuple(t if t is None or t is lines[2] else t[a:z] for t in lines)
+            d.tmpl = None if tmpl is None else tmpl[a:z]
         self.min_fixed = 0
         if pre is not None:
             lens = [len(p) for p in pre]
@@ -882,7 +1011,8 @@ class GreedyDecoder:
 
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None,
-                 use_graph=None, teacher=None, tap=None, prefix=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None):
+                 use_graph=None, teacher=None, tap=None, prefix=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None,
+                 templates=None):
         """batch: dict with topic_ids/tpw_* [B,P], topic_emb, img_embs, r_embs (no targets needed).
         Runs `length` iterations of the reference loop and returns the lyric ids
         [B, 1 + length] (column 0 is the initial [#START#]).  top_k = 1, top_p = 0 is the greedy setting;
@@ -897,9 +1027,13 @@ class GreedyDecoder:
         (``begin``, include/mmtg_hip.h); 0 (the default) is off.
         line_lengths / line_end_ids: the form of the lyric (``check_lines``): line_lengths=7 makes every line seven content
         tokens long, line_lengths=(1, 20) forbids empty lines, line_end_ids=[None, ids, None, ids] ends lines 1 and 3 on one of
-        ids.  A line is full at its hi (the row pads from there), cannot end below its lo, and with an end set ends on a member."""
+        ids.  A line is full at its hi (the row pads from there), cannot end below its lo, and with an end set ends on a member.
+        templates: what the opening columns of a line hold (``check_lines``): templates=[(a, ...), (b, ...)] opens line 0 with id
+        a and line 1 with id b (an acrostic), (a, None, None, b) is a four-token line a ? ? b, a set in place of an id confines
+        the column to its members."""
         n_steps = self.begin(batch, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix,
-                             no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths, line_end_ids=line_end_ids)
+                             no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths, line_end_ids=line_end_ids,
+                             templates=templates)
         eng, sh = self.eng, self.eng.sh
         saved_mode = self.use_graph
         if use_graph is not None:
@@ -976,11 +1110,13 @@ class BeamDecoder(GreedyDecoder):
         PAD is) act in the candidates; the merge is the prefix-aware one or the plain one."""
         sh = self.eng.sh
         temperature, rep, _, _ = self.params
-        cand, merge = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None)
+        tmpl = getattr(self, "tmpl", None)
+        cand, merge = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=tmpl is not None)
         fe = self.fixed_end if self.use_fixed else None
         if with_head:
             hip._beam_candidates(cand, self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2, temperature,
-                                 rep, self.nb, self.cand_val, self.cand_id, self.B, fixed_end=fe, ngram=self.ngram, tables=self.lines)
+                                 rep, self.nb, self.cand_val, self.cand_id, self.B, fixed_end=fe, ngram=self.ngram, tables=self.lines,
+                                 tmpl=tmpl)
         hip._beam_merge(merge, self.cand_val if with_head else None, self.cand_id if with_head else None, self.scores, self.seq, self.keep,
                         self.rows, self.pos, sh.P, sh.msl + 2, self.nb, self.n_prompts, self.pos_next, fixed_end=fe)
 
@@ -992,15 +1128,15 @@ class BeamDecoder(GreedyDecoder):
 
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
-              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None):
-        """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill, the prefix and the line
-        constraints: one per prompt), the ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at
+              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None):
+        """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill, the prefix, the line
+        constraints and the templates: one per prompt), the ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at
         the free positions after a prompt's prefix."""
         n = batch["img_embs"].shape[0]
         if n != self.n_prompts:
             raise ValueError("decoder was built for %d prompts, got %d" % (self.n_prompts, n))
         _, prefix, tables = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, n, length, self.eng.sh,
-                                               "%d prompts" % n)
+                                               "%d prompts" % n, templates=templates)
         if tables is not None:
             tables = tables.repeat(self.nb)
         if prefix is not None:
@@ -1017,14 +1153,15 @@ class BeamDecoder(GreedyDecoder):
 
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None, no_repeat_ngram_size=0,
-                 line_lengths=None, line_end_ids=None):
+                 line_lengths=None, line_end_ids=None, templates=None):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_beams, 1 + length] in
         GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row.
         prefix: one per prompt (check_prefix), shared by its beams.  no_repeat_ngram_size: as GreedyDecoder.generate, per beam
-        on its own (reordered) history.  line_lengths / line_end_ids: as GreedyDecoder.generate, one per prompt, shared by its beams."""
+        on its own (reordered) history.  line_lengths / line_end_ids / templates: as GreedyDecoder.generate, one per prompt, shared by
+        its beams (a given column adds nothing to a score)."""
         ids = super().generate(batch, length, temperature=temperature, repitition_penalty=repitition_penalty, use_graph=use_graph,
                                prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths,
-                               line_end_ids=line_end_ids)
+                               line_end_ids=line_end_ids, templates=templates)
         n, nb = self.n_prompts, self.nb
         ids = ids.view(n, nb, -1)
         sc = self.scores.view(n, nb).clone()

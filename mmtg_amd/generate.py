@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .data import encode_line_end, encode_prefix  # noqa: F401  (public: the opening lines / the line-end sets of generate_samples / generate_beams)
+from .data import encode_line_end, encode_prefix, encode_template  # noqa: F401  (public: the opening lines / the line-end sets / the line templates of generate_samples / generate_beams)
 
 SENT_SLOT = 22  # generate.py:118-121
 BANNED = (1, 2, 100, 102)  # [#START#] [#EOS#] [UNK] [SEP] in src/vocab/vocab.txt
@@ -153,24 +153,22 @@ def _prompt_prefixes(prefixes, n_prompts, length, sh):
     return check_prefix(prefixes, n_prompts, length, sent=sh.msl + 2, V=sh.V)
 
 
-def _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre):
-    """The packed line constraints (decode.check_lines: one per prompt, or one for all), or None; validated before any device work."""
+def _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre, templates=None):
+    """The packed line constraints and templates (decode.check_lines: one per prompt, or one for all), or None; validated before any
+    device work."""
     from .decode import check_lines
-    return check_lines(line_lengths, line_end_ids, n_prompts, length, sent=sh.msl + 2, V=min(sh.V, 13317), prefix=pre)
+    return check_lines(line_lengths, line_end_ids, n_prompts, length, sent=sh.msl + 2, V=min(sh.V, 13317), prefix=pre,
+                       templates=templates)
 
 
 def _chunk_lines(tables, idx):
     """Rows idx (one prompt index per decoder row) of the prompts' line tables."""
-    from .decode import LineTables
-    if tables is None:
-        return None
-    take = lambda a: None if a is None else np.ascontiguousarray(a[idx])      # noqa: E731
-    return LineTables(take(tables.lo), take(tables.hi), take(tables.set_of), tables.sets, tables.sent, tables.V)
+    return None if tables is None else tables.take(idx)
 
 
 def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperature=1.1, top_k=10, top_p=0.7,
                      repetition_penalty=1.5, max_batch=256, generator=None, decoder=None, prefixes=None, no_repeat_ngram_size=0,
-                     line_lengths=None, line_end_ids=None):
+                     line_lengths=None, line_end_ids=None, templates=None):
     """n_samples texts per prompt (generate.sh's loop, generate.py:205-235) on the batched, graph-replayed decoder:
     every prompt is replicated over n_samples rows, rows are decoded max_batch at a time with the device-side
     top-k / top-p sampler (one uniform per row and position from `generator`), each row is cut back to what
@@ -182,7 +180,10 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     continues it, and its text includes the given lines.
     no_repeat_ngram_size (optional, decode.check_ngram): n > 0 keeps every row from writing a content n-gram it already holds.
     line_lengths / line_end_ids (optional, decode.check_lines; one per prompt or one for all): bounds on every line's number of
-    tokens and sets (encode_line_end) a line's last token comes from; every sample of a prompt follows its prompt's."""
+    tokens and sets (encode_line_end) a line's last token comes from; every sample of a prompt follows its prompt's.
+    templates (optional, decode.check_lines; one list of line templates per prompt or one for all): given characters, free columns
+    and id classes for the opening columns of a line (encode_template), e.g. an acrostic
+    templates=[encode_template(tokenizer, c + "…") for c in "春夏秋冬"]."""
     from .decode import GreedyDecoder, check_ngram
     eng = model.engine()
     sh = eng.sh
@@ -190,7 +191,7 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     length = sh.max_seq_length if length is None else length
     n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
     pre = _prompt_prefixes(prefixes, n_prompts, length, sh)
-    lines = _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre)
+    lines = _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre, templates)
     keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
     if isinstance(rows, dict):
         stacked = {k: torch.as_tensor(np.asarray(rows[k])) for k in keys}
@@ -224,14 +225,15 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
 
 
 def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature=1.1, repetition_penalty=1.5, max_batch=256,
-                   return_all=False, prefixes=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None):
+                   return_all=False, prefixes=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None):
     """Beam search per prompt on the batched, graph-replayed decoder (BeamDecoder): prompts are decoded max_batch // num_beams at
     a time, every beam is cut back to what sample_sequence would have returned (GreedyDecoder.reference_return) and
     post-processed as generate_samples does.  rows: as generate_samples.  Returns one string per prompt (its best beam), or with
     return_all=True one list per prompt of num_beams (text, score) pairs, best first (score: the sum of the fp32 log-probabilities
     of the processed logits at the positions the model chose; see BeamDecoder).  prefixes: as generate_samples (the prefix
     positions add nothing to a score).  no_repeat_ngram_size: as generate_samples, on every beam's own history.  line_lengths /
-    line_end_ids: as generate_samples, shared by a prompt's beams (a full line adds nothing to a score)."""
+    line_end_ids / templates: as generate_samples, shared by a prompt's beams (a full line and a given column add nothing to a
+    score)."""
     from .decode import BeamDecoder, GreedyDecoder, check_ngram
     eng = model.engine()
     sh = eng.sh
@@ -239,7 +241,7 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
     length = sh.max_seq_length if length is None else length
     n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
     pre = _prompt_prefixes(prefixes, n_prompts, length, sh)
-    lines = _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre)
+    lines = _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre, templates)
     keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
     if isinstance(rows, dict):
         stacked = {k: torch.as_tensor(np.asarray(rows[k])) for k in keys}

@@ -118,6 +118,11 @@ _SIGS = {
                                  _vp, _vp], _i),
     "mmtg_decode_beam_candidates_lines": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
                                           _vp, _vp], _i),
+    "mmtg_decode_select_tmpl": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp], _i),
+    "mmtg_decode_sample_tmpl": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i,
+                                _vp, _vp, _vp], _i),
+    "mmtg_decode_beam_candidates_tmpl": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
+                                         _vp, _vp, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
     "mmtg_decode_mlp_sync_words": ([], _i),
     "mmtg_decode_mlp_census": ([_vp, _vp], _i),
@@ -859,34 +864,47 @@ def _lines(tables, B, V):
     return _p(lo), _p(hi), lo.shape[1], _p(sets), n_sets, _p(set_of)
 
 
-def _rule_tail(form, B, V, fixed_end, ngram, tables):
-    """What the selection entry of `form` ("" plain, "_fixed", "_ngram", "_lines") takes between its own arguments and the stream."""
+def _template(tmpl, tables, B, sent):
+    """The symbol table of decode.check_lines on the device, int32 [rows >= B, n_lines of the line tables, sent - 2] (None is passed
+    on: the library rejects it)."""
+    if tmpl is not None:
+        if not (tmpl.dtype == torch.int32 and tmpl.dim() == 3 and tmpl.shape[0] >= B and tmpl.shape[1] == tables[0].shape[1]
+                and tmpl.shape[2] == sent - 2 and tmpl.is_contiguous()):
+            raise ValueError("template table must be contiguous int32 [rows >= %d, n_lines, sent - 2 = %d]" % (B, sent - 2))
+    return _p(tmpl)
+
+
+def _rule_tail(form, B, V, fixed_end, ngram, tables, tmpl=None, sent=0):
+    """What the selection entry of `form` ("" plain, "_fixed", "_ngram", "_lines", "_tmpl") takes between its own arguments and the
+    stream."""
     if form == "":
         return ()
     tail = (_fixed(fixed_end, B),)
     if form != "_fixed":
         tail += (int(ngram),)
-    if form == "_lines":
+    if form in ("_lines", "_tmpl"):
         tail += _lines(tables, B, V)
+    if form == "_tmpl":
+        tail += (_template(tmpl, tables, B, sent),)
     return tail
 
 
 def _select(form, logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, sampling=None, fixed_end=None, ngram=0,
-            tables=None):
+            tables=None, tmpl=None):
     """mmtg_decode_select<form>, or with sampling = (top_k, top_p, uniforms) mmtg_decode_sample<form>."""
     name = ("decode_select" if sampling is None else "decode_sample") + form
     draw = () if sampling is None else (int(sampling[0]), float(sampling[1]), _p(sampling[2]), sampling[2].stride(0))
     _check(getattr(lib(), "mmtg_" + name)(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
-                                          float(rep_penalty), *draw, B, _p(pos_next), *_rule_tail(form, B, V, fixed_end, ngram, tables),
-                                          _stream()), name)
+                                          float(rep_penalty), *draw, B, _p(pos_next),
+                                          *_rule_tail(form, B, V, fixed_end, ngram, tables, tmpl, sent), _stream()), name)
 
 
 def _beam_candidates(form, logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=None, ngram=0,
-                     tables=None):
+                     tables=None, tmpl=None):
     name = "decode_beam_candidates" + form
     _check(getattr(lib(), "mmtg_" + name)(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
                                           float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B,
-                                          *_rule_tail(form, B, V, fixed_end, ngram, tables), _stream()), name)
+                                          *_rule_tail(form, B, V, fixed_end, ngram, tables, tmpl, sent), _stream()), name)
 
 
 def _beam_merge(form, cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next, fixed_end=None):
@@ -969,6 +987,27 @@ def decode_beam_candidates_lines(logits, ldl, V, seq, pos, P, sent, temperature,
     """decode_beam_candidates_ngram (ngram may be 0) under the line rule: a full line offers PAD the way sticky PAD does."""
     _beam_candidates("_lines", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=fixed_end,
                      ngram=ngram, tables=tables)
+
+
+def decode_select_tmpl(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, tables, tmpl, ngram=0, fixed_end=None,
+                       pos_next=None):
+    """decode_select_lines under the line templates of `tmpl` (include/mmtg_hip.h): a given column writes its id, a class column is
+    confined to the class."""
+    _select("_tmpl", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, fixed_end=fixed_end, ngram=ngram,
+            tables=tables, tmpl=tmpl)
+
+
+def decode_sample_tmpl(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, tables, tmpl, ngram=0,
+                       fixed_end=None, pos_next=None):
+    _select("_tmpl", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, (top_k, top_p, uniforms),
+            fixed_end=fixed_end, ngram=ngram, tables=tables, tmpl=tmpl)
+
+
+def decode_beam_candidates_tmpl(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, tables, tmpl,
+                                ngram=0, fixed_end=None):
+    """decode_beam_candidates_lines under the line templates: a given column offers its id the way a full line offers PAD."""
+    _beam_candidates("_tmpl", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=fixed_end,
+                     ngram=ngram, tables=tables, tmpl=tmpl)
 
 
 def decode_advance(pos):
