@@ -680,6 +680,42 @@ MMTG_API int mmtg_decode_beam_candidates_tmpl(const float* logits, long ldl, int
                                      int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
                                      void* stream);
 
+/* ---- rhyme schemes (GreedyDecoder / BeamDecoder with rhyme_scheme=, mmtg_amd/decode.py): lines that end on one rhyme, the rhyme
+ * being the model's choice.  The reference has no such constraint (generate.py:117-142).  The caller partitions the ids that have a
+ * rhyme into classes, rows of the SAME `sets` bit table the end sets and template classes use: class_of int16 [V], class_of[v] the row
+ * of v's class or -1.  A scheme ("AABB") groups the lines; the first line of a group with more than one line is its leader, the
+ * others its followers: lead int8 [B, n_lines], lead[b, l] = the leader's line (< l) of follower l, else -1 (so n_lines <= 128).
+ *   leader: an ordinary line whose static end set (set_of) is the union of the classes; nothing here is new for it;
+ *   follower l with leader r: t = the last non-PAD id among lyric columns r * sent + 1 .. r * sent + sent - 2 of the row's own
+ *     history (a beam's reordered history; given prefix columns count), k = class_of[t].  If t and k exist, the line behaves as a
+ *     line whose end set is row k of `sets`: PAD is -inf unless the previous token is a member, and at c == hi - 1 every id outside
+ *     the row is -inf.  With distinct != 0 the end ids of the earlier lines of the group (leader included) are taken out of that set
+ *     for both effects.  If the leader's line is empty or t has no class, line l has no rhyme constraint in that row.  A follower's
+ *     own set_of entry is -1 (the host rejects a static end set on a follower).
+ * The rule acts where the end set acts and composes with n-gram bans, bounds and templates (an id survives only if every rule admits
+ * it); all -inf behaves as in the *_lines entries.  tmpl may be null (no templates): one form serves both.  Finding t reads at most
+ * sent - 2 ids of the row before the occurrence count; the mask is read from global memory in the *_tmpl entries' one pass over the
+ * count words, so the dynamic LDS request is theirs; distinct adds one sentinel write per earlier line of the group.  Each entry is
+ * its *_tmpl namesake plus (class_of, lead, distinct) before the stream; a null class_of or lead, n_sets == 0, n_lines > 128 or a
+ * distinct other than 0 / 1 fails before any device call.  The beam merge is unchanged.  The kernels of every earlier entry compile
+ * to the same code as before these were added.                                                                                      */
+MMTG_API int mmtg_decode_select_rhyme(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                            int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, const int* fixed_end,
+                            int ngram, const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets,
+                            int n_sets, const short* set_of, const int* tmpl, const short* class_of, const signed char* lead,
+                            int distinct, void* stream);
+MMTG_API int mmtg_decode_sample_rhyme(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                            int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                            const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, int ngram,
+                            const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
+                            const short* set_of, const int* tmpl, const short* class_of, const signed char* lead, int distinct,
+                            void* stream);
+MMTG_API int mmtg_decode_beam_candidates_rhyme(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                     int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                     int B, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
+                                     int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
+                                     const short* class_of, const signed char* lead, int distinct, void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

@@ -1093,7 +1093,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void de
 }
 
 // The selection kernels below end in one argument, the step's rule R: NoRule (the plain entries), FixedEnd (*_fixed), NgramBan
-// (*_ngram), LineRule (*_lines) or TemplateRule (*_tmpl).  A rule says which rows it holds (held) and, with R::ngram (the sentinel of penalize<true> is
+// (*_ngram), LineRule (*_lines), TemplateRule (*_tmpl) or RhymeRule (*_rhyme).  A rule says which rows it holds (held) and, with R::ngram (the sentinel of penalize<true> is
 // in use; bans() gives the NgramBan) and R::lines (PAD's slot is read; col() says what the line wants of a free column), which
 // edits of the occurrence table the kernel makes after count_ids.
 //
@@ -1108,13 +1108,13 @@ struct LineCol {
 };
 
 struct NoRule {
-    static constexpr bool ngram = false, lines = false, tmpl = false;
+    static constexpr bool ngram = false, lines = false, tmpl = false, rhyme = false;
     __device__ __forceinline__ bool held(int, int) const { return false; }
 };
 
 struct FixedEnd {
     const int* fixed_end;   // int32 [B]
-    static constexpr bool ngram = false, lines = false, tmpl = false;
+    static constexpr bool ngram = false, lines = false, tmpl = false, rhyme = false;
     __device__ __forceinline__ bool held(int b, int pos) const { return pos + 1 < fixed_end[b]; }
 };
 
@@ -1126,7 +1126,7 @@ struct NgramBan {
     const int* fixed_end;   // int32 [B] or null
     int n;                  // 1 .. sent - 2
     int hist_cap;           // ints of dynamic LDS for the staged history (>= the longest history, min(ldseq - P, MAXGEN))
-    static constexpr bool ngram = true, lines = false, tmpl = false;
+    static constexpr bool ngram = true, lines = false, tmpl = false, rhyme = false;
     __device__ __forceinline__ bool held(int b, int pos) const { return fixed_end && pos + 1 < fixed_end[b]; }
     __host__ __device__ __forceinline__ const NgramBan& bans() const { return *this; }
 };
@@ -1164,7 +1164,7 @@ struct LineRule {
     const short* set_of;           // [B, n_lines] row of `sets` (-1: no end set), or null
     const unsigned* sets;          // [n_sets, words] bit v of a row: content id v is in the set
     int n_lines, n_sets, words;    // words >= ceil(V / 32)
-    static constexpr bool ngram = true, lines = true, tmpl = false;
+    static constexpr bool ngram = true, lines = true, tmpl = false, rhyme = false;
     __device__ __forceinline__ bool held(int b, int pos) const { return ng.held(b, pos); }
     __host__ __device__ __forceinline__ const NgramBan& bans() const { return ng; }
 
@@ -1214,7 +1214,7 @@ struct TmplCol {
 struct TemplateRule {
     LineRule ln;
     const int* table;              // [B, n_lines, sent - 2]
-    static constexpr bool ngram = true, lines = true, tmpl = true;
+    static constexpr bool ngram = true, lines = true, tmpl = true, rhyme = false;
     __device__ __forceinline__ bool held(int b, int pos) const { return ln.held(b, pos); }
     __host__ __device__ __forceinline__ const NgramBan& bans() const { return ln.ng; }
     __device__ __forceinline__ LineCol col(int b, int j, int sent, const long long* gen) const { return ln.col(b, j, sent, gen); }
@@ -1245,6 +1245,84 @@ __device__ __forceinline__ void ban_line_tmpl(unsigned* cnt, int V, const LineCo
     __syncthreads();
 }
 
+// Rhyme schemes (the *_rhyme entries, include/mmtg_hip.h): a TemplateRule (its table may be null: no templates) whose end set, on
+// a follower line, is found at run time.  lead[b, l] is the line whose last content id t decides line l's rhyme (-1: no follower);
+// class_of[t] is t's class, a row of the line rule's own `sets` (-1: none).  A leader is an ordinary line with a static end set (the
+// union of the classes), so only followers are new here; a follower whose leader gave no class is an ordinary line.
+struct RhymeRule {
+    TemplateRule tm;               // tm.table may be null
+    const short* class_of;         // [V] row of `sets`, or -1
+    const signed char* lead;       // [B, n_lines] the leader's line (< l), or -1
+    int distinct;                  // a follower may not end on an id an earlier line of its group ends on
+    int V;
+    static constexpr bool ngram = true, lines = true, tmpl = true, rhyme = true;
+    __device__ __forceinline__ bool held(int b, int pos) const { return tm.held(b, pos); }
+    __host__ __device__ __forceinline__ const NgramBan& bans() const { return tm.ln.ng; }
+    __device__ __forceinline__ TmplCol sym(int b, int j, int sent) const {
+        return tm.table ? tm.sym(b, j, sent) : TmplCol{-1, nullptr};
+    }
+
+    // the last content id of line r of the row (0: the line is empty); at most sent - 2 reads, every thread the same
+    __device__ __forceinline__ int line_end(int r, int sent, const long long* gen) const {
+        long long t = 0;
+        for (int q = r * sent + 1; q < r * sent + sent - 1; ++q) {
+            const long long v = gen[q];
+            if (v != 0) t = v;
+        }
+        return t > 0 && t < V ? (int)t : 0;
+    }
+
+    // row b's leader of line l, or -1 (a leader lies before its follower, so its line is complete when the follower is written)
+    __device__ __forceinline__ int leader(int b, int l) const {
+        const int r = lead[(long)b * tm.ln.n_lines + l];
+        return r >= 0 && r < l ? r : -1;
+    }
+
+    // LineRule::col with a follower's set index taken from class_of[t]; *rhymes: the column is a follower's and its leader gave a class
+    __device__ __forceinline__ LineCol col(int b, int j, int sent, const long long* gen, bool* rhymes) const {
+        const LineRule& ln = tm.ln;
+        const int l = j / sent, c = j % sent - 1;
+        const int r = l < ln.n_lines ? leader(b, l) : -1;
+        *rhymes = false;
+        if (r < 0) return ln.col(b, j, sent, gen);
+        LineCol lc = {false, false, nullptr};
+        const long at = (long)b * ln.n_lines + l;
+        const int lo_ = ln.lo[at], hi_ = ln.hi[at];
+        lc.force_pad = c >= hi_;
+        lc.pad_ban = c < lo_;
+        if (lc.force_pad) return lc;
+        const int t = line_end(r, sent, gen);
+        const int s = t ? (int)class_of[t] : -1;
+        if (s >= 0 && s < ln.n_sets) {
+            const unsigned* m = ln.sets + (long)s * ln.words;
+            const long long prev = gen[j - 1];
+            const bool in = prev >= 0 && prev < 32LL * ln.words && ((m[prev >> 5] >> (prev & 31)) & 1u);
+            lc.pad_ban = lc.pad_ban || !in;
+            if (c == hi_ - 1) lc.mask = m;
+            *rhymes = true;
+        }
+        return lc;
+    }
+
+    // rhyme_distinct, after ban_line_tmpl on a column col() said rhymes: thread m < l looks at line m; if it is of the follower's
+    // group, its end id loses its place in the set -- the sentinel at the mask column, and PAD's sentinel where it is the previous
+    // token.  All threads of the block call (rhymes is uniform over the block).
+    __device__ __forceinline__ void ban_distinct(unsigned* cnt, int b, int j, int sent, const long long* gen, const LineCol& lc,
+                                                 bool rhymes, int tid) const {
+        const LineRule& ln = tm.ln;
+        if (!distinct || !rhymes) return;
+        const int l = j / sent, r = leader(b, l);
+        if (tid < l && (tid == r || lead[(long)b * ln.n_lines + tid] == r)) {
+            const int t = line_end(tid, sent, gen);
+            if (t) {
+                if (lc.mask) atomicOr(cnt + (t >> 1), 0xFFFFu << (16 * (t & 1)));
+                if (gen[j - 1] == t) atomicOr(cnt, 0xFFFFu);
+            }
+        }
+        __syncthreads();
+    }
+};
+
 // logits processor + arg-max + forced-token cadence + append (generate.py:117-142), device-driven.
 template <typename R>
 __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restrict__ logits, long ldl, int V,
@@ -1268,8 +1346,10 @@ __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restr
     const int n = min(j, MAXGEN);
     if (gen[n - 1] == 0) { if (tid == 0) gen[j] = 0; return; }                   // sticky PAD
     LineCol lc = {false, false, nullptr};
+    [[maybe_unused]] bool rhymes = false;
     if constexpr (R::lines) {
-        lc = rule.col(b, j, sent, gen);
+        if constexpr (R::rhyme) lc = rule.col(b, j, sent, gen, &rhymes);
+        else lc = rule.col(b, j, sent, gen);
         if (lc.force_pad) { if (tid == 0) gen[j] = 0; return; }                  // the line is full: PAD, as sticky PAD writes it
     }
     TmplCol tc = {-1, nullptr};
@@ -1285,10 +1365,11 @@ __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restr
     }
     if constexpr (R::tmpl) ban_line_tmpl(cnt, V, lc, tc.cls, tid);
     else if constexpr (R::lines) ban_line(cnt, V, lc, tid);
+    if constexpr (R::rhyme) rule.ban_distinct(cnt, b, j, sent, gen, lc, rhymes, tid);
     if (uniforms) {            // stochastic: uniforms[pos, b] drives the draw (top_k == 1 and top_p == 0 is the greedy path)
         float* px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
         int pick;
-        if constexpr (R::tmpl)     // (sample_row's comment: an instantiation of its own, inlined by force)
+        if constexpr (R::tmpl)     // (sample_row's comment: an instantiation of its own, inlined by force; the rhyme form's too)
             [[clang::always_inline]] pick = sample_row<true, true, true>(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k,
                                                                          top_p, uniforms[(long)pos * ldu + b], tid, nullptr);
         else
@@ -1352,8 +1433,10 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __res
         return;
     }
     LineCol lc = {false, false, nullptr};
+    [[maybe_unused]] bool rhymes = false;
     if constexpr (R::lines) {
-        lc = rule.col(b, j, sent, gen);
+        if constexpr (R::rhyme) lc = rule.col(b, j, sent, gen, &rhymes);
+        else lc = rule.col(b, j, sent, gen);
         if (lc.force_pad) {                                // the line is full: PAD with the score unchanged, as sticky PAD offers it
             if (tid < nb) { cv[tid] = tid == 0 ? 0.f : -INFINITY; ci[tid] = 0; }
             return;
@@ -1374,6 +1457,7 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __res
     }
     if constexpr (R::tmpl) ban_line_tmpl(cnt, V, lc, tc.cls, tid);
     else if constexpr (R::lines) ban_line(cnt, V, lc, tid);
+    if constexpr (R::rhyme) rule.ban_distinct(cnt, b, j, sent, gen, lc, rhymes, tid);
     const float* row = logits + (long)b * ldl;
     float mx = -INFINITY;
     for (int v = tid; v < V; v += 256) {
@@ -1894,6 +1978,62 @@ extern "C" int mmtg_decode_beam_candidates_tmpl(const float* logits, long ldl, i
         return e;
     return beam_candidates_launch("decode_beam_candidates_tmpl", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
                                   nb, cand_val, cand_id, B, stream, tr);
+}
+
+// (a *_rhyme entry's checks: its *_lines namesake's -- the template table is optional here -- and the rhyme tables)
+static int rhyme_check(const char* what, const float* logits, int V, long ldseq, int P, int sent, const int* fixed_end, int ngram,
+                       const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
+                       const short* set_of, const int* tmpl, const short* class_of, const signed char* lead, int distinct,
+                       RhymeRule* rr) {
+    LineRule lr;
+    if (int e = lines_check(what, logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, &lr)) return e;
+    MMTG_REQUIRE(class_of && lead, "%s: class_of [V] and lead [B, n_lines] are needed", what);
+    MMTG_REQUIRE(n_sets > 0, "%s: rhyme classes are rows of sets (n_sets %d)", what, n_sets);
+    MMTG_REQUIRE(n_lines <= 128, "%s: %d lines, a leader's line index must fit a signed char (128)", what, n_lines);
+    MMTG_REQUIRE(distinct == 0 || distinct == 1, "%s: distinct is 0 or 1 (got %d)", what, distinct);
+    *rr = RhymeRule{TemplateRule{lr, tmpl}, class_of, lead, distinct, V};
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_select_rhyme(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                        int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, const int* fixed_end,
+                                        int ngram, const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets,
+                                        int n_sets, const short* set_of, const int* tmpl, const short* class_of,
+                                        const signed char* lead, int distinct, void* stream) {
+    RhymeRule rr;
+    if (int e = rhyme_check("decode_select_rhyme", logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, tmpl,
+                            class_of, lead, distinct, &rr))
+        return e;
+    return decode_select_launch("decode_select_rhyme", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, 1, 0.f, nullptr,
+                                0, B, pos_next, stream, rr);
+}
+
+extern "C" int mmtg_decode_sample_rhyme(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                        int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                                        const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, int ngram,
+                                        const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
+                                        const short* set_of, const int* tmpl, const short* class_of, const signed char* lead,
+                                        int distinct, void* stream) {
+    RhymeRule rr;
+    if (int e = rhyme_check("decode_sample_rhyme", logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, tmpl,
+                            class_of, lead, distinct, &rr))
+        return e;
+    if (int e = sample_args_check("decode_sample_rhyme", uniforms, ldu, B, top_k, top_p)) return e;
+    return decode_select_launch("decode_sample_rhyme", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p,
+                                uniforms, ldu, B, pos_next, stream, rr);
+}
+
+extern "C" int mmtg_decode_beam_candidates_rhyme(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                                 int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                                 int B, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
+                                                 int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
+                                                 const short* class_of, const signed char* lead, int distinct, void* stream) {
+    RhymeRule rr;
+    if (int e = rhyme_check("decode_beam_candidates_rhyme", logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets,
+                            set_of, tmpl, class_of, lead, distinct, &rr))
+        return e;
+    return beam_candidates_launch("decode_beam_candidates_rhyme", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
+                                  nb, cand_val, cand_id, B, stream, rr);
 }
 
 extern "C" int mmtg_ln_fold_weights(const void* W, long ldw, const float* gamma, const float* beta, const float* bias, void* Wf,

@@ -87,6 +87,26 @@ def encode_line_end(tokenizer, chars, vocab_cut=13317):
     return frozenset(ids)
 
 
+def encode_rhyme_classes(tokenizer, groups, vocab_cut=13317):
+    """The rhyme classes of decode.check_lines' rhyme_classes from strings of characters that rhyme, e.g. ["光忙香", "天年前"]: one
+    frozenset of ids per string, one character one token.  As encode_line_end, a character the tokenizer does not know, a non-content
+    id or one at or above the generation's vocabulary cut raises ValueError; so do an empty string and a character in two classes
+    (the classes are a partition of the ids that have a rhyme).  The project ships no pronunciation data: the caller supplies it."""
+    classes, owner = [], {}
+    for i, chars in enumerate(groups):
+        ids = encode_line_end(tokenizer, chars, vocab_cut)
+        if not ids:
+            raise ValueError("rhyme class %d (%r) holds no character" % (i, chars))
+        for v in sorted(ids):
+            if v in owner:
+                raise ValueError("id %d is in rhyme classes %d and %d" % (v, owner[v], i))
+            owner[v] = i
+        classes.append(ids)
+    if not classes:
+        raise ValueError("no rhyme class given")
+    return classes
+
+
 def encode_template(tokenizer, text, classes=None, vocab_cut=13317):
     """One line's template (decode.check_lines' templates) from a string, one character per content column: `?` / `？` is a free
     column, a character that is a key of `classes` (a dict from one character to an id set, e.g. encode_line_end's) stands for that

@@ -79,10 +79,14 @@ class LineTables:
     """The packed line constraints check_lines returns: lo, hi uint8 [rows, n_lines]; set_of int16 [rows, n_lines] (-1: no end set)
     and sets uint32 [n_sets, ceil(V / 32)] (bit v & 31 of word v >> 5: id v is a member), or both None when no line has a set.
     tmpl (templates= only, else None): int32 [rows, n_lines, sent - 2], one symbol per content column -- v >= 0 a given id, -1 free,
-    v <= -2 the class `sets[-2 - v]` (classes and end sets share the table); a template's length is folded into lo / hi."""
+    v <= -2 the class `sets[-2 - v]` (classes and end sets share the table); a template's length is folded into lo / hi.
+    class_of, lead, distinct (rhyme_scheme= only, else None, None, False): class_of int16 [V], the row of `sets` that is id v's rhyme
+    class or -1; lead int8 [rows, n_lines], the leader's line of a follower line or -1; a leader's static end set (the union of the
+    classes) is folded into set_of."""
 
-    def __init__(self, lo, hi, set_of, sets, sent, V, tmpl=None):
+    def __init__(self, lo, hi, set_of, sets, sent, V, tmpl=None, class_of=None, lead=None, distinct=False):
         self.lo, self.hi, self.set_of, self.sets, self.sent, self.V, self.tmpl = lo, hi, set_of, sets, sent, V, tmpl
+        self.class_of, self.lead, self.distinct = class_of, lead, bool(distinct)
 
     @property
     def rows(self):
@@ -91,12 +95,26 @@ class LineTables:
     def repeat(self, k):
         """Every row k times in place of itself (the beams of a prompt share its constraints)."""
         rep = lambda a: None if a is None else np.repeat(a, k, axis=0)      # noqa: E731
-        return LineTables(rep(self.lo), rep(self.hi), rep(self.set_of), self.sets, self.sent, self.V, rep(self.tmpl))
+        return LineTables(rep(self.lo), rep(self.hi), rep(self.set_of), self.sets, self.sent, self.V, rep(self.tmpl),
+                          self.class_of, rep(self.lead), self.distinct)
 
     def take(self, idx):
         """Rows idx (a list of row indices) as tables of their own; the sets are shared."""
         sub = lambda a: None if a is None else np.ascontiguousarray(a[idx])      # noqa: E731
-        return LineTables(sub(self.lo), sub(self.hi), sub(self.set_of), self.sets, self.sent, self.V, sub(self.tmpl))
+        return LineTables(sub(self.lo), sub(self.hi), sub(self.set_of), self.sets, self.sent, self.V, sub(self.tmpl),
+                          self.class_of, sub(self.lead), self.distinct)
+
+    def leader(self, b, l):
+        """The line whose ending decides the rhyme of row b's line l (l is a follower), or None."""
+        if self.lead is None or l >= self.lead.shape[1] or self.lead[b, l] < 0:
+            return None
+        return int(self.lead[b, l])
+
+    def rhyme_class(self, v):
+        """The rhyme class of id v as a frozenset, or None (no scheme, or v has no rhyme)."""
+        if self.class_of is None or not 0 <= v < len(self.class_of) or self.class_of[v] < 0:
+            return None
+        return self.members(int(self.class_of[v]))
 
     def symbol(self, b, l, c):
         """What row b's template says of content column c of line l: an int (a given id), a frozenset (a class) or None (free, no
@@ -173,7 +191,40 @@ def _content_id(v, V):
     return not (v == 0 or v in BANNED or v < 0 or (V is not None and v >= V))
 
 
-def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefix=None, templates=None):
+def _scheme_rows(spec, rows):
+    """rhyme_scheme as one string (or None) per row: one string for all rows, or a list with one string or None per row."""
+    if isinstance(spec, str):
+        spec = [spec] * rows
+    elif not isinstance(spec, (list, tuple)) or not all(r is None or isinstance(r, str) for r in spec):
+        raise ValueError("rhyme_scheme: a string (or a list with one string or None per row) expected, got %r" % (spec,))
+    if len(spec) != rows:
+        raise ValueError("rhyme_scheme has %d rows, the generation %d" % (len(spec), rows))
+    return ["" if r is None else r for r in spec]
+
+
+def _rhyme_classes(classes, V):
+    """rhyme_classes as a list of frozensets: pairwise disjoint, non-empty sets of content ids below V."""
+    if not isinstance(classes, (list, tuple)) or not classes:
+        raise ValueError("rhyme_classes: a non-empty list of id sets expected, got %r" % (classes,))
+    out, owner = [], {}
+    for i, e in enumerate(classes):
+        if not _is_ids(e) or (isinstance(e, np.ndarray) and e.ndim != 1) or not all(_is_int(v) for v in e):
+            raise ValueError("rhyme_classes, class %d: a collection of ids expected, got %r" % (i, e))
+        ids = frozenset(int(v) for v in e)
+        if not ids:
+            raise ValueError("rhyme_classes, class %d: the class is empty" % i)
+        for v in sorted(ids):
+            if not _content_id(v, V):
+                raise ValueError("rhyme_classes, class %d: id %d is not a content id below the vocabulary cut" % (i, v))
+            if v in owner:
+                raise ValueError("rhyme_classes: id %d is in classes %d and %d (the classes are disjoint)" % (v, owner[v], i))
+            owner[v] = i
+        out.append(ids)
+    return out
+
+
+def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefix=None, templates=None, rhyme_scheme=None,
+                rhyme_classes=None, rhyme_distinct=False):
     """Validate line-length bounds and line-end id sets on the host, before any device work; returns the packed LineTables, or
     None when both arguments are None (no constraints: the decoders then run the launches of a generation without them).
 
@@ -196,9 +247,25 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
     or None per row.  Given ids and class members are content ids below V; on a line with an end set whose length the template
     fixes (hi == k) the last symbol must leave a member of the set possible.  A partial prefix line must agree with its line's
     template.  So a column that only classes and end sets constrain always has a live id; only n-gram bans can empty one.
-    Raises ValueError for bounds outside 0 .. sent - 2, lo > hi, more entries than lines, and any end set or template that breaks
-    the above."""
-    if line_lengths is None and line_end_ids is None and templates is None:
+    rhyme_scheme / rhyme_classes / rhyme_distinct: a scheme is a string with one symbol per line -- a letter names the line's
+    group, `.` leaves the line alone, a shorter string leaves the later lines alone -- one for every row or a list with one string
+    or None per row.  rhyme_classes (required with a scheme) is a list of pairwise disjoint, non-empty sets of content ids below V:
+    the ids that have a rhyme, by rhyme.  The first line of a group of two or more is its leader and gets the union of the classes
+    as a static end set (intersected with its line_end_ids set, which must leave an id), so it is not empty (hi >= 1); the others
+    are followers: they end in the class of the id their leader ended on in that row (include/mmtg_hip.h), with rhyme_distinct not
+    on an id an earlier line of the group ended on.  A follower takes no line_end_ids set of its own, needs hi >= 1, and a template
+    that fixes its last possible column (hi == k) must leave every class possible there: no given id, and a class symbol that
+    meets every rhyme class (with rhyme_distinct in as many ids as the group has lines up to this one).  With rhyme_distinct every
+    class has at least as many ids as the largest group has lines; rhyme_distinct without a scheme raises.  A group of one line is
+    unconstrained.
+    Raises ValueError for bounds outside 0 .. sent - 2, lo > hi, more entries than lines, and any end set, template or scheme that
+    breaks the above."""
+    if (rhyme_scheme is None) != (rhyme_classes is None):
+        raise ValueError("rhyme_scheme and rhyme_classes come together (got %s alone)"
+                         % ("rhyme_scheme" if rhyme_classes is None else "rhyme_classes"))
+    if rhyme_distinct and rhyme_scheme is None:
+        raise ValueError("rhyme_distinct without a rhyme_scheme")
+    if line_lengths is None and line_end_ids is None and templates is None and rhyme_scheme is None:
         return None
     if length < 1 or not 3 <= sent <= 257:
         raise ValueError("line constraints need length >= 1 and 3 <= sent <= 257 (got length %d, sent %d)" % (length, sent))
@@ -214,6 +281,14 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
     tmpls = _template_rows(templates, rows)
     tmpl = None if templates is None else np.full((rows, n_lines, cap), -1, np.int32)
     table, seen = [], {}
+    schemes = lead = classes = rhymed = None
+    if rhyme_scheme is not None:
+        schemes, classes = _scheme_rows(rhyme_scheme, rows), _rhyme_classes(rhyme_classes, V)
+        if n_lines > 128:
+            raise ValueError("rhyme_scheme: a generation of %d lines (a scheme serves up to 128)" % n_lines)
+        rhymed = frozenset().union(*classes)
+        lead = np.full((rows, n_lines), -1, np.int8)
+    place = {}                                               # (row, follower line) -> how many lines of its group lie before it
 
     def set_index(ids):
         if ids not in seen:
@@ -249,6 +324,35 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
                         if v == 0 or v in BANNED or v < 0 or (V is not None and v >= V):
                             raise ValueError("line_end_ids row %d, line %d: id %d is not a content id below the vocabulary cut" % (b, l, v))
                     set_of[b, l] = set_index(ids)
+        if schemes is not None:
+            sch = schemes[b]
+            if not all(ch == "." or ch.isalpha() for ch in sch):
+                raise ValueError("rhyme_scheme row %d: %r holds symbols other than letters and '.'" % (b, sch))
+            if len(sch) > n_lines:
+                raise ValueError("rhyme_scheme row %d has %d lines, a generation of length %d holds %d" % (b, len(sch), length, n_lines))
+            groups = {}
+            for l, ch in enumerate(sch):
+                if ch != ".":
+                    groups.setdefault(ch, []).append(l)
+            for ch, ls in groups.items():
+                if len(ls) < 2:
+                    continue                                     # a group of one line is unconstrained
+                if rhyme_distinct and min(len(k) for k in classes) < len(ls):
+                    raise ValueError("rhyme_scheme row %d: rhyme_distinct and group %r of %d lines, but a rhyme class of %d ids"
+                                     % (b, ch, len(ls), min(len(k) for k in classes)))
+                for i, l in enumerate(ls):
+                    if hi[b, l] == 0:
+                        raise ValueError("rhyme_scheme row %d, line %d: a rhyming line with hi = 0" % (b, l))
+                    if i == 0:                                   # the leader: a static end set, the ids that have a rhyme
+                        ids = rhymed if set_of[b, l] < 0 else rhymed & table[set_of[b, l]]
+                        if not ids:
+                            raise ValueError("rhyme_scheme row %d, line %d: no id of the line's end set has a rhyme class" % (b, l))
+                        set_of[b, l] = set_index(ids)
+                    else:
+                        if set_of[b, l] >= 0:
+                            raise ValueError("rhyme_scheme row %d, line %d: a follower line takes no line_end_ids set of its own" % (b, l))
+                        lead[b, l] = ls[0]
+                        place[b, l] = i
         for l in range(n_lines):
             if set_of[b, l] >= 0 and hi[b, l] == 0:
                 raise ValueError("line_end_ids row %d, line %d: an end set on a line with hi = 0" % (b, l))
@@ -297,6 +401,15 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
                     raise ValueError("%s: the line ends on the given id %d, which is not in its end set" % (at, int(y)))
                 if isinstance(y, (set, frozenset)) and not members & frozenset(int(v) for v in y):
                     raise ValueError("%s: the last column's class and the line's end set share no id" % at)
+            if (b, l) in place and hi[b, l] == k:                # a follower whose last possible column the template fixes
+                y = syms[-1]
+                if _is_int(y):
+                    raise ValueError("%s: a follower line of the rhyme scheme ends on the given id %d" % (at, int(y)))
+                if isinstance(y, (set, frozenset)):
+                    need = place[b, l] + 1 if rhyme_distinct else 1
+                    if any(len(kls & frozenset(int(v) for v in y)) < need for kls in classes):
+                        raise ValueError("%s: the last column's class leaves a rhyme class with fewer than %d ids on a follower line"
+                                         % (at, need))
         if prefix is not None:
             p = prefix[b]
             l, q = (len(p) - 1) // sent, (len(p) - 1) % sent
@@ -311,6 +424,7 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
                 given = sum(1 for v in p[l * sent + 1:] if v != 0)
                 if given > hi[b, l]:
                     raise ValueError("prefix row %d gives %d content tokens of line %d, more than its hi = %d" % (b, given, l, hi[b, l]))
+    rows_of = None if classes is None else [set_index(k) for k in classes]
     sets = None
     if table:
         if V is None:
@@ -319,23 +433,30 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
         for i, t in enumerate(table):
             for v in t:
                 sets[i, v >> 5] |= np.uint32(1 << (v & 31))
-    return LineTables(lo, hi, set_of if table else None, sets, sent, V, tmpl)
+    class_of = None
+    if classes is not None:
+        class_of = np.full(V, -1, np.int16)
+        for i, k in zip(rows_of, classes):
+            class_of[sorted(k)] = i
+    return LineTables(lo, hi, set_of if table else None, sets, sent, V, tmpl, class_of, lead, rhyme_distinct and lead is not None)
 
 
-def select_forms(with_head, prefix, ngram, lines, templates=False):
+def select_forms(with_head, prefix, ngram, lines, templates=False, rhymes=False):
     """Which selection entries a token step ends in: (form of mmtg_decode_select / _sample or mmtg_decode_beam_candidates, form of
-    mmtg_decode_beam_merge), each "" (plain), "_fixed", "_ngram", "_lines" or "_tmpl".  with_head: the step calls the model's head;
-    prefix: the generation has one; ngram: no_repeat_ngram_size; lines: line constraints are given; templates: line templates are
-    given (every step that calls the head then ends in "_tmpl").  The bans act where logits are read, so
+    mmtg_decode_beam_merge), each "" (plain), "_fixed", "_ngram", "_lines", "_tmpl" or "_rhyme".  with_head: the step calls the
+    model's head; prefix: the generation has one; ngram: no_repeat_ngram_size; lines: line constraints are given; templates: line
+    templates are given (every step that calls the head then ends in "_tmpl"); rhymes: a rhyme scheme is given (every such step
+    ends in "_rhyme", with or without templates).  The bans act where logits are read, so
     a step without the head (select with null logits; no candidates launch, merge with null candidates) and every merge only know
     the prefix -- a generation without constraints runs the plain entries throughout."""
     held = "_fixed" if prefix else ""
     if not with_head:
         return held, held
-    return ("_tmpl" if templates else "_lines" if lines else "_ngram" if ngram else held), held
+    return ("_rhyme" if rhymes else "_tmpl" if templates else "_lines" if lines else "_ngram" if ngram else held), held
 
 
-def _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, rows, length, sh, what, templates=None):
+def _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, rows, length, sh, what, templates=None,
+                       rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False):
     """The constraint arguments of ``begin`` for `rows` rows (`what` names them in messages): (n-gram size, checked prefix or None,
     LineTables or None).  A LineTables given as line_lengths is taken as checked."""
     sent = sh.msl + 2
@@ -343,9 +464,12 @@ def _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids,
     pre = None if prefix is None else check_prefix(prefix, rows, length, sent=sent, V=sh.V)
     if not isinstance(line_lengths, LineTables):
         return ngram, pre, check_lines(line_lengths, line_end_ids, rows, length, sent=sent, V=min(sh.V, 13317), prefix=pre,
-                                       templates=templates)
-    if line_lengths.rows != rows or line_end_ids is not None or templates is not None:
-        raise ValueError("line tables of %d rows for %s (and no line_end_ids / templates beside them)" % (line_lengths.rows, what))
+                                       templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes,
+                                       rhyme_distinct=rhyme_distinct)
+    if (line_lengths.rows != rows or line_end_ids is not None or templates is not None or rhyme_scheme is not None
+            or rhyme_classes is not None or rhyme_distinct):
+        raise ValueError("line tables of %d rows for %s (and no line_end_ids / templates / rhyme_scheme beside them)"
+                         % (line_lengths.rows, what))
     return ngram, pre, line_lengths
 
 
@@ -521,6 +645,10 @@ class GreedyDecoder:
         # every step that calls the head in the *_tmpl selection entries
         self.tmpl = None
         self._tmpl_buf = None
+        # rhyme scheme (rhyme_scheme=): (class_of int16 [V], this decoder's rows of lead int8 [B, lines of max_len], distinct); not None
+        # ends every step that calls the head in the *_rhyme selection entries
+        self.rhyme = None
+        self._rhyme_buf = None
 
     def _conv1d(self, x, wkey, out, **kw):
         # bf16: Engine._fwd routes Conv1D weights through their [out,in] copies (NT layout), which is
@@ -583,16 +711,19 @@ class GreedyDecoder:
         """The step's last launch: logits processing + arg-max / draw + the forced cadence + the next position (generate.py:117-142),
         through the entry select_forms names: the *_fixed ones leave row b's column pos + 1 alone while pos + 1 < fixed_end[b] (the
         host wrote it), the *_ngram ones also ban every id that would complete a content n-gram the row already holds, the *_lines
-        ones (n possibly 0) add the line-length bounds and line-end sets of include/mmtg_hip.h, the *_tmpl ones the line templates."""
+        ones (n possibly 0) add the line-length bounds and line-end sets of include/mmtg_hip.h, the *_tmpl ones the line templates,
+        the *_rhyme ones (templates or none) the rhyme scheme."""
         sh = self.eng.sh
         temperature, rep, top_k, top_p = self.params
-        tmpl = getattr(self, "tmpl", None)
-        form, _ = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=tmpl is not None)
+        tmpl, rhyme = getattr(self, "tmpl", None), getattr(self, "rhyme", None)
+        form, _ = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=tmpl is not None,
+                               rhymes=rhyme is not None)
         logits, ldl, V = (self.logits, self.eng.layout.Vpad, min(sh.V, 13317)) if with_head else (None, 0, 0)
         # stochastic: the draw of each position reads its row of the pre-filled uniforms
         sampling = (top_k, top_p, self.uniforms) if with_head and not (top_k == 1 and top_p == 0.0) else None
         hip._select(form, logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, self.B, self.pos_next, sampling,
-                    fixed_end=self.fixed_end if self.use_fixed else None, ngram=self.ngram, tables=self.lines, tmpl=tmpl)
+                    fixed_end=self.fixed_end if self.use_fixed else None, ngram=self.ngram, tables=self.lines, tmpl=tmpl,
+                    **({} if rhyme is None else {"rhyme": rhyme}))
 
     def _upload_lines(self, tables):
         """The line tables into this decoder's device buffers (allocated once, so captured graphs keep their addresses; a `sets`
@@ -622,7 +753,7 @@ class GreedyDecoder:
                 while cap < need:
                     cap *= 2
                 sets = self._line_buf[3] = torch.zeros(cap, tables.sets.shape[1], dtype=torch.int32, device=dev)
-                self.graphs = {k: g for k, g in self.graphs.items() if "lines" not in k and "tmpl" not in k}
+                self.graphs = {k: g for k, g in self.graphs.items() if "lines" not in k and "tmpl" not in k and "rhyme" not in k}
             sets.zero_()
             sets[:need].copy_(torch.from_numpy(tables.sets.view(np.int32)))
             set_of.copy_(padded(tables.set_of, -1, np.int16))
@@ -640,6 +771,25 @@ class GreedyDecoder:
         full[:, :tables.tmpl.shape[1]] = tables.tmpl
         self._tmpl_buf.copy_(torch.from_numpy(full))
         return self._tmpl_buf
+
+    def _upload_rhyme(self, tables):
+        """The rhyme tables of a generation with a scheme into this decoder's buffers (allocated once: captured graphs hold their
+        addresses), lines past the generation's without a leader (-1); None without a scheme.  `distinct` is a launch argument, so it
+        is part of the graph key."""
+        if tables is None or tables.lead is None:
+            return None
+        if self._rhyme_buf is None:
+            sent, dev = self.eng.sh.msl + 2, self.eng.dev
+            self._rhyme_buf = (torch.zeros(min(self.eng.sh.V, 13317), dtype=torch.int16, device=dev),
+                               torch.zeros(self.B, (self.max_len - 1) // sent + 1, dtype=torch.int8, device=dev))
+        class_of, lead = self._rhyme_buf
+        full = np.full(tuple(class_of.shape), -1, np.int16)
+        full[:len(tables.class_of)] = tables.class_of[:len(full)]
+        class_of.copy_(torch.from_numpy(full))
+        full = np.full(tuple(lead.shape), -1, np.int8)
+        full[:, :tables.lead.shape[1]] = tables.lead
+        lead.copy_(torch.from_numpy(full))
+        return class_of, lead, bool(tables.distinct)
 
     def _step_x3(self, with_head):
         """The split-precision token step: embedding -> projector -> 12 blocks -> head, every product through mmtg_decode_gemm_x3
@@ -848,9 +998,14 @@ class GreedyDecoder:
         """What the step's launches depend on: the settings, and the constraints as far as select_forms lets them reach this step
         (a step without the head runs the launches it always ran)."""
         key = (with_head, parity, self.params) + (("prefix",) if self.use_fixed else ()) + (("ngram", self.ngram) if self.ngram else ())
-        form = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=getattr(self, "tmpl", None) is not None)[0]
+        rhyme = getattr(self, "rhyme", None)
+        form = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=getattr(self, "tmpl", None) is not None,
+                            rhymes=rhyme is not None)[0]
         if form in ("_lines", "_tmpl"):
             key += (form[1:], "sets" if self.lines[2] is not None else "bounds")
+        if form == "_rhyme":                # (what the captured launch holds by value: the template table or none, distinct)
+            key += ("rhyme", "sets" if self.lines[2] is not None else "bounds") + (("tmpl",) if getattr(self, "tmpl", None) is not None else ())
+            key += ("distinct",) if rhyme[2] else ()
         return key
 
     def _step_state(self):
@@ -879,7 +1034,8 @@ class GreedyDecoder:
 
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
-              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None):
+              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
+              rhyme_distinct=False):
         """Everything of a generation that happens once: the settings, the uniforms of a stochastic run, fresh weight copies /
         LayerNorm folds, the experience encoder, the prompt (prefilled in one batched pass: ``first_pos`` = P afterwards) and the
         reset position.  Returns the end position n; ``step_at(pos)`` for pos = first_pos .. n - 1 then runs the token steps (``generate`` does both; tools/decode_lanes_threads.py drives
@@ -901,7 +1057,12 @@ class GreedyDecoder:
 
         templates (check_lines states the forms, include/mmtg_hip.h the rule): given ids, free columns and id classes for the opening
         columns of a line.  With templates every step that calls the head ends in the *_tmpl selection entries; the symbol table is
-        uploaded here, once, beside the line tables.  None runs exactly the launches and graphs of a generation without them."""
+        uploaded here, once, beside the line tables.  None runs exactly the launches and graphs of a generation without them.
+
+        rhyme_scheme / rhyme_classes / rhyme_distinct (check_lines states the forms, include/mmtg_hip.h the rule): which lines end on
+        one rhyme, e.g. "AABB", over the caller's partition of the ids that have a rhyme; which rhyme is each row's own choice,
+        made when it ends the group's first line.  With a scheme every step that calls the head ends in the *_rhyme selection
+        entries; the tables are uploaded here, once.  None runs exactly the launches and graphs of a generation without it."""
         eng, sh = self.eng, self.eng.sh
         B = batch["img_embs"].shape[0]
         if B != self.B:
@@ -909,7 +1070,8 @@ class GreedyDecoder:
         if length > self.max_len:
             raise ValueError("length %d exceeds max_len %d" % (length, self.max_len))
         ngram, pre, tables = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, B, length, sh,
-                                                "a batch of %d" % B, templates=templates)
+                                                "a batch of %d" % B, templates=templates, rhyme_scheme=rhyme_scheme,
+                                                rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct)
         self.params = (float(temperature), float(repitition_penalty), int(top_k), float(top_p))
         if not (int(top_k) == 1 and float(top_p) == 0.0):
             if self.uniforms is None:
@@ -936,11 +1098,13 @@ class GreedyDecoder:
         # (a view since construction) and its rows of the line tables (the sets are shared)
         lines = self._upload_lines(tables)
         tmpl = self._upload_templates(tables)
+        rhyme = self._upload_rhyme(tables)
         for i, d in enumerate([self] + self.children):
             a, z = (0, B) if d is self else ((i - 1) * d.B, i * d.B)
             d.use_fixed, d.ngram = pre is not None, ngram
             d.lines = None if lines is None else tuple(t if t is None or t is lines[2] else t[a:z] for t in lines)
             d.tmpl = None if tmpl is None else tmpl[a:z]
+            d.rhyme = None if rhyme is None else (rhyme[0], rhyme[1][a:z], rhyme[2])
         self.min_fixed = 0
         if pre is not None:
             lens = [len(p) for p in pre]
@@ -1012,7 +1176,7 @@ class GreedyDecoder:
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None,
                  use_graph=None, teacher=None, tap=None, prefix=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None,
-                 templates=None):
+                 templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False):
         """batch: dict with topic_ids/tpw_* [B,P], topic_emb, img_embs, r_embs (no targets needed).
         Runs `length` iterations of the reference loop and returns the lyric ids
         [B, 1 + length] (column 0 is the initial [#START#]).  top_k = 1, top_p = 0 is the greedy setting;
@@ -1030,10 +1194,13 @@ class GreedyDecoder:
         ids.  A line is full at its hi (the row pads from there), cannot end below its lo, and with an end set ends on a member.
         templates: what the opening columns of a line hold (``check_lines``): templates=[(a, ...), (b, ...)] opens line 0 with id
         a and line 1 with id b (an acrostic), (a, None, None, b) is a four-token line a ? ? b, a set in place of an id confines
-        the column to its members."""
+        the column to its members.
+        rhyme_scheme / rhyme_classes / rhyme_distinct: lines that end on one rhyme (``check_lines``): rhyme_scheme="AABB" with
+        rhyme_classes=[ids that rhyme, ...] makes lines 0 / 1 and 2 / 3 end in one class each, the class being what the row ended
+        the first line of the pair on; rhyme_distinct=True keeps a line from ending on the id an earlier line of its group ended on."""
         n_steps = self.begin(batch, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix,
                              no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths, line_end_ids=line_end_ids,
-                             templates=templates)
+                             templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct)
         eng, sh = self.eng, self.eng.sh
         saved_mode = self.use_graph
         if use_graph is not None:
@@ -1110,13 +1277,14 @@ class BeamDecoder(GreedyDecoder):
         PAD is) act in the candidates; the merge is the prefix-aware one or the plain one."""
         sh = self.eng.sh
         temperature, rep, _, _ = self.params
-        tmpl = getattr(self, "tmpl", None)
-        cand, merge = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=tmpl is not None)
+        tmpl, rhyme = getattr(self, "tmpl", None), getattr(self, "rhyme", None)
+        cand, merge = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=tmpl is not None,
+                                   rhymes=rhyme is not None)
         fe = self.fixed_end if self.use_fixed else None
         if with_head:
             hip._beam_candidates(cand, self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2, temperature,
                                  rep, self.nb, self.cand_val, self.cand_id, self.B, fixed_end=fe, ngram=self.ngram, tables=self.lines,
-                                 tmpl=tmpl)
+                                 tmpl=tmpl, **({} if rhyme is None else {"rhyme": rhyme}))
         hip._beam_merge(merge, self.cand_val if with_head else None, self.cand_id if with_head else None, self.scores, self.seq, self.keep,
                         self.rows, self.pos, sh.P, sh.msl + 2, self.nb, self.n_prompts, self.pos_next, fixed_end=fe)
 
@@ -1128,15 +1296,18 @@ class BeamDecoder(GreedyDecoder):
 
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
-              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None):
+              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
+              rhyme_distinct=False):
         """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill, the prefix, the line
-        constraints and the templates: one per prompt), the ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at
-        the free positions after a prompt's prefix."""
+        constraints, the templates and the rhyme scheme: one per prompt; every beam finds its leader's rhyme in its own history), the
+        ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at the free positions
+        after a prompt's prefix."""
         n = batch["img_embs"].shape[0]
         if n != self.n_prompts:
             raise ValueError("decoder was built for %d prompts, got %d" % (self.n_prompts, n))
         _, prefix, tables = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, n, length, self.eng.sh,
-                                               "%d prompts" % n, templates=templates)
+                                               "%d prompts" % n, templates=templates, rhyme_scheme=rhyme_scheme,
+                                               rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct)
         if tables is not None:
             tables = tables.repeat(self.nb)
         if prefix is not None:
@@ -1153,15 +1324,17 @@ class BeamDecoder(GreedyDecoder):
 
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None, no_repeat_ngram_size=0,
-                 line_lengths=None, line_end_ids=None, templates=None):
+                 line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_beams, 1 + length] in
         GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row.
         prefix: one per prompt (check_prefix), shared by its beams.  no_repeat_ngram_size: as GreedyDecoder.generate, per beam
         on its own (reordered) history.  line_lengths / line_end_ids / templates: as GreedyDecoder.generate, one per prompt, shared by
-        its beams (a given column adds nothing to a score)."""
+        its beams (a given column adds nothing to a score).  rhyme_scheme / rhyme_classes / rhyme_distinct: as GreedyDecoder.generate,
+        one scheme per prompt; each beam rhymes with its own earlier lines."""
         ids = super().generate(batch, length, temperature=temperature, repitition_penalty=repitition_penalty, use_graph=use_graph,
                                prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths,
-                               line_end_ids=line_end_ids, templates=templates)
+                               line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes,
+                               rhyme_distinct=rhyme_distinct)
         n, nb = self.n_prompts, self.nb
         ids = ids.view(n, nb, -1)
         sc = self.scores.view(n, nb).clone()

@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .data import encode_line_end, encode_prefix, encode_template  # noqa: F401  (public: the opening lines / the line-end sets / the line templates of generate_samples / generate_beams)
+from .data import encode_line_end, encode_prefix, encode_rhyme_classes, encode_template  # noqa: F401  (public: the opening lines / the line-end sets / the line templates / the rhyme classes of generate_samples / generate_beams)
 
 SENT_SLOT = 22  # generate.py:118-121
 BANNED = (1, 2, 100, 102)  # [#START#] [#EOS#] [UNK] [SEP] in src/vocab/vocab.txt
@@ -153,12 +153,13 @@ def _prompt_prefixes(prefixes, n_prompts, length, sh):
     return check_prefix(prefixes, n_prompts, length, sent=sh.msl + 2, V=sh.V)
 
 
-def _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre, templates=None):
-    """The packed line constraints and templates (decode.check_lines: one per prompt, or one for all), or None; validated before any
-    device work."""
+def _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre, templates=None, rhyme_scheme=None, rhyme_classes=None,
+                  rhyme_distinct=False):
+    """The packed line constraints, templates and rhyme scheme (decode.check_lines: one per prompt, or one for all), or None;
+    validated before any device work."""
     from .decode import check_lines
     return check_lines(line_lengths, line_end_ids, n_prompts, length, sent=sh.msl + 2, V=min(sh.V, 13317), prefix=pre,
-                       templates=templates)
+                       templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct)
 
 
 def _chunk_lines(tables, idx):
@@ -168,7 +169,7 @@ def _chunk_lines(tables, idx):
 
 def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperature=1.1, top_k=10, top_p=0.7,
                      repetition_penalty=1.5, max_batch=256, generator=None, decoder=None, prefixes=None, no_repeat_ngram_size=0,
-                     line_lengths=None, line_end_ids=None, templates=None):
+                     line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False):
     """n_samples texts per prompt (generate.sh's loop, generate.py:205-235) on the batched, graph-replayed decoder:
     every prompt is replicated over n_samples rows, rows are decoded max_batch at a time with the device-side
     top-k / top-p sampler (one uniform per row and position from `generator`), each row is cut back to what
@@ -183,7 +184,10 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     tokens and sets (encode_line_end) a line's last token comes from; every sample of a prompt follows its prompt's.
     templates (optional, decode.check_lines; one list of line templates per prompt or one for all): given characters, free columns
     and id classes for the opening columns of a line (encode_template), e.g. an acrostic
-    templates=[encode_template(tokenizer, c + "…") for c in "春夏秋冬"]."""
+    templates=[encode_template(tokenizer, c + "…") for c in "春夏秋冬"].
+    rhyme_scheme / rhyme_classes / rhyme_distinct (optional, decode.check_lines; one scheme per prompt or one for all): lines that
+    end on one rhyme, e.g. rhyme_scheme="AABB", rhyme_classes=encode_rhyme_classes(tokenizer, ["光忙香", "天年前"]); every sample
+    chooses its own rhymes.  rhyme_distinct=True keeps a line from ending on the character an earlier line of its group ended on."""
     from .decode import GreedyDecoder, check_ngram
     eng = model.engine()
     sh = eng.sh
@@ -191,7 +195,7 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     length = sh.max_seq_length if length is None else length
     n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
     pre = _prompt_prefixes(prefixes, n_prompts, length, sh)
-    lines = _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre, templates)
+    lines = _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre, templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
     keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
     if isinstance(rows, dict):
         stacked = {k: torch.as_tensor(np.asarray(rows[k])) for k in keys}
@@ -225,7 +229,8 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
 
 
 def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature=1.1, repetition_penalty=1.5, max_batch=256,
-                   return_all=False, prefixes=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None):
+                   return_all=False, prefixes=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None,
+                   rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False):
     """Beam search per prompt on the batched, graph-replayed decoder (BeamDecoder): prompts are decoded max_batch // num_beams at
     a time, every beam is cut back to what sample_sequence would have returned (GreedyDecoder.reference_return) and
     post-processed as generate_samples does.  rows: as generate_samples.  Returns one string per prompt (its best beam), or with
@@ -233,7 +238,7 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
     of the processed logits at the positions the model chose; see BeamDecoder).  prefixes: as generate_samples (the prefix
     positions add nothing to a score).  no_repeat_ngram_size: as generate_samples, on every beam's own history.  line_lengths /
     line_end_ids / templates: as generate_samples, shared by a prompt's beams (a full line and a given column add nothing to a
-    score)."""
+    score).  rhyme_scheme / rhyme_classes / rhyme_distinct: as generate_samples; every beam rhymes with its own earlier lines."""
     from .decode import BeamDecoder, GreedyDecoder, check_ngram
     eng = model.engine()
     sh = eng.sh
@@ -241,7 +246,7 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
     length = sh.max_seq_length if length is None else length
     n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
     pre = _prompt_prefixes(prefixes, n_prompts, length, sh)
-    lines = _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre, templates)
+    lines = _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre, templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
     keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
     if isinstance(rows, dict):
         stacked = {k: torch.as_tensor(np.asarray(rows[k])) for k in keys}

@@ -123,6 +123,12 @@ _SIGS = {
                                 _vp, _vp, _vp], _i),
     "mmtg_decode_beam_candidates_tmpl": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
                                          _vp, _vp, _vp], _i),
+    "mmtg_decode_select_rhyme": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i,
+                                  _vp], _i),
+    "mmtg_decode_sample_rhyme": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i,
+                                 _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "mmtg_decode_beam_candidates_rhyme": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
+                                          _vp, _vp, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
     "mmtg_decode_mlp_sync_words": ([], _i),
     "mmtg_decode_mlp_census": ([_vp, _vp], _i),
@@ -874,37 +880,53 @@ def _template(tmpl, tables, B, sent):
     return _p(tmpl)
 
 
-def _rule_tail(form, B, V, fixed_end, ngram, tables, tmpl=None, sent=0):
-    """What the selection entry of `form` ("" plain, "_fixed", "_ngram", "_lines", "_tmpl") takes between its own arguments and the
-    stream."""
+def _rhyme(rhyme, tables, B, V):
+    """The rhyme tables of decode.check_lines on the device, (class_of int16 [V], lead int8 [rows >= B, n_lines of the line tables],
+    distinct), as the *_rhyme entries' last arguments before the stream (None is passed on: the library rejects it)."""
+    if rhyme is None:
+        return _p(None), _p(None), 0
+    class_of, lead, distinct = rhyme
+    if not (class_of.dtype == torch.int16 and class_of.dim() == 1 and class_of.numel() >= V and class_of.is_contiguous()):
+        raise ValueError("rhyme tables: class_of must be a contiguous int16 vector of at least V = %d entries" % V)
+    if not (lead.dtype == torch.int8 and lead.dim() == 2 and lead.shape[0] >= B and lead.shape[1] == tables[0].shape[1]
+            and lead.is_contiguous()):
+        raise ValueError("rhyme tables: lead must be contiguous int8 [rows >= %d, n_lines]" % B)
+    return _p(class_of), _p(lead), int(bool(distinct))
+
+
+def _rule_tail(form, B, V, fixed_end, ngram, tables, tmpl=None, sent=0, rhyme=None):
+    """What the selection entry of `form` ("" plain, "_fixed", "_ngram", "_lines", "_tmpl", "_rhyme") takes between its own arguments
+    and the stream (the template table of "_rhyme" may be None: a scheme without templates)."""
     if form == "":
         return ()
     tail = (_fixed(fixed_end, B),)
     if form != "_fixed":
         tail += (int(ngram),)
-    if form in ("_lines", "_tmpl"):
+    if form in ("_lines", "_tmpl", "_rhyme"):
         tail += _lines(tables, B, V)
-    if form == "_tmpl":
+    if form in ("_tmpl", "_rhyme"):
         tail += (_template(tmpl, tables, B, sent),)
+    if form == "_rhyme":
+        tail += _rhyme(rhyme, tables, B, V)
     return tail
 
 
 def _select(form, logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, sampling=None, fixed_end=None, ngram=0,
-            tables=None, tmpl=None):
+            tables=None, tmpl=None, rhyme=None):
     """mmtg_decode_select<form>, or with sampling = (top_k, top_p, uniforms) mmtg_decode_sample<form>."""
     name = ("decode_select" if sampling is None else "decode_sample") + form
     draw = () if sampling is None else (int(sampling[0]), float(sampling[1]), _p(sampling[2]), sampling[2].stride(0))
     _check(getattr(lib(), "mmtg_" + name)(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
                                           float(rep_penalty), *draw, B, _p(pos_next),
-                                          *_rule_tail(form, B, V, fixed_end, ngram, tables, tmpl, sent), _stream()), name)
+                                          *_rule_tail(form, B, V, fixed_end, ngram, tables, tmpl, sent, rhyme), _stream()), name)
 
 
 def _beam_candidates(form, logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=None, ngram=0,
-                     tables=None, tmpl=None):
+                     tables=None, tmpl=None, rhyme=None):
     name = "decode_beam_candidates" + form
     _check(getattr(lib(), "mmtg_" + name)(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
                                           float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B,
-                                          *_rule_tail(form, B, V, fixed_end, ngram, tables, tmpl, sent), _stream()), name)
+                                          *_rule_tail(form, B, V, fixed_end, ngram, tables, tmpl, sent, rhyme), _stream()), name)
 
 
 def _beam_merge(form, cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next, fixed_end=None):
@@ -1008,6 +1030,27 @@ def decode_beam_candidates_tmpl(logits, ldl, V, seq, pos, P, sent, temperature, 
     """decode_beam_candidates_lines under the line templates: a given column offers its id the way a full line offers PAD."""
     _beam_candidates("_tmpl", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=fixed_end,
                      ngram=ngram, tables=tables, tmpl=tmpl)
+
+
+def decode_select_rhyme(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, tables, rhyme, tmpl=None, ngram=0,
+                        fixed_end=None, pos_next=None):
+    """decode_select_tmpl (tmpl may be None) under the rhyme tables `rhyme` = (class_of, lead, distinct) of include/mmtg_hip.h: a
+    follower line ends in the class its leader's last content id has."""
+    _select("_rhyme", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, fixed_end=fixed_end, ngram=ngram,
+            tables=tables, tmpl=tmpl, rhyme=rhyme)
+
+
+def decode_sample_rhyme(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, tables, rhyme,
+                        tmpl=None, ngram=0, fixed_end=None, pos_next=None):
+    _select("_rhyme", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, (top_k, top_p, uniforms),
+            fixed_end=fixed_end, ngram=ngram, tables=tables, tmpl=tmpl, rhyme=rhyme)
+
+
+def decode_beam_candidates_rhyme(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, tables, rhyme,
+                                 tmpl=None, ngram=0, fixed_end=None):
+    """decode_beam_candidates_tmpl under the rhyme tables: every beam reads its own (reordered) history for its leader's rhyme."""
+    _beam_candidates("_rhyme", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=fixed_end,
+                     ngram=ngram, tables=tables, tmpl=tmpl, rhyme=rhyme)
 
 
 def decode_advance(pos):
