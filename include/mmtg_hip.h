@@ -716,6 +716,23 @@ MMTG_API int mmtg_decode_beam_candidates_rhyme(const float* logits, long ldl, in
                                      int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
                                      const short* class_of, const signed char* lead, int distinct, void* stream);
 
+/* ---- token log-probabilities (GreedyDecoder with return_logprobs=, mmtg_amd/decode.py): what the model itself says of the id a
+ * step has placed.  The reference has no such output (generate.py:117-142 keeps the ids only).  Launched after a step's selection
+ * entry on the same stream; one workgroup of 256 threads per row b.  With pos = *pos_ptr, j = pos + 1 - P and
+ * v = seq[b * ldseq + pos + 1] (the id the column holds AFTER the selection), over the RAW logits x = logits[b * ldl + 0 .. V - 1]:
+ *   out[b * ldo + j] = x[v] - max - log(sum_u exp(x[u] - max)),   max = max_u x[u],   fp32 throughout.
+ * No penalty, no temperature, no bans: V is the cut the selection uses, nothing else of the selection's rule reaches the number, so
+ * the entry scores a pick, a draw, a template's given id, a full line's PAD, a sticky PAD and a held prefix id alike.
+ *   j < 0, j >= ncols, pos + 1 >= ldseq or v outside 0 .. V - 1: nothing is written;
+ *   -inf entries add 0 to the sum; x[v] == -inf gives -inf; a row whose maximum is -inf gives -inf (never NaN).
+ * The row is read once (16-byte aligned rows as float4, up to 16 per thread in flight; otherwise and for the tail one logit at a
+ * time), reduced by wave shuffles and four words of static LDS in a fixed order: equal inputs give equal bits.  It reads *pos_ptr,
+ * which the selection entries leave alone (they publish into pos_next), and changes nothing but that one column of `out`.  A null
+ * pointer, V < 1, ldl < V, ldseq <= P, ncols < 1 or ldo < ncols fails before any device call.  The kernels of every earlier entry
+ * compile to the same code as before this was added (profiles/r14_logprob_decode_disassembly_diff.txt).                            */
+MMTG_API int mmtg_decode_logprob(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr, int P,
+                        float* out, long ldo, int ncols, int B, void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

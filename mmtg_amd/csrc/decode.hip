@@ -2257,3 +2257,98 @@ extern "C" int mmtg_decode_attn_split_x3_rows(const float* part, int splits, con
     MMTG_LAUNCH_CHECK("decode_attn_split_x3_rows");
     return MMTG_OK;
 }
+
+// ------------------------------------------------------------------ token log-probabilities (GreedyDecoder with return_logprobs=)
+// One workgroup per row, launched after the step's selection entry on the same stream: the log-probability the model gives the id
+// the step has just placed, log_softmax of the RAW logits (no penalty, no temperature, no bans; cut at V) at seq[b, pos + 1].  The
+// kernel knows nothing of the selection's rule -- it scores whatever the column holds (a pick, a draw, a given id, a PAD, a held
+// prefix id) -- so it is one kernel of its own behind all twelve selection forms, which stay the code they were
+// (profiles/r14_logprob_decode_disassembly_diff.txt).  It reads *pos_ptr, which the selection leaves alone (it publishes the next
+// position into the pair's other word).
+namespace {
+
+// (max, sum of exp(x - max)) of two parts as one; a part whose max is -inf holds nothing, and two such parts stay (-inf, 0)
+__device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os) {
+    const float nm = fmaxf(m, om);
+    s = nm == -INFINITY ? 0.f : s * expf(m - nm) + os * expf(om - nm);
+    m = nm;
+}
+
+// scan_row's load shape: 16-byte aligned rows as float4, all of a pass's loads (up to 16 per thread) requested before the first is
+// used; each pass folds its own (max, sum) into the thread's running pair.  The tail and unaligned rows go one logit at a time.
+// -inf entries add 0 to the sum.  Fixed order throughout: the result is bit-reproducible.
+// (UN, the loads per thread and pass, is a template parameter so that the kernel is emitted where it is instantiated, behind every
+// other function of the code object: a plain kernel is emitted among the first, and the calls that cross it get other offsets)
+template <int UN>
+__global__ __launch_bounds__(256) void decode_logprob_kernel(const float* __restrict__ logits, long ldl, int V,
+        const long long* __restrict__ seq, long ldseq, const int* __restrict__ pos_ptr, int P, float* __restrict__ out, long ldo,
+        int ncols) {
+    __shared__ float sm[4];
+    __shared__ float ss[4];
+    const int b = blockIdx.x, tid = threadIdx.x, pos = *pos_ptr;
+    const int j = pos + 1 - P;                 // lyric index of the token the step has placed
+    if (j < 0 || j >= ncols || pos + 1 >= ldseq) return;
+    const long long v = seq[(long)b * ldseq + pos + 1];
+    if (v < 0 || v >= V) return;
+    const float* row = logits + (long)b * ldl;
+    float m = -INFINITY, s = 0.f;
+    int done = 0;
+    if ((reinterpret_cast<uintptr_t>(row) & 15) == 0) {
+        const int nvec = V >> 2;
+        const f32x4* row4 = reinterpret_cast<const f32x4*>(row);
+        for (int base = 0; base < nvec; base += 256 * UN) {
+            f32x4 r[UN];
+#pragma unroll
+            for (int i = 0; i < UN; ++i) {
+                const int idx = base + i * 256 + tid;
+                r[i] = idx < nvec ? row4[idx] : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+            }
+            float pm = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < UN; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pm = fmaxf(pm, r[i][e]);
+            if (pm != -INFINITY) {
+                float ps = 0.f;
+#pragma unroll
+                for (int i = 0; i < UN; ++i)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ps += expf(r[i][e] - pm);      // exp(-inf) = 0: -inf entries and the fillers add nothing
+                lse_merge(m, s, pm, ps);
+            }
+        }
+        done = nvec << 2;
+    }
+    for (int u = done + tid; u < V; u += 256) {
+        const float x = row[u];
+        if (x != -INFINITY) lse_merge(m, s, x, 1.f);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(m, o, 64);
+        const float os = __shfl_xor(s, o, 64);
+        lse_merge(m, s, om, os);
+    }
+    if ((tid & 63) == 0) { sm[tid >> 6] = m; ss[tid >> 6] = s; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w) lse_merge(m, s, sm[w], ss[w]);
+        // a row whose maximum is -inf has no distribution: -inf, never NaN; a chosen -inf entry gives -inf by the arithmetic
+        out[(long)b * ldo + j] = m == -INFINITY ? -INFINITY : row[v] - m - logf(s);
+    }
+}
+
+}  // namespace
+
+extern "C" int mmtg_decode_logprob(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr, int P,
+                                   float* out, long ldo, int ncols, int B, void* stream) {
+    MMTG_REQUIRE(logits && seq && pos_ptr && out, "decode_logprob: null pointer");
+    MMTG_REQUIRE(B > 0 && V > 0 && ldl >= V && P >= 0 && ldseq > P && ncols > 0 && ldo >= ncols,
+                 "decode_logprob: logits [B, ldl >= V], seq [B, ldseq > P], out [B, ldo >= ncols > 0] (B %d, V %d, ldl %ld, P %d, ldseq %ld, "
+                 "ncols %d, ldo %ld)", B, V, ldl, P, ldseq, ncols, ldo);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, 2.0 * B * V, 4.0 * B * V);
+    hipLaunchKernelGGL(decode_logprob_kernel<16>, dim3(B), dim3(256), 0, s, logits, ldl, V, seq, ldseq, pos_ptr, P, out, ldo, ncols);
+    MMTG_LAUNCH_CHECK("decode_logprob");
+    return MMTG_OK;
+}

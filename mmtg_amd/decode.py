@@ -75,6 +75,41 @@ def check_ngram(n, sent=22):
     return n
 
 
+def chosen_mask(ids, sent=22, prefix_lens=None):
+    """Which columns of generated lyric ids count towards a row's score: bool [B, 1 + length], host only.  Column j >= 1 of row b
+    counts iff it is not a cadence column (j % sent not in {0, sent - 1}: the forced [#START#] / [#EOS#]), it lies past the row's
+    prefix (j >= prefix_lens[b]; None: no prefix) and the previous column is not PAD (ids[b][j - 1] != 0) -- so the first PAD of a
+    line counts (the model ended the line there; in an empty line that is its first content column) and the sticky PADs behind
+    it, which no model call decided, do not.
+    Columns that a constraint decided (a template's given id, a full line's PAD) count: their value is the model's log-probability
+    of that id.  Samples of one prompt share their constraints, so ranking among them is fair."""
+    a = np.asarray(ids.detach().cpu().numpy() if torch.is_tensor(ids) else ids)
+    if a.ndim != 2:
+        raise ValueError("ids must be [rows, 1 + length] (got shape %s)" % (a.shape,))
+    B, n = a.shape
+    pl = np.zeros(B, np.int64) if prefix_lens is None else np.asarray(prefix_lens, np.int64).reshape(-1)
+    if pl.shape[0] != B:
+        raise ValueError("prefix_lens has %d rows, ids %d" % (pl.shape[0], B))
+    j = np.arange(n)
+    mask = np.zeros((B, n), bool)
+    mask[:, 1:] = a[:, :-1] != 0
+    mask &= ((j >= 1) & (j % sent != 0) & (j % sent != sent - 1))[None, :]
+    mask &= j[None, :] >= pl[:, None]
+    return mask
+
+
+def sequence_scores(ids, logprobs, sent=22, prefix_lens=None, upto=None):
+    """(sum float64 [B], count int64 [B]) of the token log-probabilities over chosen_mask's columns below `upto` (None: all; for
+    the text generate_samples returns, 1 + the last iteration that called the model: GreedyDecoder.reference_return).  Host only."""
+    mask = chosen_mask(ids, sent=sent, prefix_lens=prefix_lens)
+    lp = np.asarray(logprobs.detach().cpu().numpy() if torch.is_tensor(logprobs) else logprobs, np.float64)
+    if lp.shape != mask.shape:
+        raise ValueError("logprobs of shape %s for ids of shape %s" % (lp.shape, mask.shape))
+    if upto is not None:
+        mask[:, max(int(upto), 0):] = False
+    return np.where(mask, lp, 0.0).sum(1), mask.sum(1).astype(np.int64)
+
+
 class LineTables:
     """The packed line constraints check_lines returns: lo, hi uint8 [rows, n_lines]; set_of int16 [rows, n_lines] (-1: no end set)
     and sets uint32 [n_sets, ceil(V / 32)] (bit v & 31 of word v >> 5: id v is a member), or both None when no line has a set.
@@ -649,6 +684,10 @@ class GreedyDecoder:
         # ends every step that calls the head in the *_rhyme selection entries
         self.rhyme = None
         self._rhyme_buf = None
+        # token log-probabilities (return_logprobs=): fp32 [B, 1 + max_len], this decoder's rows; on, every step that calls the head
+        # ends in one more launch, mmtg_decode_logprob, which writes the step's column (allocated once: captured graphs hold its address)
+        self.return_logprobs = False
+        self.tok_lp = None
 
     def _conv1d(self, x, wkey, out, **kw):
         # bf16: Engine._fwd routes Conv1D weights through their [out,in] copies (NT layout), which is
@@ -680,6 +719,7 @@ class GreedyDecoder:
         if getattr(self, "x3", False):
             self._step_x3(with_head)
             self._select(with_head)
+            self._logprob(with_head)
             return
         hip.decode_embed(eng.table, self.seq, self.c, self.x, self.pos, self.tpw_type, self.tpw_mask, self.types,
                          self.keep, B, sh.P, sh.S, E, sh.two_sents, eng.table.shape[0], sent,
@@ -706,6 +746,7 @@ class GreedyDecoder:
         if with_head and not fused:
             hip.gemm(self.a, eng.Wp("wte"), self.logits, B, eng.layout.Vpad, D, transB=True, ldb=D, out_f32=True)
         self._select(with_head)
+        self._logprob(with_head)
 
     def _select(self, with_head):
         """The step's last launch: logits processing + arg-max / draw + the forced cadence + the next position (generate.py:117-142),
@@ -724,6 +765,15 @@ class GreedyDecoder:
         hip._select(form, logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, self.B, self.pos_next, sampling,
                     fixed_end=self.fixed_end if self.use_fixed else None, ngram=self.ngram, tables=self.lines, tmpl=tmpl,
                     **({} if rhyme is None else {"rhyme": rhyme}))
+
+    def _logprob(self, with_head):
+        """With return_logprobs, after the selection of a step that called the head: tok_lp[b, pos + 1 - P] = log_softmax of the row's
+        raw logits at the id column pos + 1 now holds (include/mmtg_hip.h, mmtg_decode_logprob).  A node of its own behind the
+        selection, on the same stream: it reads self.pos, which the selection leaves alone, and the selection kernels stay what they
+        were.  Off, nothing is launched."""
+        if with_head and getattr(self, "return_logprobs", False):
+            sh = self.eng.sh
+            hip.decode_logprob(self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, self.tok_lp, self.B)
 
     def _upload_lines(self, tables):
         """The line tables into this decoder's device buffers (allocated once, so captured graphs keep their addresses; a `sets`
@@ -1006,6 +1056,8 @@ class GreedyDecoder:
         if form == "_rhyme":                # (what the captured launch holds by value: the template table or none, distinct)
             key += ("rhyme", "sets" if self.lines[2] is not None else "bounds") + (("tmpl",) if getattr(self, "tmpl", None) is not None else ())
             key += ("distinct",) if rhyme[2] else ()
+        if with_head and getattr(self, "return_logprobs", False):
+            key += ("logprob",)
         return key
 
     def _step_state(self):
@@ -1035,7 +1087,7 @@ class GreedyDecoder:
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
               no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
-              rhyme_distinct=False):
+              rhyme_distinct=False, return_logprobs=False):
         """Everything of a generation that happens once: the settings, the uniforms of a stochastic run, fresh weight copies /
         LayerNorm folds, the experience encoder, the prompt (prefilled in one batched pass: ``first_pos`` = P afterwards) and the
         reset position.  Returns the end position n; ``step_at(pos)`` for pos = first_pos .. n - 1 then runs the token steps (``generate`` does both; tools/decode_lanes_threads.py drives
@@ -1062,7 +1114,18 @@ class GreedyDecoder:
         rhyme_scheme / rhyme_classes / rhyme_distinct (check_lines states the forms, include/mmtg_hip.h the rule): which lines end on
         one rhyme, e.g. "AABB", over the caller's partition of the ids that have a rhyme; which rhyme is each row's own choice,
         made when it ends the group's first line.  With a scheme every step that calls the head ends in the *_rhyme selection
-        entries; the tables are uploaded here, once.  None runs exactly the launches and graphs of a generation without it."""
+        entries; the tables are uploaded here, once.  None runs exactly the launches and graphs of a generation without it.
+
+        return_logprobs: keep ``tok_lp`` fp32 [B, 1 + max_len], zeroed here: every step that calls the head then ends in one more
+        launch, mmtg_decode_logprob, which writes column j of the step -- the log-probability the model's raw logits (no penalty, no
+        temperature, no bans; cut at 13317) give the id the column holds after the selection, whoever decided it: the model's pick, a
+        draw, a template's given id, a full line's PAD, a sticky PAD or a held prefix id.  Column 0, the forced [#START#] / [#EOS#]
+        columns and every step that skips the head stay 0.  No step skips the head because every row is held by its prefix (the
+        shortcut of ``step_at``), so held columns carry the given id's log-probability.  Scoring mode: when every row's prefix is
+        the whole row (1 + length ids), the prefill covers the prompt only and every content column goes through a token step --
+        teacher forcing through the kernels that generate.  A shorter prefix keeps the prefill of the generation without the
+        argument (its ids are bit-equal to that generation's), and the columns the prefill covers stay 0.  False runs exactly the
+        launches, graphs and graph keys of a generation without the argument."""
         eng, sh = self.eng, self.eng.sh
         B = batch["img_embs"].shape[0]
         if B != self.B:
@@ -1094,6 +1157,10 @@ class GreedyDecoder:
         self.seq[:, :sh.P] = batch["topic_ids"].to(eng.dev).long()
         self.seq[:, sh.P] = 1                                   # [#START#]
         lmin = 1
+        if return_logprobs:
+            if self.tok_lp is None:
+                self.tok_lp = torch.zeros(B, 1 + self.max_len, dtype=torch.float32, device=eng.dev)
+            self.tok_lp.zero_()
         # the generation's constraints, on the decoder and its lanes: a lane's _select reads its own flags, its slice of fixed_end
         # (a view since construction) and its rows of the line tables (the sets are shared)
         lines = self._upload_lines(tables)
@@ -1105,10 +1172,13 @@ class GreedyDecoder:
             d.lines = None if lines is None else tuple(t if t is None or t is lines[2] else t[a:z] for t in lines)
             d.tmpl = None if tmpl is None else tmpl[a:z]
             d.rhyme = None if rhyme is None else (rhyme[0], rhyme[1][a:z], rhyme[2])
+            d.return_logprobs = bool(return_logprobs)
+            if return_logprobs and d is not self:
+                d.tok_lp = self.tok_lp[a:z]
         self.min_fixed = 0
         if pre is not None:
             lens = [len(p) for p in pre]
-            lmin = min(lens)
+            lmin = 1 if return_logprobs and min(lens) == length + 1 else min(lens)      # (scoring mode: the prompt only)
             host = torch.zeros(B, max(lens), dtype=torch.long)
             for b, p in enumerate(pre):
                 host[b, :len(p)] = torch.tensor(p, dtype=torch.long)
@@ -1168,7 +1238,7 @@ class GreedyDecoder:
         sh = self.eng.sh
         j = pos + 1 - sh.P                                      # lyric index appended after this step
         forced = j < 1 or (j > 1 and (j + 1) % (sh.msl + 2) in (0, 1))
-        if self.use_fixed and pos + 1 < self.min_fixed:
+        if self.use_fixed and pos + 1 < self.min_fixed and not self.return_logprobs:
             forced = True                                       # every row's column pos + 1 is a prefix id: no model call
         self._run_step(with_head=not forced, parity=pos & 1)
         return not forced
@@ -1176,7 +1246,7 @@ class GreedyDecoder:
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None,
                  use_graph=None, teacher=None, tap=None, prefix=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None,
-                 templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False):
+                 templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_logprobs=False):
         """batch: dict with topic_ids/tpw_* [B,P], topic_emb, img_embs, r_embs (no targets needed).
         Runs `length` iterations of the reference loop and returns the lyric ids
         [B, 1 + length] (column 0 is the initial [#START#]).  top_k = 1, top_p = 0 is the greedy setting;
@@ -1197,10 +1267,14 @@ class GreedyDecoder:
         the column to its members.
         rhyme_scheme / rhyme_classes / rhyme_distinct: lines that end on one rhyme (``check_lines``): rhyme_scheme="AABB" with
         rhyme_classes=[ids that rhyme, ...] makes lines 0 / 1 and 2 / 3 end in one class each, the class being what the row ended
-        the first line of the pair on; rhyme_distinct=True keeps a line from ending on the id an earlier line of its group ended on."""
+        the first line of the pair on; rhyme_distinct=True keeps a line from ending on the id an earlier line of its group ended on.
+        return_logprobs: return (ids, tok_lp [B, 1 + length] fp32) -- per column the log-probability the model's raw logits give the
+        id the column holds, 0 where no step called the head (``begin``; ``chosen_mask`` / ``sequence_scores`` turn them into a
+        score per row).  With a prefix that covers every row whole it scores given text (generate.score_sequences)."""
         n_steps = self.begin(batch, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix,
                              no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths, line_end_ids=line_end_ids,
-                             templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct)
+                             templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct,
+                             **({"return_logprobs": True} if return_logprobs else {}))
         eng, sh = self.eng, self.eng.sh
         saved_mode = self.use_graph
         if use_graph is not None:
@@ -1220,7 +1294,8 @@ class GreedyDecoder:
         finally:
             self.use_graph = saved_mode
         self.check_mlp_error()
-        return self.seq[:, sh.P:sh.P + 1 + length].clone()
+        ids = self.seq[:, sh.P:sh.P + 1 + length].clone()
+        return (ids, self.tok_lp[:, :1 + length].clone()) if return_logprobs else ids
 
     def check_mlp_error(self):
         """Raise if a mmtg_decode_mlp launch of this generation reported a bounded wait that ran out or a hand-off group split over
@@ -1291,17 +1366,26 @@ class BeamDecoder(GreedyDecoder):
     def _step_state(self):
         return super()._step_state() + [self.rows, self.scores]
 
+    @staticmethod
+    def _no_logprobs(return_logprobs):
+        """Beam search keeps no token log-probabilities: the merge reorders the rows after the selection, and tok_lp would have to be
+        reordered with seq.  Beams are scored afterwards, through generate.score_sequences."""
+        if return_logprobs:
+            raise ValueError("beam search has no return_logprobs (the merge reorders rows after the selection); score the beams "
+                             "with generate.score_sequences")
+
     def describe(self):
         return "%d beams per prompt, " % self.nb + super().describe()
 
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
               no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
-              rhyme_distinct=False):
+              rhyme_distinct=False, return_logprobs=False):
         """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill, the prefix, the line
         constraints, the templates and the rhyme scheme: one per prompt; every beam finds its leader's rhyme in its own history), the
         ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at the free positions
-        after a prompt's prefix."""
+        after a prompt's prefix.  return_logprobs=True raises ValueError (``_no_logprobs``)."""
+        self._no_logprobs(return_logprobs)
         n = batch["img_embs"].shape[0]
         if n != self.n_prompts:
             raise ValueError("decoder was built for %d prompts, got %d" % (self.n_prompts, n))
@@ -1324,13 +1408,16 @@ class BeamDecoder(GreedyDecoder):
 
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None, no_repeat_ngram_size=0,
-                 line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False):
+                 line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False,
+                 return_logprobs=False):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_beams, 1 + length] in
         GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row.
         prefix: one per prompt (check_prefix), shared by its beams.  no_repeat_ngram_size: as GreedyDecoder.generate, per beam
         on its own (reordered) history.  line_lengths / line_end_ids / templates: as GreedyDecoder.generate, one per prompt, shared by
         its beams (a given column adds nothing to a score).  rhyme_scheme / rhyme_classes / rhyme_distinct: as GreedyDecoder.generate,
-        one scheme per prompt; each beam rhymes with its own earlier lines."""
+        one scheme per prompt; each beam rhymes with its own earlier lines.  return_logprobs=True raises ValueError before any device
+        work: the scores here are sums over the PROCESSED logits; generate.score_sequences gives a beam's raw log-probabilities."""
+        self._no_logprobs(return_logprobs)
         ids = super().generate(batch, length, temperature=temperature, repitition_penalty=repitition_penalty, use_graph=use_graph,
                                prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths,
                                line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes,

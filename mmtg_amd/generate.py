@@ -167,9 +167,19 @@ def _chunk_lines(tables, idx):
     return None if tables is None else tables.take(idx)
 
 
+def rank_scored(scored, rank_by):
+    """One prompt's (text, logprob_sum, n_tokens) triples best first: by the sum ("sum") or by sum / max(n_tokens, 1) ("mean", so a
+    sample without a counted token ranks by its sum, 0).  The sort is stable: equal keys keep their draw order."""
+    if rank_by not in ("sum", "mean"):
+        raise ValueError('rank_by must be "sum", "mean" or None, got %r' % (rank_by,))
+    key = (lambda t: t[1]) if rank_by == "sum" else (lambda t: t[1] / max(t[2], 1))
+    return sorted(scored, key=key, reverse=True)
+
+
 def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperature=1.1, top_k=10, top_p=0.7,
                      repetition_penalty=1.5, max_batch=256, generator=None, decoder=None, prefixes=None, no_repeat_ngram_size=0,
-                     line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False):
+                     line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False,
+                     return_scores=False, rank_by=None):
     """n_samples texts per prompt (generate.sh's loop, generate.py:205-235) on the batched, graph-replayed decoder:
     every prompt is replicated over n_samples rows, rows are decoded max_batch at a time with the device-side
     top-k / top-p sampler (one uniform per row and position from `generator`), each row is cut back to what
@@ -187,8 +197,18 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     templates=[encode_template(tokenizer, c + "…") for c in "春夏秋冬"].
     rhyme_scheme / rhyme_classes / rhyme_distinct (optional, decode.check_lines; one scheme per prompt or one for all): lines that
     end on one rhyme, e.g. rhyme_scheme="AABB", rhyme_classes=encode_rhyme_classes(tokenizer, ["光忙香", "天年前"]); every sample
-    chooses its own rhymes.  rhyme_distinct=True keeps a line from ending on the character an earlier line of its group ended on."""
-    from .decode import GreedyDecoder, check_ngram
+    chooses its own rhymes.  rhyme_distinct=True keeps a line from ending on the character an earlier line of its group ended on.
+    return_scores: each prompt's entry is a list of (text, logprob_sum, n_tokens) instead -- the sum of the model's own token
+    log-probabilities (raw logits: no penalty, no temperature, no bans, so comparable across sampling settings;
+    GreedyDecoder.begin, return_logprobs) over the columns of the returned text that decode.chosen_mask counts, past the prompt's
+    prefix, and how many those are.  Columns a constraint decided (a template's given id, a full line's PAD) count, at the model's
+    log-probability of that id; the samples of a prompt share their constraints, so ranking among them is fair.
+    rank_by: "sum" or "mean" (sum / max(n_tokens, 1)) orders a prompt's samples best first (stable) and implies return_scores.
+    The texts are the strings, from the same `generator` state, of the call without the two arguments."""
+    from .decode import GreedyDecoder, check_ngram, sequence_scores
+    if rank_by is not None and rank_by not in ("sum", "mean"):
+        raise ValueError('rank_by must be "sum", "mean" or None, got %r' % (rank_by,))
+    scoring = bool(return_scores) or rank_by is not None
     eng = model.engine()
     sh = eng.sh
     ngram = check_ngram(no_repeat_ngram_size, sh.msl + 2)
@@ -221,16 +241,70 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
         clines = _chunk_lines(lines, [r // n_samples for r in range(lo, hi)] + [lo // n_samples] * (bsz - (hi - lo)))
         ids = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty,
                            top_k=top_k, top_p=top_p, generator=generator, prefix=cpre, no_repeat_ngram_size=ngram,
-                           line_lengths=clines).cpu().numpy()
+                           line_lengths=clines, **({"return_logprobs": True} if scoring else {}))
+        if scoring:
+            ids, lp = ids[0].cpu().numpy(), ids[1].cpu().numpy()
+            upto = len(GreedyDecoder.reference_return(ids[0].tolist(), length, sent=sh.msl + 2))        # 1 + the last model call
+            sums, counts = sequence_scores(ids, lp, sent=sh.msl + 2, prefix_lens=None if cpre is None else [len(p) for p in cpre],
+                                           upto=upto)
+        else:
+            ids = ids.cpu().numpy()
         for r in range(hi - lo):
             seq = GreedyDecoder.reference_return(ids[r].tolist(), length, sent=sh.msl + 2)
-            texts.append(postprocess_tokens(tokenizer.convert_ids_to_tokens(seq)))
-    return [texts[i * n_samples:(i + 1) * n_samples] for i in range(n_prompts)]
+            text = postprocess_tokens(tokenizer.convert_ids_to_tokens(seq))
+            texts.append((text, float(sums[r]), int(counts[r])) if scoring else text)
+    out = [texts[i * n_samples:(i + 1) * n_samples] for i in range(n_prompts)]
+    return [rank_scored(e, rank_by) for e in out] if rank_by is not None else out
+
+
+def score_sequences(model, rows, ids, max_batch=256):
+    """Per-token log-probabilities of GIVEN lyric ids under their prompts: float32 numpy [n, 1 + length].  rows: as
+    generate_samples; ids: one row of 1 + length lyric ids per prompt in decode.check_prefix's layout (what GreedyDecoder.generate
+    and BeamDecoder.generate return, or encode_prefix of written lines padded to whole rows).  Column j holds the log-probability
+    the model's raw logits give ids[b][j] after ids[b][:j]; column 0 and the forced [#START#] / [#EOS#] columns hold 0
+    (decode.sequence_scores sums the columns that count).
+    This is the decoder's scoring mode (GreedyDecoder.begin: the ids as a prefix that covers every row whole, return_logprobs):
+    teacher forcing through the token-step kernels that generate, chunked and padded to the batch like generate_samples.  The cost
+    is `length` token steps per chunk of max_batch rows, not one batched pass: it is built to agree with the generator's numerics
+    (the values a generation reported for its own ids come back within rounding), not for bulk evaluation -- that is
+    MMTGTrainer.evaluate."""
+    from .decode import GreedyDecoder, check_prefix
+    eng = model.engine()
+    sh = eng.sh
+    n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
+    given = ids.detach().cpu().numpy() if torch.is_tensor(ids) else np.asarray(ids)
+    if given.ndim != 2 or given.shape[0] != n_prompts or given.shape[1] < 2:
+        raise ValueError("ids must be [%d prompts, 1 + length] (got shape %s)" % (n_prompts, given.shape))
+    length = given.shape[1] - 1
+    pre = check_prefix(given, n_prompts, length, sent=sh.msl + 2, V=min(sh.V, 13317))
+    if any(len(p) != length + 1 for p in pre):
+        raise ValueError("ids must cover every row whole (no -1 padding)")
+    keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
+    if isinstance(rows, dict):
+        stacked = {k: torch.as_tensor(np.asarray(rows[k])) for k in keys}
+    else:
+        stacked = {k: torch.as_tensor(np.stack([np.asarray(r[k]) for r in rows])) for k in keys}
+    bsz = min(max_batch, n_prompts)
+    dec = GreedyDecoder(model, max_batch=bsz, max_len=length)
+    out = np.zeros((n_prompts, 1 + length), np.float32)
+    for lo in range(0, n_prompts, bsz):
+        hi = min(n_prompts, lo + bsz)
+        chunk = {k: v[lo:hi] for k, v in stacked.items()}
+        cpre = pre[lo:hi] + [pre[lo]] * (bsz - (hi - lo))
+        if hi - lo < bsz:          # the decoder's batch is fixed: pad the last chunk by repeating its first row
+            pad = bsz - (hi - lo)
+            chunk = {k: torch.cat([v, v[:1].expand(pad, *v.shape[1:])], 0) for k, v in chunk.items()}
+        chunk = {k: v.to(eng.dev) for k, v in chunk.items()}
+        back, lp = dec.generate(chunk, length, prefix=cpre, return_logprobs=True)
+        if not np.array_equal(back[:hi - lo].cpu().numpy(), given[lo:hi]):
+            raise RuntimeError("score_sequences: the decoder changed a given id")
+        out[lo:hi] = lp[:hi - lo].cpu().numpy()
+    return out
 
 
 def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature=1.1, repetition_penalty=1.5, max_batch=256,
                    return_all=False, prefixes=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None,
-                   rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False):
+                   rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_ids=False):
     """Beam search per prompt on the batched, graph-replayed decoder (BeamDecoder): prompts are decoded max_batch // num_beams at
     a time, every beam is cut back to what sample_sequence would have returned (GreedyDecoder.reference_return) and
     post-processed as generate_samples does.  rows: as generate_samples.  Returns one string per prompt (its best beam), or with
@@ -238,7 +312,9 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
     of the processed logits at the positions the model chose; see BeamDecoder).  prefixes: as generate_samples (the prefix
     positions add nothing to a score).  no_repeat_ngram_size: as generate_samples, on every beam's own history.  line_lengths /
     line_end_ids / templates: as generate_samples, shared by a prompt's beams (a full line and a given column add nothing to a
-    score).  rhyme_scheme / rhyme_classes / rhyme_distinct: as generate_samples; every beam rhymes with its own earlier lines."""
+    score).  rhyme_scheme / rhyme_classes / rhyme_distinct: as generate_samples; every beam rhymes with its own earlier lines.
+    return_ids (with return_all): (text, score, ids) triples, ids the beam's 1 + length lyric ids -- a row score_sequences takes, which
+    gives the beam the model's raw token log-probabilities (the score here changes with temperature, penalty and every ban)."""
     from .decode import BeamDecoder, GreedyDecoder, check_ngram
     eng = model.engine()
     sh = eng.sh
@@ -274,6 +350,7 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
             beams = []
             for k in range(num_beams):
                 seq = GreedyDecoder.reference_return(ids[r, k].tolist(), length, sent=sh.msl + 2)
-                beams.append((postprocess_tokens(tokenizer.convert_ids_to_tokens(seq)), float(scores[r, k])))
+                beams.append((postprocess_tokens(tokenizer.convert_ids_to_tokens(seq)), float(scores[r, k]))
+                             + ((ids[r, k].tolist(),) if return_ids else ()))
             out.append(beams if return_all else beams[0][0])
     return out

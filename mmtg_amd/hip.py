@@ -129,6 +129,7 @@ _SIGS = {
                                  _vp, _vp, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_beam_candidates_rhyme": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
                                           _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "mmtg_decode_logprob": ([_vp, _l, _i, _vp, _l, _vp, _i, _vp, _l, _i, _i, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
     "mmtg_decode_mlp_sync_words": ([], _i),
     "mmtg_decode_mlp_census": ([_vp, _vp], _i),
@@ -1051,6 +1052,15 @@ def decode_beam_candidates_rhyme(logits, ldl, V, seq, pos, P, sent, temperature,
     """decode_beam_candidates_tmpl under the rhyme tables: every beam reads its own (reordered) history for its leader's rhyme."""
     _beam_candidates("_rhyme", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=fixed_end,
                      ngram=ngram, tables=tables, tmpl=tmpl, rhyme=rhyme)
+
+
+def decode_logprob(logits, ldl, V, seq, pos, P, out, B):
+    """out[b, pos + 1 - P] = log_softmax(logits[b, :V])[seq[b, pos + 1]] over the raw fp32 logits (include/mmtg_hip.h,
+    mmtg_decode_logprob); out is fp32 [B, ncols], and a column outside it or an id outside 0 .. V - 1 writes nothing."""
+    if out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1:
+        raise ValueError("out must be fp32 [B, ncols] with unit column stride")
+    _check(lib().mmtg_decode_logprob(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, _p(out), out.stride(0), out.shape[1], B,
+                                     _stream()), "decode_logprob")
 
 
 def decode_advance(pos):
