@@ -593,6 +593,34 @@ MMTG_API int mmtg_decode_beam_merge_fixed(const float* cand_val, const int* cand
                                  long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
                                  int* pos_next, const int* fixed_end, void* stream);
 
+/* ---- diverse beam search (BeamDecoder with num_beam_groups=G, diversity_penalty=lambda, mmtg_amd/decode.py): the nb beams of a
+ * prompt are G groups of s = nb / G rows, rows b0 + g*s .. b0 + g*s + s - 1 being group g; each group runs its own beam search
+ * (the caller starts every group at [0, -inf, ...]) and is penalised for an id an earlier group chose at the same step.  At a
+ * step with candidates (not forced, not a held prefix column, cand_val not null) the groups are served in order g = 0 .. G - 1:
+ *   group g sees the s * nb candidates (p, k) whose parent p is one of its own rows; with v = cand_id[p, k],
+ *     base = scores[p] + cand_val[p, k]  (NaN becomes -inf),   sel = base - lambda * n(v)  (fp32: the product, then the difference),
+ *   n(v) = the number of slots groups 0 .. g - 1 filled at this step with id v whose stored score is above -inf, counted only for
+ *   a content id v (not 0, 1, 2, 100, 102: PAD ends a line, it is structure and never penalised);
+ *   the group keeps its s best by (sel descending, p ascending, k ascending -- k the unpenalised rank of the candidates kernel),
+ *   which become its rows in that order: seq / keep / rows reordered in place as in mmtg_decode_beam_merge, seq[b, pos + 1] = v,
+ *   rows[b, pos + 1] = b and scores[b] = base -- the penalty steers the choice and is not remembered, so scores stay the sums of
+ *   the processed log-probabilities and compare across groups.
+ * The candidates' top nb per parent is enough: earlier groups placed at most nb - s distinct ids, the penalty only lowers those,
+ * so a parent's s best ids after the penalty lie among its s + (nb - s) = nb best before it -- the selection equals a penalised
+ * search over the whole vocabulary.  Forced positions, null candidates and (the *_fixed form) held prompts do what
+ * mmtg_decode_beam_merge / mmtg_decode_beam_merge_fixed do.  groups = 1 selects exactly what those select, whatever the penalty.
+ * One kernel (beam_merge_groups_kernel: one workgroup per prompt, one candidate per thread, G rounds with one barrier pair each,
+ * no atomics, equal inputs give equal bits); every other kernel compiles to the same code as before these were added.
+ * Each entry is its namesake plus groups and diversity_penalty; groups < 1, nb % groups != 0, a negative or non-finite penalty
+ * (and nb outside 1..16, a null fixed_end) fail before any device call.                                                        */
+MMTG_API int mmtg_decode_beam_merge_groups(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
+                                  long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
+                                  int* pos_next, int groups, float diversity_penalty, void* stream);
+MMTG_API int mmtg_decode_beam_merge_groups_fixed(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq,
+                                        int* keep, long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb,
+                                        int n_prompts, int* pos_next, const int* fixed_end, int groups, float diversity_penalty,
+                                        void* stream);
+
 /* ---- n-gram blocking (GreedyDecoder / BeamDecoder with no_repeat_ngram_size=n, mmtg_amd/decode.py): a row never writes a content
  * n-gram it already holds.  Row b about to fill a free lyric column j (not forced, not sticky PAD, not a held prefix column) has the
  * history g[0..j-1], its own lyric columns (prefix columns included, the topic prompt not).  Content ids: all but 0, 1, 2, 100, 102

@@ -1599,6 +1599,111 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
     }
 }
 
+// Diverse beams (the *_merge_groups entries, include/mmtg_hip.h): the prompt's nb beams are G groups of s = nb / G rows, served in
+// order.  Round g ranks the s * nb candidates whose parent is one of group g's rows by sel = base - lambda * n(v), n(v) = the live
+// slots (score above -inf) earlier rounds filled with the content id v at this step, and keeps the s best by (sel descending,
+// parent ascending, rank ascending) with the score base.  The s best after the penalty lie among each parent's nb best before it
+// (at most nb - s ids are penalised), so the candidates kernels' tables are enough.  Held prompts, forced columns and null
+// candidates do what beam_merge_kernel does; G = 1 is beam_merge_kernel's selection (n is 0 throughout).
+template <typename R>
+__global__ __launch_bounds__(256) void beam_merge_groups_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_id,
+        float* __restrict__ scores, long long* __restrict__ seq, long ldseq, int* __restrict__ keep, long ldkeep,
+        int* __restrict__ rows, long ldrows, const int* __restrict__ pos_ptr, int P, int sent, int nb, int* __restrict__ pos_next,
+        int groups, float lambda, R rule) {
+    __shared__ float sc[BEAM_MAX * BEAM_MAX];
+    __shared__ float s_sc[BEAM_MAX];
+    __shared__ int s_par[BEAM_MAX], s_tok[BEAM_MAX];
+    __shared__ long long st_seq[BEAM_MAX][BEAM_TW];
+    __shared__ int st_keep[BEAM_MAX][BEAM_TW], st_rows[BEAM_MAX][BEAM_TW];
+    const int g = blockIdx.x, tid = threadIdx.x, pos = *pos_ptr, b0 = g * nb;
+    if (pos_next && g == 0 && tid == 0) *pos_next = pos + 1;
+    const int j = pos + 1 - P;
+    const bool next_ok = pos + 1 < ldrows;
+    if (rule.held(b0, pos)) {
+        if (tid < nb && next_ok) rows[(long)(b0 + tid) * ldrows + pos + 1] = b0 + tid;
+        return;
+    }
+    if (j < 1 || beam_forced(j, sent) || !cand_val) {
+        if (tid < nb) {
+            const long b = b0 + tid;
+            if (j >= 1 && beam_forced(j, sent)) seq[b * ldseq + pos + 1] = (j + 1) % sent == 0 ? 2 : 1;
+            if (next_ok) rows[b * ldrows + pos + 1] = (int)b;
+        }
+        return;
+    }
+    const int nc = nb * nb, gs = nb / groups, gc = gs * nb;   // candidates in all, rows and candidates of one group
+    float base = -INFINITY;
+    int mp = 0, mk = 0, mv = 0;
+    if (tid < nc) {
+        mp = tid / nb;
+        mk = tid - mp * nb;
+        base = scores[b0 + mp] + cand_val[(long)(b0 + mp) * nb + mk];
+        if (base != base) base = -INFINITY;
+        mv = cand_id[(long)(b0 + mp) * nb + mk];
+    }
+    const bool content = ngram_content(mv);
+    for (int r = 0; r < groups; ++r) {
+        const int c0 = r * gc, r0 = r * gs;                    // the round's first candidate and first slot
+        const bool mine = tid >= c0 && tid < c0 + gc;
+        float sel = base;
+        if (mine) {
+            int n = 0;
+            if (content)
+                for (int q = 0; q < r0; ++q) n += s_tok[q] == mv && s_sc[q] > -INFINITY;
+            if (n) {
+#pragma clang fp contract(off)
+                const float pen = lambda * (float)n;           // (two roundings, as a host restatement in fp32 has them)
+                sel = base - pen;
+            }
+            sc[tid] = sel;
+        }
+        __syncthreads();
+        if (mine) {
+            int place = 0;
+            for (int o = c0; o < c0 + gc; ++o) {
+                const float so = sc[o];
+                place += (so > sel) || (so == sel && o < tid);
+            }
+            if (place < gs) { s_par[r0 + place] = mp; s_tok[r0 + place] = mv; s_sc[r0 + place] = base; }
+        }
+        __syncthreads();
+    }
+    bool ident = true;
+    for (int r = 0; r < nb; ++r) ident = ident && s_par[r] == r;
+    if (!ident) {
+        for (int c0 = 0; c0 <= pos; c0 += BEAM_TW) {
+            const int w = min(BEAM_TW, pos + 1 - c0);
+            for (int e = tid; e < nb * BEAM_TW; e += 256) {
+                const int r = e / BEAM_TW, c = e - r * BEAM_TW;
+                if (c < w) {
+                    const long b = b0 + r;
+                    st_seq[r][c] = seq[b * ldseq + c0 + c];
+                    st_keep[r][c] = keep[b * ldkeep + c0 + c];
+                    st_rows[r][c] = rows[b * ldrows + c0 + c];
+                }
+            }
+            __syncthreads();
+            for (int e = tid; e < nb * BEAM_TW; e += 256) {
+                const int r = e / BEAM_TW, c = e - r * BEAM_TW;
+                if (c < w) {
+                    const long b = b0 + r;
+                    const int p = s_par[r];
+                    seq[b * ldseq + c0 + c] = st_seq[p][c];
+                    keep[b * ldkeep + c0 + c] = st_keep[p][c];
+                    rows[b * ldrows + c0 + c] = st_rows[p][c];
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (tid < nb) {
+        const long b = b0 + tid;
+        scores[b] = s_sc[tid];
+        seq[b * ldseq + pos + 1] = s_tok[tid];
+        if (next_ok) rows[b * ldrows + pos + 1] = (int)b;
+    }
+}
+
 }  // namespace
 
 extern "C" int mmtg_decode_embed(int dtype, const void* table, const long long* seq, long ldseq, const void* c, void* x,
@@ -1767,6 +1872,25 @@ static int beam_merge_launch(const char* what, const float* cand_val, const int*
     return MMTG_OK;
 }
 
+// (the grouped merge: groups divides nb, the penalty is finite and >= 0; the plain merge's checks besides)
+template <typename R>
+static int beam_merge_groups_launch(const char* what, const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq,
+                                    int* keep, long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb,
+                                    int n_prompts, int* pos_next, int groups, float diversity_penalty, void* stream, R rule) {
+    MMTG_REQUIRE(nb >= 1 && nb <= BEAM_MAX, "%s: %d beams per prompt (1..%d)", what, nb, BEAM_MAX);
+    MMTG_REQUIRE(groups >= 1 && nb % groups == 0, "%s: %d groups do not divide %d beams", what, groups, nb);
+    MMTG_REQUIRE(diversity_penalty >= 0.f && diversity_penalty < INFINITY, "%s: diversity penalty must be finite and >= 0", what);
+    MMTG_REQUIRE(scores && seq && keep && rows && pos_ptr && n_prompts > 0 && sent > 1 && ldrows > 0 && (!cand_val || cand_id),
+                 "%s: bad args", what);
+    MMTG_REQUIRE(pos_next != pos_ptr, "%s: pos_next must not alias pos_ptr", what);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, (double)n_prompts * nb * nb, 32.0 * n_prompts * nb * (double)ldrows);
+    hipLaunchKernelGGL(beam_merge_groups_kernel<R>, dim3(n_prompts), dim3(256), 0, s, cand_val, cand_id, scores, seq, ldseq, keep, ldkeep,
+                       rows, ldrows, pos_ptr, P, sent, nb, pos_next, groups, diversity_penalty, rule);
+    MMTG_LAUNCH_CHECK(what);
+    return MMTG_OK;
+}
+
 // (what every sample_* entry asks of its own arguments)
 static int sample_args_check(const char* what, const float* uniforms, long ldu, int B, int top_k, float top_p) {
     MMTG_REQUIRE(uniforms && ldu >= B && top_k >= 0 && top_p >= 0.f, "%s: uniforms [positions, ldu >= B], top_k >= 0, top_p >= 0", what);
@@ -1865,6 +1989,22 @@ extern "C" int mmtg_decode_beam_merge_fixed(const float* cand_val, const int* ca
     MMTG_REQUIRE(fixed_end, "decode_beam_merge_fixed: null fixed_end");
     return beam_merge_launch("decode_beam_merge_fixed", cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows, ldrows, pos_ptr, P, sent,
                              nb, n_prompts, pos_next, stream, FixedEnd{fixed_end});
+}
+
+extern "C" int mmtg_decode_beam_merge_groups(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq, int* keep,
+                                             long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb, int n_prompts,
+                                             int* pos_next, int groups, float diversity_penalty, void* stream) {
+    return beam_merge_groups_launch("decode_beam_merge_groups", cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows, ldrows, pos_ptr, P,
+                                    sent, nb, n_prompts, pos_next, groups, diversity_penalty, stream, NoRule{});
+}
+
+extern "C" int mmtg_decode_beam_merge_groups_fixed(const float* cand_val, const int* cand_id, float* scores, long long* seq, long ldseq,
+                                                   int* keep, long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent, int nb,
+                                                   int n_prompts, int* pos_next, const int* fixed_end, int groups, float diversity_penalty,
+                                                   void* stream) {
+    MMTG_REQUIRE(fixed_end, "decode_beam_merge_groups_fixed: null fixed_end");
+    return beam_merge_groups_launch("decode_beam_merge_groups_fixed", cand_val, cand_id, scores, seq, ldseq, keep, ldkeep, rows, ldrows,
+                                    pos_ptr, P, sent, nb, n_prompts, pos_next, groups, diversity_penalty, stream, FixedEnd{fixed_end});
 }
 
 extern "C" int mmtg_decode_select_ngram(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,

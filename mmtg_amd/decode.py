@@ -13,6 +13,7 @@ only because it never batches; identical at batch 1).
 """
 from __future__ import annotations
 
+import math
 import os
 
 import numpy as np
@@ -73,6 +74,23 @@ def check_ngram(n, sent=22):
     if not 0 <= n <= sent - 2:
         raise ValueError("no_repeat_ngram_size %d outside 0..%d (sent - 2)" % (n, sent - 2))
     return n
+
+
+def check_groups(num_beams, num_beam_groups=1, diversity_penalty=0.0):
+    """The beam groups of a diverse beam search: (G, penalty) for `num_beams` beams.  1 <= G <= num_beams and G divides num_beams;
+    the penalty is finite and >= 0, and 0 unless G > 1 (a penalty on one group would do nothing: that is a mistake, not a setting)."""
+    nb = int(num_beams)
+    if not _is_int(num_beam_groups):
+        raise ValueError("num_beam_groups must be an integer, got %r" % (num_beam_groups,))
+    G = int(num_beam_groups)
+    if not 1 <= G <= nb or nb % G:
+        raise ValueError("num_beam_groups %d must be in 1..%d and divide num_beams %d" % (G, nb, nb))
+    lam = float(diversity_penalty)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError("diversity_penalty must be finite and >= 0, got %r" % (diversity_penalty,))
+    if G == 1 and lam != 0.0:
+        raise ValueError("diversity_penalty %r needs num_beam_groups > 1 (one group has no earlier group to differ from)" % (diversity_penalty,))
+    return G, lam
 
 
 def chosen_mask(ids, sent=22, prefix_lens=None):
@@ -476,18 +494,21 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
     return LineTables(lo, hi, set_of if table else None, sets, sent, V, tmpl, class_of, lead, rhyme_distinct and lead is not None)
 
 
-def select_forms(with_head, prefix, ngram, lines, templates=False, rhymes=False):
+def select_forms(with_head, prefix, ngram, lines, templates=False, rhymes=False, groups=False):
     """Which selection entries a token step ends in: (form of mmtg_decode_select / _sample or mmtg_decode_beam_candidates, form of
     mmtg_decode_beam_merge), each "" (plain), "_fixed", "_ngram", "_lines", "_tmpl" or "_rhyme".  with_head: the step calls the
     model's head; prefix: the generation has one; ngram: no_repeat_ngram_size; lines: line constraints are given; templates: line
     templates are given (every step that calls the head then ends in "_tmpl"); rhymes: a rhyme scheme is given (every such step
     ends in "_rhyme", with or without templates).  The bans act where logits are read, so
     a step without the head (select with null logits; no candidates launch, merge with null candidates) and every merge only know
-    the prefix -- a generation without constraints runs the plain entries throughout."""
+    the prefix -- a generation without constraints runs the plain entries throughout.  groups: the beams are in more than one
+    group (diverse beam search): the merge of a step with the head is then "_groups" / "_groups_fixed"; a step without the head
+    has no candidates to choose among and keeps the merge it always ran."""
     held = "_fixed" if prefix else ""
     if not with_head:
         return held, held
-    return ("_rhyme" if rhymes else "_tmpl" if templates else "_lines" if lines else "_ngram" if ngram else held), held
+    return (("_rhyme" if rhymes else "_tmpl" if templates else "_lines" if lines else "_ngram" if ngram else held),
+            "_groups" + held if groups else held)
 
 
 def _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, rows, length, sh, what, templates=None,
@@ -1058,6 +1079,8 @@ class GreedyDecoder:
             key += ("distinct",) if rhyme[2] else ()
         if with_head and getattr(self, "return_logprobs", False):
             key += ("logprob",)
+        if with_head and getattr(self, "groups", 1) > 1:     # (the grouped merge holds both by value)
+            key += (("groups", self.groups, float(self.diversity_penalty)),)
         return key
 
     def _step_state(self):
@@ -1246,7 +1269,7 @@ class GreedyDecoder:
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None,
                  use_graph=None, teacher=None, tap=None, prefix=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None,
-                 templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_logprobs=False):
+                 templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_logprobs=False, **begin_kw):
         """batch: dict with topic_ids/tpw_* [B,P], topic_emb, img_embs, r_embs (no targets needed).
         Runs `length` iterations of the reference loop and returns the lyric ids
         [B, 1 + length] (column 0 is the initial [#START#]).  top_k = 1, top_p = 0 is the greedy setting;
@@ -1270,11 +1293,12 @@ class GreedyDecoder:
         the first line of the pair on; rhyme_distinct=True keeps a line from ending on the id an earlier line of its group ended on.
         return_logprobs: return (ids, tok_lp [B, 1 + length] fp32) -- per column the log-probability the model's raw logits give the
         id the column holds, 0 where no step called the head (``begin``; ``chosen_mask`` / ``sequence_scores`` turn them into a
-        score per row).  With a prefix that covers every row whole it scores given text (generate.score_sequences)."""
+        score per row).  With a prefix that covers every row whole it scores given text (generate.score_sequences).
+        begin_kw: what a subclass's ``begin`` takes beyond these (BeamDecoder: the beam groups); ``begin`` here takes none."""
         n_steps = self.begin(batch, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix,
                              no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths, line_end_ids=line_end_ids,
                              templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct,
-                             **({"return_logprobs": True} if return_logprobs else {}))
+                             **({"return_logprobs": True} if return_logprobs else {}), **begin_kw)
         eng, sh = self.eng, self.eng.sh
         saved_mode = self.use_graph
         if use_graph is not None:
@@ -1323,7 +1347,9 @@ class BeamDecoder(GreedyDecoder):
     `num_beams` by (score descending, parent beam ascending, rank inside the parent: x descending, id ascending), so one beam
     picks what greedy picks.  Forced [#EOS#] / [#START#] positions and sticky PAD keep the score; a PAD-terminated beam keeps its
     frozen score (no length penalty, no early stop: every beam has the same length).  Beam scores start at [0, -inf, ...], so the
-    replicated beams of a prompt never yield duplicate hypotheses.
+    replicated beams of a prompt never yield duplicate hypotheses.  With `num_beam_groups` > 1 (``begin``) the beams are groups
+    that search on their own, each started at [0, -inf, ...], a later group steered away from the ids earlier groups take at the
+    same step by `diversity_penalty`; the scores stay the unpenalised sums described here.
 
     The KV cache is never copied: a row writes its new K / V into its own slot `pos`, and the ancestry table `rows` [B, Tmax]
     (rows[b, j] = the cache row holding position j of beam b's history) is reordered with seq / keep by the merge; the attention
@@ -1346,22 +1372,25 @@ class BeamDecoder(GreedyDecoder):
         self.scores = torch.zeros(self.B, dtype=torch.float32, device=dev)
         self.cand_val = torch.zeros(self.B, nb, dtype=torch.float32, device=dev)
         self.cand_id = torch.zeros(self.B, nb, dtype=torch.int32, device=dev)
+        self.groups, self.diversity_penalty = 1, 0.0
 
     def _select(self, with_head):
         """The step's last two launches, through the entries select_forms names: the bans (and a full line's PAD, offered as sticky
-        PAD is) act in the candidates; the merge is the prefix-aware one or the plain one."""
+        PAD is) act in the candidates; the merge is the prefix-aware one or the plain one -- with beam groups, on a step with the
+        head, the grouped one of either (the candidates do not know of groups)."""
         sh = self.eng.sh
         temperature, rep, _, _ = self.params
         tmpl, rhyme = getattr(self, "tmpl", None), getattr(self, "rhyme", None)
         cand, merge = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=tmpl is not None,
-                                   rhymes=rhyme is not None)
+                                   rhymes=rhyme is not None, groups=getattr(self, "groups", 1) > 1)
         fe = self.fixed_end if self.use_fixed else None
         if with_head:
             hip._beam_candidates(cand, self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2, temperature,
                                  rep, self.nb, self.cand_val, self.cand_id, self.B, fixed_end=fe, ngram=self.ngram, tables=self.lines,
                                  tmpl=tmpl, **({} if rhyme is None else {"rhyme": rhyme}))
         hip._beam_merge(merge, self.cand_val if with_head else None, self.cand_id if with_head else None, self.scores, self.seq, self.keep,
-                        self.rows, self.pos, sh.P, sh.msl + 2, self.nb, self.n_prompts, self.pos_next, fixed_end=fe)
+                        self.rows, self.pos, sh.P, sh.msl + 2, self.nb, self.n_prompts, self.pos_next, fixed_end=fe,
+                        groups=getattr(self, "groups", 1), diversity_penalty=getattr(self, "diversity_penalty", 0.0))
 
     def _step_state(self):
         return super()._step_state() + [self.rows, self.scores]
@@ -1380,12 +1409,19 @@ class BeamDecoder(GreedyDecoder):
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
               no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
-              rhyme_distinct=False, return_logprobs=False):
+              rhyme_distinct=False, return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0):
         """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill, the prefix, the line
         constraints, the templates and the rhyme scheme: one per prompt; every beam finds its leader's rhyme in its own history), the
         ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at the free positions
-        after a prompt's prefix.  return_logprobs=True raises ValueError (``_no_logprobs``)."""
+        after a prompt's prefix.  return_logprobs=True raises ValueError (``_no_logprobs``).
+
+        num_beam_groups / diversity_penalty (``check_groups``; the rule's home is include/mmtg_hip.h): G > 1 splits a prompt's beams
+        into G groups of s = num_beams / G rows, each started at [0, -inf, ...] and searched on its own; at every step that calls
+        the head the merge (mmtg_decode_beam_merge_groups) serves the groups in order and lowers a candidate by the penalty per
+        earlier group's beam that took the same content id at this step.  The penalty steers the choice only: the scores stay the
+        unpenalised sums.  G = 1 (the default) runs exactly the launches, graphs and graph keys of a search without the argument."""
         self._no_logprobs(return_logprobs)
+        G, lam = check_groups(self.nb, num_beam_groups, diversity_penalty)
         n = batch["img_embs"].shape[0]
         if n != self.n_prompts:
             raise ValueError("decoder was built for %d prompts, got %d" % (self.n_prompts, n))
@@ -1401,29 +1437,36 @@ class BeamDecoder(GreedyDecoder):
                                 no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=tables)
         B, dev = self.B, self.eng.dev
         self.rows.copy_(torch.arange(B, dtype=torch.int32, device=dev)[:, None].expand(B, self.Tmax))
+        self.groups, self.diversity_penalty = G, lam
         sc = torch.full((n, self.nb), float("-inf"), dtype=torch.float32, device=dev)
-        sc[:, 0] = 0.0
+        sc[:, ::self.nb // G] = 0.0                              # the first row of every group
         self.scores.copy_(sc.view(-1))
         return n_steps
 
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None, no_repeat_ngram_size=0,
                  line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False,
-                 return_logprobs=False):
+                 return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, return_groups=False):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_beams, 1 + length] in
         GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row.
         prefix: one per prompt (check_prefix), shared by its beams.  no_repeat_ngram_size: as GreedyDecoder.generate, per beam
         on its own (reordered) history.  line_lengths / line_end_ids / templates: as GreedyDecoder.generate, one per prompt, shared by
         its beams (a given column adds nothing to a score).  rhyme_scheme / rhyme_classes / rhyme_distinct: as GreedyDecoder.generate,
         one scheme per prompt; each beam rhymes with its own earlier lines.  return_logprobs=True raises ValueError before any device
-        work: the scores here are sums over the PROCESSED logits; generate.score_sequences gives a beam's raw log-probabilities."""
+        work: the scores here are sums over the PROCESSED logits; generate.score_sequences gives a beam's raw log-probabilities.
+        num_beam_groups / diversity_penalty: diverse beam search (``begin``): G groups of num_beams / G beams, a later group steered
+        away from the ids earlier groups take at the same step.  The result keeps its form: all num_beams hypotheses of a prompt,
+        best first by their (unpenalised) scores.  return_groups=True adds a third tensor, int64 [n, num_beams]: the group (final
+        row // (num_beams / G)) of the hypothesis returned at that place."""
         self._no_logprobs(return_logprobs)
+        G, lam = check_groups(self.nb, num_beam_groups, diversity_penalty)
         ids = super().generate(batch, length, temperature=temperature, repitition_penalty=repitition_penalty, use_graph=use_graph,
                                prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths,
                                line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes,
-                               rhyme_distinct=rhyme_distinct)
+                               rhyme_distinct=rhyme_distinct, **({"num_beam_groups": G, "diversity_penalty": lam} if G > 1 else {}))
         n, nb = self.n_prompts, self.nb
         ids = ids.view(n, nb, -1)
         sc = self.scores.view(n, nb).clone()
         order = torch.sort(sc, dim=1, descending=True, stable=True).indices
-        return torch.gather(ids, 1, order[:, :, None].expand_as(ids)), torch.gather(sc, 1, order)
+        out = torch.gather(ids, 1, order[:, :, None].expand_as(ids)), torch.gather(sc, 1, order)
+        return out + (order // (nb // G),) if return_groups else out

@@ -304,7 +304,8 @@ def score_sequences(model, rows, ids, max_batch=256):
 
 def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature=1.1, repetition_penalty=1.5, max_batch=256,
                    return_all=False, prefixes=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None,
-                   rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_ids=False):
+                   rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_ids=False, num_beam_groups=1,
+                   diversity_penalty=0.0, best_per_group=False):
     """Beam search per prompt on the batched, graph-replayed decoder (BeamDecoder): prompts are decoded max_batch // num_beams at
     a time, every beam is cut back to what sample_sequence would have returned (GreedyDecoder.reference_return) and
     post-processed as generate_samples does.  rows: as generate_samples.  Returns one string per prompt (its best beam), or with
@@ -314,8 +315,16 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
     line_end_ids / templates: as generate_samples, shared by a prompt's beams (a full line and a given column add nothing to a
     score).  rhyme_scheme / rhyme_classes / rhyme_distinct: as generate_samples; every beam rhymes with its own earlier lines.
     return_ids (with return_all): (text, score, ids) triples, ids the beam's 1 + length lyric ids -- a row score_sequences takes, which
-    gives the beam the model's raw token log-probabilities (the score here changes with temperature, penalty and every ban)."""
-    from .decode import BeamDecoder, GreedyDecoder, check_ngram
+    gives the beam the model's raw token log-probabilities (the score here changes with temperature, penalty and every ban).
+    num_beam_groups / diversity_penalty: diverse beam search (BeamDecoder.begin): G groups of num_beams / G beams, a later group
+    lowered by the penalty for every earlier group's beam that takes the same content id at the same step; scores stay the
+    unpenalised sums, so the list of return_all is still best first over all groups.  best_per_group=True returns one list per
+    prompt of G entries in group order, each the best hypothesis of its group as (text, score), or (text, score, ids) with
+    return_ids; it excludes return_all."""
+    from .decode import BeamDecoder, GreedyDecoder, check_groups, check_ngram
+    G, lam = check_groups(num_beams, num_beam_groups, diversity_penalty)
+    if best_per_group and return_all:
+        raise ValueError("best_per_group returns one hypothesis per group, return_all every beam: ask for one of them")
     eng = model.engine()
     sh = eng.sh
     ngram = check_ngram(no_repeat_ngram_size, sh.msl + 2)
@@ -343,14 +352,18 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
             cpre = pre[lo:hi] + [pre[lo]] * (per - (hi - lo))
         chunk = {k: v.to(eng.dev) for k, v in chunk.items()}
         clines = _chunk_lines(lines, list(range(lo, hi)) + [lo] * (per - (hi - lo)))
-        ids, scores = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty, prefix=cpre,
-                                   no_repeat_ngram_size=ngram, line_lengths=clines)
-        ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
+        ids, scores, group = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty, prefix=cpre,
+                                          no_repeat_ngram_size=ngram, line_lengths=clines, num_beam_groups=G, diversity_penalty=lam,
+                                          return_groups=True)
+        ids, scores, group = ids.cpu().numpy(), scores.cpu().numpy(), group.cpu().numpy()
         for r in range(hi - lo):
             beams = []
             for k in range(num_beams):
                 seq = GreedyDecoder.reference_return(ids[r, k].tolist(), length, sent=sh.msl + 2)
                 beams.append((postprocess_tokens(tokenizer.convert_ids_to_tokens(seq)), float(scores[r, k]))
                              + ((ids[r, k].tolist(),) if return_ids else ()))
-            out.append(beams if return_all else beams[0][0])
+            if best_per_group:         # (best first, so a group's first place is its best)
+                out.append([beams[int(np.argmax(group[r] == g))] for g in range(G)])
+            else:
+                out.append(beams if return_all else beams[0][0])
     return out

@@ -110,6 +110,8 @@ _SIGS = {
     "mmtg_decode_sample_fixed": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp, _vp], _i),
     "mmtg_decode_beam_candidates_fixed": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _vp], _i),
     "mmtg_decode_beam_merge_fixed": ([_vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "mmtg_decode_beam_merge_groups": ([_vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _i, _f, _vp], _i),
+    "mmtg_decode_beam_merge_groups_fixed": ([_vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _i, _f, _vp], _i),
     "mmtg_decode_select_ngram": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_sample_ngram": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_beam_candidates_ngram": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp], _i),
@@ -930,11 +932,18 @@ def _beam_candidates(form, logits, ldl, V, seq, pos, P, sent, temperature, rep_p
                                           *_rule_tail(form, B, V, fixed_end, ngram, tables, tmpl, sent, rhyme), _stream()), name)
 
 
-def _beam_merge(form, cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next, fixed_end=None):
+def _beam_merge(form, cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next, fixed_end=None, groups=1,
+                diversity_penalty=0.0):
+    """mmtg_decode_beam_merge<form>, form "" / "_fixed" or, for the grouped merge, "_groups" / "_groups_fixed" (the held form's
+    tail, then groups and the penalty)."""
     name = "decode_beam_merge" + form
+    grouped = form.startswith("_groups")
+    tail = _rule_tail(form[len("_groups"):] if grouped else form, n_prompts * nb, 0, fixed_end, 0, None)
+    if grouped:
+        tail += (int(groups), float(diversity_penalty))
     _check(getattr(lib(), "mmtg_" + name)(_p(cand_val), _p(cand_id), _p(scores), _p(seq), seq.stride(0), _p(keep), keep.stride(0),
                                           _p(rows), rows.stride(0), _p(pos), P, sent, int(nb), int(n_prompts), _p(pos_next),
-                                          *_rule_tail(form, n_prompts * nb, 0, fixed_end, 0, None), _stream()), name)
+                                          *tail, _stream()), name)
 
 
 def decode_select(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next=None):
@@ -972,6 +981,21 @@ def decode_beam_candidates_fixed(logits, ldl, V, seq, pos, P, sent, temperature,
 def decode_beam_merge_fixed(cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, fixed_end, pos_next=None):
     """decode_beam_merge; a prompt on a prefix column keeps every beam, score and token (include/mmtg_hip.h)."""
     _beam_merge("_fixed", cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next, fixed_end=fixed_end)
+
+
+def decode_beam_merge_groups(cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, groups, diversity_penalty,
+                             pos_next=None):
+    """decode_beam_merge over `groups` beam groups per prompt, a later group penalised by diversity_penalty per earlier slot that
+    chose the same content id at this step; the stored scores are unpenalised (include/mmtg_hip.h)."""
+    _beam_merge("_groups", cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next, groups=groups,
+                diversity_penalty=diversity_penalty)
+
+
+def decode_beam_merge_groups_fixed(cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, fixed_end, groups,
+                                   diversity_penalty, pos_next=None):
+    """decode_beam_merge_groups; a prompt on a prefix column keeps every beam, score and token (include/mmtg_hip.h)."""
+    _beam_merge("_groups_fixed", cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next, fixed_end=fixed_end,
+                groups=groups, diversity_penalty=diversity_penalty)
 
 
 def decode_select_ngram(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, ngram, fixed_end=None, pos_next=None):
