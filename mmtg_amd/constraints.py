@@ -1,0 +1,550 @@
+"""The constraints of a generation, checked and packed on the host before any device work (prefix, n-gram size, beam groups; line
+bounds / end sets / templates / rhyme scheme as LineTables), and the host-side scoring of token log-probabilities.  numpy and
+Python only: decode.py uploads the tables and chooses the launches, include/mmtg_hip.h states the rules the kernels apply."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+BANNED = (1, 2, 100, 102)           # never a content id: [#START#] [#EOS#] [UNK] [SEP] (src/generate.py:135)
+
+
+def check_prefix(prefix, rows, length, sent=22, V=None):
+    """Validate a prefixed generation's opening lyric ids on the host, before any device work; returns one list of ids per row.
+
+    prefix: a [rows, Lmax] integer tensor / array padded with -1, or a list of `rows` id lists.  Row b's prefix p (L >= 1 ids) is
+    lyric columns 0 .. L - 1 in the slot layout of the training data (data.MyDataset): column c holds [#START#] (1) where
+    c % sent == 0, [#EOS#] (2) where c % sent == sent - 1, and a content id or PAD (0) elsewhere -- never one of the banned ids
+    1, 2, 100, 102.  So p is whole lines (L % sent == 1: it ends on the next line's [#START#]) or whole lines plus a partial line.
+    L <= length + 1: the output has 1 + length columns."""
+    if isinstance(prefix, (list, tuple)):
+        ids = [[int(v) for v in np.asarray(r).reshape(-1).tolist()] for r in prefix]
+    else:
+        a = prefix.detach().cpu().numpy() if torch.is_tensor(prefix) else np.asarray(prefix)
+        if a.ndim != 2:
+            raise ValueError("prefix must be a [rows, Lmax] array padded with -1 or a list of id lists (got shape %s)" % (a.shape,))
+        ids = []
+        for r in a.tolist():
+            n = r.index(-1) if -1 in r else len(r)
+            if any(v != -1 for v in r[n:]):
+                raise ValueError("prefix row %d: ids after the -1 padding" % len(ids))
+            ids.append([int(v) for v in r[:n]])
+    if len(ids) != rows:
+        raise ValueError("prefix has %d rows, the generation %d" % (len(ids), rows))
+    for b, p in enumerate(ids):
+        if not p:
+            raise ValueError("prefix row %d is empty (it starts with [#START#])" % b)
+        if len(p) > length + 1:
+            raise ValueError("prefix row %d has %d ids, more than length + 1 = %d" % (b, len(p), length + 1))
+        for c, v in enumerate(p):
+            if c % sent == 0 and v != 1:
+                raise ValueError("prefix row %d, column %d: [#START#] (1) expected, got %d" % (b, c, v))
+            if c % sent == sent - 1 and v != 2:
+                raise ValueError("prefix row %d, column %d: [#EOS#] (2) expected, got %d" % (b, c, v))
+            if 0 < c % sent < sent - 1 and (v in BANNED or v < 0 or (V is not None and v >= V)):
+                raise ValueError("prefix row %d, column %d: id %d is not a content id or PAD" % (b, c, v))
+    return ids
+
+
+def check_ngram(n, sent=22):
+    """Validate no_repeat_ngram_size on the host, before any device work; returns it as an int.  0 is off; 1 .. sent - 2 blocks
+    every content n-gram a row already holds (include/mmtg_hip.h states the rule; a longer n-gram can never be all content).
+    Bools and non-integers raise ValueError, as do values out of range."""
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)):
+        raise ValueError("no_repeat_ngram_size must be an integer, got %r" % (n,))
+    n = int(n)
+    if not 0 <= n <= sent - 2:
+        raise ValueError("no_repeat_ngram_size %d outside 0..%d (sent - 2)" % (n, sent - 2))
+    return n
+
+
+def check_groups(num_beams, num_beam_groups=1, diversity_penalty=0.0):
+    """The beam groups of a diverse beam search: (G, penalty) for `num_beams` beams.  1 <= G <= num_beams and G divides num_beams;
+    the penalty is finite and >= 0, and 0 unless G > 1 (a penalty on one group would do nothing: that is a mistake, not a setting)."""
+    nb = int(num_beams)
+    if not _is_int(num_beam_groups):
+        raise ValueError("num_beam_groups must be an integer, got %r" % (num_beam_groups,))
+    G = int(num_beam_groups)
+    if not 1 <= G <= nb or nb % G:
+        raise ValueError("num_beam_groups %d must be in 1..%d and divide num_beams %d" % (G, nb, nb))
+    lam = float(diversity_penalty)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError("diversity_penalty must be finite and >= 0, got %r" % (diversity_penalty,))
+    if G == 1 and lam != 0.0:
+        raise ValueError("diversity_penalty %r needs num_beam_groups > 1 (one group has no earlier group to differ from)" % (diversity_penalty,))
+    return G, lam
+
+
+def chosen_mask(ids, sent=22, prefix_lens=None):
+    """Which columns of generated lyric ids count towards a row's score: bool [B, 1 + length], host only.  Column j >= 1 of row b
+    counts iff it is not a cadence column (j % sent not in {0, sent - 1}: the forced [#START#] / [#EOS#]), it lies past the row's
+    prefix (j >= prefix_lens[b]; None: no prefix) and the previous column is not PAD (ids[b][j - 1] != 0) -- so the first PAD of a
+    line counts (the model ended the line there; in an empty line that is its first content column) and the sticky PADs behind
+    it, which no model call decided, do not.
+    Columns that a constraint decided (a template's given id, a full line's PAD) count: their value is the model's log-probability
+    of that id.  Samples of one prompt share their constraints, so ranking among them is fair."""
+    a = np.asarray(ids.detach().cpu().numpy() if torch.is_tensor(ids) else ids)
+    if a.ndim != 2:
+        raise ValueError("ids must be [rows, 1 + length] (got shape %s)" % (a.shape,))
+    B, n = a.shape
+    pl = np.zeros(B, np.int64) if prefix_lens is None else np.asarray(prefix_lens, np.int64).reshape(-1)
+    if pl.shape[0] != B:
+        raise ValueError("prefix_lens has %d rows, ids %d" % (pl.shape[0], B))
+    j = np.arange(n)
+    mask = np.zeros((B, n), bool)
+    mask[:, 1:] = a[:, :-1] != 0
+    mask &= ((j >= 1) & (j % sent != 0) & (j % sent != sent - 1))[None, :]
+    mask &= j[None, :] >= pl[:, None]
+    return mask
+
+
+def sequence_scores(ids, logprobs, sent=22, prefix_lens=None, upto=None):
+    """(sum float64 [B], count int64 [B]) of the token log-probabilities over chosen_mask's columns below `upto` (None: all; for
+    the text generate_samples returns, 1 + the last iteration that called the model: GreedyDecoder.reference_return).  Host only."""
+    mask = chosen_mask(ids, sent=sent, prefix_lens=prefix_lens)
+    lp = np.asarray(logprobs.detach().cpu().numpy() if torch.is_tensor(logprobs) else logprobs, np.float64)
+    if lp.shape != mask.shape:
+        raise ValueError("logprobs of shape %s for ids of shape %s" % (lp.shape, mask.shape))
+    if upto is not None:
+        mask[:, max(int(upto), 0):] = False
+    return np.where(mask, lp, 0.0).sum(1), mask.sum(1).astype(np.int64)
+
+
+class LineTables:
+    """The packed line constraints check_lines returns: lo, hi uint8 [rows, n_lines]; set_of int16 [rows, n_lines] (-1: no end set)
+    and sets uint32 [n_sets, ceil(V / 32)] (bit v & 31 of word v >> 5: id v is a member), or both None when no line has a set.
+    tmpl (templates= only, else None): int32 [rows, n_lines, sent - 2], one symbol per content column -- v >= 0 a given id, -1 free,
+    v <= -2 the class `sets[-2 - v]` (classes and end sets share the table); a template's length is folded into lo / hi.
+    class_of, lead, distinct (rhyme_scheme= only, else None, None, False): class_of int16 [V], the row of `sets` that is id v's rhyme
+    class or -1; lead int8 [rows, n_lines], the leader's line of a follower line or -1; a leader's static end set (the union of the
+    classes) is folded into set_of."""
+
+    def __init__(self, lo, hi, set_of, sets, sent, V, tmpl=None, class_of=None, lead=None, distinct=False):
+        self.lo, self.hi, self.set_of, self.sets, self.sent, self.V, self.tmpl = lo, hi, set_of, sets, sent, V, tmpl
+        self.class_of, self.lead, self.distinct = class_of, lead, bool(distinct)
+
+    @property
+    def rows(self):
+        return self.lo.shape[0]
+
+    def repeat(self, k):
+        """Every row k times in place of itself (the beams of a prompt share its constraints)."""
+        rep = lambda a: None if a is None else np.repeat(a, k, axis=0)      # noqa: E731
+        return LineTables(rep(self.lo), rep(self.hi), rep(self.set_of), self.sets, self.sent, self.V, rep(self.tmpl),
+                          self.class_of, rep(self.lead), self.distinct)
+
+    def take(self, idx):
+        """Rows idx (a list of row indices) as tables of their own; the sets are shared."""
+        sub = lambda a: None if a is None else np.ascontiguousarray(a[idx])      # noqa: E731
+        return LineTables(sub(self.lo), sub(self.hi), sub(self.set_of), self.sets, self.sent, self.V, sub(self.tmpl),
+                          self.class_of, sub(self.lead), self.distinct)
+
+    def leader(self, b, l):
+        """The line whose ending decides the rhyme of row b's line l (l is a follower), or None."""
+        if self.lead is None or l >= self.lead.shape[1] or self.lead[b, l] < 0:
+            return None
+        return int(self.lead[b, l])
+
+    def rhyme_class(self, v):
+        """The rhyme class of id v as a frozenset, or None (no scheme, or v has no rhyme)."""
+        if self.class_of is None or not 0 <= v < len(self.class_of) or self.class_of[v] < 0:
+            return None
+        return self.members(int(self.class_of[v]))
+
+    def symbol(self, b, l, c):
+        """What row b's template says of content column c of line l: an int (a given id), a frozenset (a class) or None (free, no
+        template, or a column / line past it)."""
+        if self.tmpl is None or l >= self.tmpl.shape[1] or not 0 <= c < self.tmpl.shape[2]:
+            return None
+        v = int(self.tmpl[b, l, c])
+        return v if v >= 0 else None if v == -1 else self.members(-2 - v)
+
+    def bounds(self, b, l):
+        """(lo, hi, end set as a frozenset or None) of row b's line l; a line past the table is unconstrained."""
+        if l >= self.lo.shape[1]:
+            return 0, self.sent - 2, None
+        s = -1 if self.set_of is None else int(self.set_of[b, l])
+        return int(self.lo[b, l]), int(self.hi[b, l]), self.members(s) if s >= 0 else None
+
+    def members(self, s):
+        """Set s of the table as a frozenset of ids."""
+        cache = self.__dict__.setdefault("_members", {})
+        if s not in cache:
+            w = self.sets[s]
+            cache[s] = frozenset(v for v in range(32 * len(w)) if (int(w[v >> 5]) >> (v & 31)) & 1)
+        return cache[s]
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _is_ids(e):
+    return isinstance(e, (set, frozenset)) or (isinstance(e, (list, tuple, np.ndarray)) and all(_is_int(v) for v in e))
+
+
+def _per_row(spec, rows, what, whole, per_row_form):
+    """spec as one list of per-line entries per row (or the marker ("all", entry): that entry on every line).  spec is None (no
+    entries), one entry for every line (`whole(spec)`), one list for all rows, or one list, entry or None per row
+    (`per_row_form(spec)`)."""
+    if spec is None:
+        return [[] for _ in range(rows)]
+    if whole(spec):
+        return [("all", spec)] * rows
+    if not isinstance(spec, (list, tuple)):
+        raise ValueError("%s: a list of per-line entries (or one list per row) expected, got %r" % (what, spec))
+    if per_row_form(spec):
+        if len(spec) != rows:
+            raise ValueError("%s has %d rows, the generation %d" % (what, len(spec), rows))
+        out = []
+        for r in spec:
+            if r is not None and not whole(r) and not isinstance(r, (list, tuple)):
+                raise ValueError("%s: a row is None, one entry or a list of per-line entries, got %r" % (what, r))
+            out.append([] if r is None else ("all", r) if whole(r) else list(r))
+        return out
+    return [list(spec)] * rows
+
+
+def _template_rows(spec, rows):
+    """templates as one list of per-line entries per row: one list for all rows, or (a list among the entries marks it) one list or
+    None per row."""
+    if spec is None:
+        return [[] for _ in range(rows)]
+    if not isinstance(spec, list):
+        raise ValueError("templates: a list of per-line templates (or one such list per row) expected, got %r" % (spec,))
+    if any(isinstance(e, list) for e in spec):
+        if len(spec) != rows:
+            raise ValueError("templates has %d rows, the generation %d" % (len(spec), rows))
+        for b, r in enumerate(spec):
+            if r is not None and not isinstance(r, list):
+                raise ValueError("templates row %d: a list of per-line templates or None expected, got %r" % (b, r))
+        return [[] if r is None else r for r in spec]
+    return [spec] * rows
+
+
+def _content_id(v, V):
+    return not (v == 0 or v in BANNED or v < 0 or (V is not None and v >= V))
+
+
+def _id_set(e, V, at, noun, expected="a collection of ids", also=None):
+    """The collection of ids e as a frozenset: non-empty, every member a content id below the cut V.  `at` opens every message and
+    `noun` names the set in them; also(v), if given, is one more check per id, run in ascending order behind the id's own."""
+    if not _is_ids(e) or (isinstance(e, np.ndarray) and e.ndim != 1) or not all(_is_int(v) for v in e):
+        raise ValueError("%s: %s expected, got %r" % (at, expected, e))
+    ids = frozenset(int(v) for v in e)
+    if not ids:
+        raise ValueError("%s: the %s is empty" % (at, noun))
+    for v in sorted(ids):
+        if not _content_id(v, V):
+            raise ValueError("%s: id %d is not a content id below the vocabulary cut" % (at, v))
+        if also is not None:
+            also(v)
+    return ids
+
+
+def _scheme_rows(spec, rows):
+    """rhyme_scheme as one string (or None) per row: one string for all rows, or a list with one string or None per row."""
+    if isinstance(spec, str):
+        spec = [spec] * rows
+    elif not isinstance(spec, (list, tuple)) or not all(r is None or isinstance(r, str) for r in spec):
+        raise ValueError("rhyme_scheme: a string (or a list with one string or None per row) expected, got %r" % (spec,))
+    if len(spec) != rows:
+        raise ValueError("rhyme_scheme has %d rows, the generation %d" % (len(spec), rows))
+    return ["" if r is None else r for r in spec]
+
+
+def _rhyme_classes(classes, V):
+    """rhyme_classes as a list of frozensets: pairwise disjoint, non-empty sets of content ids below V."""
+    if not isinstance(classes, (list, tuple)) or not classes:
+        raise ValueError("rhyme_classes: a non-empty list of id sets expected, got %r" % (classes,))
+    out, owner = [], {}
+    for i, e in enumerate(classes):
+        def own(v):
+            if v in owner:
+                raise ValueError("rhyme_classes: id %d is in classes %d and %d (the classes are disjoint)" % (v, owner[v], i))
+            owner[v] = i
+        out.append(_id_set(e, V, "rhyme_classes, class %d" % i, "class", also=own))
+    return out
+
+
+class _Draft:
+    """The tables of check_lines while its steps fill them, row by row: the arrays of LineTables, the id sets in the order they
+    were first seen (`table`; LineTables.sets is packed from it) and, with a scheme, the rhyme classes, their union and `place`."""
+
+    def __init__(self, rows, length, sent, V, templates):
+        self.length, self.sent, self.V = length, sent, V
+        self.n_lines, self.cap = n_lines, cap = (length - 1) // sent + 1, sent - 2
+        self.lo = np.zeros((rows, n_lines), np.uint8)
+        self.hi = np.full((rows, n_lines), cap, np.uint8)
+        self.set_of = np.full((rows, n_lines), -1, np.int16)
+        self.tmpl = np.full((rows, n_lines, cap), -1, np.int32) if templates else None
+        self.table, self.seen = [], {}
+        self.classes = self.rhymed = self.lead = None
+        self.distinct = False
+        self.place = {}                                          # (row, follower line) -> how many lines of its group lie before it
+
+    def set_index(self, ids):
+        if ids not in self.seen:
+            self.seen[ids] = len(self.table)
+            self.table.append(ids)
+        if self.seen[ids] > 32767:
+            raise ValueError("line_end_ids / templates: more than 32768 distinct id sets")
+        return self.seen[ids]
+
+    def fit(self, what, b, spec):
+        """Row b's per-line entries of argument `what` as a list no longer than the generation's lines."""
+        if isinstance(spec, tuple) and spec and spec[0] == "all":
+            spec = [spec[1]] * self.n_lines
+        if len(spec) > self.n_lines:
+            raise ValueError("%s row %d has %d lines, a generation of length %d holds %d" % (what, b, len(spec), self.length, self.n_lines))
+        return spec
+
+
+def _line_bounds(t, b, spec):
+    """Step 1a: row b's line_lengths entries into lo / hi."""
+    for l, e in enumerate(t.fit("line_lengths", b, spec)):
+        if e is None:
+            continue
+        pair = (e, e) if _is_int(e) else e
+        if not (isinstance(pair, tuple) and len(pair) == 2 and all(_is_int(v) for v in pair)):
+            raise ValueError("line_lengths row %d, line %d: an int, a (lo, hi) tuple or None expected, got %r" % (b, l, e))
+        a, z = int(pair[0]), int(pair[1])
+        if not 0 <= a <= z <= t.cap:
+            raise ValueError("line_lengths row %d, line %d: (%d, %d) is not 0 <= lo <= hi <= %d (sent - 2)" % (b, l, a, z, t.cap))
+        t.lo[b, l], t.hi[b, l] = a, z
+
+
+def _line_ends(t, b, spec):
+    """Step 1b: row b's line_end_ids entries into set_of."""
+    for l, e in enumerate(t.fit("line_end_ids", b, spec)):
+        if e is not None:
+            ids = _id_set(e, t.V, "line_end_ids row %d, line %d" % (b, l), "end set", "a collection of ids or None")
+            t.set_of[b, l] = t.set_index(ids)
+
+
+def _rhyme_scheme(t, b, sch):
+    """Step 2: row b's scheme.  A group's first line (the leader) gets the ids that have a rhyme as a static end set; the others
+    (followers) get their leader's line in `lead` and their rank in `place`."""
+    if not all(ch == "." or ch.isalpha() for ch in sch):
+        raise ValueError("rhyme_scheme row %d: %r holds symbols other than letters and '.'" % (b, sch))
+    groups = {}
+    for l, ch in enumerate(t.fit("rhyme_scheme", b, sch)):
+        if ch != ".":
+            groups.setdefault(ch, []).append(l)
+    for ch, ls in groups.items():
+        if len(ls) < 2:
+            continue                                     # a group of one line is unconstrained
+        if t.distinct and min(len(k) for k in t.classes) < len(ls):
+            raise ValueError("rhyme_scheme row %d: rhyme_distinct and group %r of %d lines, but a rhyme class of %d ids"
+                             % (b, ch, len(ls), min(len(k) for k in t.classes)))
+        for i, l in enumerate(ls):
+            if t.hi[b, l] == 0:
+                raise ValueError("rhyme_scheme row %d, line %d: a rhyming line with hi = 0" % (b, l))
+            if i == 0:
+                ids = t.rhymed if t.set_of[b, l] < 0 else t.rhymed & t.table[t.set_of[b, l]]
+                if not ids:
+                    raise ValueError("rhyme_scheme row %d, line %d: no id of the line's end set has a rhyme class" % (b, l))
+                t.set_of[b, l] = t.set_index(ids)
+            else:
+                if t.set_of[b, l] >= 0:
+                    raise ValueError("rhyme_scheme row %d, line %d: a follower line takes no line_end_ids set of its own" % (b, l))
+                t.lead[b, l] = ls[0]
+                t.place[b, l] = i
+
+
+def _sets_need_room(t, b):
+    """Step 3: a line that ends on a member of a set holds at least one token."""
+    for l in range(t.n_lines):
+        if t.set_of[b, l] >= 0 and t.hi[b, l] == 0:
+            raise ValueError("line_end_ids row %d, line %d: an end set on a line with hi = 0" % (b, l))
+
+
+def _line_templates(t, b, spec):
+    """Step 4: row b's templates into tmpl, their lengths folded into lo / hi; a template that fixes the line's last column is held
+    against the line's end set and, on a follower line, against the rhyme classes."""
+    for l, e in enumerate(t.fit("templates", b, spec)):
+        if e is None:
+            continue
+        at = "templates row %d, line %d" % (b, l)
+        if not isinstance(e, tuple):
+            raise ValueError("%s: a tuple of symbols or None expected, got %r" % (at, e))
+        open_ = len(e) > 0 and e[-1] is Ellipsis
+        syms = e[:-1] if open_ else e
+        k = len(syms)
+        if not 1 <= k <= t.cap:
+            raise ValueError("%s: %d symbols, not 1 .. %d (sent - 2)" % (at, k, t.cap))
+        for c, y in enumerate(syms):
+            if y is None:
+                continue
+            if _is_int(y):
+                if not _content_id(int(y), t.V):
+                    raise ValueError("%s, column %d: id %d is not a content id below the vocabulary cut" % (at, c, int(y)))
+                t.tmpl[b, l, c] = int(y)
+            elif isinstance(y, (set, frozenset)) and all(_is_int(v) for v in y):
+                t.tmpl[b, l, c] = -2 - t.set_index(_id_set(y, t.V, "%s, column %d" % (at, c), "class"))
+            else:
+                raise ValueError("%s, column %d: an int, None or a set of ids expected, got %r" % (at, c, y))
+        a, z = int(t.lo[b, l]), int(t.hi[b, l])
+        if open_:
+            if z < k:
+                raise ValueError("%s: an open template of %d symbols on a line with hi = %d" % (at, k, z))
+            t.lo[b, l] = max(a, k)
+        else:
+            if not a <= k <= z:
+                raise ValueError("%s: a closed template of %d symbols outside the line's bounds (%d, %d)" % (at, k, a, z))
+            t.lo[b, l] = t.hi[b, l] = k
+        y = syms[-1]
+        last = frozenset(int(v) for v in y) if isinstance(y, (set, frozenset)) else None
+        if t.set_of[b, l] >= 0 and t.hi[b, l] == k:              # the template's last column is the line's last: the end set's
+            members = t.table[t.set_of[b, l]]
+            if _is_int(y) and int(y) not in members:
+                raise ValueError("%s: the line ends on the given id %d, which is not in its end set" % (at, int(y)))
+            if last is not None and not members & last:
+                raise ValueError("%s: the last column's class and the line's end set share no id" % at)
+        if (b, l) in t.place and t.hi[b, l] == k:                # a follower whose last possible column the template fixes
+            if _is_int(y):
+                raise ValueError("%s: a follower line of the rhyme scheme ends on the given id %d" % (at, int(y)))
+            need = t.place[b, l] + 1 if t.distinct else 1
+            if last is not None and any(len(kls & last) < need for kls in t.classes):
+                raise ValueError("%s: the last column's class leaves a rhyme class with fewer than %d ids on a follower line" % (at, need))
+
+
+def _prefix_line(t, b, p):
+    """Step 5: row b's prefix p where it stops inside a line: the given columns against the line's template and its hi."""
+    l, q = (len(p) - 1) // t.sent, (len(p) - 1) % t.sent
+    if not (1 <= q <= t.cap and l < t.n_lines):
+        return
+    if t.tmpl is not None:
+        for c in range(min(q, t.cap)):
+            v, y = int(p[l * t.sent + 1 + c]), int(t.tmpl[b, l, c])
+            if y >= 0 and v != y:
+                raise ValueError("prefix row %d gives id %d at column %d of line %d, its template %d" % (b, v, c, l, y))
+            if y <= -2 and v not in t.table[-2 - y]:
+                raise ValueError("prefix row %d gives id %d at column %d of line %d, outside its template's class" % (b, v, c, l))
+    given = sum(1 for v in p[l * t.sent + 1:] if v != 0)
+    if given > t.hi[b, l]:
+        raise ValueError("prefix row %d gives %d content tokens of line %d, more than its hi = %d" % (b, given, l, t.hi[b, l]))
+
+
+def _pack(t):
+    """Step 6: the rhyme classes join the sets, last; the sets as bit rows, class_of, and the LineTables."""
+    rows_of = None if t.classes is None else [t.set_index(k) for k in t.classes]
+    V, sets, class_of = t.V, None, None
+    if t.table:
+        if V is None:
+            V = max(max(s) for s in t.table) + 1
+        sets = np.zeros((len(t.table), (V + 31) // 32), np.uint32)
+        for i, s in enumerate(t.table):
+            for v in s:
+                sets[i, v >> 5] |= np.uint32(1 << (v & 31))
+    if t.classes is not None:
+        class_of = np.full(V, -1, np.int16)
+        for i, k in zip(rows_of, t.classes):
+            class_of[sorted(k)] = i
+    return LineTables(t.lo, t.hi, t.set_of if t.table else None, sets, t.sent, V, t.tmpl, class_of, t.lead, t.distinct)
+
+
+def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefix=None, templates=None, rhyme_scheme=None,
+                rhyme_classes=None, rhyme_distinct=False):
+    """Validate line-length bounds and line-end id sets on the host, before any device work; returns the packed LineTables, or
+    None when both arguments are None (no constraints: the decoders then run the launches of a generation without them).
+
+    A generation of `length` holds n_lines = (length - 1) // sent + 1 lines (those with a content column); line l of row b is
+    lyric columns l * sent .. l * sent + sent - 1 and holds up to sent - 2 content tokens.
+    line_lengths: a line's entry is an int (exactly that many content tokens), a (lo, hi) tuple or None (unconstrained, the
+    same as (0, sent - 2)).  Given as one entry (every line of every row), one list of entries (line by line, for every row; a
+    shorter list leaves the later lines unconstrained) or a list with one such list, entry or None per row (the lists, not tuples,
+    mark this form).
+    line_end_ids: a line's entry is None or a non-empty collection of content ids below the vocabulary cut V (no PAD, none of
+    1, 2, 100, 102): the line's last content token is one of them, so the line is not empty and its hi must be >= 1.  Given as
+    one set / frozenset (every line), one list of entries, or one list of entries (or None) per row.
+    prefix (check_prefix's result, optional): a row whose prefix stops inside a line continues that line under its bounds; given
+    content beyond the line's hi raises.  Whole given lines are the caller's text and are not checked.
+    templates: a line's entry is None or a tuple of k symbols (1 <= k <= sent - 2), one per content column from column 0 -- an int
+    (given: the row writes this content id), None (free) or a set / frozenset of content ids (a class: the column's id is a
+    member) -- optionally ending in `...` (Ellipsis: an open template).  A closed template fixes the line's length, its bounds
+    become (k, k) and k must lie inside the line's line_lengths bounds; an open one makes lo = max(lo, k) and needs hi >= k.  Given
+    as one list of entries (for every row; a shorter list leaves the later lines without a template) or a list with one such list
+    or None per row.  Given ids and class members are content ids below V; on a line with an end set whose length the template
+    fixes (hi == k) the last symbol must leave a member of the set possible.  A partial prefix line must agree with its line's
+    template.  So a column that only classes and end sets constrain always has a live id; only n-gram bans can empty one.
+    rhyme_scheme / rhyme_classes / rhyme_distinct: a scheme is a string with one symbol per line -- a letter names the line's
+    group, `.` leaves the line alone, a shorter string leaves the later lines alone -- one for every row or a list with one string
+    or None per row.  rhyme_classes (required with a scheme) is a list of pairwise disjoint, non-empty sets of content ids below V:
+    the ids that have a rhyme, by rhyme.  The first line of a group of two or more is its leader and gets the union of the classes
+    as a static end set (intersected with its line_end_ids set, which must leave an id), so it is not empty (hi >= 1); the others
+    are followers: they end in the class of the id their leader ended on in that row (include/mmtg_hip.h), with rhyme_distinct not
+    on an id an earlier line of the group ended on.  A follower takes no line_end_ids set of its own, needs hi >= 1, and a template
+    that fixes its last possible column (hi == k) must leave every class possible there: no given id, and a class symbol that
+    meets every rhyme class (with rhyme_distinct in as many ids as the group has lines up to this one).  With rhyme_distinct every
+    class has at least as many ids as the largest group has lines; rhyme_distinct without a scheme raises.  A group of one line is
+    unconstrained.
+    Raises ValueError for bounds outside 0 .. sent - 2, lo > hi, more entries than lines, and any end set, template or scheme that
+    breaks the above."""
+    if (rhyme_scheme is None) != (rhyme_classes is None):
+        raise ValueError("rhyme_scheme and rhyme_classes come together (got %s alone)"
+                         % ("rhyme_scheme" if rhyme_classes is None else "rhyme_classes"))
+    if rhyme_distinct and rhyme_scheme is None:
+        raise ValueError("rhyme_distinct without a rhyme_scheme")
+    if line_lengths is None and line_end_ids is None and templates is None and rhyme_scheme is None:
+        return None
+    if length < 1 or not 3 <= sent <= 257:
+        raise ValueError("line constraints need length >= 1 and 3 <= sent <= 257 (got length %d, sent %d)" % (length, sent))
+    t = _Draft(rows, length, sent, V, templates is not None)
+    lens = _per_row(line_lengths, rows, "line_lengths", lambda e: _is_int(e) or (isinstance(e, tuple) and len(e) == 2),
+                    lambda s: any(isinstance(e, list) for e in s))
+    ends = _per_row(line_end_ids, rows, "line_end_ids", lambda e: isinstance(e, (set, frozenset)),
+                    lambda s: any(isinstance(e, (list, tuple)) and not _is_ids(e) for e in s))
+    tmpls = _template_rows(templates, rows)
+    schemes = None
+    if rhyme_scheme is not None:
+        schemes, t.classes, t.distinct = _scheme_rows(rhyme_scheme, rows), _rhyme_classes(rhyme_classes, V), bool(rhyme_distinct)
+        if t.n_lines > 128:
+            raise ValueError("rhyme_scheme: a generation of %d lines (a scheme serves up to 128)" % t.n_lines)
+        t.rhymed = frozenset().union(*t.classes)
+        t.lead = np.full((rows, t.n_lines), -1, np.int8)
+    for b in range(rows):                                        # row by row, so the sets keep the order they arise in
+        _line_bounds(t, b, lens[b])
+        _line_ends(t, b, ends[b])
+        if schemes is not None:
+            _rhyme_scheme(t, b, schemes[b])
+        _sets_need_room(t, b)
+        _line_templates(t, b, tmpls[b])
+        if prefix is not None:
+            _prefix_line(t, b, prefix[b])
+    return _pack(t)
+
+
+class Constraints:
+    """The checked constraints of a generation's rows: ngram (the n-gram size), prefix (check_prefix's lists, or None) and lines
+    (LineTables, or None).  take(idx) / repeat(k) are LineTables' own, on the prefix and the tables together."""
+
+    def __init__(self, ngram, prefix, lines):
+        self.ngram, self.prefix, self.lines = ngram, prefix, lines
+
+    def take(self, idx):
+        return Constraints(self.ngram, None if self.prefix is None else [self.prefix[i] for i in idx],
+                           None if self.lines is None else self.lines.take(idx))
+
+    def repeat(self, k):
+        return Constraints(self.ngram, None if self.prefix is None else [p for p in self.prefix for _ in range(k)],
+                           None if self.lines is None else self.lines.repeat(k))
+
+
+def _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, rows, length, sh, what, templates=None,
+                       rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False):
+    """The constraint arguments of ``begin`` for `rows` rows (`what` names them in messages), checked, as Constraints.  A LineTables
+    given as line_lengths is taken as checked."""
+    sent = sh.msl + 2
+    ngram = check_ngram(no_repeat_ngram_size, sent)
+    pre = None if prefix is None else check_prefix(prefix, rows, length, sent=sent, V=sh.V)
+    if not isinstance(line_lengths, LineTables):
+        line_lengths = check_lines(line_lengths, line_end_ids, rows, length, sent=sent, V=min(sh.V, 13317), prefix=pre, templates=templates,
+                                   rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct)
+    elif (line_lengths.rows != rows or line_end_ids is not None or templates is not None or rhyme_scheme is not None
+            or rhyme_classes is not None or rhyme_distinct):
+        raise ValueError("line tables of %d rows for %s (and no line_end_ids / templates / rhyme_scheme beside them)"
+                         % (line_lengths.rows, what))
+    return Constraints(ngram, pre, line_lengths)

@@ -13,485 +13,16 @@ only because it never batches; identical at batch 1).
 """
 from __future__ import annotations
 
-import math
 import os
 
 import numpy as np
 import torch
 
 from . import hip
-
+from .constraints import (BANNED, LineTables, _check_constraints, check_groups, check_lines, check_ngram, check_prefix,  # noqa: F401
+                          chosen_mask, sequence_scores)         # (the host-side checks keep their names here)
 
 _PLACEMENT = {}
-
-BANNED = (1, 2, 100, 102)           # never a content id: [#START#] [#EOS#] [UNK] [SEP] (src/generate.py:135)
-
-
-def check_prefix(prefix, rows, length, sent=22, V=None):
-    """Validate a prefixed generation's opening lyric ids on the host, before any device work; returns one list of ids per row.
-
-    prefix: a [rows, Lmax] integer tensor / array padded with -1, or a list of `rows` id lists.  Row b's prefix p (L >= 1 ids) is
-    lyric columns 0 .. L - 1 in the slot layout of the training data (data.MyDataset): column c holds [#START#] (1) where
-    c % sent == 0, [#EOS#] (2) where c % sent == sent - 1, and a content id or PAD (0) elsewhere -- never one of the banned ids
-    1, 2, 100, 102.  So p is whole lines (L % sent == 1: it ends on the next line's [#START#]) or whole lines plus a partial line.
-    L <= length + 1: the output has 1 + length columns."""
-    if isinstance(prefix, (list, tuple)):
-        ids = [[int(v) for v in np.asarray(r).reshape(-1).tolist()] for r in prefix]
-    else:
-        a = prefix.detach().cpu().numpy() if torch.is_tensor(prefix) else np.asarray(prefix)
-        if a.ndim != 2:
-            raise ValueError("prefix must be a [rows, Lmax] array padded with -1 or a list of id lists (got shape %s)" % (a.shape,))
-        ids = []
-        for r in a.tolist():
-            n = r.index(-1) if -1 in r else len(r)
-            if any(v != -1 for v in r[n:]):
-                raise ValueError("prefix row %d: ids after the -1 padding" % len(ids))
-            ids.append([int(v) for v in r[:n]])
-    if len(ids) != rows:
-        raise ValueError("prefix has %d rows, the generation %d" % (len(ids), rows))
-    for b, p in enumerate(ids):
-        if not p:
-            raise ValueError("prefix row %d is empty (it starts with [#START#])" % b)
-        if len(p) > length + 1:
-            raise ValueError("prefix row %d has %d ids, more than length + 1 = %d" % (b, len(p), length + 1))
-        for c, v in enumerate(p):
-            if c % sent == 0 and v != 1:
-                raise ValueError("prefix row %d, column %d: [#START#] (1) expected, got %d" % (b, c, v))
-            if c % sent == sent - 1 and v != 2:
-                raise ValueError("prefix row %d, column %d: [#EOS#] (2) expected, got %d" % (b, c, v))
-            if 0 < c % sent < sent - 1 and (v in BANNED or v < 0 or (V is not None and v >= V)):
-                raise ValueError("prefix row %d, column %d: id %d is not a content id or PAD" % (b, c, v))
-    return ids
-
-
-def check_ngram(n, sent=22):
-    """Validate no_repeat_ngram_size on the host, before any device work; returns it as an int.  0 is off; 1 .. sent - 2 blocks
-    every content n-gram a row already holds (include/mmtg_hip.h states the rule; a longer n-gram can never be all content).
-    Bools and non-integers raise ValueError, as do values out of range."""
-    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)):
-        raise ValueError("no_repeat_ngram_size must be an integer, got %r" % (n,))
-    n = int(n)
-    if not 0 <= n <= sent - 2:
-        raise ValueError("no_repeat_ngram_size %d outside 0..%d (sent - 2)" % (n, sent - 2))
-    return n
-
-
-def check_groups(num_beams, num_beam_groups=1, diversity_penalty=0.0):
-    """The beam groups of a diverse beam search: (G, penalty) for `num_beams` beams.  1 <= G <= num_beams and G divides num_beams;
-    the penalty is finite and >= 0, and 0 unless G > 1 (a penalty on one group would do nothing: that is a mistake, not a setting)."""
-    nb = int(num_beams)
-    if not _is_int(num_beam_groups):
-        raise ValueError("num_beam_groups must be an integer, got %r" % (num_beam_groups,))
-    G = int(num_beam_groups)
-    if not 1 <= G <= nb or nb % G:
-        raise ValueError("num_beam_groups %d must be in 1..%d and divide num_beams %d" % (G, nb, nb))
-    lam = float(diversity_penalty)
-    if not (math.isfinite(lam) and lam >= 0.0):
-        raise ValueError("diversity_penalty must be finite and >= 0, got %r" % (diversity_penalty,))
-    if G == 1 and lam != 0.0:
-        raise ValueError("diversity_penalty %r needs num_beam_groups > 1 (one group has no earlier group to differ from)" % (diversity_penalty,))
-    return G, lam
-
-
-def chosen_mask(ids, sent=22, prefix_lens=None):
-    """Which columns of generated lyric ids count towards a row's score: bool [B, 1 + length], host only.  Column j >= 1 of row b
-    counts iff it is not a cadence column (j % sent not in {0, sent - 1}: the forced [#START#] / [#EOS#]), it lies past the row's
-    prefix (j >= prefix_lens[b]; None: no prefix) and the previous column is not PAD (ids[b][j - 1] != 0) -- so the first PAD of a
-    line counts (the model ended the line there; in an empty line that is its first content column) and the sticky PADs behind
-    it, which no model call decided, do not.
-    Columns that a constraint decided (a template's given id, a full line's PAD) count: their value is the model's log-probability
-    of that id.  Samples of one prompt share their constraints, so ranking among them is fair."""
-    a = np.asarray(ids.detach().cpu().numpy() if torch.is_tensor(ids) else ids)
-    if a.ndim != 2:
-        raise ValueError("ids must be [rows, 1 + length] (got shape %s)" % (a.shape,))
-    B, n = a.shape
-    pl = np.zeros(B, np.int64) if prefix_lens is None else np.asarray(prefix_lens, np.int64).reshape(-1)
-    if pl.shape[0] != B:
-        raise ValueError("prefix_lens has %d rows, ids %d" % (pl.shape[0], B))
-    j = np.arange(n)
-    mask = np.zeros((B, n), bool)
-    mask[:, 1:] = a[:, :-1] != 0
-    mask &= ((j >= 1) & (j % sent != 0) & (j % sent != sent - 1))[None, :]
-    mask &= j[None, :] >= pl[:, None]
-    return mask
-
-
-def sequence_scores(ids, logprobs, sent=22, prefix_lens=None, upto=None):
-    """(sum float64 [B], count int64 [B]) of the token log-probabilities over chosen_mask's columns below `upto` (None: all; for
-    the text generate_samples returns, 1 + the last iteration that called the model: GreedyDecoder.reference_return).  Host only."""
-    mask = chosen_mask(ids, sent=sent, prefix_lens=prefix_lens)
-    lp = np.asarray(logprobs.detach().cpu().numpy() if torch.is_tensor(logprobs) else logprobs, np.float64)
-    if lp.shape != mask.shape:
-        raise ValueError("logprobs of shape %s for ids of shape %s" % (lp.shape, mask.shape))
-    if upto is not None:
-        mask[:, max(int(upto), 0):] = False
-    return np.where(mask, lp, 0.0).sum(1), mask.sum(1).astype(np.int64)
-
-
-class LineTables:
-    """The packed line constraints check_lines returns: lo, hi uint8 [rows, n_lines]; set_of int16 [rows, n_lines] (-1: no end set)
-    and sets uint32 [n_sets, ceil(V / 32)] (bit v & 31 of word v >> 5: id v is a member), or both None when no line has a set.
-    tmpl (templates= only, else None): int32 [rows, n_lines, sent - 2], one symbol per content column -- v >= 0 a given id, -1 free,
-    v <= -2 the class `sets[-2 - v]` (classes and end sets share the table); a template's length is folded into lo / hi.
-    class_of, lead, distinct (rhyme_scheme= only, else None, None, False): class_of int16 [V], the row of `sets` that is id v's rhyme
-    class or -1; lead int8 [rows, n_lines], the leader's line of a follower line or -1; a leader's static end set (the union of the
-    classes) is folded into set_of."""
-
-    def __init__(self, lo, hi, set_of, sets, sent, V, tmpl=None, class_of=None, lead=None, distinct=False):
-        self.lo, self.hi, self.set_of, self.sets, self.sent, self.V, self.tmpl = lo, hi, set_of, sets, sent, V, tmpl
-        self.class_of, self.lead, self.distinct = class_of, lead, bool(distinct)
-
-    @property
-    def rows(self):
-        return self.lo.shape[0]
-
-    def repeat(self, k):
-        """Every row k times in place of itself (the beams of a prompt share its constraints)."""
-        rep = lambda a: None if a is None else np.repeat(a, k, axis=0)      # noqa: E731
-        return LineTables(rep(self.lo), rep(self.hi), rep(self.set_of), self.sets, self.sent, self.V, rep(self.tmpl),
-                          self.class_of, rep(self.lead), self.distinct)
-
-    def take(self, idx):
-        """Rows idx (a list of row indices) as tables of their own; the sets are shared."""
-        sub = lambda a: None if a is None else np.ascontiguousarray(a[idx])      # noqa: E731
-        return LineTables(sub(self.lo), sub(self.hi), sub(self.set_of), self.sets, self.sent, self.V, sub(self.tmpl),
-                          self.class_of, sub(self.lead), self.distinct)
-
-    def leader(self, b, l):
-        """The line whose ending decides the rhyme of row b's line l (l is a follower), or None."""
-        if self.lead is None or l >= self.lead.shape[1] or self.lead[b, l] < 0:
-            return None
-        return int(self.lead[b, l])
-
-    def rhyme_class(self, v):
-        """The rhyme class of id v as a frozenset, or None (no scheme, or v has no rhyme)."""
-        if self.class_of is None or not 0 <= v < len(self.class_of) or self.class_of[v] < 0:
-            return None
-        return self.members(int(self.class_of[v]))
-
-    def symbol(self, b, l, c):
-        """What row b's template says of content column c of line l: an int (a given id), a frozenset (a class) or None (free, no
-        template, or a column / line past it)."""
-        if self.tmpl is None or l >= self.tmpl.shape[1] or not 0 <= c < self.tmpl.shape[2]:
-            return None
-        v = int(self.tmpl[b, l, c])
-        return v if v >= 0 else None if v == -1 else self.members(-2 - v)
-
-    def bounds(self, b, l):
-        """(lo, hi, end set as a frozenset or None) of row b's line l; a line past the table is unconstrained."""
-        if l >= self.lo.shape[1]:
-            return 0, self.sent - 2, None
-        s = -1 if self.set_of is None else int(self.set_of[b, l])
-        return int(self.lo[b, l]), int(self.hi[b, l]), self.members(s) if s >= 0 else None
-
-    def members(self, s):
-        """Set s of the table as a frozenset of ids."""
-        cache = self.__dict__.setdefault("_members", {})
-        if s not in cache:
-            w = self.sets[s]
-            cache[s] = frozenset(v for v in range(32 * len(w)) if (int(w[v >> 5]) >> (v & 31)) & 1)
-        return cache[s]
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-
-
-def _is_ids(e):
-    return isinstance(e, (set, frozenset)) or (isinstance(e, (list, tuple, np.ndarray)) and all(_is_int(v) for v in e))
-
-
-def _per_row(spec, rows, what, whole, per_row_form):
-    """spec as one list of per-line entries per row (or the marker ("all", entry): that entry on every line).  spec is None (no
-    entries), one entry for every line (`whole(spec)`), one list for all rows, or one list, entry or None per row
-    (`per_row_form(spec)`)."""
-    if spec is None:
-        return [[] for _ in range(rows)]
-    if whole(spec):
-        return [("all", spec)] * rows
-    if not isinstance(spec, (list, tuple)):
-        raise ValueError("%s: a list of per-line entries (or one list per row) expected, got %r" % (what, spec))
-    if per_row_form(spec):
-        if len(spec) != rows:
-            raise ValueError("%s has %d rows, the generation %d" % (what, len(spec), rows))
-        out = []
-        for r in spec:
-            if r is not None and not whole(r) and not isinstance(r, (list, tuple)):
-                raise ValueError("%s: a row is None, one entry or a list of per-line entries, got %r" % (what, r))
-            out.append([] if r is None else ("all", r) if whole(r) else list(r))
-        return out
-    return [list(spec)] * rows
-
-
-def _template_rows(spec, rows):
-    """templates as one list of per-line entries per row: one list for all rows, or (a list among the entries marks it) one list or
-    None per row."""
-    if spec is None:
-        return [[] for _ in range(rows)]
-    if not isinstance(spec, list):
-        raise ValueError("templates: a list of per-line templates (or one such list per row) expected, got %r" % (spec,))
-    if any(isinstance(e, list) for e in spec):
-        if len(spec) != rows:
-            raise ValueError("templates has %d rows, the generation %d" % (len(spec), rows))
-        for b, r in enumerate(spec):
-            if r is not None and not isinstance(r, list):
-                raise ValueError("templates row %d: a list of per-line templates or None expected, got %r" % (b, r))
-        return [[] if r is None else r for r in spec]
-    return [spec] * rows
-
-
-def _content_id(v, V):
-    return not (v == 0 or v in BANNED or v < 0 or (V is not None and v >= V))
-
-
-def _scheme_rows(spec, rows):
-    """rhyme_scheme as one string (or None) per row: one string for all rows, or a list with one string or None per row."""
-    if isinstance(spec, str):
-        spec = [spec] * rows
-    elif not isinstance(spec, (list, tuple)) or not all(r is None or isinstance(r, str) for r in spec):
-        raise ValueError("rhyme_scheme: a string (or a list with one string or None per row) expected, got %r" % (spec,))
-    if len(spec) != rows:
-        raise ValueError("rhyme_scheme has %d rows, the generation %d" % (len(spec), rows))
-    return ["" if r is None else r for r in spec]
-
-
-def _rhyme_classes(classes, V):
-    """rhyme_classes as a list of frozensets: pairwise disjoint, non-empty sets of content ids below V."""
-    if not isinstance(classes, (list, tuple)) or not classes:
-        raise ValueError("rhyme_classes: a non-empty list of id sets expected, got %r" % (classes,))
-    out, owner = [], {}
-    for i, e in enumerate(classes):
-        if not _is_ids(e) or (isinstance(e, np.ndarray) and e.ndim != 1) or not all(_is_int(v) for v in e):
-            raise ValueError("rhyme_classes, class %d: a collection of ids expected, got %r" % (i, e))
-        ids = frozenset(int(v) for v in e)
-        if not ids:
-            raise ValueError("rhyme_classes, class %d: the class is empty" % i)
-        for v in sorted(ids):
-            if not _content_id(v, V):
-                raise ValueError("rhyme_classes, class %d: id %d is not a content id below the vocabulary cut" % (i, v))
-            if v in owner:
-                raise ValueError("rhyme_classes: id %d is in classes %d and %d (the classes are disjoint)" % (v, owner[v], i))
-            owner[v] = i
-        out.append(ids)
-    return out
-
-
-def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefix=None, templates=None, rhyme_scheme=None,
-                rhyme_classes=None, rhyme_distinct=False):
-    """Validate line-length bounds and line-end id sets on the host, before any device work; returns the packed LineTables, or
-    None when both arguments are None (no constraints: the decoders then run the launches of a generation without them).
-
-    A generation of `length` holds n_lines = (length - 1) // sent + 1 lines (those with a content column); line l of row b is
-    lyric columns l * sent .. l * sent + sent - 1 and holds up to sent - 2 content tokens.
-    line_lengths: a line's entry is an int (exactly that many content tokens), a (lo, hi) tuple or None (unconstrained, the
-    same as (0, sent - 2)).  Given as one entry (every line of every row), one list of entries (line by line, for every row; a
-    shorter list leaves the later lines unconstrained) or a list with one such list, entry or None per row (the lists, not tuples,
-    mark this form).
-    line_end_ids: a line's entry is None or a non-empty collection of content ids below the vocabulary cut V (no PAD, none of
-    1, 2, 100, 102): the line's last content token is one of them, so the line is not empty and its hi must be >= 1.  Given as
-    one set / frozenset (every line), one list of entries, or one list of entries (or None) per row.
-    prefix (check_prefix's result, optional): a row whose prefix stops inside a line continues that line under its bounds; given
-    content beyond the line's hi raises.  Whole given lines are the caller's text and are not checked.
-    templates: a line's entry is None or a tuple of k symbols (1 <= k <= sent - 2), one per content column from column 0 -- an int
-    (given: the row writes this content id), None (free) or a set / frozenset of content ids (a class: the column's id is a
-    member) -- optionally ending in `...` (Ellipsis: an open template).  A closed template fixes the line's length, its bounds
-    become (k, k) and k must lie inside the line's line_lengths bounds; an open one makes lo = max(lo, k) and needs hi >= k.  Given
-    as one list of entries (for every row; a shorter list leaves the later lines without a template) or a list with one such list
-    or None per row.  Given ids and class members are content ids below V; on a line with an end set whose length the template
-    fixes (hi == k) the last symbol must leave a member of the set possible.  A partial prefix line must agree with its line's
-    template.  So a column that only classes and end sets constrain always has a live id; only n-gram bans can empty one.
-    rhyme_scheme / rhyme_classes / rhyme_distinct: a scheme is a string with one symbol per line -- a letter names the line's
-    group, `.` leaves the line alone, a shorter string leaves the later lines alone -- one for every row or a list with one string
-    or None per row.  rhyme_classes (required with a scheme) is a list of pairwise disjoint, non-empty sets of content ids below V:
-    the ids that have a rhyme, by rhyme.  The first line of a group of two or more is its leader and gets the union of the classes
-    as a static end set (intersected with its line_end_ids set, which must leave an id), so it is not empty (hi >= 1); the others
-    are followers: they end in the class of the id their leader ended on in that row (include/mmtg_hip.h), with rhyme_distinct not
-    on an id an earlier line of the group ended on.  A follower takes no line_end_ids set of its own, needs hi >= 1, and a template
-    that fixes its last possible column (hi == k) must leave every class possible there: no given id, and a class symbol that
-    meets every rhyme class (with rhyme_distinct in as many ids as the group has lines up to this one).  With rhyme_distinct every
-    class has at least as many ids as the largest group has lines; rhyme_distinct without a scheme raises.  A group of one line is
-    unconstrained.
-    Raises ValueError for bounds outside 0 .. sent - 2, lo > hi, more entries than lines, and any end set, template or scheme that
-    breaks the above."""
-    if (rhyme_scheme is None) != (rhyme_classes is None):
-        raise ValueError("rhyme_scheme and rhyme_classes come together (got %s alone)"
-                         % ("rhyme_scheme" if rhyme_classes is None else "rhyme_classes"))
-    if rhyme_distinct and rhyme_scheme is None:
-        raise ValueError("rhyme_distinct without a rhyme_scheme")
-    if line_lengths is None and line_end_ids is None and templates is None and rhyme_scheme is None:
-        return None
-    if length < 1 or not 3 <= sent <= 257:
-        raise ValueError("line constraints need length >= 1 and 3 <= sent <= 257 (got length %d, sent %d)" % (length, sent))
-    n_lines, cap = (length - 1) // sent + 1, sent - 2
-    is_len = lambda e: _is_int(e) or (isinstance(e, tuple) and len(e) == 2)                     # noqa: E731
-    lens = _per_row(line_lengths, rows, "line_lengths", is_len,
-                    lambda s: any(isinstance(e, list) for e in s))
-    ends = _per_row(line_end_ids, rows, "line_end_ids", lambda e: isinstance(e, (set, frozenset)),
-                    lambda s: any(isinstance(e, (list, tuple)) and not _is_ids(e) for e in s))
-    lo = np.zeros((rows, n_lines), np.uint8)
-    hi = np.full((rows, n_lines), cap, np.uint8)
-    set_of = np.full((rows, n_lines), -1, np.int16)
-    tmpls = _template_rows(templates, rows)
-    tmpl = None if templates is None else np.full((rows, n_lines, cap), -1, np.int32)
-    table, seen = [], {}
-    schemes = lead = classes = rhymed = None
-    if rhyme_scheme is not None:
-        schemes, classes = _scheme_rows(rhyme_scheme, rows), _rhyme_classes(rhyme_classes, V)
-        if n_lines > 128:
-            raise ValueError("rhyme_scheme: a generation of %d lines (a scheme serves up to 128)" % n_lines)
-        rhymed = frozenset().union(*classes)
-        lead = np.full((rows, n_lines), -1, np.int8)
-    place = {}                                               # (row, follower line) -> how many lines of its group lie before it
-
-    def set_index(ids):
-        if ids not in seen:
-            seen[ids] = len(table)
-            table.append(ids)
-        if seen[ids] > 32767:
-            raise ValueError("line_end_ids / templates: more than 32768 distinct id sets")
-        return seen[ids]
-    for b in range(rows):
-        for what, spec in (("line_lengths", lens[b]), ("line_end_ids", ends[b])):
-            if isinstance(spec, tuple) and spec and spec[0] == "all":
-                spec = [spec[1]] * n_lines
-            if len(spec) > n_lines:
-                raise ValueError("%s row %d has %d lines, a generation of length %d holds %d" % (what, b, len(spec), length, n_lines))
-            for l, e in enumerate(spec):
-                if e is None:
-                    continue
-                if what == "line_lengths":
-                    pair = (e, e) if _is_int(e) else e
-                    if not (isinstance(pair, tuple) and len(pair) == 2 and all(_is_int(v) for v in pair)):
-                        raise ValueError("line_lengths row %d, line %d: an int, a (lo, hi) tuple or None expected, got %r" % (b, l, e))
-                    a, z = int(pair[0]), int(pair[1])
-                    if not 0 <= a <= z <= cap:
-                        raise ValueError("line_lengths row %d, line %d: (%d, %d) is not 0 <= lo <= hi <= %d (sent - 2)" % (b, l, a, z, cap))
-                    lo[b, l], hi[b, l] = a, z
-                else:
-                    if not _is_ids(e) or (isinstance(e, np.ndarray) and e.ndim != 1) or not all(_is_int(v) for v in e):
-                        raise ValueError("line_end_ids row %d, line %d: a collection of ids or None expected, got %r" % (b, l, e))
-                    ids = frozenset(int(v) for v in e)
-                    if not ids:
-                        raise ValueError("line_end_ids row %d, line %d: the end set is empty" % (b, l))
-                    for v in sorted(ids):
-                        if v == 0 or v in BANNED or v < 0 or (V is not None and v >= V):
-                            raise ValueError("line_end_ids row %d, line %d: id %d is not a content id below the vocabulary cut" % (b, l, v))
-                    set_of[b, l] = set_index(ids)
-        if schemes is not None:
-            sch = schemes[b]
-            if not all(ch == "." or ch.isalpha() for ch in sch):
-                raise ValueError("rhyme_scheme row %d: %r holds symbols other than letters and '.'" % (b, sch))
-            if len(sch) > n_lines:
-                raise ValueError("rhyme_scheme row %d has %d lines, a generation of length %d holds %d" % (b, len(sch), length, n_lines))
-            groups = {}
-            for l, ch in enumerate(sch):
-                if ch != ".":
-                    groups.setdefault(ch, []).append(l)
-            for ch, ls in groups.items():
-                if len(ls) < 2:
-                    continue                                     # a group of one line is unconstrained
-                if rhyme_distinct and min(len(k) for k in classes) < len(ls):
-                    raise ValueError("rhyme_scheme row %d: rhyme_distinct and group %r of %d lines, but a rhyme class of %d ids"
-                                     % (b, ch, len(ls), min(len(k) for k in classes)))
-                for i, l in enumerate(ls):
-                    if hi[b, l] == 0:
-                        raise ValueError("rhyme_scheme row %d, line %d: a rhyming line with hi = 0" % (b, l))
-                    if i == 0:                                   # the leader: a static end set, the ids that have a rhyme
-                        ids = rhymed if set_of[b, l] < 0 else rhymed & table[set_of[b, l]]
-                        if not ids:
-                            raise ValueError("rhyme_scheme row %d, line %d: no id of the line's end set has a rhyme class" % (b, l))
-                        set_of[b, l] = set_index(ids)
-                    else:
-                        if set_of[b, l] >= 0:
-                            raise ValueError("rhyme_scheme row %d, line %d: a follower line takes no line_end_ids set of its own" % (b, l))
-                        lead[b, l] = ls[0]
-                        place[b, l] = i
-        for l in range(n_lines):
-            if set_of[b, l] >= 0 and hi[b, l] == 0:
-                raise ValueError("line_end_ids row %d, line %d: an end set on a line with hi = 0" % (b, l))
-        if len(tmpls[b]) > n_lines:
-            raise ValueError("templates row %d has %d lines, a generation of length %d holds %d" % (b, len(tmpls[b]), length, n_lines))
-        for l, e in enumerate(tmpls[b]):
-            if e is None:
-                continue
-            at = "templates row %d, line %d" % (b, l)
-            if not isinstance(e, tuple):
-                raise ValueError("%s: a tuple of symbols or None expected, got %r" % (at, e))
-            open_ = len(e) > 0 and e[-1] is Ellipsis
-            syms = e[:-1] if open_ else e
-            k = len(syms)
-            if not 1 <= k <= cap:
-                raise ValueError("%s: %d symbols, not 1 .. %d (sent - 2)" % (at, k, cap))
-            for c, y in enumerate(syms):
-                if y is None:
-                    continue
-                if _is_int(y):
-                    if not _content_id(int(y), V):
-                        raise ValueError("%s, column %d: id %d is not a content id below the vocabulary cut" % (at, c, int(y)))
-                    tmpl[b, l, c] = int(y)
-                elif isinstance(y, (set, frozenset)) and all(_is_int(v) for v in y):
-                    ids = frozenset(int(v) for v in y)
-                    if not ids:
-                        raise ValueError("%s, column %d: the class is empty" % (at, c))
-                    for v in sorted(ids):
-                        if not _content_id(v, V):
-                            raise ValueError("%s, column %d: id %d is not a content id below the vocabulary cut" % (at, c, v))
-                    tmpl[b, l, c] = -2 - set_index(ids)
-                else:
-                    raise ValueError("%s, column %d: an int, None or a set of ids expected, got %r" % (at, c, y))
-            a, z = int(lo[b, l]), int(hi[b, l])
-            if open_:
-                if z < k:
-                    raise ValueError("%s: an open template of %d symbols on a line with hi = %d" % (at, k, z))
-                lo[b, l] = max(a, k)
-            else:
-                if not a <= k <= z:
-                    raise ValueError("%s: a closed template of %d symbols outside the line's bounds (%d, %d)" % (at, k, a, z))
-                lo[b, l] = hi[b, l] = k
-            if set_of[b, l] >= 0 and hi[b, l] == k:              # the template's last column is the line's last: the end set's
-                members, y = table[set_of[b, l]], syms[-1]
-                if _is_int(y) and int(y) not in members:
-                    raise ValueError("%s: the line ends on the given id %d, which is not in its end set" % (at, int(y)))
-                if isinstance(y, (set, frozenset)) and not members & frozenset(int(v) for v in y):
-                    raise ValueError("%s: the last column's class and the line's end set share no id" % at)
-            if (b, l) in place and hi[b, l] == k:                # a follower whose last possible column the template fixes
-                y = syms[-1]
-                if _is_int(y):
-                    raise ValueError("%s: a follower line of the rhyme scheme ends on the given id %d" % (at, int(y)))
-                if isinstance(y, (set, frozenset)):
-                    need = place[b, l] + 1 if rhyme_distinct else 1
-                    if any(len(kls & frozenset(int(v) for v in y)) < need for kls in classes):
-                        raise ValueError("%s: the last column's class leaves a rhyme class with fewer than %d ids on a follower line"
-                                         % (at, need))
-        if prefix is not None:
-            p = prefix[b]
-            l, q = (len(p) - 1) // sent, (len(p) - 1) % sent
-            if 1 <= q <= cap and l < n_lines and tmpl is not None:   # the given columns of line l against its template
-                for c in range(min(q, cap)):
-                    v, y = int(p[l * sent + 1 + c]), int(tmpl[b, l, c])
-                    if y >= 0 and v != y:
-                        raise ValueError("prefix row %d gives id %d at column %d of line %d, its template %d" % (b, v, c, l, y))
-                    if y <= -2 and v not in table[-2 - y]:
-                        raise ValueError("prefix row %d gives id %d at column %d of line %d, outside its template's class" % (b, v, c, l))
-            if 1 <= q <= cap and l < n_lines:                        # the prefix stops inside line l: q content columns are given
-                given = sum(1 for v in p[l * sent + 1:] if v != 0)
-                if given > hi[b, l]:
-                    raise ValueError("prefix row %d gives %d content tokens of line %d, more than its hi = %d" % (b, given, l, hi[b, l]))
-    rows_of = None if classes is None else [set_index(k) for k in classes]
-    sets = None
-    if table:
-        if V is None:
-            V = max(max(t) for t in table) + 1
-        sets = np.zeros((len(table), (V + 31) // 32), np.uint32)
-        for i, t in enumerate(table):
-            for v in t:
-                sets[i, v >> 5] |= np.uint32(1 << (v & 31))
-    class_of = None
-    if classes is not None:
-        class_of = np.full(V, -1, np.int16)
-        for i, k in zip(rows_of, classes):
-            class_of[sorted(k)] = i
-    return LineTables(lo, hi, set_of if table else None, sets, sent, V, tmpl, class_of, lead, rhyme_distinct and lead is not None)
 
 
 def select_forms(with_head, prefix, ngram, lines, templates=False, rhymes=False, groups=False):
@@ -511,22 +42,20 @@ def select_forms(with_head, prefix, ngram, lines, templates=False, rhymes=False,
             "_groups" + held if groups else held)
 
 
-def _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, rows, length, sh, what, templates=None,
-                       rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False):
-    """The constraint arguments of ``begin`` for `rows` rows (`what` names them in messages): (n-gram size, checked prefix or None,
-    LineTables or None).  A LineTables given as line_lengths is taken as checked."""
-    sent = sh.msl + 2
-    ngram = check_ngram(no_repeat_ngram_size, sent)
-    pre = None if prefix is None else check_prefix(prefix, rows, length, sent=sent, V=sh.V)
-    if not isinstance(line_lengths, LineTables):
-        return ngram, pre, check_lines(line_lengths, line_end_ids, rows, length, sent=sent, V=min(sh.V, 13317), prefix=pre,
-                                       templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes,
-                                       rhyme_distinct=rhyme_distinct)
-    if (line_lengths.rows != rows or line_end_ids is not None or templates is not None or rhyme_scheme is not None
-            or rhyme_classes is not None or rhyme_distinct):
-        raise ValueError("line tables of %d rows for %s (and no line_end_ids / templates / rhyme_scheme beside them)"
-                         % (line_lengths.rows, what))
-    return ngram, pre, line_lengths
+def _step_forms(dec, with_head):
+    """select_forms' answer for a step of decoder `dec`, and whether mmtg_decode_logprob follows it: (selection form, merge form,
+    logprob).  A decoder without the newer fields (tmpl, rhyme, groups, return_logprobs) is one whose generation does not use them."""
+    return select_forms(with_head, dec.use_fixed, dec.ngram, dec.lines is not None, templates=getattr(dec, "tmpl", None) is not None,
+                        rhymes=getattr(dec, "rhyme", None) is not None, groups=getattr(dec, "groups", 1) > 1) + (
+        bool(with_head and getattr(dec, "return_logprobs", False)),)
+
+
+def _fill(buf, src, fill, axis):
+    """The host array src into the device buffer buf (allocated once: captured graphs hold its address), which is longer along
+    `axis`; the rest of buf becomes `fill`."""
+    full = np.full(tuple(buf.shape), fill, src.dtype)
+    full[(slice(None),) * axis + (slice(0, src.shape[axis]),)] = src
+    return buf.copy_(torch.from_numpy(full))
 
 
 def _placement_ok(dev):
@@ -609,6 +138,7 @@ class GreedyDecoder:
         #  with the one-slice c_fc + fused GELU: 2,3,1,8 -> 940, 2,3,1,6 -> 943, 1,3,1,8 -> 963, 2,3,1,12 -> 1003)
         #  round 2, 64x64 tiles (graph-replayed per-product times, profiles/r02_decode_gemm_tiles.log): 2,4,1,8)
         self.children, self.side = [], []
+        self.fused = self.mlp = False       # (set below for a decoder that runs the step itself: not the parent of row blocks)
         if lanes > 1:
             self.children = [GreedyDecoder(model, B // lanes, max_len, use_graph=False, _parent=self, _lane=i) for i in range(lanes)]
             self.side = [torch.cuda.Stream(device=dev) for _ in range(lanes - 1)]
@@ -737,7 +267,7 @@ class GreedyDecoder:
         D, H, E = sh.D, sh.H, sh.E
         pre = "decoder.gpt2.transformer."
         sent = sh.msl + 2
-        if getattr(self, "x3", False):
+        if self.x3:
             self._step_x3(with_head)
             self._select(with_head)
             self._logprob(with_head)
@@ -747,7 +277,7 @@ class GreedyDecoder:
                          sh.max_seq_length // sent + 1)
         eng._fwd(self.x, "decoder.projector_layer1.weight", self.h1, B, "linear",
                  bias=eng.P("decoder.projector_layer1.bias"), epi=hip.EPI_TANH)
-        fused = getattr(self, "fused", False)
+        fused = self.fused
         if fused and self.embed_in_proj:
             # projector_layer2 + the GPT-2 input embedding (wpe[pos] + wte[type]) + the first LayerNorm statistics in one launch
             w2 = eng.W("decoder.projector_layer2.weight")
@@ -778,8 +308,7 @@ class GreedyDecoder:
         sh = self.eng.sh
         temperature, rep, top_k, top_p = self.params
         tmpl, rhyme = getattr(self, "tmpl", None), getattr(self, "rhyme", None)
-        form, _ = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=tmpl is not None,
-                               rhymes=rhyme is not None)
+        form = _step_forms(self, with_head)[0]
         logits, ldl, V = (self.logits, self.eng.layout.Vpad, min(sh.V, 13317)) if with_head else (None, 0, 0)
         # stochastic: the draw of each position reads its row of the pre-filled uniforms
         sampling = (top_k, top_p, self.uniforms) if with_head and not (top_k == 1 and top_p == 0.0) else None
@@ -792,7 +321,7 @@ class GreedyDecoder:
         raw logits at the id column pos + 1 now holds (include/mmtg_hip.h, mmtg_decode_logprob).  A node of its own behind the
         selection, on the same stream: it reads self.pos, which the selection leaves alone, and the selection kernels stay what they
         were.  Off, nothing is launched."""
-        if with_head and getattr(self, "return_logprobs", False):
+        if _step_forms(self, with_head)[2]:
             sh = self.eng.sh
             hip.decode_logprob(self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, self.tok_lp, self.B)
 
@@ -802,33 +331,26 @@ class GreedyDecoder:
         sets or None, set_of or None) over all rows, or None without tables."""
         if tables is None:
             return None
-        sh, dev, B = self.eng.sh, self.eng.dev, self.B
-        sent = sh.msl + 2
-        ml = (self.max_len - 1) // sent + 1
+        dev, B, sent = self.eng.dev, self.B, self.eng.sh.msl + 2
         if self._line_buf is None:
+            ml = (self.max_len - 1) // sent + 1
             self._line_buf = [torch.zeros(B, ml, dtype=torch.uint8, device=dev), torch.zeros(B, ml, dtype=torch.uint8, device=dev),
                               torch.zeros(B, ml, dtype=torch.int16, device=dev), None]
         lo, hi, set_of, sets = self._line_buf
-        n = tables.lo.shape[1]
-
-        def padded(a, fill, dtype):
-            full = np.full((B, ml), fill, dtype)
-            full[:, :n] = a
-            return torch.from_numpy(full)
-        lo.copy_(padded(tables.lo, 0, np.uint8))
-        hi.copy_(padded(tables.hi, sent - 2, np.uint8))
-        if tables.sets is not None:
-            need = tables.sets.shape[0]
-            if sets is None or sets.shape[0] < need:
-                cap = 16
-                while cap < need:
-                    cap *= 2
-                sets = self._line_buf[3] = torch.zeros(cap, tables.sets.shape[1], dtype=torch.int32, device=dev)
-                self.graphs = {k: g for k, g in self.graphs.items() if "lines" not in k and "tmpl" not in k and "rhyme" not in k}
-            sets.zero_()
-            sets[:need].copy_(torch.from_numpy(tables.sets.view(np.int32)))
-            set_of.copy_(padded(tables.set_of, -1, np.int16))
-        return (lo, hi, sets, set_of) if tables.sets is not None else (lo, hi, None, None)
+        _fill(lo, tables.lo, 0, 1)
+        _fill(hi, tables.hi, sent - 2, 1)
+        if tables.sets is None:
+            return lo, hi, None, None
+        need = tables.sets.shape[0]
+        if sets is None or sets.shape[0] < need:
+            cap = 16
+            while cap < need:
+                cap *= 2
+            sets = self._line_buf[3] = torch.zeros(cap, tables.sets.shape[1], dtype=torch.int32, device=dev)
+            self.graphs = {k: g for k, g in self.graphs.items() if "lines" not in k and "tmpl" not in k and "rhyme" not in k}
+        _fill(sets, tables.sets.view(np.int32), 0, 0)
+        _fill(set_of, tables.set_of, -1, 1)
+        return lo, hi, sets, set_of
 
     def _upload_templates(self, tables):
         """The symbol table of a templated generation into this decoder's buffer (allocated once: captured graphs hold its address),
@@ -838,10 +360,7 @@ class GreedyDecoder:
         sent = self.eng.sh.msl + 2
         if self._tmpl_buf is None:
             self._tmpl_buf = torch.zeros(self.B, (self.max_len - 1) // sent + 1, sent - 2, dtype=torch.int32, device=self.eng.dev)
-        full = np.full(tuple(self._tmpl_buf.shape), -1, np.int32)
-        full[:, :tables.tmpl.shape[1]] = tables.tmpl
-        self._tmpl_buf.copy_(torch.from_numpy(full))
-        return self._tmpl_buf
+        return _fill(self._tmpl_buf, tables.tmpl, -1, 1)
 
     def _upload_rhyme(self, tables):
         """The rhyme tables of a generation with a scheme into this decoder's buffers (allocated once: captured graphs hold their
@@ -854,12 +373,8 @@ class GreedyDecoder:
             self._rhyme_buf = (torch.zeros(min(self.eng.sh.V, 13317), dtype=torch.int16, device=dev),
                                torch.zeros(self.B, (self.max_len - 1) // sent + 1, dtype=torch.int8, device=dev))
         class_of, lead = self._rhyme_buf
-        full = np.full(tuple(class_of.shape), -1, np.int16)
-        full[:len(tables.class_of)] = tables.class_of[:len(full)]
-        class_of.copy_(torch.from_numpy(full))
-        full = np.full(tuple(lead.shape), -1, np.int8)
-        full[:, :tables.lead.shape[1]] = tables.lead
-        lead.copy_(torch.from_numpy(full))
+        _fill(class_of, tables.class_of[:class_of.shape[0]], -1, 0)
+        _fill(lead, tables.lead, -1, 1)
         return class_of, lead, bool(tables.distinct)
 
     def _step_x3(self, with_head):
@@ -979,7 +494,7 @@ class GreedyDecoder:
         eng, sh = self.eng, self.eng.sh
         D = sh.D
         pre = "decoder.gpt2.transformer."
-        if getattr(self, "x3", False):
+        if self.x3:
             for l in range(sh.L):
                 p = f"{pre}h.{l}."
                 wf, c, b = self.fq[l]
@@ -1018,7 +533,7 @@ class GreedyDecoder:
         nslab = -(-D // kper)
         x, xo = hcur, hnext
         st, sto = self.st
-        mlp = getattr(self, "mlp", False)
+        mlp = self.mlp
         npx = NP            # statistics partials of the block's input rows (the projector's / a mode-2 product's: one per 32 columns)
         for l in range(sh.L):
             p = f"{pre}h.{l}."
@@ -1069,17 +584,15 @@ class GreedyDecoder:
         """What the step's launches depend on: the settings, and the constraints as far as select_forms lets them reach this step
         (a step without the head runs the launches it always ran)."""
         key = (with_head, parity, self.params) + (("prefix",) if self.use_fixed else ()) + (("ngram", self.ngram) if self.ngram else ())
-        rhyme = getattr(self, "rhyme", None)
-        form = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=getattr(self, "tmpl", None) is not None,
-                            rhymes=rhyme is not None)[0]
+        form, merge, logprob = _step_forms(self, with_head)
         if form in ("_lines", "_tmpl"):
             key += (form[1:], "sets" if self.lines[2] is not None else "bounds")
         if form == "_rhyme":                # (what the captured launch holds by value: the template table or none, distinct)
             key += ("rhyme", "sets" if self.lines[2] is not None else "bounds") + (("tmpl",) if getattr(self, "tmpl", None) is not None else ())
-            key += ("distinct",) if rhyme[2] else ()
-        if with_head and getattr(self, "return_logprobs", False):
+            key += ("distinct",) if self.rhyme[2] else ()
+        if logprob:
             key += ("logprob",)
-        if with_head and getattr(self, "groups", 1) > 1:     # (the grouped merge holds both by value)
+        if merge.startswith("_groups"):     # (the grouped merge holds both by value)
             key += (("groups", self.groups, float(self.diversity_penalty)),)
         return key
 
@@ -1093,15 +606,15 @@ class GreedyDecoder:
         return how + (", %d row blocks of %d side by side" % (self.lanes, self.B // self.lanes) if self.lanes > 1 else "")
 
     def kernel_name(self):
-        if getattr(self, "x3", False):
+        if self.x3:
             return ("decode token step (bf16x3): decode_gemm_x3_kernel<64x64> weight streaming over (hi | lo) plane pairs, three bf16 matrix-core "
                     "passes per product (split-K reduced in the kernel, LayerNorm applied algebraically, fp32 residual stream) + decode_attn "
                     "streaming an fp32 KV cache, 5 graph nodes per block")
-        if getattr(self, "fused", False) and getattr(self, "mlp", False):
+        if self.fused and self.mlp:
             return ("decode token step: decode_gemm_kernel<64x64> weight streaming (c_attn LN-fold slabs, attn.c_proj split-K reduced in the "
                     "kernel) + decode_attn KV-cache streaming + decode_mlp_kernel (c_fc -> GELU -> mlp.c_proj in one launch, hidden dimension "
                     "split over the XCDs, %s hand-off), 4 graph nodes per block" % ("L2" if self.mlp_plain else "write-through"))
-        if getattr(self, "fused", False):
+        if self.fused:
             return ("decode token step: decode_gemm_kernel<64x64> weight streaming (split-K reduced in the kernel, LayerNorm applied "
                     "algebraically) + decode_attn KV-cache streaming, 5 graph nodes per block")
         return ("decode token step: split-K gemm_dma_kernel<64x64> weight streaming + decode_attn KV-cache streaming + finish kernels"
@@ -1155,9 +668,9 @@ class GreedyDecoder:
             raise ValueError("decoder was built for batch %d, got %d" % (self.B, B))
         if length > self.max_len:
             raise ValueError("length %d exceeds max_len %d" % (length, self.max_len))
-        ngram, pre, tables = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, B, length, sh,
-                                                "a batch of %d" % B, templates=templates, rhyme_scheme=rhyme_scheme,
-                                                rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct)
+        cons = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, B, length, sh, "a batch of %d" % B,
+                                  templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
+        pre = cons.prefix
         self.params = (float(temperature), float(repitition_penalty), int(top_k), float(top_p))
         if not (int(top_k) == 1 and float(top_p) == 0.0):
             if self.uniforms is None:
@@ -1169,12 +682,12 @@ class GreedyDecoder:
                 if ch.uniforms is None:
                     ch.uniforms = torch.empty_like(blk, memory_format=torch.contiguous_format)
                 ch.uniforms.copy_(blk)
-        if getattr(self, "mlp", False):
+        if self.mlp:
             self.mlp_sync.zero_()           # counters armed, error report cleared (check_mlp_error reads it after the generation)
         eng.invalidate_copies()
         self.eng.refresh_copies()
         for d in ([self] + self.children):          # (a lane has its own folded copies: they are part of its scratch)
-            if getattr(d, "fused", False) or getattr(d, "x3", False):
+            if d.fused or d.x3:
                 d._refresh_folds()
         self.seq.zero_()
         self.seq[:, :sh.P] = batch["topic_ids"].to(eng.dev).long()
@@ -1186,12 +699,10 @@ class GreedyDecoder:
             self.tok_lp.zero_()
         # the generation's constraints, on the decoder and its lanes: a lane's _select reads its own flags, its slice of fixed_end
         # (a view since construction) and its rows of the line tables (the sets are shared)
-        lines = self._upload_lines(tables)
-        tmpl = self._upload_templates(tables)
-        rhyme = self._upload_rhyme(tables)
+        lines, tmpl, rhyme = self._upload_lines(cons.lines), self._upload_templates(cons.lines), self._upload_rhyme(cons.lines)
         for i, d in enumerate([self] + self.children):
             a, z = (0, B) if d is self else ((i - 1) * d.B, i * d.B)
-            d.use_fixed, d.ngram = pre is not None, ngram
+            d.use_fixed, d.ngram = pre is not None, cons.ngram
             d.lines = None if lines is None else tuple(t if t is None or t is lines[2] else t[a:z] for t in lines)
             d.tmpl = None if tmpl is None else tmpl[a:z]
             d.rhyme = None if rhyme is None else (rhyme[0], rhyme[1][a:z], rhyme[2])
@@ -1324,7 +835,7 @@ class GreedyDecoder:
     def check_mlp_error(self):
         """Raise if a mmtg_decode_mlp launch of this generation reported a bounded wait that ran out or a hand-off group split over
         two XCDs (include/mmtg_hip.h): its results are undefined then.  One device read (the ids are read right after anyway)."""
-        if getattr(self, "mlp", False):
+        if self.mlp:
             code = int(self.mlp_sync[65].item())
             if code:
                 raise RuntimeError("mmtg_decode_mlp reported error %d (2: a wait ran into its 4 ms bound -- the 256 workgroups were not "
@@ -1364,7 +875,7 @@ class BeamDecoder(GreedyDecoder):
         super().__init__(model, int(max_prompts) * nb, max_len=max_len, use_graph=use_graph, lanes=1)
         if not self.fast:
             raise ValueError("beam search needs the split decode step (MMTG_DECODE_PLAIN has no table-aware attention)")
-        if not (self.x3 or getattr(self, "fused", False)) and os.environ.get("MMTG_DECODE_ATTN_SPLIT", "1") != "1":
+        if not (self.x3 or self.fused) and os.environ.get("MMTG_DECODE_ATTN_SPLIT", "1") != "1":
             raise ValueError("beam search needs the split attention (MMTG_DECODE_ATTN_SPLIT=0 has no table-aware attention)")
         dev = self.eng.dev
         self.nb, self.n_prompts = nb, int(max_prompts)
@@ -1381,8 +892,7 @@ class BeamDecoder(GreedyDecoder):
         sh = self.eng.sh
         temperature, rep, _, _ = self.params
         tmpl, rhyme = getattr(self, "tmpl", None), getattr(self, "rhyme", None)
-        cand, merge = select_forms(with_head, self.use_fixed, self.ngram, self.lines is not None, templates=tmpl is not None,
-                                   rhymes=rhyme is not None, groups=getattr(self, "groups", 1) > 1)
+        cand, merge, _ = _step_forms(self, with_head)
         fe = self.fixed_end if self.use_fixed else None
         if with_head:
             hip._beam_candidates(cand, self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2, temperature,
@@ -1425,16 +935,11 @@ class BeamDecoder(GreedyDecoder):
         n = batch["img_embs"].shape[0]
         if n != self.n_prompts:
             raise ValueError("decoder was built for %d prompts, got %d" % (self.n_prompts, n))
-        _, prefix, tables = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, n, length, self.eng.sh,
-                                               "%d prompts" % n, templates=templates, rhyme_scheme=rhyme_scheme,
-                                               rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct)
-        if tables is not None:
-            tables = tables.repeat(self.nb)
-        if prefix is not None:
-            prefix = [p for p in prefix for _ in range(self.nb)]
+        cons = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, n, length, self.eng.sh, "%d prompts" % n,
+                                  templates, rhyme_scheme, rhyme_classes, rhyme_distinct).repeat(self.nb)
         rep = {k: (v.repeat_interleave(self.nb, 0) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        n_steps = super().begin(rep, length, temperature, repitition_penalty, 1, 0.0, prefix=prefix,
-                                no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=tables)
+        n_steps = super().begin(rep, length, temperature, repitition_penalty, 1, 0.0, prefix=cons.prefix,
+                                no_repeat_ngram_size=cons.ngram, line_lengths=cons.lines)
         B, dev = self.B, self.eng.dev
         self.rows.copy_(torch.arange(B, dtype=torch.int32, device=dev)[:, None].expand(B, self.Tmax))
         self.groups, self.diversity_penalty = G, lam

@@ -17,10 +17,11 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
+from .constraints import BANNED, Constraints, _check_constraints, check_groups, check_prefix, sequence_scores
+from .decode import BeamDecoder, GreedyDecoder
 from .data import encode_line_end, encode_prefix, encode_rhyme_classes, encode_template  # noqa: F401  (public: the opening lines / the line-end sets / the line templates / the rhyme classes of generate_samples / generate_beams)
 
 SENT_SLOT = 22  # generate.py:118-121
-BANNED = (1, 2, 100, 102)  # [#START#] [#EOS#] [UNK] [SEP] in src/vocab/vocab.txt
 
 
 def top_k_top_p_filtering(logits, top_k=0, top_p=0.0, filter_value=-float("Inf")):
@@ -64,7 +65,6 @@ def _cached_decoder(model, start_input, length):
     sh = m.shapes
     if t.shape[0] != 1 or int(t[0]) != 1 or length < 1 or sh.P + length + 1 > sh.NP:
         return None
-    from .decode import GreedyDecoder
     cache = m.__dict__.setdefault("_sample_decoders", {})
     key = (m._flat.data_ptr(), int(length))
     dec = cache.get(key)
@@ -145,26 +145,23 @@ def postprocess_tokens(preds):
     return text
 
 
-def _prompt_prefixes(prefixes, n_prompts, length, sh):
-    """One validated prefix (a list of lyric ids, e.g. encode_prefix's) per prompt, or None: decode.check_prefix before any device work."""
-    if prefixes is None:
-        return None
-    from .decode import check_prefix
-    return check_prefix(prefixes, n_prompts, length, sent=sh.msl + 2, V=sh.V)
+def _stack_rows(rows):
+    """rows (a list of dataset items, or a dict of stacked arrays) as one tensor per model input, a prompt per row."""
+    keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
+    if isinstance(rows, dict):
+        return {k: torch.as_tensor(np.asarray(rows[k])) for k in keys}
+    return {k: torch.as_tensor(np.stack([np.asarray(r[k]) for r in rows])) for k in keys}
 
 
-def _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre, templates=None, rhyme_scheme=None, rhyme_classes=None,
-                  rhyme_distinct=False):
-    """The packed line constraints, templates and rhyme scheme (decode.check_lines: one per prompt, or one for all), or None;
-    validated before any device work."""
-    from .decode import check_lines
-    return check_lines(line_lengths, line_end_ids, n_prompts, length, sent=sh.msl + 2, V=min(sh.V, 13317), prefix=pre,
-                       templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct)
-
-
-def _chunk_lines(tables, idx):
-    """Rows idx (one prompt index per decoder row) of the prompts' line tables."""
-    return None if tables is None else tables.take(idx)
+def _chunks(stacked, cons, size, dev, copies=1):
+    """The prompts of `stacked`, each `copies` times in a row, cut into decoder batches of exactly `size` rows on `dev`: yields
+    (batch, the rows' Constraints, the number of real rows).  The decoder's batch is fixed, so the last chunk is padded by repeating
+    its first row."""
+    total = stacked["topic_ids"].shape[0] * copies
+    for lo in range(0, total, size):
+        n = min(total, lo + size) - lo
+        idx = [r // copies for r in range(lo, lo + n)] + [lo // copies] * (size - n)
+        yield {k: v[idx].to(dev) for k, v in stacked.items()}, cons.take(idx), n
 
 
 def rank_scored(scored, rank_by):
@@ -205,51 +202,30 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     log-probability of that id; the samples of a prompt share their constraints, so ranking among them is fair.
     rank_by: "sum" or "mean" (sum / max(n_tokens, 1)) orders a prompt's samples best first (stable) and implies return_scores.
     The texts are the strings, from the same `generator` state, of the call without the two arguments."""
-    from .decode import GreedyDecoder, check_ngram, sequence_scores
     if rank_by is not None and rank_by not in ("sum", "mean"):
         raise ValueError('rank_by must be "sum", "mean" or None, got %r' % (rank_by,))
     scoring = bool(return_scores) or rank_by is not None
     eng = model.engine()
     sh = eng.sh
-    ngram = check_ngram(no_repeat_ngram_size, sh.msl + 2)
     length = sh.max_seq_length if length is None else length
     n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
-    pre = _prompt_prefixes(prefixes, n_prompts, length, sh)
-    lines = _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre, templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
-    keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
-    if isinstance(rows, dict):
-        stacked = {k: torch.as_tensor(np.asarray(rows[k])) for k in keys}
-    else:
-        stacked = {k: torch.as_tensor(np.stack([np.asarray(r[k]) for r in rows])) for k in keys}
-    n_prompts = stacked["topic_ids"].shape[0]
-    rep = {k: v.repeat_interleave(n_samples, dim=0) for k, v in stacked.items()}
-    total = n_prompts * n_samples
-    bsz = min(max_batch, total)
+    cons = _check_constraints(prefixes, no_repeat_ngram_size, line_lengths, line_end_ids, n_prompts, length, sh, "%d prompts" % n_prompts,
+                              templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
+    bsz = min(max_batch, n_prompts * n_samples)
     dec = decoder if decoder is not None and decoder.B == bsz else GreedyDecoder(model, max_batch=bsz, max_len=length)
     texts = []
-    for lo in range(0, total, bsz):
-        hi = min(total, lo + bsz)
-        chunk = {k: v[lo:hi] for k, v in rep.items()}
-        if hi - lo < bsz:          # the decoder's batch is fixed: pad the last chunk by repeating its first row
-            pad = bsz - (hi - lo)
-            chunk = {k: torch.cat([v, v[:1].expand(pad, *v.shape[1:])], 0) for k, v in chunk.items()}
-        cpre = None
-        if pre is not None:
-            cpre = [pre[r // n_samples] for r in range(lo, hi)]
-            cpre += [cpre[0]] * (bsz - len(cpre))
-        chunk = {k: v.to(eng.dev) for k, v in chunk.items()}
-        clines = _chunk_lines(lines, [r // n_samples for r in range(lo, hi)] + [lo // n_samples] * (bsz - (hi - lo)))
+    for chunk, c, n in _chunks(_stack_rows(rows), cons, bsz, eng.dev, copies=n_samples):
         ids = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty,
-                           top_k=top_k, top_p=top_p, generator=generator, prefix=cpre, no_repeat_ngram_size=ngram,
-                           line_lengths=clines, **({"return_logprobs": True} if scoring else {}))
+                           top_k=top_k, top_p=top_p, generator=generator, prefix=c.prefix, no_repeat_ngram_size=c.ngram,
+                           line_lengths=c.lines, **({"return_logprobs": True} if scoring else {}))
         if scoring:
             ids, lp = ids[0].cpu().numpy(), ids[1].cpu().numpy()
             upto = len(GreedyDecoder.reference_return(ids[0].tolist(), length, sent=sh.msl + 2))        # 1 + the last model call
-            sums, counts = sequence_scores(ids, lp, sent=sh.msl + 2, prefix_lens=None if cpre is None else [len(p) for p in cpre],
-                                           upto=upto)
+            sums, counts = sequence_scores(ids, lp, sent=sh.msl + 2, upto=upto,
+                                           prefix_lens=None if c.prefix is None else [len(p) for p in c.prefix])
         else:
             ids = ids.cpu().numpy()
-        for r in range(hi - lo):
+        for r in range(n):
             seq = GreedyDecoder.reference_return(ids[r].tolist(), length, sent=sh.msl + 2)
             text = postprocess_tokens(tokenizer.convert_ids_to_tokens(seq))
             texts.append((text, float(sums[r]), int(counts[r])) if scoring else text)
@@ -268,7 +244,6 @@ def score_sequences(model, rows, ids, max_batch=256):
     is `length` token steps per chunk of max_batch rows, not one batched pass: it is built to agree with the generator's numerics
     (the values a generation reported for its own ids come back within rounding), not for bulk evaluation -- that is
     MMTGTrainer.evaluate."""
-    from .decode import GreedyDecoder, check_prefix
     eng = model.engine()
     sh = eng.sh
     n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
@@ -279,27 +254,15 @@ def score_sequences(model, rows, ids, max_batch=256):
     pre = check_prefix(given, n_prompts, length, sent=sh.msl + 2, V=min(sh.V, 13317))
     if any(len(p) != length + 1 for p in pre):
         raise ValueError("ids must cover every row whole (no -1 padding)")
-    keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
-    if isinstance(rows, dict):
-        stacked = {k: torch.as_tensor(np.asarray(rows[k])) for k in keys}
-    else:
-        stacked = {k: torch.as_tensor(np.stack([np.asarray(r[k]) for r in rows])) for k in keys}
     bsz = min(max_batch, n_prompts)
     dec = GreedyDecoder(model, max_batch=bsz, max_len=length)
-    out = np.zeros((n_prompts, 1 + length), np.float32)
-    for lo in range(0, n_prompts, bsz):
-        hi = min(n_prompts, lo + bsz)
-        chunk = {k: v[lo:hi] for k, v in stacked.items()}
-        cpre = pre[lo:hi] + [pre[lo]] * (bsz - (hi - lo))
-        if hi - lo < bsz:          # the decoder's batch is fixed: pad the last chunk by repeating its first row
-            pad = bsz - (hi - lo)
-            chunk = {k: torch.cat([v, v[:1].expand(pad, *v.shape[1:])], 0) for k, v in chunk.items()}
-        chunk = {k: v.to(eng.dev) for k, v in chunk.items()}
-        back, lp = dec.generate(chunk, length, prefix=cpre, return_logprobs=True)
-        if not np.array_equal(back[:hi - lo].cpu().numpy(), given[lo:hi]):
+    out = []
+    for chunk, c, n in _chunks(_stack_rows(rows), Constraints(0, pre, None), bsz, eng.dev):
+        back, lp = dec.generate(chunk, length, prefix=c.prefix, return_logprobs=True)
+        if not np.array_equal(back[:n].cpu().numpy(), np.asarray(c.prefix[:n])):
             raise RuntimeError("score_sequences: the decoder changed a given id")
-        out[lo:hi] = lp[:hi - lo].cpu().numpy()
-    return out
+        out.append(lp[:n].cpu().numpy())
+    return np.concatenate(out)
 
 
 def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature=1.1, repetition_penalty=1.5, max_batch=256,
@@ -321,42 +284,24 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
     unpenalised sums, so the list of return_all is still best first over all groups.  best_per_group=True returns one list per
     prompt of G entries in group order, each the best hypothesis of its group as (text, score), or (text, score, ids) with
     return_ids; it excludes return_all."""
-    from .decode import BeamDecoder, GreedyDecoder, check_groups, check_ngram
     G, lam = check_groups(num_beams, num_beam_groups, diversity_penalty)
     if best_per_group and return_all:
         raise ValueError("best_per_group returns one hypothesis per group, return_all every beam: ask for one of them")
     eng = model.engine()
     sh = eng.sh
-    ngram = check_ngram(no_repeat_ngram_size, sh.msl + 2)
     length = sh.max_seq_length if length is None else length
     n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
-    pre = _prompt_prefixes(prefixes, n_prompts, length, sh)
-    lines = _prompt_lines(line_lengths, line_end_ids, n_prompts, length, sh, pre, templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
-    keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
-    if isinstance(rows, dict):
-        stacked = {k: torch.as_tensor(np.asarray(rows[k])) for k in keys}
-    else:
-        stacked = {k: torch.as_tensor(np.stack([np.asarray(r[k]) for r in rows])) for k in keys}
-    n_prompts = stacked["topic_ids"].shape[0]
+    cons = _check_constraints(prefixes, no_repeat_ngram_size, line_lengths, line_end_ids, n_prompts, length, sh, "%d prompts" % n_prompts,
+                              templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
     per = max(1, min(max_batch // num_beams, n_prompts))
     dec = BeamDecoder(model, per, num_beams, max_len=length)
     out = []
-    for lo in range(0, n_prompts, per):
-        hi = min(n_prompts, lo + per)
-        chunk = {k: v[lo:hi] for k, v in stacked.items()}
-        if hi - lo < per:          # the decoder's prompt count is fixed: pad the last chunk by repeating its first prompt
-            pad = per - (hi - lo)
-            chunk = {k: torch.cat([v, v[:1].expand(pad, *v.shape[1:])], 0) for k, v in chunk.items()}
-        cpre = None
-        if pre is not None:
-            cpre = pre[lo:hi] + [pre[lo]] * (per - (hi - lo))
-        chunk = {k: v.to(eng.dev) for k, v in chunk.items()}
-        clines = _chunk_lines(lines, list(range(lo, hi)) + [lo] * (per - (hi - lo)))
-        ids, scores, group = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty, prefix=cpre,
-                                          no_repeat_ngram_size=ngram, line_lengths=clines, num_beam_groups=G, diversity_penalty=lam,
+    for chunk, c, n in _chunks(_stack_rows(rows), cons, per, eng.dev):
+        ids, scores, group = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty, prefix=c.prefix,
+                                          no_repeat_ngram_size=c.ngram, line_lengths=c.lines, num_beam_groups=G, diversity_penalty=lam,
                                           return_groups=True)
         ids, scores, group = ids.cpu().numpy(), scores.cpu().numpy(), group.cpu().numpy()
-        for r in range(hi - lo):
+        for r in range(n):
             beams = []
             for k in range(num_beams):
                 seq = GreedyDecoder.reference_return(ids[r, k].tolist(), length, sent=sh.msl + 2)
