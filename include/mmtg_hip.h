@@ -761,6 +761,57 @@ MMTG_API int mmtg_decode_beam_candidates_rhyme(const float* logits, long ldl, in
 MMTG_API int mmtg_decode_logprob(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr, int P,
                         float* out, long ldo, int ncols, int B, void* stream);
 
+/* ---- keyword-constrained beam search (BeamDecoder with keywords=, mmtg_amd/decode.py): lyrics that contain given words, each at a
+ * place of the model's choice -- the banked beam allocation of Post & Vilar (2018) / Hu et al. (2019) in the step's last two launches.
+ * Keywords.  A prompt carries K keywords, 0 <= K <= 8, shared by its beams: phrases int32 [prompts, 8, 4] and phrase_len int8
+ *   [prompts, 8] (prompt = row / nb).  A keyword is a phrase of 1 .. 4 content ids (not 0, 1, 2, 100, 102; below the vocabulary
+ *   cut): one character is one token, so four ids are a four-character word.  The phrases of a prompt are distinct and none is a
+ *   contiguous sub-phrase of another (the host refuses both).  nb * (nb + K) <= 256: one merge workgroup has a candidate per thread.
+ *   The tables live on the device, so an entry cannot read them: phrase_cap is the caller's bound on the longest phrase, checked
+ *   here (1 .. 4), and the kernel ignores a keyword whose stored length is outside 1 .. phrase_cap (no slot, nothing in a bank).
+ * History and met.  A row's history h is its own lyric columns 1 .. j - 1 (prefix columns included, the prompt not; a beam's is
+ *   its reordered history).  A keyword is met in h if its phrase occurs in h as a contiguous window.  Phrases hold content ids
+ *   only, so no window spans [#EOS#] / [#START#] / PAD: a keyword always lies inside one line, with no special case.
+ * Bank.  met(s): the keywords met in s.  prog(s): the largest m, 1 <= m < len_i, over the keywords i not in met(s), with the last m
+ *   ids of s equal to phrase_i[0..m); 0 if none.  bank(s) = sum over i in met(s) of len_i + prog(s).  The bank is stateless: it is
+ *   recomputed from the history at every step, so an abandoned partial phrase unwinds by itself and nothing is reordered with the
+ *   beams.
+ * Candidates (mmtg_decode_beam_candidates_kw; cand_val / cand_id / cand_bank are [B, W], W = nb + K).  A row that chooses at a free
+ *   column offers W slots.  Slots 0 .. nb - 1 are mmtg_decode_beam_candidates_rhyme's on the same inputs, in value, id and order.
+ *   Slot nb + i belongs to keyword i: if it is not met in h, with m_i the largest m < len_i such that the last m ids of h equal
+ *   phrase_i[0..m) (0 if none), the slot offers t = phrase_i[m_i] at the value (x[t] - max) - log(sum) of the processed logits, as
+ *   the top slots.  The slot is dead (value -inf, id 0) if the keyword is met, if x[t] is -inf (any ban of any rule wins: keywords
+ *   compose with n-gram bans, bounds, end sets, templates and rhymes and never override them; an id at or above V is banned), if
+ *   t is among the row's top nb ids, or if an earlier keyword slot of this row offers t.  cand_bank[b, k] = bank(h + [id]) of the
+ *   slot, 0 for a dead one.  A row that offers one candidate (sticky PAD, a full line's PAD, a template's given id) offers it in
+ *   slot 0 with bank(h + [id]) -- a given id may complete a keyword, PAD resets prog -- and W - 1 dead slots.  The rule is the
+ *   *_rhyme entry's (fixed_end .. distinct as there), except that n_lines = 0 with every table null means no line rule at all,
+ *   and with n_lines > 0 n_sets may be 0 (lead all -1: no followers; class_of is then never read but still needed).
+ * Merge (mmtg_decode_beam_merge_kw / _kw_fixed; one workgroup per prompt, candidate o = p * W + k).  base = scores[p] +
+ *   cand_val[p, k], NaN becomes -inf; live means base > -inf.  A live candidate's r is the number of live candidates of the SAME
+ *   bank that precede it by (base descending, o ascending).  The live candidates are ordered by (r ascending, bank descending):
+ *   the best of every bank, highest bank first, then the second best of every bank, and so on; the dead ones follow in o order.
+ *   The first nb are kept in that order with the stored score base: the allocation steers the choice, the score stays the sum of
+ *   the processed log-probabilities.  Held prefix columns, forced cadence columns and null candidates do what
+ *   mmtg_decode_beam_merge / mmtg_decode_beam_merge_fixed do.  With every bank equal (K = 0) the order is the plain merge's, bit for
+ *   bit.  No atomics, a fixed order: equal inputs give equal bits.
+ * The search is best effort: a keyword that no allowed column can hold stays unmet; nothing here fails on the device.
+ * Null pointers, K outside 0..8, nb * (nb + K) > 256 and (K > 0) phrase_cap outside 1..4 fail before any device call.  Two new
+ * kernels (beam_candidates_kw_kernel, beam_merge_kw_kernel<NoRule | FixedEnd>); every other kernel compiles to the same code as
+ * before these were added.                                                                                                   */
+MMTG_API int mmtg_decode_beam_candidates_kw(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                   int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                   int B, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
+                                   int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
+                                   const short* class_of, const signed char* lead, int distinct, const int* phrases,
+                                   const signed char* phrase_len, int K, int phrase_cap, int* cand_bank, void* stream);
+MMTG_API int mmtg_decode_beam_merge_kw(const float* cand_val, const int* cand_id, const int* cand_bank, float* scores, long long* seq,
+                              long ldseq, int* keep, long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent,
+                              int nb, int n_prompts, int* pos_next, int K, void* stream);
+MMTG_API int mmtg_decode_beam_merge_kw_fixed(const float* cand_val, const int* cand_id, const int* cand_bank, float* scores, long long* seq,
+                                    long ldseq, int* keep, long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent,
+                                    int nb, int n_prompts, int* pos_next, const int* fixed_end, int K, void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

@@ -548,3 +548,137 @@ def _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids,
         raise ValueError("line tables of %d rows for %s (and no line_end_ids / templates / rhyme_scheme beside them)"
                          % (line_lengths.rows, what))
     return Constraints(ngram, pre, line_lengths)
+
+
+# ------------------------------------------------------------------ keywords (BeamDecoder with keywords=; the rule's home is include/mmtg_hip.h)
+KW_MAX, KW_LEN = 8, 4
+NOT_CONTENT = (0,) + BANNED
+
+
+class KeywordTables:
+    """The checked keywords of `rows` prompts: lists[b] = prompt b's phrases (tuples of ids), phrases int32 [rows, 8, 4] (-1 beyond a
+    phrase), lens int8 [rows, 8] (0 beyond a prompt's keywords), K = the most keywords a prompt has and cap = the longest phrase (the
+    candidates entry's phrase_cap)."""
+
+    def __init__(self, lists):
+        self.lists = [tuple(tuple(int(v) for v in p) for p in row) for row in lists]
+        self.rows = len(self.lists)
+        self.K = max([len(r) for r in self.lists] + [0])
+        self.cap = max([len(p) for r in self.lists for p in r] + [1])
+        self.phrases = np.full((self.rows, KW_MAX, KW_LEN), -1, np.int32)
+        self.lens = np.zeros((self.rows, KW_MAX), np.int8)
+        for b, row in enumerate(self.lists):
+            for i, p in enumerate(row):
+                self.phrases[b, i, :len(p)] = p
+                self.lens[b, i] = len(p)
+
+    def take(self, idx):
+        return KeywordTables([self.lists[i] for i in idx])
+
+
+def _keyword_lists(keywords, rows):
+    """keywords as one list of phrases per prompt: it is one list of phrases for all prompts (a phrase: a sequence of ids) or a list
+    of `rows` such lists."""
+    def is_phrase(e):
+        return isinstance(e, (list, tuple, np.ndarray)) and len(e) > 0 and all(_is_int(v) for v in e)
+
+    if not isinstance(keywords, (list, tuple)):
+        raise ValueError("keywords must be a list of phrases (id sequences) or one such list per prompt, got %r" % (keywords,))
+    if all(is_phrase(e) for e in keywords):
+        return [list(keywords) for _ in range(rows)]
+    if all(isinstance(e, (list, tuple)) for e in keywords) and len(keywords) == rows:
+        return [list(e) for e in keywords]
+    if any(isinstance(e, (list, tuple, np.ndarray)) and len(e) == 0 for e in keywords):
+        raise ValueError("keywords: an empty phrase (a keyword is 1..%d content ids)" % KW_LEN)
+    raise ValueError("keywords must be a list of phrases (id sequences) or one such list for each of the %d prompts" % rows)
+
+
+def _windows(ids, phrase):
+    n, L = len(ids), len(phrase)
+    return any(tuple(ids[i:i + L]) == tuple(phrase) for i in range(n - L + 1))
+
+
+def check_keywords(keywords, n_prompts, nb, V, sent=22, prefix=None):
+    """Validate keywords= on the host, before any device work, and pack them: a KeywordTables (None for keywords=None; a KeywordTables
+    is taken as checked).  keywords: one list of phrases for all prompts or one list per prompt; a phrase is 1 .. 4 content ids (not
+    0, 1, 2, 100, 102, below min(V, 13317)) and no longer than a line holds (sent - 2).  A prompt has at most 8 phrases, all
+    distinct, none a contiguous sub-phrase of another, and nb * (nb + K) <= 256 (K the most keywords a prompt has): one merge
+    workgroup has one candidate per thread.  prefix (check_prefix's lists): one per prompt; a keyword that already lies in a prompt's
+    prefix is no error -- the history includes the prefix, so it is met from the start and its slot is dead."""
+    if keywords is None:
+        return None
+    if isinstance(keywords, KeywordTables):
+        if keywords.rows != n_prompts:
+            raise ValueError("keyword tables of %d prompts for %d prompts" % (keywords.rows, n_prompts))
+        tabs = keywords
+    else:
+        lists = _keyword_lists(keywords, n_prompts)
+        cut = min(int(V), 13317)
+        for b, row in enumerate(lists):
+            if len(row) > KW_MAX:
+                raise ValueError("keywords of prompt %d: %d phrases, at most %d" % (b, len(row), KW_MAX))
+            for i, p in enumerate(row):
+                if not isinstance(p, (list, tuple, np.ndarray)) or not 1 <= len(p) <= min(KW_LEN, sent - 2):
+                    raise ValueError("keywords of prompt %d, phrase %d: a keyword is 1..%d content ids, got %r" % (b, i, min(KW_LEN, sent - 2), p))
+                for v in p:
+                    if not _is_int(v) or int(v) in NOT_CONTENT or not 0 <= int(v) < cut:
+                        raise ValueError("keywords of prompt %d, phrase %d: %r is not a content id below %d" % (b, i, v, cut))
+            ps = [tuple(int(v) for v in p) for p in row]
+            for i, p in enumerate(ps):
+                for k, q in enumerate(ps):
+                    if i < k and p == q:
+                        raise ValueError("keywords of prompt %d: phrases %d and %d are the same" % (b, i, k))
+                    if i != k and len(p) < len(q) and _windows(q, p):
+                        raise ValueError("keywords of prompt %d: phrase %d lies inside phrase %d" % (b, i, k))
+        tabs = KeywordTables(lists)
+    if int(nb) * (int(nb) + tabs.K) > 256:
+        raise ValueError("keywords: %d beams x (%d beams + %d keywords) candidates exceed 256 (one merge workgroup)" % (nb, nb, tabs.K))
+    if prefix is not None:
+        if len(prefix) != n_prompts:
+            raise ValueError("keywords: prefix of %d rows for %d prompts" % (len(prefix), n_prompts))
+    return tabs
+
+
+def keyword_met_mask(ids, phrases):
+    """Per phrase: it occurs in the id sequence `ids` as a contiguous window."""
+    ids = [int(v) for v in ids]
+    return [_windows(ids, p) for p in phrases]
+
+
+def keywords_met(ids, phrases):
+    """How many of the phrases occur in `ids` as contiguous windows."""
+    return int(sum(keyword_met_mask(ids, phrases)))
+
+
+def keyword_bank(ids, phrases):
+    """bank(s) of include/mmtg_hip.h for the sequence s = ids: the lengths of the met phrases plus prog(s), the largest m with
+    1 <= m < len_i over the unmet phrases i such that s ends in phrase_i[0..m) (0 if none).  Host only, from the definition."""
+    s = [int(v) for v in ids]
+    met = keyword_met_mask(s, phrases)
+    bank = sum(len(p) for p, m in zip(phrases, met) if m)
+    prog = 0
+    for p, m in zip(phrases, met):
+        if not m:
+            for k in range(1, len(p)):
+                if k <= len(s) and tuple(s[len(s) - k:]) == tuple(p[:k]):
+                    prog = max(prog, k)
+    return bank + prog
+
+
+def keyword_select(cands, nb):
+    """The keyword merge's selection on the host.  cands: (base, bank, token) in candidate order o (parent-major, slot-minor).  A NaN
+    base is -inf; live means base > -inf.  A live candidate's r is the number of live candidates of its bank before it by (base
+    descending, o ascending); the live ones are ordered by (r ascending, bank descending), the dead ones follow in o order.  Returns
+    the first nb as (o, base fp32, bank, token)."""
+    keyed = []
+    for o, (base, bank, tok) in enumerate(cands):
+        base = np.float32(base)
+        keyed.append((o, np.float32(-np.inf) if np.isnan(base) else base, int(bank), int(tok)))
+    live = [c for c in keyed if c[1] > -np.inf]
+    dead = [c for c in keyed if not c[1] > -np.inf]
+    rank = {}
+    for bank in {c[2] for c in live}:
+        for r, c in enumerate(sorted((c for c in live if c[2] == bank), key=lambda c: (-float(c[1]), c[0]))):
+            rank[c[0]] = r
+    live.sort(key=lambda c: (rank[c[0]], -c[2]))
+    return (live + dead)[:nb]

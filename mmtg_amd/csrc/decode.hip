@@ -1704,6 +1704,318 @@ __global__ __launch_bounds__(256) void beam_merge_groups_kernel(const float* __r
     }
 }
 
+// Keyword-constrained beams (the *_kw entries, include/mmtg_hip.h): a prompt carries K <= KW_MAX phrases of 1 .. KW_LEN content
+// ids its lyric should contain somewhere.  The candidates kernel offers W = nb + K slots per row -- the top nb as ever, then one
+// slot per keyword with the phrase's next id -- and the bank of every slot, bank(h + [id]) = the lengths of the keywords met in the
+// history plus the longest partial phrase it ends in; the merge shares the nb places among the banks.  The bank is a function of
+// the history alone, recomputed at every step: nothing is carried from step to step or reordered with the beams.
+constexpr int KW_MAX = 8, KW_LEN = 4;
+
+struct Keywords {
+    const int* phrases;          // int32 [prompts, KW_MAX, KW_LEN]
+    const signed char* lens;     // int8 [prompts, KW_MAX]; a length outside 1 .. cap makes its keyword inert (no slot, no bank)
+    int K;                       // keywords per prompt, 0 .. KW_MAX
+    int cap;                     // the longest phrase of the call, 1 .. KW_LEN
+    int* cand_bank;              // int32 [B, nb + K]
+};
+
+// tail: the last KW_LEN - 1 ids of the history h, oldest first (-1 before the row's start).  The id d places before the end of
+// h + [t] (APP) or of h itself (d = 0: the last one)
+template <bool APP>
+__device__ __forceinline__ int kw_at(const int* tail, int t, int d) {
+    return APP ? (d == 0 ? t : tail[KW_LEN - 1 - d]) : tail[KW_LEN - 2 - d];
+}
+
+// the largest m <= top with the last m ids of h + [t] (APP; top <= KW_LEN) or of h (top < KW_LEN) equal to ph[0..m), 0 if none
+template <bool APP>
+__device__ __forceinline__ int kw_match(const int* ph, int top, const int* tail, int t) {
+    int best = 0;
+    for (int m = 1; m <= top; ++m) {
+        bool eq = true;
+        for (int k = 0; k < m; ++k) eq = eq && kw_at<APP>(tail, t, m - 1 - k) == ph[k];
+        if (eq) best = m;
+    }
+    return best;
+}
+
+// the id an unmet keyword of length L offers after h: phrase[m], m its progress (the longest proper prefix of the phrase h ends in)
+__device__ __forceinline__ int kw_offer(const int* ph, int L, const int* tail) { return ph[kw_match<false>(ph, L - 1, tail, 0)]; }
+
+// bank(h + [t]) from met(h) and the last ids of h: a keyword of met(h), or one the window ending in t completes, counts its
+// length; of the others the longest progress counts
+__device__ __forceinline__ int kw_bank(const int (*ph)[KW_LEN], const int* len, int K, unsigned met, const int* tail, int t) {
+    int bank = 0, prog = 0;
+    for (int q = 0; q < K; ++q) {
+        const int L = len[q];
+        if (L < 1) continue;
+        if ((met >> q) & 1u) { bank += L; continue; }
+        const int m = kw_match<true>(ph[q], L, tail, t);
+        if (m == L) bank += L;
+        else prog = max(prog, m);
+    }
+    return bank + prog;
+}
+
+// beam_candidates_kernel<RhymeRule> (its processing, line by line; the rule's tables may be empty: n_lines 0 constrains nothing)
+// with the keyword slots and the banks.  A kernel of its own, so that the forms without keywords keep their code (a template, as
+// they are: R is RhymeRule, the one form that serves every rule or none).
+template <typename R>
+__global__ __launch_bounds__(256) void beam_candidates_kw_kernel(const float* __restrict__ logits, long ldl, int V,
+        const long long* __restrict__ seq, long ldseq, const int* __restrict__ pos_ptr, int P, int sent,
+        float temperature, float rep_penalty, int nb, float* __restrict__ cand_val, int* __restrict__ cand_id, R rule,
+        Keywords kw) {
+    static_assert(R::rhyme, "the keyword candidates are built over the rhyme form");
+    extern __shared__ unsigned cnt[];          // (V + 1) / 2 count words | V processed logits | the n-gram form's history
+    float* const px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
+    __shared__ float sval[4], sx[BEAM_MAX];
+    __shared__ int sidx[4], si[BEAM_MAX];
+    __shared__ int s_ph[KW_MAX][KW_LEN], s_len[KW_MAX], s_tail[KW_LEN - 1];
+    __shared__ unsigned s_met;
+    const int b = blockIdx.x, tid = threadIdx.x, pos = *pos_ptr;
+    const int j = pos + 1 - P;
+    if (j < 1 || beam_forced(j, sent)) return;
+    if (rule.held(b, pos)) return;
+    const int K = kw.K, W = nb + K;
+    float* const cv = cand_val + (long)b * W;
+    int* const ci = cand_id + (long)b * W;
+    int* const cb = kw.cand_bank + (long)b * W;
+    const long long* gen = seq + (long)b * ldseq + P;
+    const int n = min(j, MAXGEN);
+    // the prompt's phrases, the history's last ids and the met mask: thread i looks at the windows that start at column i
+    const long kw0 = (long)(b / nb) * KW_MAX;
+    if (tid < KW_MAX * KW_LEN) s_ph[tid / KW_LEN][tid % KW_LEN] = tid / KW_LEN < K ? kw.phrases[kw0 * KW_LEN + tid] : -1;
+    if (tid < KW_MAX) {
+        const int L = tid < K ? (int)kw.lens[kw0 + tid] : 0;
+        s_len[tid] = L >= 1 && L <= kw.cap ? L : 0;
+    }
+    if (tid < KW_LEN - 1) {
+        const int c = j - (KW_LEN - 1) + tid;
+        s_tail[tid] = c >= 0 ? (int)gen[c] : -1;
+    }
+    if (tid == 0) s_met = 0u;
+    __syncthreads();
+    for (int i = tid; i < j; i += 256) {
+        unsigned hit = 0u;
+        for (int q = 0; q < K; ++q) {
+            const int L = s_len[q];
+            bool eq = L >= 1 && i + L <= j;
+            for (int k = 0; eq && k < L; ++k) eq = gen[i + k] == (long long)s_ph[q][k];
+            if (eq) hit |= 1u << q;
+        }
+        if (hit) atomicOr(&s_met, hit);
+    }
+    __syncthreads();
+    const unsigned met = s_met;
+    int one = -1;                                          // >= 0: the row offers this id alone, with the score unchanged
+    if (gen[n - 1] == 0) one = 0;                          // sticky PAD
+    bool rhymes = false;
+    LineCol lc = {false, false, nullptr};
+    TmplCol tc = {-1, nullptr};
+    if (one < 0) {
+        lc = rule.col(b, j, sent, gen, &rhymes);
+        if (lc.force_pad) one = 0;                         // the line is full
+    }
+    if (one < 0) {
+        tc = rule.sym(b, j, sent);
+        if (tc.given >= 0) one = tc.given;                 // a given column (it may complete a phrase)
+    }
+    if (one >= 0) {
+        if (tid < W) {
+            cv[tid] = tid == 0 ? 0.f : -INFINITY;
+            ci[tid] = tid == 0 ? one : 0;
+            cb[tid] = tid == 0 ? kw_bank(s_ph, s_len, K, met, s_tail, one) : 0;
+        }
+        return;
+    }
+    count_ids(cnt, V, gen, n, tid);
+    const NgramBan ng = rule.bans();
+    if (ng.n > 0) ban_ngrams(cnt, reinterpret_cast<int*>(px + V), V, gen, min(n, ng.hist_cap), ng.n, tid);
+    ban_line_tmpl(cnt, V, lc, tc.cls, tid);
+    rule.ban_distinct(cnt, b, j, sent, gen, lc, rhymes, tid);
+    const float* row = logits + (long)b * ldl;
+    float mx = -INFINITY;
+    for (int v = tid; v < V; v += 256) {
+        float x = row[v];
+        if (v != 102) {
+            const int c = (cnt[v >> 1] >> (16 * (v & 1))) & 0xFFFF;
+            x = penalize<true>(x, c, rep_penalty);
+        }
+        x = x / temperature;
+        if (v == 1 || v == 2 || v == 100 || v == 102) x = -INFINITY;
+        px[v] = x;
+        mx = fmaxf(mx, x);
+    }
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) sval[tid >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(sval[0], sval[1]), fmaxf(sval[2], sval[3]));
+    float sum = 0.f;
+    for (int v = tid; v < V; v += 256) sum += expf(px[v] - mx);
+    sum = wave_sum(sum);
+    __syncthreads();
+    if ((tid & 63) == 0) sval[tid >> 6] = sum;
+    __syncthreads();
+    const float lsum = logf(sval[0] + sval[1] + sval[2] + sval[3]);
+    for (int r = 0; r < nb; ++r) {
+        __syncthreads();
+        float best = -INFINITY;
+        int besti = 0x7fffffff;
+        for (int v = tid; v < V; v += 256) {
+            const float x = px[v];
+            if (x > best || (x == best && v < besti)) { best = x; besti = v; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(best, o, 64);
+            const int oi = __shfl_xor(besti, o, 64);
+            if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        }
+        if ((tid & 63) == 0) { sval[tid >> 6] = best; sidx[tid >> 6] = besti; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < 4; ++w)
+                if (sval[w] > best || (sval[w] == best && sidx[w] < besti)) { best = sval[w]; besti = sidx[w]; }
+            sx[r] = best;
+            si[r] = besti;
+            if (besti >= 0 && besti < V) px[besti] = __int_as_float(0x7fc00000);
+        }
+    }
+    __syncthreads();
+    if (tid < nb) {
+        const float x = sx[tid];
+        const bool ok = si[tid] >= 0 && si[tid] < V && x > -INFINITY && mx > -INFINITY;
+        cv[tid] = ok ? (x - mx) - lsum : -INFINITY;
+        ci[tid] = ok ? si[tid] : 0;
+        cb[tid] = ok ? kw_bank(s_ph, s_len, K, met, s_tail, si[tid]) : 0;
+    } else if (tid < W) {
+        // keyword q's slot: the phrase's next id, unless the keyword is met, the id is banned (-inf), among the top nb (marked NaN
+        // by the rounds above) or offered by an earlier keyword's slot (an earlier unmet keyword with the same next id: were that
+        // slot dead for a ban or for the top nb, this one would be too)
+        const int q = tid - nb, L = s_len[q];
+        float val = -INFINITY;
+        int id = 0, bank = 0;
+        if (L >= 1 && !((met >> q) & 1u)) {
+            const int t = kw_offer(s_ph[q], L, s_tail);
+            bool dup = false;
+            for (int e = 0; e < q; ++e) dup = dup || (s_len[e] >= 1 && !((met >> e) & 1u) && kw_offer(s_ph[e], s_len[e], s_tail) == t);
+            if (t > 0 && t < V && !dup) {
+                const float x = px[t];
+                if (x > -INFINITY && mx > -INFINITY) {
+                    val = (x - mx) - lsum;
+                    id = t;
+                    bank = kw_bank(s_ph, s_len, K, met, s_tail, t);
+                }
+            }
+        }
+        cv[tid] = val;
+        ci[tid] = id;
+        cb[tid] = bank;
+    }
+}
+
+// beam_merge_kernel over W = nb + K candidates per parent and their banks (candidate o = p * W + k, one per thread).  A live
+// candidate (base above -inf) has the rank r it holds inside its own bank by (base descending, o ascending); the live ones are
+// ordered by (r ascending, bank descending) -- the best of every bank, highest bank first, then the second best of every bank --
+// the dead ones follow in o order, and the first nb are kept with the score base.  With every bank equal that is the plain order.
+template <typename R>
+__global__ __launch_bounds__(256) void beam_merge_kw_kernel(const float* __restrict__ cand_val, const int* __restrict__ cand_id,
+        const int* __restrict__ cand_bank, float* __restrict__ scores, long long* __restrict__ seq, long ldseq,
+        int* __restrict__ keep, long ldkeep, int* __restrict__ rows, long ldrows, const int* __restrict__ pos_ptr, int P, int sent,
+        int nb, int* __restrict__ pos_next, int K, R rule) {
+    __shared__ float sc[BEAM_MAX * BEAM_MAX];
+    __shared__ int s_bank[BEAM_MAX * BEAM_MAX], s_rank[BEAM_MAX * BEAM_MAX];
+    __shared__ float s_sc[BEAM_MAX];
+    __shared__ int s_par[BEAM_MAX], s_tok[BEAM_MAX];
+    __shared__ long long st_seq[BEAM_MAX][BEAM_TW];
+    __shared__ int st_keep[BEAM_MAX][BEAM_TW], st_rows[BEAM_MAX][BEAM_TW];
+    const int g = blockIdx.x, tid = threadIdx.x, pos = *pos_ptr, b0 = g * nb;
+    if (pos_next && g == 0 && tid == 0) *pos_next = pos + 1;
+    const int j = pos + 1 - P;
+    const bool next_ok = pos + 1 < ldrows;
+    if (rule.held(b0, pos)) {
+        if (tid < nb && next_ok) rows[(long)(b0 + tid) * ldrows + pos + 1] = b0 + tid;
+        return;
+    }
+    if (j < 1 || beam_forced(j, sent) || !cand_val) {
+        if (tid < nb) {
+            const long b = b0 + tid;
+            if (j >= 1 && beam_forced(j, sent)) seq[b * ldseq + pos + 1] = (j + 1) % sent == 0 ? 2 : 1;
+            if (next_ok) rows[b * ldrows + pos + 1] = (int)b;
+        }
+        return;
+    }
+    constexpr int DEAD = 0x7fffffff;
+    const int W = nb + K, nc = nb * W;                          // nc <= 256 (the entry checks)
+    float my = -INFINITY;
+    int mp = 0, mk = 0, bank = 0;
+    if (tid < nc) {
+        mp = tid / W;
+        mk = tid - mp * W;
+        my = scores[b0 + mp] + cand_val[(long)(b0 + mp) * W + mk];
+        if (my != my) my = -INFINITY;
+        bank = cand_bank[(long)(b0 + mp) * W + mk];
+        sc[tid] = my;
+        s_bank[tid] = bank;
+    }
+    __syncthreads();
+    const bool live = my > -INFINITY;
+    int r = DEAD;
+    if (tid < nc) {
+        if (live) {
+            r = 0;
+            for (int o = 0; o < nc; ++o) {
+                const float so = sc[o];
+                r += s_bank[o] == bank && ((so > my) || (so == my && o < tid));      // (so >= my is live)
+            }
+        }
+        s_rank[tid] = r;
+    }
+    __syncthreads();
+    if (tid < nc) {
+        int place = 0;
+        for (int o = 0; o < nc; ++o) {
+            const int ro = s_rank[o];
+            place += live ? (ro < r || (ro == r && s_bank[o] > bank)) : (ro != DEAD || o < tid);
+        }
+        if (place < nb) { s_par[place] = mp; s_tok[place] = cand_id[(long)(b0 + mp) * W + mk]; s_sc[place] = my; }
+    }
+    __syncthreads();
+    bool ident = true;
+    for (int q = 0; q < nb; ++q) ident = ident && s_par[q] == q;
+    if (!ident) {
+        for (int c0 = 0; c0 <= pos; c0 += BEAM_TW) {
+            const int w = min(BEAM_TW, pos + 1 - c0);
+            for (int e = tid; e < nb * BEAM_TW; e += 256) {
+                const int q = e / BEAM_TW, c = e - q * BEAM_TW;
+                if (c < w) {
+                    const long b = b0 + q;
+                    st_seq[q][c] = seq[b * ldseq + c0 + c];
+                    st_keep[q][c] = keep[b * ldkeep + c0 + c];
+                    st_rows[q][c] = rows[b * ldrows + c0 + c];
+                }
+            }
+            __syncthreads();
+            for (int e = tid; e < nb * BEAM_TW; e += 256) {
+                const int q = e / BEAM_TW, c = e - q * BEAM_TW;
+                if (c < w) {
+                    const long b = b0 + q;
+                    const int p = s_par[q];
+                    seq[b * ldseq + c0 + c] = st_seq[p][c];
+                    keep[b * ldkeep + c0 + c] = st_keep[p][c];
+                    rows[b * ldrows + c0 + c] = st_rows[p][c];
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (tid < nb) {
+        const long b = b0 + tid;
+        scores[b] = s_sc[tid];
+        seq[b * ldseq + pos + 1] = s_tok[tid];
+        if (next_ok) rows[b * ldrows + pos + 1] = (int)b;
+    }
+}
+
 }  // namespace
 
 extern "C" int mmtg_decode_embed(int dtype, const void* table, const long long* seq, long ldseq, const void* c, void* x,
@@ -2174,6 +2486,93 @@ extern "C" int mmtg_decode_beam_candidates_rhyme(const float* logits, long ldl, 
         return e;
     return beam_candidates_launch("decode_beam_candidates_rhyme", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
                                   nb, cand_val, cand_id, B, stream, rr);
+}
+
+// (what every *_kw entry asks of K and nb: one merge workgroup holds a candidate per thread)
+static int kw_check(const char* what, int nb, int K) {
+    MMTG_REQUIRE(nb >= 1 && nb <= BEAM_MAX, "%s: %d beams per prompt (1..%d)", what, nb, BEAM_MAX);
+    MMTG_REQUIRE(K >= 0 && K <= KW_MAX, "%s: %d keywords per prompt (0..%d)", what, K, KW_MAX);
+    MMTG_REQUIRE(nb * (nb + K) <= 256, "%s: %d beams x (%d beams + %d keywords) candidates exceed the merge workgroup (256)", what, nb, nb, K);
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_beam_candidates_kw(const float* logits, long ldl, int V, const long long* seq, long ldseq, const int* pos_ptr,
+                                              int P, int sent, float temperature, float rep_penalty, int nb, float* cand_val, int* cand_id,
+                                              int B, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
+                                              int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
+                                              const short* class_of, const signed char* lead, int distinct, const int* phrases,
+                                              const signed char* phrase_len, int K, int phrase_cap, int* cand_bank, void* stream) {
+    const char* what = "decode_beam_candidates_kw";
+    if (int e = kw_check(what, nb, K)) return e;
+    MMTG_REQUIRE(cand_bank, "%s: null cand_bank", what);
+    MMTG_REQUIRE(K == 0 || (phrases && phrase_len), "%s: phrases [prompts, %d, %d] and phrase_len [prompts, %d] are needed", what, KW_MAX,
+                 KW_LEN, KW_MAX);
+    MMTG_REQUIRE(K == 0 || (phrase_cap >= 1 && phrase_cap <= KW_LEN), "%s: phrase length %d outside 1..%d", what, phrase_cap, KW_LEN);
+    MMTG_REQUIRE(logits && seq && pos_ptr && cand_val && cand_id && B > 0 && B % nb == 0 && sent > 2 && V > 0 && ldl >= V, "%s: bad args", what);
+    MMTG_REQUIRE(temperature > 0.f && rep_penalty > 0.f, "%s: temperature / penalty must be > 0", what);
+    MMTG_REQUIRE(V <= 24000, "%s: vocabulary of %d exceeds the LDS row image (24000)", what, V);
+    RhymeRule rr;
+    if (n_lines == 0) {         // no line rule at all: the rhyme form with empty tables constrains nothing (every line is past n_lines)
+        MMTG_REQUIRE(!lo && !hi && !sets && !set_of && !tmpl && !class_of && !lead && n_sets == 0 && distinct == 0,
+                     "%s: line tables without lines (n_lines 0)", what);
+        MMTG_REQUIRE(ngram >= 0 && ngram <= sent - 2, "%s: n-gram size %d outside 0..%d (sent - 2)", what, ngram, sent - 2);
+        int cap = 0;
+        if (ngram > 0) {
+            if (int e = ngram_check(what, logits, ldseq, P, sent, ngram, &cap)) return e;
+        } else MMTG_REQUIRE(ldseq > P && P >= 0, "%s: bad sequence layout (ldseq %ld, P %d)", what, ldseq, P);
+        rr = RhymeRule{TemplateRule{LineRule{NgramBan{fixed_end, ngram, cap}, nullptr, nullptr, nullptr, nullptr, 0, 0, (V + 31) / 32}, nullptr},
+                       nullptr, nullptr, 0, V};
+    } else {                    // the *_rhyme entry's tables, except that the classes may be absent when no line has a leader
+        LineRule lr;
+        if (int e = lines_check(what, logits, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, &lr)) return e;
+        MMTG_REQUIRE(class_of && lead, "%s: class_of [V] and lead [B, n_lines] are needed", what);
+        MMTG_REQUIRE(n_lines <= 128, "%s: %d lines, a leader's line index must fit a signed char (128)", what, n_lines);
+        MMTG_REQUIRE(distinct == 0 || distinct == 1, "%s: distinct is 0 or 1 (got %d)", what, distinct);
+        rr = RhymeRule{TemplateRule{lr, tmpl}, class_of, lead, distinct, V};
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, 4.0 * B * V, 4.0 * B * V);
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute((const void*)beam_candidates_kw_kernel<RhymeRule>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
+            MMTG_FAIL(MMTG_ERR_HIP, "%s: cannot raise dynamic LDS", what);
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(beam_candidates_kw_kernel<RhymeRule>, dim3(B), dim3(256), select_lds(V, true, rr), s, logits, ldl, V, seq, ldseq, pos_ptr, P, sent,
+                       temperature, rep_penalty, nb, cand_val, cand_id, rr, Keywords{phrases, phrase_len, K, K ? phrase_cap : 0, cand_bank});
+    MMTG_LAUNCH_CHECK(what);
+    return MMTG_OK;
+}
+
+template <typename R>
+static int beam_merge_kw_launch(const char* what, const float* cand_val, const int* cand_id, const int* cand_bank, float* scores,
+                                long long* seq, long ldseq, int* keep, long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P,
+                                int sent, int nb, int n_prompts, int* pos_next, int K, void* stream, R rule) {
+    if (int e = kw_check(what, nb, K)) return e;
+    MMTG_REQUIRE(scores && seq && keep && rows && pos_ptr && n_prompts > 0 && sent > 1 && ldrows > 0 && (!cand_val || (cand_id && cand_bank)),
+                 "%s: bad args", what);
+    MMTG_REQUIRE(pos_next != pos_ptr, "%s: pos_next must not alias pos_ptr", what);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, (double)n_prompts * nb * (nb + K), 32.0 * n_prompts * nb * (double)ldrows);
+    hipLaunchKernelGGL(beam_merge_kw_kernel<R>, dim3(n_prompts), dim3(256), 0, s, cand_val, cand_id, cand_bank, scores, seq, ldseq, keep, ldkeep,
+                       rows, ldrows, pos_ptr, P, sent, nb, pos_next, K, rule);
+    MMTG_LAUNCH_CHECK(what);
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_beam_merge_kw(const float* cand_val, const int* cand_id, const int* cand_bank, float* scores, long long* seq,
+                                         long ldseq, int* keep, long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent,
+                                         int nb, int n_prompts, int* pos_next, int K, void* stream) {
+    return beam_merge_kw_launch("decode_beam_merge_kw", cand_val, cand_id, cand_bank, scores, seq, ldseq, keep, ldkeep, rows, ldrows, pos_ptr, P,
+                                sent, nb, n_prompts, pos_next, K, stream, NoRule{});
+}
+
+extern "C" int mmtg_decode_beam_merge_kw_fixed(const float* cand_val, const int* cand_id, const int* cand_bank, float* scores, long long* seq,
+                                               long ldseq, int* keep, long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P,
+                                               int sent, int nb, int n_prompts, int* pos_next, const int* fixed_end, int K, void* stream) {
+    MMTG_REQUIRE(fixed_end, "decode_beam_merge_kw_fixed: null fixed_end");
+    return beam_merge_kw_launch("decode_beam_merge_kw_fixed", cand_val, cand_id, cand_bank, scores, seq, ldseq, keep, ldkeep, rows, ldrows,
+                                pos_ptr, P, sent, nb, n_prompts, pos_next, K, stream, FixedEnd{fixed_end});
 }
 
 extern "C" int mmtg_ln_fold_weights(const void* W, long ldw, const float* gamma, const float* beta, const float* bias, void* Wf,

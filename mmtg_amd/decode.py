@@ -19,13 +19,13 @@ import numpy as np
 import torch
 
 from . import hip
-from .constraints import (BANNED, LineTables, _check_constraints, check_groups, check_lines, check_ngram, check_prefix,  # noqa: F401
-                          chosen_mask, sequence_scores)         # (the host-side checks keep their names here)
+from .constraints import (BANNED, KeywordTables, LineTables, _check_constraints, check_groups, check_keywords, check_lines,  # noqa: F401
+                          check_ngram, check_prefix, chosen_mask, keywords_met, sequence_scores)   # (the host-side checks keep their names here)
 
 _PLACEMENT = {}
 
 
-def select_forms(with_head, prefix, ngram, lines, templates=False, rhymes=False, groups=False):
+def select_forms(with_head, prefix, ngram, lines, templates=False, rhymes=False, groups=False, keywords=False):
     """Which selection entries a token step ends in: (form of mmtg_decode_select / _sample or mmtg_decode_beam_candidates, form of
     mmtg_decode_beam_merge), each "" (plain), "_fixed", "_ngram", "_lines", "_tmpl" or "_rhyme".  with_head: the step calls the
     model's head; prefix: the generation has one; ngram: no_repeat_ngram_size; lines: line constraints are given; templates: line
@@ -34,10 +34,14 @@ def select_forms(with_head, prefix, ngram, lines, templates=False, rhymes=False,
     a step without the head (select with null logits; no candidates launch, merge with null candidates) and every merge only know
     the prefix -- a generation without constraints runs the plain entries throughout.  groups: the beams are in more than one
     group (diverse beam search): the merge of a step with the head is then "_groups" / "_groups_fixed"; a step without the head
-    has no candidates to choose among and keeps the merge it always ran."""
+    has no candidates to choose among and keeps the merge it always ran.  keywords: the prompts carry keywords (keyword-constrained
+    beam search): a step with the head ends in the "_kw" candidates -- one entry over the rhyme form, which serves every rule above
+    or none -- and the "_kw" / "_kw_fixed" merge; a step without the head keeps the merge it always ran."""
     held = "_fixed" if prefix else ""
     if not with_head:
         return held, held
+    if keywords:
+        return "_kw", "_kw" + held
     return (("_rhyme" if rhymes else "_tmpl" if templates else "_lines" if lines else "_ngram" if ngram else held),
             "_groups" + held if groups else held)
 
@@ -46,8 +50,28 @@ def _step_forms(dec, with_head):
     """select_forms' answer for a step of decoder `dec`, and whether mmtg_decode_logprob follows it: (selection form, merge form,
     logprob).  A decoder without the newer fields (tmpl, rhyme, groups, return_logprobs) is one whose generation does not use them."""
     return select_forms(with_head, dec.use_fixed, dec.ngram, dec.lines is not None, templates=getattr(dec, "tmpl", None) is not None,
-                        rhymes=getattr(dec, "rhyme", None) is not None, groups=getattr(dec, "groups", 1) > 1) + (
+                        rhymes=getattr(dec, "rhyme", None) is not None, groups=getattr(dec, "groups", 1) > 1,
+                        keywords=getattr(dec, "kw", None) is not None) + (
         bool(with_head and getattr(dec, "return_logprobs", False)),)
+
+
+def _keywords_need_beams(keywords):
+    if keywords is not None:
+        raise ValueError("keywords= needs beams: a lyric that contains given words is found by a search over several hypotheses "
+                         "(BeamDecoder / generate_beams), not by greedy decoding or sampling")
+
+
+def _rhyme_key(dec):
+    """What a captured launch of the rhyme form holds by value, for decoder `dec`'s graph key: end sets or bounds only, the template
+    table or none, a scheme's distinct flag (the "_kw" candidates run the form with line tables but possibly without a scheme:
+    "lines" then)."""
+    rhyme = getattr(dec, "rhyme", None)
+    key = ("lines" if rhyme is None else "rhyme", "sets" if dec.lines[2] is not None else "bounds")
+    if getattr(dec, "tmpl", None) is not None:
+        key += ("tmpl",)
+    if rhyme is not None and rhyme[2]:
+        key += ("distinct",)
+    return key
 
 
 def _fill(buf, src, fill, axis):
@@ -587,13 +611,16 @@ class GreedyDecoder:
         form, merge, logprob = _step_forms(self, with_head)
         if form in ("_lines", "_tmpl"):
             key += (form[1:], "sets" if self.lines[2] is not None else "bounds")
-        if form == "_rhyme":                # (what the captured launch holds by value: the template table or none, distinct)
-            key += ("rhyme", "sets" if self.lines[2] is not None else "bounds") + (("tmpl",) if getattr(self, "tmpl", None) is not None else ())
-            key += ("distinct",) if self.rhyme[2] else ()
+        if form == "_rhyme":
+            key += _rhyme_key(self)
         if logprob:
             key += ("logprob",)
         if merge.startswith("_groups"):     # (the grouped merge holds both by value)
             key += (("groups", self.groups, float(self.diversity_penalty)),)
+        if form == "_kw":                   # (K and the phrase bound by value; then what the rhyme form under them holds by value)
+            key += (("kw", self.kw[2]), ("cap", self.kw[3]))
+            if self.lines is not None:
+                key += _rhyme_key(self)
         return key
 
     def _step_state(self):
@@ -623,7 +650,7 @@ class GreedyDecoder:
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
               no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
-              rhyme_distinct=False, return_logprobs=False):
+              rhyme_distinct=False, return_logprobs=False, keywords=None):
         """Everything of a generation that happens once: the settings, the uniforms of a stochastic run, fresh weight copies /
         LayerNorm folds, the experience encoder, the prompt (prefilled in one batched pass: ``first_pos`` = P afterwards) and the
         reset position.  Returns the end position n; ``step_at(pos)`` for pos = first_pos .. n - 1 then runs the token steps (``generate`` does both; tools/decode_lanes_threads.py drives
@@ -661,7 +688,11 @@ class GreedyDecoder:
         the whole row (1 + length ids), the prefill covers the prompt only and every content column goes through a token step --
         teacher forcing through the kernels that generate.  A shorter prefix keeps the prefill of the generation without the
         argument (its ids are bit-equal to that generation's), and the columns the prefill covers stay 0.  False runs exactly the
-        launches, graphs and graph keys of a generation without the argument."""
+        launches, graphs and graph keys of a generation without the argument.
+
+        keywords: refused here (ValueError).  A lyric that contains given words needs a search, and greedy decoding and sampling
+        follow one path: BeamDecoder takes keywords=."""
+        _keywords_need_beams(keywords)
         eng, sh = self.eng, self.eng.sh
         B = batch["img_embs"].shape[0]
         if B != self.B:
@@ -884,6 +915,11 @@ class BeamDecoder(GreedyDecoder):
         self.cand_val = torch.zeros(self.B, nb, dtype=torch.float32, device=dev)
         self.cand_id = torch.zeros(self.B, nb, dtype=torch.int32, device=dev)
         self.groups, self.diversity_penalty = 1, 0.0
+        # keywords (keywords=): (phrases int32 [prompts, 8, 4], lens int8 [prompts, 8], K, the longest phrase) on the device; not
+        # None ends every step that calls the head in the *_kw entries, over the nb + K wide candidate tables of _kw_cand
+        self.kw = None
+        self._kw_buf = None         # the two tables, the wide candidate storage and the rhyme form's empty tables: allocated once
+        self._kw_cand = None        # (cand_val, cand_id, cand_bank) [B, nb + K]: views of that storage
 
     def _select(self, with_head):
         """The step's last two launches, through the entries select_forms names: the bans (and a full line's PAD, offered as sticky
@@ -894,6 +930,16 @@ class BeamDecoder(GreedyDecoder):
         tmpl, rhyme = getattr(self, "tmpl", None), getattr(self, "rhyme", None)
         cand, merge, _ = _step_forms(self, with_head)
         fe = self.fixed_end if self.use_fixed else None
+        if cand == "_kw":
+            # the rhyme form serves every rule or none; line tables without a scheme get a lead table that names no leader
+            cv, ci, cb = self._kw_cand
+            hip.decode_beam_candidates_kw(self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2,
+                                          temperature, rep, self.nb, cv, ci, cb, self.B, self.kw, tables=self.lines, tmpl=tmpl,
+                                          rhyme=(rhyme if rhyme is not None else self._kw_buf[3]) if self.lines is not None else None,
+                                          ngram=self.ngram, fixed_end=fe)
+            hip.decode_beam_merge_kw(cv, ci, cb, self.scores, self.seq, self.keep, self.rows, self.pos, sh.P, sh.msl + 2, self.nb,
+                                     self.n_prompts, self.kw[2], fixed_end=fe, pos_next=self.pos_next)
+            return
         if with_head:
             hip._beam_candidates(cand, self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2, temperature,
                                  rep, self.nb, self.cand_val, self.cand_id, self.B, fixed_end=fe, ngram=self.ngram, tables=self.lines,
@@ -904,6 +950,34 @@ class BeamDecoder(GreedyDecoder):
 
     def _step_state(self):
         return super()._step_state() + [self.rows, self.scores]
+
+    def _upload_keywords(self, tabs):
+        """The keyword tables of a generation into this decoder's buffers, and the nb + K wide candidate tables as views of storage
+        sized for the most keywords nb allows -- all allocated once: captured graphs hold their addresses (K is in the graph key).
+        None without keywords."""
+        if tabs is None:
+            return None
+        dev, B, nb = self.eng.dev, self.B, self.nb
+        if self._kw_buf is None:
+            sent, wmax = self.eng.sh.msl + 2, min(nb + 8, 256 // nb)
+            none = (torch.full((min(self.eng.sh.V, 13317),), -1, dtype=torch.int16, device=dev),
+                    torch.full((B, (self.max_len - 1) // sent + 1), -1, dtype=torch.int8, device=dev), False)
+            self._kw_buf = (torch.zeros(self.n_prompts, 8, 4, dtype=torch.int32, device=dev),
+                            torch.zeros(self.n_prompts, 8, dtype=torch.int8, device=dev),
+                            (torch.zeros(B * wmax, dtype=torch.float32, device=dev), torch.zeros(B * wmax, dtype=torch.int32, device=dev),
+                             torch.zeros(B * wmax, dtype=torch.int32, device=dev)), none)
+        phrases, lens, store, _ = self._kw_buf
+        phrases.copy_(torch.from_numpy(tabs.phrases))
+        lens.copy_(torch.from_numpy(tabs.lens))
+        W = nb + tabs.K
+        self._kw_cand = tuple(t[:B * W].view(B, W) for t in store)
+        return phrases, lens, tabs.K, tabs.cap
+
+    @staticmethod
+    def _keywords_alone(keywords, G):
+        """Keywords share the beams among banks, groups among themselves: one allocation at a time."""
+        if keywords is not None and G > 1:
+            raise ValueError("keywords= and num_beam_groups > 1 both allocate the beams: ask for one of them")
 
     @staticmethod
     def _no_logprobs(return_logprobs):
@@ -919,7 +993,7 @@ class BeamDecoder(GreedyDecoder):
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
               no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
-              rhyme_distinct=False, return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0):
+              rhyme_distinct=False, return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, keywords=None):
         """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill, the prefix, the line
         constraints, the templates and the rhyme scheme: one per prompt; every beam finds its leader's rhyme in its own history), the
         ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at the free positions
@@ -929,20 +1003,32 @@ class BeamDecoder(GreedyDecoder):
         into G groups of s = num_beams / G rows, each started at [0, -inf, ...] and searched on its own; at every step that calls
         the head the merge (mmtg_decode_beam_merge_groups) serves the groups in order and lowers a candidate by the penalty per
         earlier group's beam that took the same content id at this step.  The penalty steers the choice only: the scores stay the
-        unpenalised sums.  G = 1 (the default) runs exactly the launches, graphs and graph keys of a search without the argument."""
+        unpenalised sums.  G = 1 (the default) runs exactly the launches, graphs and graph keys of a search without the argument.
+
+        keywords (``check_keywords``; the rule's home is include/mmtg_hip.h): phrases of 1 .. 4 content ids the lyric should contain,
+        each at a place of the model's choice -- one list for all prompts or one per prompt, shared by a prompt's beams.  Every step
+        that calls the head then ends in mmtg_decode_beam_candidates_kw (each row also offers its unmet keywords' next ids, where no
+        other rule bans them) and mmtg_decode_beam_merge_kw (the beams are shared among the banks: how much of the keywords a
+        hypothesis holds).  The tables are uploaded here, once.  Best effort: a keyword no allowed column can hold stays unmet.
+        With num_beam_groups > 1 it is a ValueError.  None runs exactly the launches, graphs and graph keys of a search without
+        the argument."""
         self._no_logprobs(return_logprobs)
         G, lam = check_groups(self.nb, num_beam_groups, diversity_penalty)
+        self._keywords_alone(keywords, G)
         n = batch["img_embs"].shape[0]
         if n != self.n_prompts:
             raise ValueError("decoder was built for %d prompts, got %d" % (self.n_prompts, n))
         cons = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, n, length, self.eng.sh, "%d prompts" % n,
-                                  templates, rhyme_scheme, rhyme_classes, rhyme_distinct).repeat(self.nb)
+                                  templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
+        kw = check_keywords(keywords, n, self.nb, self.eng.sh.V, self.eng.sh.msl + 2, prefix=cons.prefix)
+        cons = cons.repeat(self.nb)
         rep = {k: (v.repeat_interleave(self.nb, 0) if torch.is_tensor(v) else v) for k, v in batch.items()}
         n_steps = super().begin(rep, length, temperature, repitition_penalty, 1, 0.0, prefix=cons.prefix,
                                 no_repeat_ngram_size=cons.ngram, line_lengths=cons.lines)
         B, dev = self.B, self.eng.dev
         self.rows.copy_(torch.arange(B, dtype=torch.int32, device=dev)[:, None].expand(B, self.Tmax))
         self.groups, self.diversity_penalty = G, lam
+        self.kw = self._upload_keywords(kw)
         sc = torch.full((n, self.nb), float("-inf"), dtype=torch.float32, device=dev)
         sc[:, ::self.nb // G] = 0.0                              # the first row of every group
         self.scores.copy_(sc.view(-1))
@@ -951,7 +1037,7 @@ class BeamDecoder(GreedyDecoder):
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None, no_repeat_ngram_size=0,
                  line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False,
-                 return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, return_groups=False):
+                 return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, return_groups=False, keywords=None, return_met=False):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_beams, 1 + length] in
         GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row.
         prefix: one per prompt (check_prefix), shared by its beams.  no_repeat_ngram_size: as GreedyDecoder.generate, per beam
@@ -962,16 +1048,31 @@ class BeamDecoder(GreedyDecoder):
         num_beam_groups / diversity_penalty: diverse beam search (``begin``): G groups of num_beams / G beams, a later group steered
         away from the ids earlier groups take at the same step.  The result keeps its form: all num_beams hypotheses of a prompt,
         best first by their (unpenalised) scores.  return_groups=True adds a third tensor, int64 [n, num_beams]: the group (final
-        row // (num_beams / G)) of the hypothesis returned at that place."""
+        row // (num_beams / G)) of the hypothesis returned at that place.
+        keywords: phrases the lyric should contain (``begin``, ``check_keywords``).  The hypotheses of a prompt are then ordered by
+        (number of keywords met descending, score descending, stable); return_met=True adds an int64 [n, num_beams] tensor, that
+        number for each hypothesis returned (``constraints.keywords_met`` of its ids).  Best effort: a keyword may stay unmet, and
+        is reported so.  Not together with num_beam_groups > 1 or return_logprobs (ValueError)."""
         self._no_logprobs(return_logprobs)
         G, lam = check_groups(self.nb, num_beam_groups, diversity_penalty)
+        self._keywords_alone(keywords, G)
+        if return_met and keywords is None:
+            raise ValueError("return_met reports the keywords a hypothesis holds: give keywords=")
         ids = super().generate(batch, length, temperature=temperature, repitition_penalty=repitition_penalty, use_graph=use_graph,
                                prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths,
                                line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes,
-                               rhyme_distinct=rhyme_distinct, **({"num_beam_groups": G, "diversity_penalty": lam} if G > 1 else {}))
+                               rhyme_distinct=rhyme_distinct, **({"num_beam_groups": G, "diversity_penalty": lam} if G > 1 else {}),
+                               **({} if keywords is None else {"keywords": keywords}))
         n, nb = self.n_prompts, self.nb
         ids = ids.view(n, nb, -1)
         sc = self.scores.view(n, nb).clone()
         order = torch.sort(sc, dim=1, descending=True, stable=True).indices
+        if keywords is not None:            # (met descending, score descending, stable): a stable sort by met of the score order
+            lists = check_keywords(keywords, n, nb, self.eng.sh.V, self.eng.sh.msl + 2).lists
+            host = ids.cpu().tolist()
+            met = torch.tensor([[keywords_met(host[p][r], lists[p]) for r in range(nb)] for p in range(n)], dtype=torch.long, device=sc.device)
+            order = torch.gather(order, 1, torch.sort(torch.gather(met, 1, order), dim=1, descending=True, stable=True).indices)
+            out = torch.gather(ids, 1, order[:, :, None].expand_as(ids)), torch.gather(sc, 1, order)
+            return out + (torch.gather(met, 1, order),) if return_met else out
         out = torch.gather(ids, 1, order[:, :, None].expand_as(ids)), torch.gather(sc, 1, order)
         return out + (order // (nb // G),) if return_groups else out

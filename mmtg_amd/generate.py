@@ -17,8 +17,8 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .constraints import BANNED, Constraints, _check_constraints, check_groups, check_prefix, sequence_scores
-from .decode import BeamDecoder, GreedyDecoder
+from .constraints import BANNED, Constraints, _check_constraints, check_groups, check_keywords, check_prefix, sequence_scores
+from .decode import BeamDecoder, GreedyDecoder, _keywords_need_beams
 from .data import encode_line_end, encode_prefix, encode_rhyme_classes, encode_template  # noqa: F401  (public: the opening lines / the line-end sets / the line templates / the rhyme classes of generate_samples / generate_beams)
 
 SENT_SLOT = 22  # generate.py:118-121
@@ -145,6 +145,27 @@ def postprocess_tokens(preds):
     return text
 
 
+def encode_keywords(tokenizer, words, vocab_cut=13317):
+    """The phrases of keywords= (constraints.check_keywords) from words, e.g. encode_keywords(tokenizer, ["月光", "海"]): one tuple of
+    ids per word, one character one token.  A word is 1 .. 4 characters; an empty or longer word raises ValueError, as does a
+    character the tokenizer does not know ([UNK]), whitespace, a special token, PAD or an id at or above the generation's
+    vocabulary cut."""
+    if isinstance(words, str):
+        raise ValueError("keywords are a list of words, got the string %r" % (words,))
+    phrases = []
+    for w in words:
+        if not isinstance(w, str) or not 1 <= len(w) <= 4:
+            raise ValueError("keyword %r: a keyword is a word of 1..4 characters" % (w,))
+        ids = []
+        for ch in w:
+            v = -1 if ch.isspace() else int(tokenizer.convert_tokens_to_ids(ch))
+            if v in (0, 1, 2, 100, 102) or not 0 <= v < vocab_cut:
+                raise ValueError("keyword %r: character %r maps to id %d, not a content id below %d" % (w, ch, v, vocab_cut))
+            ids.append(v)
+        phrases.append(tuple(ids))
+    return phrases
+
+
 def _stack_rows(rows):
     """rows (a list of dataset items, or a dict of stacked arrays) as one tensor per model input, a prompt per row."""
     keys = ("topic_ids", "tpw_attention_mask", "tpw_type_ids", "topic_emb", "img_embs", "r_embs")
@@ -176,7 +197,7 @@ def rank_scored(scored, rank_by):
 def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperature=1.1, top_k=10, top_p=0.7,
                      repetition_penalty=1.5, max_batch=256, generator=None, decoder=None, prefixes=None, no_repeat_ngram_size=0,
                      line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False,
-                     return_scores=False, rank_by=None):
+                     return_scores=False, rank_by=None, keywords=None):
     """n_samples texts per prompt (generate.sh's loop, generate.py:205-235) on the batched, graph-replayed decoder:
     every prompt is replicated over n_samples rows, rows are decoded max_batch at a time with the device-side
     top-k / top-p sampler (one uniform per row and position from `generator`), each row is cut back to what
@@ -201,7 +222,9 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     prefix, and how many those are.  Columns a constraint decided (a template's given id, a full line's PAD) count, at the model's
     log-probability of that id; the samples of a prompt share their constraints, so ranking among them is fair.
     rank_by: "sum" or "mean" (sum / max(n_tokens, 1)) orders a prompt's samples best first (stable) and implies return_scores.
-    The texts are the strings, from the same `generator` state, of the call without the two arguments."""
+    The texts are the strings, from the same `generator` state, of the call without the two arguments.
+    keywords: refused (ValueError): a lyric that contains given words needs a search over beams -- generate_beams(keywords=)."""
+    _keywords_need_beams(keywords)
     if rank_by is not None and rank_by not in ("sum", "mean"):
         raise ValueError('rank_by must be "sum", "mean" or None, got %r' % (rank_by,))
     scoring = bool(return_scores) or rank_by is not None
@@ -268,7 +291,7 @@ def score_sequences(model, rows, ids, max_batch=256):
 def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature=1.1, repetition_penalty=1.5, max_batch=256,
                    return_all=False, prefixes=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None,
                    rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_ids=False, num_beam_groups=1,
-                   diversity_penalty=0.0, best_per_group=False):
+                   diversity_penalty=0.0, best_per_group=False, keywords=None, return_met=False):
     """Beam search per prompt on the batched, graph-replayed decoder (BeamDecoder): prompts are decoded max_batch // num_beams at
     a time, every beam is cut back to what sample_sequence would have returned (GreedyDecoder.reference_return) and
     post-processed as generate_samples does.  rows: as generate_samples.  Returns one string per prompt (its best beam), or with
@@ -283,8 +306,16 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
     lowered by the penalty for every earlier group's beam that takes the same content id at the same step; scores stay the
     unpenalised sums, so the list of return_all is still best first over all groups.  best_per_group=True returns one list per
     prompt of G entries in group order, each the best hypothesis of its group as (text, score), or (text, score, ids) with
-    return_ids; it excludes return_all."""
+    return_ids; it excludes return_all.
+    keywords: words the lyric should contain, each at a place of the model's choice -- encode_keywords(tokenizer, ["月光", "海"]), one
+    list for all prompts or one list per prompt (constraints.check_keywords; BeamDecoder.begin).  A prompt's beams are then ordered
+    by (keywords met descending, score descending), so the text returned is the best hypothesis that holds the most keywords.  The
+    search is best effort: return_met=True (with return_all) appends the number of keywords met to each beam's tuple.  Not together
+    with num_beam_groups > 1."""
     G, lam = check_groups(num_beams, num_beam_groups, diversity_penalty)
+    BeamDecoder._keywords_alone(keywords, G)
+    if return_met and (keywords is None or not return_all):
+        raise ValueError("return_met reports, per beam of return_all, the keywords it holds: give keywords= and return_all=True")
     if best_per_group and return_all:
         raise ValueError("best_per_group returns one hypothesis per group, return_all every beam: ask for one of them")
     eng = model.engine()
@@ -293,20 +324,29 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
     n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
     cons = _check_constraints(prefixes, no_repeat_ngram_size, line_lengths, line_end_ids, n_prompts, length, sh, "%d prompts" % n_prompts,
                               templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
+    kw = check_keywords(keywords, n_prompts, num_beams, sh.V, sh.msl + 2, prefix=cons.prefix)
     per = max(1, min(max_batch // num_beams, n_prompts))
     dec = BeamDecoder(model, per, num_beams, max_len=length)
     out = []
+    done = 0
     for chunk, c, n in _chunks(_stack_rows(rows), cons, per, eng.dev):
-        ids, scores, group = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty, prefix=c.prefix,
-                                          no_repeat_ngram_size=c.ngram, line_lengths=c.lines, num_beam_groups=G, diversity_penalty=lam,
-                                          return_groups=True)
+        if kw is None:
+            ids, scores, group = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty, prefix=c.prefix,
+                                              no_repeat_ngram_size=c.ngram, line_lengths=c.lines, num_beam_groups=G, diversity_penalty=lam,
+                                              return_groups=True)
+        else:                      # (the chunk's prompts' keywords; the padding rows repeat the chunk's first prompt, as _chunks does)
+            idx = list(range(done, done + n)) + [done] * (per - n)
+            ids, scores, met = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty, prefix=c.prefix,
+                                            no_repeat_ngram_size=c.ngram, line_lengths=c.lines, keywords=kw.take(idx), return_met=True)
+            group, met = torch.zeros_like(met), met.cpu().numpy()
+        done += n
         ids, scores, group = ids.cpu().numpy(), scores.cpu().numpy(), group.cpu().numpy()
         for r in range(n):
             beams = []
             for k in range(num_beams):
                 seq = GreedyDecoder.reference_return(ids[r, k].tolist(), length, sent=sh.msl + 2)
                 beams.append((postprocess_tokens(tokenizer.convert_ids_to_tokens(seq)), float(scores[r, k]))
-                             + ((ids[r, k].tolist(),) if return_ids else ()))
+                             + ((ids[r, k].tolist(),) if return_ids else ()) + ((int(met[r, k]),) if return_met else ()))
             if best_per_group:         # (best first, so a group's first place is its best)
                 out.append([beams[int(np.argmax(group[r] == g))] for g in range(G)])
             else:

@@ -132,6 +132,10 @@ _SIGS = {
     "mmtg_decode_beam_candidates_rhyme": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
                                           _vp, _vp, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_logprob": ([_vp, _l, _i, _vp, _l, _vp, _i, _vp, _l, _i, _i, _vp], _i),
+    "mmtg_decode_beam_candidates_kw": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
+                                       _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp], _i),
+    "mmtg_decode_beam_merge_kw": ([_vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _i, _vp], _i),
+    "mmtg_decode_beam_merge_kw_fixed": ([_vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
     "mmtg_decode_mlp_sync_words": ([], _i),
     "mmtg_decode_mlp_census": ([_vp, _vp], _i),
@@ -1076,6 +1080,66 @@ def decode_beam_candidates_rhyme(logits, ldl, V, seq, pos, P, sent, temperature,
     """decode_beam_candidates_tmpl under the rhyme tables: every beam reads its own (reordered) history for its leader's rhyme."""
     _beam_candidates("_rhyme", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=fixed_end,
                      ngram=ngram, tables=tables, tmpl=tmpl, rhyme=rhyme)
+
+
+def _keywords(keywords, n_prompts):
+    """The keyword tables of constraints.check_keywords on the device, (phrases int32 [prompts, 8, 4], lens int8 [prompts, 8], K,
+    the longest phrase), as the *_kw candidates entry takes them (phrases, phrase_len, K, phrase_cap)."""
+    phrases, lens, K, cap = keywords
+    if not (phrases.dtype == torch.int32 and phrases.dim() == 3 and phrases.shape[0] >= n_prompts and tuple(phrases.shape[1:]) == (8, 4)
+            and phrases.is_contiguous()):
+        raise ValueError("keyword tables: phrases must be contiguous int32 [prompts >= %d, 8, 4]" % n_prompts)
+    if not (lens.dtype == torch.int8 and lens.dim() == 2 and lens.shape[0] >= n_prompts and lens.shape[1] == 8 and lens.is_contiguous()):
+        raise ValueError("keyword tables: lens must be contiguous int8 [prompts >= %d, 8]" % n_prompts)
+    return _p(phrases), _p(lens), int(K), int(cap)
+
+
+def _cand_tables(cand_val, cand_id, cand_bank, B, W):
+    if cand_val is None and cand_id is None:
+        return
+    for t, dt in ((cand_val, torch.float32), (cand_id, torch.int32), (cand_bank, torch.int32)):
+        if t is None or t.dtype != dt or t.dim() != 2 or t.shape[0] < B or t.shape[1] != W or not t.is_contiguous():
+            raise ValueError("keyword candidates: cand_val fp32 / cand_id int32 / cand_bank int32 must be contiguous [rows >= %d, nb + K = %d]"
+                             % (B, W))
+
+
+def decode_beam_candidates_kw(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, cand_bank, B, keywords,
+                              tables=None, rhyme=None, tmpl=None, ngram=0, fixed_end=None):
+    """decode_beam_candidates_rhyme (tables None: no line rule at all; rhyme None with tables: the caller's lead table says no line
+    has a leader) offering nb + K slots per row, the last K the keywords' next ids, and each slot's bank (include/mmtg_hip.h).
+    keywords: (phrases, lens, K, longest phrase) on the device; cand_val / cand_id / cand_bank are [B, nb + K]."""
+    kw = _keywords(keywords, B // max(int(nb), 1))
+    _cand_tables(cand_val, cand_id, cand_bank, B, int(nb) + kw[2])
+    if tables is None:
+        if rhyme is not None or tmpl is not None:
+            raise ValueError("keyword candidates: templates / a rhyme scheme come with line tables")
+        rule = (_fixed(fixed_end, B), int(ngram), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+    else:
+        rule = _rule_tail("_rhyme", B, V, fixed_end, ngram, tables, tmpl, sent, rhyme)
+    _check(lib().mmtg_decode_beam_candidates_kw(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                                float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B, *rule, *kw, _p(cand_bank),
+                                                _stream()), "decode_beam_candidates_kw")
+
+
+def decode_beam_merge_kw(cand_val, cand_id, cand_bank, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, K, fixed_end=None,
+                         pos_next=None):
+    """decode_beam_merge (fixed_end given: decode_beam_merge_fixed) over nb + K candidates per parent and their banks: the nb places
+    go to the best of every bank, highest bank first, then the second best of every bank, and so on (include/mmtg_hip.h)."""
+    _cand_tables(cand_val, cand_id, cand_bank, n_prompts * nb, int(nb) + int(K))
+    held = () if fixed_end is None else (_fixed(fixed_end, n_prompts * nb),)
+    name = "decode_beam_merge_kw" + ("_fixed" if held else "")
+    _check(getattr(lib(), "mmtg_" + name)(_p(cand_val), _p(cand_id), _p(cand_bank), _p(scores), _p(seq), seq.stride(0), _p(keep),
+                                          keep.stride(0), _p(rows), rows.stride(0), _p(pos), P, sent, int(nb), int(n_prompts), _p(pos_next),
+                                          *held, int(K), _stream()), name)
+
+
+def decode_beam_merge_kw_fixed(cand_val, cand_id, cand_bank, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, fixed_end, K,
+                               pos_next=None):
+    """decode_beam_merge_kw; a prompt on a prefix column keeps every beam, score and token (include/mmtg_hip.h)."""
+    if fixed_end is None:
+        raise ValueError("decode_beam_merge_kw_fixed needs fixed_end")
+    decode_beam_merge_kw(cand_val, cand_id, cand_bank, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, K, fixed_end=fixed_end,
+                         pos_next=pos_next)
 
 
 def decode_logprob(logits, ldl, V, seq, pos, P, out, B):
