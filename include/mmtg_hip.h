@@ -525,6 +525,13 @@ MMTG_API int mmtg_decode_embed_x3(const float* table, const long long* seq, long
  * LN-fold products, LN(x) W^T + b = rstd (x Wf^T - mu colsum) + bias_f.  W: [N, ldw] bf16 K-contiguous; bias may be null.   */
 MMTG_API int mmtg_ln_fold_weights(const void* W, long ldw, const float* gamma, const float* beta, const float* bias, void* Wf,
                          float* colsum, float* bias_f, int N, int K, void* stream);
+/* qkv [B, 3 * nH * 64]: the token's q | k | v.  k and v are stored into slot *pos_ptr of kcache / vcache [B, nH, Tmax, 64]; out [B, nH * 64]
+ * = softmax(q . K / 8) V over the slots 0 .. *pos_ptr whose keep[b, slot] is non-zero (keep: int32, row stride ldkeep).  No slot above
+ * *pos_ptr is read, nor (at *pos_ptr >= 1) slot *pos_ptr itself before it is written.
+ * Cache contents (a condition on the caller, for this entry and every mmtg_decode_attn_split* form): every slot at or below
+ * max(*pos_ptr - 1, 0) of both caches must hold FINITE values, whether its key is masked or not -- a masked key's value row is not
+ * skipped but weighted with an exact zero, and at *pos_ptr = 0 the old contents of slot 0 are read the same way before the token's
+ * own row replaces them.  A NaN or infinity there reaches the output (0 * NaN).  Caches allocated zeroed satisfy it.            */
 MMTG_API int mmtg_decode_attn(int dtype, const void* qkv, void* kcache, void* vcache, const int* keep, long ldkeep,
                      const int* pos_ptr, void* out, int B, int nH, int dh, int Tmax, void* stream);
 /* the same, taking the c_attn product as MMTG_EPI_SPLIT slabs (part: f32 [splits][B][3*D]) plus its bias:

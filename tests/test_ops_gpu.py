@@ -15,34 +15,10 @@ pytestmark = pytest.mark.gpu
 
 from mmtg_amd import hip  # noqa: E402
 from oracle import mmtg_oracle as O  # noqa: E402
+from helpers import close, rnd, tol  # noqa: E402,F401
 
 DEV = "cuda"
 DTYPES = [torch.float32, torch.bfloat16]
-
-
-def rnd(*shape, dtype=torch.float32, scale=1.0, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(*shape, generator=g) * scale
-    return x.to(dtype)
-
-
-def tol(dtype, k=1):
-    """(atol, rtol) for an output of O(1) magnitude reduced over k terms."""
-    if dtype == torch.float32:
-        return 2e-5 * max(1.0, math.sqrt(k) / 8), 2e-5
-    return 1e-2 * max(1.0, math.sqrt(k) / 16), 1.2e-2
-
-
-def close(got, ref, dtype, k=1, name="", scale=None):
-    got = got.detach().float().cpu()
-    ref = ref.detach().float().cpu()
-    atol, rtol = tol(dtype, k)
-    s = float(ref.abs().max()) if scale is None else scale
-    atol *= max(s, 1e-6)
-    err = (got - ref).abs()
-    bad = err > atol + rtol * ref.abs()
-    assert not bad.any(), "%s: %d/%d mismatches, max err %.3e (ref max %.3e, atol %.2e)" % (
-        name, int(bad.sum()), bad.numel(), float(err.max()), s, atol)
 
 
 # ------------------------------------------------------------------ GEMM

@@ -11,13 +11,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from mmtg_amd import hip  # noqa: E402
+from helpers import planes_of  # noqa: E402
 
 DEV = "cuda"
-
-
-def planes_of(x):
-    rows, cols = x.shape
-    return hip.split_planes(x.contiguous(), rows, cols, hip.Planes.empty(rows, cols, x.device))
 
 
 def test_split_planes_reconstructs_to_2_pow_minus_17():
