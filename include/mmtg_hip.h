@@ -302,7 +302,13 @@ MMTG_API int mmtg_dropout_apply(int dtype, const void* x, void* y, long n, int N
 /* ---------------------------------------------------------------- LM head loss (loss.py:45-74 + GPT-2's internal CE)
  * logits: f32 [M, ldl] (columns >= V ignored).  labels per row t are
  * cat(topic_ids, targets)[b, t+1] (label_zero != 0: all labels 0, the
- * inference branch's dummy labels, model.py:314).
+ * inference branch's dummy labels, model.py:314).  A label outside
+ * [0, V) is clamped into the row (forward and backward alike): below 0
+ * reads column 0, V or more reads column V - 1.  The logits in columns
+ * below V must be finite: rows longer than 16384 are reduced with a running
+ * (max, sum), and there an aligned run of eight -inf followed by a finite
+ * slice turns the row's sum into NaN (training logits are an unmasked
+ * product, so nothing masks them with -inf).
  * Outputs (all f32): nll[M] (0 on each sample's last row), lse[M],
  * sample_ce[B], coef[B] = d loss / d CE_b / n_tok / batch_denominator,
  * scalars[0] = MyLoss (sum_b l_b / batch_den), scalars[1] = GPT-2 LM loss.    */
@@ -393,7 +399,8 @@ MMTG_API int mmtg_sumsq(const float* x, long n, float* out, float* ws, long ws_f
  * (bias-corrected, eps outside the sqrt, decoupled wd) + optional bf16 copy.
  * count (optional, device scalar): g holds a SUM over rows and *count the global row count
  * (all-reduced on the device, never read by the host): the gradient is g * grad_scale / *count;
- * *count == 0 leaves every buffer untouched (the reference skips an empty batch, train.py:184-185). */
+ * a *count that is not greater than 0 (0, negative, NaN) skips the step: p, m, v and both copies keep
+ * every bit (the reference skips an empty batch, train.py:184-185). */
 /* p_lo (nullable; with p_bf16): the x3 mode's lo plane, bf16(p - bf16(p)) -- p_bf16 / p_lo are then the weights' plane pair. */
 MMTG_API int mmtg_adamw(float* p, const float* g, float* m, float* v, void* p_bf16, void* p_lo, long n,
                float lr, float beta1, float beta2, float eps, float wd, int step,

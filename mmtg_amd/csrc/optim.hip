@@ -35,6 +35,20 @@ __global__ __launch_bounds__(256) void sumsq_final_kernel(const float* __restric
     if (threadIdx.x == 0) out[0] = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
+// One parameter's update, shared by the 16-byte path and the scalar fallback of adamw_kernel so that both round alike: left to
+// the compiler's contraction the two loops fused b1 m + (1 - b1) g differently (the vector loop around (1 - b1) g, the scalar
+// loop around b1 m), and the last bit of m depended on the alignment of the pointers.  The fused forms are the vector loop's.
+__device__ __forceinline__ void adamw_update(float g, float& m, float& v, float& p, float coef, float b1, float b2, float eps,
+                                             float lrwd, float step_size) {
+#pragma clang fp contract(off)
+    const float gi = g * coef;
+    const float mi = fmaf(1.f - b1, gi, b1 * m);
+    const float vi = fmaf(b2, v, gi * ((1.f - b2) * gi));
+    float pi = fmaf(-step_size, mi / (sqrtf(vi) + eps), p);
+    if (lrwd > 0.f) pi = fmaf(-lrwd, pi, pi);
+    m = mi; v = vi; p = pi;
+}
+
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
         float* __restrict__ m, float* __restrict__ v, bf16* __restrict__ pc, bf16* __restrict__ pl, long n, float lr, float b1, float b2,
         float eps, float wd, float step_size, const float* __restrict__ normsq, float max_norm, float gscale,
@@ -53,6 +67,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
         const float nrm = sqrtf(*normsq) * gscale;
         coef *= fminf(1.0f, max_norm / (nrm + 1e-6f));
     }
+    const float lrwd = wd > 0.f ? lr * wd : 0.f;      // decoupled decay p -= lr wd p (wd > 0 only)
     // 16-byte vectors (four parameters per lane and pass); the flat buffers are 16-byte aligned and n is a multiple of 4
     // for every layout the engine builds (a scalar tail covers anything else)
     const bool vec_ok = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
@@ -64,11 +79,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
         bf16x4 c4, l4;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float gi = g4[e] * coef;
-            const float mi = b1 * m4[e] + (1.f - b1) * gi;
-            const float vi = b2 * v4[e] + (1.f - b2) * gi * gi;
-            float pi = p4[e] - step_size * (mi / (sqrtf(vi) + eps));
-            if (wd > 0.f) pi -= lr * wd * pi;
+            float mi = m4[e], vi = v4[e], pi = p4[e];
+            adamw_update(g4[e], mi, vi, pi, coef, b1, b2, eps, lrwd, step_size);
             m4[e] = mi; v4[e] = vi; p4[e] = pi;
             c4[e] = (bf16)pi;
             l4[e] = (bf16)(pi - (float)c4[e]);
@@ -80,11 +92,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
         if (pl) reinterpret_cast<bf16x4*>(pl)[i] = l4;
     }
     for (long i = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float gi = g[i] * coef;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        float pi = p[i] - step_size * (mi / (sqrtf(vi) + eps));
-        if (wd > 0.f) pi -= lr * wd * pi;
+        float mi = m[i], vi = v[i], pi = p[i];
+        adamw_update(g[i], mi, vi, pi, coef, b1, b2, eps, lrwd, step_size);
         m[i] = mi; v[i] = vi; p[i] = pi;
         if (pc) pc[i] = (bf16)pi;
         if (pl) pl[i] = (bf16)(pi - (float)(bf16)pi);
