@@ -826,6 +826,50 @@ MMTG_API int mmtg_decode_beam_merge_kw_fixed(const float* cand_val, const int* c
                                     long ldseq, int* keep, long ldkeep, int* rows, long ldrows, const int* pos_ptr, int P, int sent,
                                     int nb, int n_prompts, int* pos_next, const int* fixed_end, int K, void* stream);
 
+/* ---- refrain schemes (GreedyDecoder / BeamDecoder with refrain_scheme=, mmtg_amd/decode.py): lines that repeat a line, whatever
+ * the model wrote there.  The reference has no such constraint (generate.py:117-142); a template repeats only text the caller knows,
+ * a rhyme makes lines agree on a class, and n-gram blocking forbids a repeated line outright.  A scheme ("AB.A") groups the lines: the
+ * first line of a letter is its source, an ordinary line under every rule above; every later line of the letter is a copy.
+ * src int8 [B, n_lines], src[b, l] = the source's line (< l) of copy line l, else -1 (so n_lines <= 128; a line l >= n_lines is no
+ * copy; a value outside 0 .. l - 1 is read as -1).  With beams a prompt's rows share its row of the table.
+ *   copy column: row b about to fill lyric index j, not on a held prefix column (pos + 1 >= fixed_end[b]) and not on a forced
+ *     [#START#] / [#EOS#] column, with l = j / sent and r = src[b, l] >= 0, writes seq[j - (l - r) * sent] of its OWN history: the id it
+ *     holds at the same column of line r (a beam's reordered history; a source inside a given prefix counts; r < l, so the source line
+ *     is complete).  The copy is literal and comes first: it is decided before the sticky-PAD test, before the test for logits, before
+ *     the line rule, the template symbol and every ban; no logits are consulted, and no ban or mask applies to it.  A source that ended
+ *     at column c is reproduced with its PADs, so no line-end logic is involved.  Beams: the id at log-probability 0 in slot 0 and id-0
+ *     fillers at -inf, as a template's given id is offered (the merge keeps every live beam and its score); on a step without logits
+ *     nothing is offered, as ever.  The copied ids are ordinary history afterwards: for the penalty, for later n-gram keys, as a later
+ *     end set's "previous token".  A copy can never trip the n-gram rule, but the text after it cannot repeat it.
+ *   every other column: the *_rhyme entry's rule on the same tables, bit for bit.
+ * The rhyme form's own tables may be the "no rule" forms, n_lines still being the width of src: lo and hi null together (no line
+ * rule at all: then sets, set_of, tmpl, class_of and lead are null and n_sets and distinct 0), and class_of and lead null together
+ * (no rhyme scheme: distinct 0).  One form so serves a refrain with or without bounds, end sets, templates and rhymes.
+ * Each entry is its *_rhyme namesake plus src before the stream.  A null src, n_lines outside 1 .. 128, tables that do not come
+ * together as above, or an n-gram size outside 0 .. sent - 2 fail before any device call.  mmtg_decode_select_refrain alone takes
+ * null logits (the decoders skip the head on a step whose every row copies or is held): a copy column is written, and every other
+ * row does what the plain entries do without logits (the forced cadence; else nothing).  The copy is one table read and one id
+ * read, the same addresses in every thread of the row's workgroup; thread 0 stores.  The beam merge is unchanged.  Keywords and a
+ * refrain are not combined: mmtg_decode_beam_candidates_kw has no src.  The kernels of every earlier entry compile to the same code as
+ * before these were added (profiles/r17_refrain_decode_disassembly_diff.txt).                                                      */
+MMTG_API int mmtg_decode_select_refrain(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                              int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, const int* fixed_end,
+                              int ngram, const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets,
+                              int n_sets, const short* set_of, const int* tmpl, const short* class_of, const signed char* lead,
+                              int distinct, const signed char* src, void* stream);
+MMTG_API int mmtg_decode_sample_refrain(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                              int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                              const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, int ngram,
+                              const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
+                              const short* set_of, const int* tmpl, const short* class_of, const signed char* lead, int distinct,
+                              const signed char* src, void* stream);
+MMTG_API int mmtg_decode_beam_candidates_refrain(const float* logits, long ldl, int V, const long long* seq, long ldseq,
+                                       const int* pos_ptr, int P, int sent, float temperature, float rep_penalty, int nb,
+                                       float* cand_val, int* cand_id, int B, const int* fixed_end, int ngram, const unsigned char* lo,
+                                       const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets, const short* set_of,
+                                       const int* tmpl, const short* class_of, const signed char* lead, int distinct,
+                                       const signed char* src, void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

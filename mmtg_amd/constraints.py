@@ -1,6 +1,6 @@
 """The constraints of a generation, checked and packed on the host before any device work (prefix, n-gram size, beam groups; line
-bounds / end sets / templates / rhyme scheme as LineTables), and the host-side scoring of token log-probabilities.  numpy and
-Python only: decode.py uploads the tables and chooses the launches, include/mmtg_hip.h states the rules the kernels apply."""
+bounds / end sets / templates / rhyme scheme / refrain scheme as LineTables), and the host-side scoring of token log-probabilities.
+numpy and Python only: decode.py uploads the tables and chooses the launches, include/mmtg_hip.h states the rules the kernels apply."""
 from __future__ import annotations
 
 import math
@@ -83,8 +83,9 @@ def chosen_mask(ids, sent=22, prefix_lens=None):
     prefix (j >= prefix_lens[b]; None: no prefix) and the previous column is not PAD (ids[b][j - 1] != 0) -- so the first PAD of a
     line counts (the model ended the line there; in an empty line that is its first content column) and the sticky PADs behind
     it, which no model call decided, do not.
-    Columns that a constraint decided (a template's given id, a full line's PAD) count: their value is the model's log-probability
-    of that id.  Samples of one prompt share their constraints, so ranking among them is fair."""
+    Columns that a constraint decided (a template's given id, a full line's PAD, a refrain's copied id) count: their value is the
+    model's log-probability of that id -- the log-probability node scores whatever the column holds.  Samples of one prompt share
+    their constraints, so ranking among them is fair."""
     a = np.asarray(ids.detach().cpu().numpy() if torch.is_tensor(ids) else ids)
     if a.ndim != 2:
         raise ValueError("ids must be [rows, 1 + length] (got shape %s)" % (a.shape,))
@@ -119,11 +120,15 @@ class LineTables:
     v <= -2 the class `sets[-2 - v]` (classes and end sets share the table); a template's length is folded into lo / hi.
     class_of, lead, distinct (rhyme_scheme= only, else None, None, False): class_of int16 [V], the row of `sets` that is id v's rhyme
     class or -1; lead int8 [rows, n_lines], the leader's line of a follower line or -1; a leader's static end set (the union of the
-    classes) is folded into set_of."""
+    classes) is folded into set_of.
+    src (refrain_scheme= only, else None): int8 [rows, n_lines], the source's line of a copy line or -1 (check_refrain).  bare: the
+    tables were made for src alone -- no line argument was given, lo / hi are the unconstrained (0, sent - 2) -- so the decoders
+    upload no line tables for them."""
 
-    def __init__(self, lo, hi, set_of, sets, sent, V, tmpl=None, class_of=None, lead=None, distinct=False):
+    def __init__(self, lo, hi, set_of, sets, sent, V, tmpl=None, class_of=None, lead=None, distinct=False, src=None, bare=False):
         self.lo, self.hi, self.set_of, self.sets, self.sent, self.V, self.tmpl = lo, hi, set_of, sets, sent, V, tmpl
         self.class_of, self.lead, self.distinct = class_of, lead, bool(distinct)
+        self.src, self.bare = src, bool(bare)
 
     @property
     def rows(self):
@@ -133,13 +138,19 @@ class LineTables:
         """Every row k times in place of itself (the beams of a prompt share its constraints)."""
         rep = lambda a: None if a is None else np.repeat(a, k, axis=0)      # noqa: E731
         return LineTables(rep(self.lo), rep(self.hi), rep(self.set_of), self.sets, self.sent, self.V, rep(self.tmpl),
-                          self.class_of, rep(self.lead), self.distinct)
+                          self.class_of, rep(self.lead), self.distinct, rep(self.src), self.bare)
 
     def take(self, idx):
         """Rows idx (a list of row indices) as tables of their own; the sets are shared."""
         sub = lambda a: None if a is None else np.ascontiguousarray(a[idx])      # noqa: E731
         return LineTables(sub(self.lo), sub(self.hi), sub(self.set_of), self.sets, self.sent, self.V, sub(self.tmpl),
-                          self.class_of, sub(self.lead), self.distinct)
+                          self.class_of, sub(self.lead), self.distinct, sub(self.src), self.bare)
+
+    def source(self, b, l):
+        """The line whose text row b's line l repeats (l is a copy line), or None."""
+        if self.src is None or l >= self.src.shape[1] or self.src[b, l] < 0:
+            return None
+        return int(self.src[b, l])
 
     def leader(self, b, l):
         """The line whose ending decides the rhyme of row b's line l (l is a follower), or None."""
@@ -517,6 +528,88 @@ def check_lines(line_lengths, line_end_ids, rows, length, sent=22, V=None, prefi
     return _pack(t)
 
 
+def _refrain_rows(spec, rows):
+    """refrain_scheme as one string per row (_scheme_rows' forms, under its own name in the messages)."""
+    try:
+        return _scheme_rows(spec, rows)
+    except ValueError as e:
+        raise ValueError(str(e).replace("rhyme_scheme", "refrain_scheme")) from None
+
+
+def check_refrain(refrain_scheme, rows, length, sent=22, lines=None, prefix=None, rhyme_scheme=None):
+    """Validate refrain_scheme= on the host, before any device work; returns src int8 [rows, n_lines] -- src[b, l] the line whose text
+    line l of row b repeats, always < l, or -1 -- or None for refrain_scheme=None.
+
+    A scheme is a string over letters and `.`, one for every row or a list with one string or None per row (rhyme_scheme's forms).
+    Character l speaks for lyric line l; lines past the string are free.  Lines with the same letter hold the same text: the first
+    line of a letter is its source, an ordinary line under every other rule, and every later line of that letter is a copy of it
+    ("AAA": lines 1 and 2 both copy line 0).  `.` and a letter used once mean nothing.  On a copy column -- not a held prefix column,
+    not a forced [#START#] / [#EOS#] -- the row writes the id its own history holds at the same column of the source line
+    (include/mmtg_hip.h states the rule); no logits, bans or masks are involved, so a copy line is not the model's to shape:
+      lines (check_lines' tables of the same generation, optional): a copy line carries no bounds other than its source's or the
+        default (0, sent - 2), no end set, no template, and in rhyme_scheme (the argument, optional) no letter other than `.`;
+      prefix (check_prefix's lists, optional): a prefix may not end inside a copy line, and a copy line it gives whole must equal its
+        source (given too, since it lies before).  Whole given lines are otherwise the caller's text, as prefix columns always are.
+    Raises ValueError for symbols other than letters and `.`, a scheme longer than the generation has lines (at most 128), and any
+    of the above."""
+    if refrain_scheme is None:
+        return None
+    if length < 1 or not 3 <= sent <= 257:
+        raise ValueError("refrain_scheme needs length >= 1 and 3 <= sent <= 257 (got length %d, sent %d)" % (length, sent))
+    n_lines, cap = (length - 1) // sent + 1, sent - 2
+    if n_lines > 128:
+        raise ValueError("refrain_scheme: a generation of %d lines (a scheme serves up to 128)" % n_lines)
+    schemes = _refrain_rows(refrain_scheme, rows)
+    rhymes = None if rhyme_scheme is None else _scheme_rows(rhyme_scheme, rows)
+    src = np.full((rows, n_lines), -1, np.int8)
+    own = "refrain_scheme row %d, line %d: a copy line repeats its source (line %d) and is not the model's to shape; it takes no %s"
+    for b, sch in enumerate(schemes):
+        if not all(ch == "." or ch.isalpha() for ch in sch):
+            raise ValueError("refrain_scheme row %d: %r holds symbols other than letters and '.'" % (b, sch))
+        if len(sch) > n_lines:
+            raise ValueError("refrain_scheme row %d has %d lines, a generation of length %d holds %d" % (b, len(sch), length, n_lines))
+        first = {}
+        for l, ch in enumerate(sch):
+            if ch == ".":
+                continue
+            if ch not in first:
+                first[ch] = l
+                continue
+            r = src[b, l] = first[ch]
+            if lines is not None and l < lines.lo.shape[1]:
+                mine, its = (int(lines.lo[b, l]), int(lines.hi[b, l])), (int(lines.lo[b, r]), int(lines.hi[b, r]))
+                if lines.tmpl is not None and (lines.tmpl[b, l] != -1).any():
+                    raise ValueError(own % (b, l, r, "template"))
+                if lines.lead is not None and lines.lead[b, l] >= 0:
+                    raise ValueError(own % (b, l, r, "rhyme letter other than '.'"))
+                if lines.set_of is not None and lines.set_of[b, l] >= 0:
+                    raise ValueError(own % (b, l, r, "end set (line_end_ids, or the leader of a rhyme group)"))
+                if mine != (0, cap) and mine != its:
+                    raise ValueError(own % (b, l, r, "bounds other than its source's %r or the default (got %r)" % (its, mine)))
+            if rhymes is not None and l < len(rhymes[b]) and rhymes[b][l] != ".":
+                raise ValueError(own % (b, l, r, "rhyme letter other than '.'"))
+        if prefix is not None:
+            p = prefix[b]
+            l, q = (len(p) - 1) // sent, (len(p) - 1) % sent
+            if 1 <= q <= cap and l < n_lines and src[b, l] >= 0:
+                raise ValueError("prefix row %d ends inside line %d, a copy line of the refrain scheme (give the line whole, or not at all)"
+                                 % (b, l))
+            for l in range(n_lines):
+                r = int(src[b, l])
+                if r >= 0 and len(p) > l * sent + cap:
+                    if list(p[l * sent + 1:l * sent + 1 + cap]) != list(p[r * sent + 1:r * sent + 1 + cap]):
+                        raise ValueError("prefix row %d gives line %d, a copy line of the refrain scheme, with a text other than its "
+                                         "source's (line %d)" % (b, l, r))
+    return src
+
+
+def _bare_tables(rows, length, sent, V, src):
+    """LineTables that carry a refrain alone: every line unconstrained."""
+    n_lines = (length - 1) // sent + 1
+    return LineTables(np.zeros((rows, n_lines), np.uint8), np.full((rows, n_lines), sent - 2, np.uint8), None, None, sent, V, src=src,
+                      bare=True)
+
+
 class Constraints:
     """The checked constraints of a generation's rows: ngram (the n-gram size), prefix (check_prefix's lists, or None) and lines
     (LineTables, or None).  take(idx) / repeat(k) are LineTables' own, on the prefix and the tables together."""
@@ -534,20 +627,33 @@ class Constraints:
 
 
 def _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, rows, length, sh, what, templates=None,
-                       rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False):
+                       rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, refrain_scheme=None):
     """The constraint arguments of ``begin`` for `rows` rows (`what` names them in messages), checked, as Constraints.  A LineTables
-    given as line_lengths is taken as checked."""
+    given as line_lengths is taken as checked (its src included: no refrain_scheme beside it).  A refrain scheme travels in the
+    tables' src; given without any line argument, the tables are bare."""
     sent = sh.msl + 2
     ngram = check_ngram(no_repeat_ngram_size, sent)
     pre = None if prefix is None else check_prefix(prefix, rows, length, sent=sent, V=sh.V)
     if not isinstance(line_lengths, LineTables):
         line_lengths = check_lines(line_lengths, line_end_ids, rows, length, sent=sent, V=min(sh.V, 13317), prefix=pre, templates=templates,
                                    rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct)
+        src = check_refrain(refrain_scheme, rows, length, sent=sent, lines=line_lengths, prefix=pre, rhyme_scheme=rhyme_scheme)
+        if src is not None:
+            if line_lengths is None:
+                line_lengths = _bare_tables(rows, length, sent, min(sh.V, 13317), src)
+            else:
+                line_lengths.src = src
     elif (line_lengths.rows != rows or line_end_ids is not None or templates is not None or rhyme_scheme is not None
-            or rhyme_classes is not None or rhyme_distinct):
-        raise ValueError("line tables of %d rows for %s (and no line_end_ids / templates / rhyme_scheme beside them)"
+            or rhyme_classes is not None or rhyme_distinct or refrain_scheme is not None):
+        raise ValueError("line tables of %d rows for %s (and no line_end_ids / templates / rhyme_scheme beside them, nor a refrain_scheme)"
                          % (line_lengths.rows, what))
     return Constraints(ngram, pre, line_lengths)
+
+
+def refrain_without_keywords(keywords, lines):
+    """keywords= together with a refrain scheme is the one combination left out: the keyword candidates know nothing of copy lines."""
+    if keywords is not None and lines is not None and lines.src is not None:
+        raise ValueError("keywords= and refrain_scheme= are not combined: the keyword candidates have no copy columns (ask for one of them)")
 
 
 # ------------------------------------------------------------------ keywords (BeamDecoder with keywords=; the rule's home is include/mmtg_hip.h)

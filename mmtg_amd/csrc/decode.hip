@@ -1093,7 +1093,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void de
 }
 
 // The selection kernels below end in one argument, the step's rule R: NoRule (the plain entries), FixedEnd (*_fixed), NgramBan
-// (*_ngram), LineRule (*_lines), TemplateRule (*_tmpl) or RhymeRule (*_rhyme).  A rule says which rows it holds (held) and, with R::ngram (the sentinel of penalize<true> is
+// (*_ngram), LineRule (*_lines), TemplateRule (*_tmpl), RhymeRule (*_rhyme) or RefrainRule (*_refrain).  A rule says which rows it holds (held) and, with R::ngram (the sentinel of penalize<true> is
 // in use; bans() gives the NgramBan) and R::lines (PAD's slot is read; col() says what the line wants of a free column), which
 // edits of the occurrence table the kernel makes after count_ids.
 //
@@ -1108,13 +1108,13 @@ struct LineCol {
 };
 
 struct NoRule {
-    static constexpr bool ngram = false, lines = false, tmpl = false, rhyme = false;
+    static constexpr bool ngram = false, lines = false, tmpl = false, rhyme = false, refrain = false;
     __device__ __forceinline__ bool held(int, int) const { return false; }
 };
 
 struct FixedEnd {
     const int* fixed_end;   // int32 [B]
-    static constexpr bool ngram = false, lines = false, tmpl = false, rhyme = false;
+    static constexpr bool ngram = false, lines = false, tmpl = false, rhyme = false, refrain = false;
     __device__ __forceinline__ bool held(int b, int pos) const { return pos + 1 < fixed_end[b]; }
 };
 
@@ -1126,7 +1126,7 @@ struct NgramBan {
     const int* fixed_end;   // int32 [B] or null
     int n;                  // 1 .. sent - 2
     int hist_cap;           // ints of dynamic LDS for the staged history (>= the longest history, min(ldseq - P, MAXGEN))
-    static constexpr bool ngram = true, lines = false, tmpl = false, rhyme = false;
+    static constexpr bool ngram = true, lines = false, tmpl = false, rhyme = false, refrain = false;
     __device__ __forceinline__ bool held(int b, int pos) const { return fixed_end && pos + 1 < fixed_end[b]; }
     __host__ __device__ __forceinline__ const NgramBan& bans() const { return *this; }
 };
@@ -1164,7 +1164,7 @@ struct LineRule {
     const short* set_of;           // [B, n_lines] row of `sets` (-1: no end set), or null
     const unsigned* sets;          // [n_sets, words] bit v of a row: content id v is in the set
     int n_lines, n_sets, words;    // words >= ceil(V / 32)
-    static constexpr bool ngram = true, lines = true, tmpl = false, rhyme = false;
+    static constexpr bool ngram = true, lines = true, tmpl = false, rhyme = false, refrain = false;
     __device__ __forceinline__ bool held(int b, int pos) const { return ng.held(b, pos); }
     __host__ __device__ __forceinline__ const NgramBan& bans() const { return ng; }
 
@@ -1214,7 +1214,7 @@ struct TmplCol {
 struct TemplateRule {
     LineRule ln;
     const int* table;              // [B, n_lines, sent - 2]
-    static constexpr bool ngram = true, lines = true, tmpl = true, rhyme = false;
+    static constexpr bool ngram = true, lines = true, tmpl = true, rhyme = false, refrain = false;
     __device__ __forceinline__ bool held(int b, int pos) const { return ln.held(b, pos); }
     __host__ __device__ __forceinline__ const NgramBan& bans() const { return ln.ng; }
     __device__ __forceinline__ LineCol col(int b, int j, int sent, const long long* gen) const { return ln.col(b, j, sent, gen); }
@@ -1255,7 +1255,7 @@ struct RhymeRule {
     const signed char* lead;       // [B, n_lines] the leader's line (< l), or -1
     int distinct;                  // a follower may not end on an id an earlier line of its group ends on
     int V;
-    static constexpr bool ngram = true, lines = true, tmpl = true, rhyme = true;
+    static constexpr bool ngram = true, lines = true, tmpl = true, rhyme = true, refrain = false;
     __device__ __forceinline__ bool held(int b, int pos) const { return tm.held(b, pos); }
     __host__ __device__ __forceinline__ const NgramBan& bans() const { return tm.ln.ng; }
     __device__ __forceinline__ TmplCol sym(int b, int j, int sent) const {
@@ -1323,6 +1323,36 @@ struct RhymeRule {
     }
 };
 
+// Refrain schemes (the *_refrain entries, include/mmtg_hip.h): a RhymeRule plus src[b, l], the line whose text line l of row b repeats
+// (-1: line l is no copy).  On a copy column the row writes the id its own history holds at the same column of the source line, before
+// every other test but the held prefix and the cadence; everywhere else the rule is rh's.  rh's own tables may be the "no rule" forms:
+// lo / hi null (no line rule at all; n_lines is still the width of src) and lead null (no rhyme scheme).
+struct RefrainRule {
+    RhymeRule rh;
+    const signed char* src;        // [B, n_lines] the source's line (< l), or -1
+    static constexpr bool ngram = true, lines = true, tmpl = true, rhyme = true, refrain = true;
+    __device__ __forceinline__ bool held(int b, int pos) const { return rh.held(b, pos); }
+    __host__ __device__ __forceinline__ const NgramBan& bans() const { return rh.bans(); }
+    __device__ __forceinline__ TmplCol sym(int b, int j, int sent) const { return rh.sym(b, j, sent); }
+    __device__ __forceinline__ LineCol col(int b, int j, int sent, const long long* gen, bool* rhymes) const {
+        if (rh.lead) return rh.col(b, j, sent, gen, rhymes);
+        *rhymes = false;
+        return rh.tm.ln.lo ? rh.tm.ln.col(b, j, sent, gen) : LineCol{false, false, nullptr};
+    }
+    __device__ __forceinline__ void ban_distinct(unsigned* cnt, int b, int j, int sent, const long long* gen, const LineCol& lc,
+                                                 bool rhymes, int tid) const {
+        rh.ban_distinct(cnt, b, j, sent, gen, lc, rhymes, tid);         // (rhymes is false without a lead table)
+    }
+
+    // the lyric index row b copies into index j (the same column of its source line; < j), or -1: no copy column
+    __device__ __forceinline__ int copy_from(int b, int j, int sent) const {
+        const int l = j / sent;
+        if (l >= rh.tm.ln.n_lines) return -1;
+        const int r = src[(long)b * rh.tm.ln.n_lines + l];
+        return r >= 0 && r < l ? j - (l - r) * sent : -1;
+    }
+};
+
 // logits processor + arg-max + forced-token cadence + append (generate.py:117-142), device-driven.
 template <typename R>
 __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restrict__ logits, long ldl, int V,
@@ -1342,6 +1372,10 @@ __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restr
     long long* gen = seq + (long)b * ldseq + P;
     if (j > 1 && (j + 1) % sent == 0) { if (tid == 0) gen[j] = 2; return; }     // [#EOS#]
     if (j > 1 && (j + 1) % sent == 1) { if (tid == 0) gen[j] = 1; return; }     // [#START#]
+    if constexpr (R::refrain) {                // a copy column: the id the row's own history holds there in the source line, literally
+        const int q = rule.copy_from(b, j, sent);
+        if (q >= 0) { const long long v = gen[q]; if (tid == 0) gen[j] = v; return; }
+    }
     if (!have_logits) return;
     const int n = min(j, MAXGEN);
     if (gen[n - 1] == 0) { if (tid == 0) gen[j] = 0; return; }                   // sticky PAD
@@ -1427,6 +1461,14 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const float* __res
     float* const cv = cand_val + (long)b * nb;
     int* const ci = cand_id + (long)b * nb;
     const long long* gen = seq + (long)b * ldseq + P;
+    if constexpr (R::refrain) {                            // a copy column: the source's id with the score unchanged, as a given id
+        const int q = rule.copy_from(b, j, sent);
+        if (q >= 0) {
+            const int v = (int)gen[q];
+            if (tid < nb) { cv[tid] = tid == 0 ? 0.f : -INFINITY; ci[tid] = tid == 0 ? v : 0; }
+            return;
+        }
+    }
     const int n = min(j, MAXGEN);
     if (gen[n - 1] == 0) {                                 // sticky PAD: PAD with the score unchanged
         if (tid < nb) { cv[tid] = tid == 0 ? 0.f : -INFINITY; ci[tid] = 0; }
@@ -2486,6 +2528,71 @@ extern "C" int mmtg_decode_beam_candidates_rhyme(const float* logits, long ldl, 
         return e;
     return beam_candidates_launch("decode_beam_candidates_rhyme", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
                                   nb, cand_val, cand_id, B, stream, rr);
+}
+
+// (a *_refrain entry's checks: src, and the rhyme form's tables where they are given -- lo / hi null: no line rule, then every other
+// table is null too; class_of / lead null: no rhyme scheme.  Logits are not asked for here: the select entry runs without them)
+static int refrain_check(const char* what, int V, long ldseq, int P, int sent, const int* fixed_end, int ngram, const unsigned char* lo,
+                         const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
+                         const short* class_of, const signed char* lead, int distinct, const signed char* src, RefrainRule* rf) {
+    MMTG_REQUIRE(src, "%s: src [B, n_lines] is needed", what);
+    MMTG_REQUIRE(n_lines >= 1 && n_lines <= 128, "%s: %d lines, a source's line index must fit a signed char (1..128)", what, n_lines);
+    MMTG_REQUIRE(sent > 2 && ngram >= 0 && ngram <= sent - 2, "%s: n-gram size %d outside 0..%d (sent - 2)", what, ngram, sent - 2);
+    MMTG_REQUIRE(ldseq > P && P >= 0 && V >= 0, "%s: bad sequence layout (ldseq %ld, P %d)", what, ldseq, P);
+    MMTG_REQUIRE((lo != nullptr) == (hi != nullptr), "%s: lo and hi come together", what);
+    MMTG_REQUIRE(n_sets >= 0 && (n_sets > 0) == (sets != nullptr) && (n_sets > 0) == (set_of != nullptr),
+                 "%s: end sets need sets, set_of and n_sets > 0 together (n_sets %d)", what, n_sets);
+    MMTG_REQUIRE(lo || (!sets && !tmpl && !class_of && !lead), "%s: line tables without lo / hi", what);
+    MMTG_REQUIRE((class_of != nullptr) == (lead != nullptr), "%s: class_of [V] and lead [B, n_lines] come together", what);
+    MMTG_REQUIRE(!lead || n_sets > 0, "%s: rhyme classes are rows of sets (n_sets %d)", what, n_sets);
+    MMTG_REQUIRE(distinct == 0 || (distinct == 1 && lead), "%s: distinct is 0 or, with a rhyme scheme, 1 (got %d)", what, distinct);
+    const int cap = ngram > 0 ? (int)(ldseq - P < MAXGEN ? ldseq - P : MAXGEN) : 0;
+    *rf = RefrainRule{RhymeRule{TemplateRule{LineRule{NgramBan{fixed_end, ngram, cap}, lo, hi, set_of, sets, n_lines, n_sets, (V + 31) / 32},
+                                             tmpl}, class_of, lead, distinct, V}, src};
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_select_refrain(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                          int P, int sent, float temperature, float rep_penalty, int B, int* pos_next, const int* fixed_end,
+                                          int ngram, const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets,
+                                          int n_sets, const short* set_of, const int* tmpl, const short* class_of,
+                                          const signed char* lead, int distinct, const signed char* src, void* stream) {
+    RefrainRule rf;
+    if (int e = refrain_check("decode_select_refrain", V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, tmpl,
+                              class_of, lead, distinct, src, &rf))
+        return e;
+    return decode_select_launch("decode_select_refrain", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, 1, 0.f,
+                                nullptr, 0, B, pos_next, stream, rf);
+}
+
+extern "C" int mmtg_decode_sample_refrain(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                          int P, int sent, float temperature, float rep_penalty, int top_k, float top_p,
+                                          const float* uniforms, long ldu, int B, int* pos_next, const int* fixed_end, int ngram,
+                                          const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
+                                          const short* set_of, const int* tmpl, const short* class_of, const signed char* lead,
+                                          int distinct, const signed char* src, void* stream) {
+    RefrainRule rf;
+    MMTG_REQUIRE(logits, "decode_sample_refrain: a draw needs logits");
+    if (int e = refrain_check("decode_sample_refrain", V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, tmpl,
+                              class_of, lead, distinct, src, &rf))
+        return e;
+    if (int e = sample_args_check("decode_sample_refrain", uniforms, ldu, B, top_k, top_p)) return e;
+    return decode_select_launch("decode_sample_refrain", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p,
+                                uniforms, ldu, B, pos_next, stream, rf);
+}
+
+extern "C" int mmtg_decode_beam_candidates_refrain(const float* logits, long ldl, int V, const long long* seq, long ldseq,
+                                                   const int* pos_ptr, int P, int sent, float temperature, float rep_penalty, int nb,
+                                                   float* cand_val, int* cand_id, int B, const int* fixed_end, int ngram,
+                                                   const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets,
+                                                   int n_sets, const short* set_of, const int* tmpl, const short* class_of,
+                                                   const signed char* lead, int distinct, const signed char* src, void* stream) {
+    RefrainRule rf;
+    if (int e = refrain_check("decode_beam_candidates_refrain", V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of,
+                              tmpl, class_of, lead, distinct, src, &rf))
+        return e;
+    return beam_candidates_launch("decode_beam_candidates_refrain", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty,
+                                  nb, cand_val, cand_id, B, stream, rf);
 }
 
 // (what every *_kw entry asks of K and nb: one merge workgroup holds a candidate per thread)

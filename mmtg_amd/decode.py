@@ -20,14 +20,16 @@ import torch
 
 from . import hip
 from .constraints import (BANNED, KeywordTables, LineTables, _check_constraints, check_groups, check_keywords, check_lines,  # noqa: F401
-                          check_ngram, check_prefix, chosen_mask, keywords_met, sequence_scores)   # (the host-side checks keep their names here)
+                          check_ngram, check_prefix, check_refrain, chosen_mask, keywords_met, refrain_without_keywords,
+                          sequence_scores)   # (the host-side checks keep their names here)
 
 _PLACEMENT = {}
 
 
-def select_forms(with_head, prefix, ngram, lines, templates=False, rhymes=False, groups=False, keywords=False):
+def select_forms(with_head, prefix, ngram, lines, templates=False, rhymes=False, groups=False, keywords=False, refrain=False,
+                 copies=False):
     """Which selection entries a token step ends in: (form of mmtg_decode_select / _sample or mmtg_decode_beam_candidates, form of
-    mmtg_decode_beam_merge), each "" (plain), "_fixed", "_ngram", "_lines", "_tmpl" or "_rhyme".  with_head: the step calls the
+    mmtg_decode_beam_merge), each "" (plain), "_fixed", "_ngram", "_lines", "_tmpl", "_rhyme" or "_refrain".  with_head: the step calls the
     model's head; prefix: the generation has one; ngram: no_repeat_ngram_size; lines: line constraints are given; templates: line
     templates are given (every step that calls the head then ends in "_tmpl"); rhymes: a rhyme scheme is given (every such step
     ends in "_rhyme", with or without templates).  The bans act where logits are read, so
@@ -36,13 +38,16 @@ def select_forms(with_head, prefix, ngram, lines, templates=False, rhymes=False,
     group (diverse beam search): the merge of a step with the head is then "_groups" / "_groups_fixed"; a step without the head
     has no candidates to choose among and keeps the merge it always ran.  keywords: the prompts carry keywords (keyword-constrained
     beam search): a step with the head ends in the "_kw" candidates -- one entry over the rhyme form, which serves every rule above
-    or none -- and the "_kw" / "_kw_fixed" merge; a step without the head keeps the merge it always ran."""
+    or none -- and the "_kw" / "_kw_fixed" merge; a step without the head keeps the merge it always ran.  refrain: a refrain scheme is
+    given: every step that calls the head ends in "_refrain", whatever other rules there are (the form is the rhyme form plus the
+    copy).  copies (GreedyDecoder, with a scheme): the step skipped the head because every row is held by its prefix or copies; it
+    ends in "_refrain" with null logits, which writes the copies.  Every other step without the head is what it always was."""
     held = "_fixed" if prefix else ""
     if not with_head:
-        return held, held
+        return ("_refrain" if refrain and copies else held), held
     if keywords:
         return "_kw", "_kw" + held
-    return (("_rhyme" if rhymes else "_tmpl" if templates else "_lines" if lines else "_ngram" if ngram else held),
+    return (("_refrain" if refrain else "_rhyme" if rhymes else "_tmpl" if templates else "_lines" if lines else "_ngram" if ngram else held),
             "_groups" + held if groups else held)
 
 
@@ -51,7 +56,8 @@ def _step_forms(dec, with_head):
     logprob).  A decoder without the newer fields (tmpl, rhyme, groups, return_logprobs) is one whose generation does not use them."""
     return select_forms(with_head, dec.use_fixed, dec.ngram, dec.lines is not None, templates=getattr(dec, "tmpl", None) is not None,
                         rhymes=getattr(dec, "rhyme", None) is not None, groups=getattr(dec, "groups", 1) > 1,
-                        keywords=getattr(dec, "kw", None) is not None) + (
+                        keywords=getattr(dec, "kw", None) is not None, refrain=getattr(dec, "refrain", None) is not None,
+                        copies=getattr(dec, "copy_step", False)) + (
         bool(with_head and getattr(dec, "return_logprobs", False)),)
 
 
@@ -74,6 +80,20 @@ def _rhyme_key(dec):
     return key
 
 
+def _refrain_key(dec):
+    """What a captured launch of the refrain form holds by value, for decoder `dec`'s graph key: which of the rhyme form's tables
+    are there at all (line tables with end sets or bounds only, the template table, a rhyme scheme and its distinct flag)."""
+    key = ("refrain",)
+    if dec.lines is not None:
+        key += ("sets" if dec.lines[2] is not None else "bounds",)
+    if getattr(dec, "tmpl", None) is not None:
+        key += ("tmpl",)
+    rhyme = getattr(dec, "rhyme", None)
+    if rhyme is not None:
+        key += ("rhyme",) + (("distinct",) if rhyme[2] else ())
+    return key
+
+
 def _fill(buf, src, fill, axis):
     """The host array src into the device buffer buf (allocated once: captured graphs hold its address), which is longer along
     `axis`; the rest of buf becomes `fill`."""
@@ -93,6 +113,8 @@ def _placement_ok(dev):
 
 
 class GreedyDecoder:
+    _skips_copies = True            # a step whose every row copies (refrain_scheme=) or is held skips the head
+
     def __init__(self, model, max_batch, max_len=None, use_graph=True, lanes=None, _parent=None, _lane=0):
         self.model = model
         self.eng = model.engine()
@@ -259,6 +281,15 @@ class GreedyDecoder:
         # ends every step that calls the head in the *_rhyme selection entries
         self.rhyme = None
         self._rhyme_buf = None
+        # refrain scheme (refrain_scheme=): this decoder's rows of src int8 [B, lines of max_len]; not None ends every step that calls
+        # the head in the *_refrain selection entries.  copy_cols (host, bool [1 + length], the parent's): the lyric columns at which
+        # every row is held by its prefix or copies, so the step skips the head; copy_step: the step being run is one of those (it ends
+        # in mmtg_decode_select_refrain with null logits); skipped_steps counts them per generation
+        self.refrain = None
+        self._refrain_buf = None
+        self.copy_cols = None
+        self.copy_step = False
+        self.skipped_steps = 0
         # token log-probabilities (return_logprobs=): fp32 [B, 1 + max_len], this decoder's rows; on, every step that calls the head
         # ends in one more launch, mmtg_decode_logprob, which writes the step's column (allocated once: captured graphs hold its address)
         self.return_logprobs = False
@@ -328,17 +359,20 @@ class GreedyDecoder:
         through the entry select_forms names: the *_fixed ones leave row b's column pos + 1 alone while pos + 1 < fixed_end[b] (the
         host wrote it), the *_ngram ones also ban every id that would complete a content n-gram the row already holds, the *_lines
         ones (n possibly 0) add the line-length bounds and line-end sets of include/mmtg_hip.h, the *_tmpl ones the line templates,
-        the *_rhyme ones (templates or none) the rhyme scheme."""
+        the *_rhyme ones (templates or none) the rhyme scheme, the *_refrain ones (any of these or none) the copy lines -- also on a
+        step that skipped the head because every row copies or is held (null logits: the copies and nothing else are written)."""
         sh = self.eng.sh
         temperature, rep, top_k, top_p = self.params
         tmpl, rhyme = getattr(self, "tmpl", None), getattr(self, "rhyme", None)
         form = _step_forms(self, with_head)[0]
         logits, ldl, V = (self.logits, self.eng.layout.Vpad, min(sh.V, 13317)) if with_head else (None, 0, 0)
+        if form == "_refrain":              # (the tables' shapes are held against the cut with or without logits)
+            V = min(sh.V, 13317)
         # stochastic: the draw of each position reads its row of the pre-filled uniforms
         sampling = (top_k, top_p, self.uniforms) if with_head and not (top_k == 1 and top_p == 0.0) else None
         hip._select(form, logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, self.B, self.pos_next, sampling,
                     fixed_end=self.fixed_end if self.use_fixed else None, ngram=self.ngram, tables=self.lines, tmpl=tmpl,
-                    **({} if rhyme is None else {"rhyme": rhyme}))
+                    **({} if rhyme is None else {"rhyme": rhyme}), **({"refrain": self.refrain} if form == "_refrain" else {}))
 
     def _logprob(self, with_head):
         """With return_logprobs, after the selection of a step that called the head: tok_lp[b, pos + 1 - P] = log_softmax of the row's
@@ -371,7 +405,8 @@ class GreedyDecoder:
             while cap < need:
                 cap *= 2
             sets = self._line_buf[3] = torch.zeros(cap, tables.sets.shape[1], dtype=torch.int32, device=dev)
-            self.graphs = {k: g for k, g in self.graphs.items() if "lines" not in k and "tmpl" not in k and "rhyme" not in k}
+            self.graphs = {k: g for k, g in self.graphs.items()
+                           if "lines" not in k and "tmpl" not in k and "rhyme" not in k and "refrain" not in k}
         _fill(sets, tables.sets.view(np.int32), 0, 0)
         _fill(set_of, tables.set_of, -1, 1)
         return lo, hi, sets, set_of
@@ -400,6 +435,33 @@ class GreedyDecoder:
         _fill(class_of, tables.class_of[:class_of.shape[0]], -1, 0)
         _fill(lead, tables.lead, -1, 1)
         return class_of, lead, bool(tables.distinct)
+
+    def _upload_refrain(self, tables):
+        """The refrain table of a generation with a scheme into this decoder's buffer (allocated once: captured graphs hold its
+        address), lines past the generation's no copies (-1); None without a scheme."""
+        if tables is None or tables.src is None:
+            return None
+        if self._refrain_buf is None:
+            sent = self.eng.sh.msl + 2
+            self._refrain_buf = torch.zeros(self.B, (self.max_len - 1) // sent + 1, dtype=torch.int8, device=self.eng.dev)
+        return _fill(self._refrain_buf, tables.src, -1, 1)
+
+    def _copy_columns(self, tables, prefix, length, return_logprobs):
+        """Which lyric columns 0 .. length skip the head under the refrain table: bool [1 + length], or None when there is nothing to
+        skip.  Column j is skipped when every row is on a held prefix column or a copy column there (and one at least copies: columns
+        every row holds are the prefix shortcut of ``step_at``) and no log-probabilities are asked for.  The forced cadence columns
+        skip the head anyway.  MMTG_DECODE_REFRAIN_SKIP=0 keeps the head on every copy column (the ids are the same)."""
+        if (tables is None or tables.src is None or return_logprobs or not self._skips_copies
+                or os.environ.get("MMTG_DECODE_REFRAIN_SKIP", "1") == "0"):
+            return None
+        sent, src = self.eng.sh.msl + 2, tables.src
+        j = np.arange(1 + length)
+        line = np.minimum(j // sent, src.shape[1] - 1)
+        content = (j % sent != 0) & (j % sent != sent - 1) & (j // sent < src.shape[1])
+        copy = (src[:, line] >= 0) & content[None, :]                      # [B, 1 + length]
+        held = np.zeros_like(copy) if prefix is None else j[None, :] < np.asarray([len(p) for p in prefix])[:, None]
+        cols = (copy | held).all(0) & (copy & ~held).any(0)
+        return cols if cols.any() else None
 
     def _step_x3(self, with_head):
         """The split-precision token step: embedding -> projector -> 12 blocks -> head, every product through mmtg_decode_gemm_x3
@@ -613,6 +675,8 @@ class GreedyDecoder:
             key += (form[1:], "sets" if self.lines[2] is not None else "bounds")
         if form == "_rhyme":
             key += _rhyme_key(self)
+        if form == "_refrain":
+            key += _refrain_key(self)
         if logprob:
             key += ("logprob",)
         if merge.startswith("_groups"):     # (the grouped merge holds both by value)
@@ -650,7 +714,7 @@ class GreedyDecoder:
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
               no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
-              rhyme_distinct=False, return_logprobs=False, keywords=None):
+              rhyme_distinct=False, return_logprobs=False, keywords=None, refrain_scheme=None):
         """Everything of a generation that happens once: the settings, the uniforms of a stochastic run, fresh weight copies /
         LayerNorm folds, the experience encoder, the prompt (prefilled in one batched pass: ``first_pos`` = P afterwards) and the
         reset position.  Returns the end position n; ``step_at(pos)`` for pos = first_pos .. n - 1 then runs the token steps (``generate`` does both; tools/decode_lanes_threads.py drives
@@ -690,6 +754,15 @@ class GreedyDecoder:
         argument (its ids are bit-equal to that generation's), and the columns the prefill covers stay 0.  False runs exactly the
         launches, graphs and graph keys of a generation without the argument.
 
+        refrain_scheme (check_refrain states the forms, include/mmtg_hip.h the rule): which lines repeat an earlier line of the row,
+        e.g. "AB.A" (line 3 is line 0 again, whatever the model wrote there).  With a scheme every step that calls the head ends in
+        the *_refrain selection entries (the rhyme form plus the copy, with whatever other rules there are or none); src is uploaded
+        here, once.  A step at which every row sits on a held prefix column or a copy column calls no head at all (``step_at``; not
+        with return_logprobs, which wants the head's word on every column): it ends in mmtg_decode_select_refrain with null logits.
+        The uniforms of a sampled generation are indexed by position, so a skipped draw consumes nothing.  ``skipped_steps`` counts
+        those steps; MMTG_DECODE_REFRAIN_SKIP=0 (read here) keeps the head on them, with the same ids.  None runs exactly the
+        launches, graphs and graph keys of a generation without the argument.
+
         keywords: refused here (ValueError).  A lyric that contains given words needs a search, and greedy decoding and sampling
         follow one path: BeamDecoder takes keywords=."""
         _keywords_need_beams(keywords)
@@ -700,7 +773,7 @@ class GreedyDecoder:
         if length > self.max_len:
             raise ValueError("length %d exceeds max_len %d" % (length, self.max_len))
         cons = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, B, length, sh, "a batch of %d" % B,
-                                  templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
+                                  templates, rhyme_scheme, rhyme_classes, rhyme_distinct, refrain_scheme)
         pre = cons.prefix
         self.params = (float(temperature), float(repitition_penalty), int(top_k), float(top_p))
         if not (int(top_k) == 1 and float(top_p) == 0.0):
@@ -730,13 +803,18 @@ class GreedyDecoder:
             self.tok_lp.zero_()
         # the generation's constraints, on the decoder and its lanes: a lane's _select reads its own flags, its slice of fixed_end
         # (a view since construction) and its rows of the line tables (the sets are shared)
-        lines, tmpl, rhyme = self._upload_lines(cons.lines), self._upload_templates(cons.lines), self._upload_rhyme(cons.lines)
+        bare = cons.lines is not None and cons.lines.bare       # (tables made for a refrain alone: no line rule to upload)
+        lines, tmpl, rhyme = self._upload_lines(None if bare else cons.lines), self._upload_templates(cons.lines), self._upload_rhyme(cons.lines)
+        refrain = self._upload_refrain(cons.lines)
+        self.copy_cols = self._copy_columns(cons.lines, pre, length, return_logprobs)
+        self.skipped_steps = 0
         for i, d in enumerate([self] + self.children):
             a, z = (0, B) if d is self else ((i - 1) * d.B, i * d.B)
             d.use_fixed, d.ngram = pre is not None, cons.ngram
             d.lines = None if lines is None else tuple(t if t is None or t is lines[2] else t[a:z] for t in lines)
             d.tmpl = None if tmpl is None else tmpl[a:z]
             d.rhyme = None if rhyme is None else (rhyme[0], rhyme[1][a:z], rhyme[2])
+            d.refrain, d.copy_step = None if refrain is None else refrain[a:z], False
             d.return_logprobs = bool(return_logprobs)
             if return_logprobs and d is not self:
                 d.tok_lp = self.tok_lp[a:z]
@@ -805,13 +883,20 @@ class GreedyDecoder:
         forced = j < 1 or (j > 1 and (j + 1) % (sh.msl + 2) in (0, 1))
         if self.use_fixed and pos + 1 < self.min_fixed and not self.return_logprobs:
             forced = True                                       # every row's column pos + 1 is a prefix id: no model call
+        copies = bool(not forced and self.copy_cols is not None and 0 <= j < len(self.copy_cols) and self.copy_cols[j])
+        if copies:                                              # every row copies or is held: no model call, the selection copies
+            forced = True
+            self.skipped_steps += 1
+        for d in [self] + self.children:
+            d.copy_step = copies
         self._run_step(with_head=not forced, parity=pos & 1)
         return not forced
 
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None,
                  use_graph=None, teacher=None, tap=None, prefix=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None,
-                 templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_logprobs=False, **begin_kw):
+                 templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_logprobs=False,
+                 refrain_scheme=None, **begin_kw):
         """batch: dict with topic_ids/tpw_* [B,P], topic_emb, img_embs, r_embs (no targets needed).
         Runs `length` iterations of the reference loop and returns the lyric ids
         [B, 1 + length] (column 0 is the initial [#START#]).  top_k = 1, top_p = 0 is the greedy setting;
@@ -833,6 +918,8 @@ class GreedyDecoder:
         rhyme_scheme / rhyme_classes / rhyme_distinct: lines that end on one rhyme (``check_lines``): rhyme_scheme="AABB" with
         rhyme_classes=[ids that rhyme, ...] makes lines 0 / 1 and 2 / 3 end in one class each, the class being what the row ended
         the first line of the pair on; rhyme_distinct=True keeps a line from ending on the id an earlier line of its group ended on.
+        refrain_scheme: lines that repeat a line (``check_refrain``): refrain_scheme="AB.A" makes line 3 the text of line 0 again,
+        copied column by column from the row's own history -- also under no_repeat_ngram_size, which otherwise forbids a chorus.
         return_logprobs: return (ids, tok_lp [B, 1 + length] fp32) -- per column the log-probability the model's raw logits give the
         id the column holds, 0 where no step called the head (``begin``; ``chosen_mask`` / ``sequence_scores`` turn them into a
         score per row).  With a prefix that covers every row whole it scores given text (generate.score_sequences).
@@ -840,7 +927,8 @@ class GreedyDecoder:
         n_steps = self.begin(batch, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix,
                              no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths, line_end_ids=line_end_ids,
                              templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct,
-                             **({"return_logprobs": True} if return_logprobs else {}), **begin_kw)
+                             **({"return_logprobs": True} if return_logprobs else {}),
+                             **({} if refrain_scheme is None else {"refrain_scheme": refrain_scheme}), **begin_kw)
         eng, sh = self.eng, self.eng.sh
         saved_mode = self.use_graph
         if use_graph is not None:
@@ -897,6 +985,8 @@ class BeamDecoder(GreedyDecoder):
     (rows[b, j] = the cache row holding position j of beam b's history) is reordered with seq / keep by the merge; the attention
     reads the prefix through it (mmtg_decode_attn_split_rows / mmtg_decode_attn_split_x3_rows)."""
 
+    _skips_copies = False           # the merge knows nothing of copies: the candidates offer them, on a step with the head
+
     def __init__(self, model, max_prompts, num_beams, max_len=None, use_graph=True, lanes=1):
         nb = int(num_beams)
         if not 1 <= nb <= 16:
@@ -943,7 +1033,8 @@ class BeamDecoder(GreedyDecoder):
         if with_head:
             hip._beam_candidates(cand, self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2, temperature,
                                  rep, self.nb, self.cand_val, self.cand_id, self.B, fixed_end=fe, ngram=self.ngram, tables=self.lines,
-                                 tmpl=tmpl, **({} if rhyme is None else {"rhyme": rhyme}))
+                                 tmpl=tmpl, **({} if rhyme is None else {"rhyme": rhyme}),
+                                 **({"refrain": self.refrain} if cand == "_refrain" else {}))
         hip._beam_merge(merge, self.cand_val if with_head else None, self.cand_id if with_head else None, self.scores, self.seq, self.keep,
                         self.rows, self.pos, sh.P, sh.msl + 2, self.nb, self.n_prompts, self.pos_next, fixed_end=fe,
                         groups=getattr(self, "groups", 1), diversity_penalty=getattr(self, "diversity_penalty", 0.0))
@@ -993,7 +1084,7 @@ class BeamDecoder(GreedyDecoder):
     @torch.no_grad()
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
               no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
-              rhyme_distinct=False, return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, keywords=None):
+              rhyme_distinct=False, return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, keywords=None, refrain_scheme=None):
         """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill, the prefix, the line
         constraints, the templates and the rhyme scheme: one per prompt; every beam finds its leader's rhyme in its own history), the
         ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at the free positions
@@ -1011,7 +1102,13 @@ class BeamDecoder(GreedyDecoder):
         other rule bans them) and mmtg_decode_beam_merge_kw (the beams are shared among the banks: how much of the keywords a
         hypothesis holds).  The tables are uploaded here, once.  Best effort: a keyword no allowed column can hold stays unmet.
         With num_beam_groups > 1 it is a ValueError.  None runs exactly the launches, graphs and graph keys of a search without
-        the argument."""
+        the argument.
+
+        refrain_scheme (``check_refrain``): one scheme per prompt, shared by its beams; every beam copies from its own (reordered)
+        history.  A copy is offered by the candidates the way a template's given id is (mmtg_decode_beam_candidates_refrain), so the
+        merge and the scores are untouched -- and so every copy column still calls the head: head skipping is GreedyDecoder's, the
+        known remainder here.  Beam groups need nothing.  keywords= together with a scheme is a ValueError: the one combination
+        left out."""
         self._no_logprobs(return_logprobs)
         G, lam = check_groups(self.nb, num_beam_groups, diversity_penalty)
         self._keywords_alone(keywords, G)
@@ -1019,7 +1116,8 @@ class BeamDecoder(GreedyDecoder):
         if n != self.n_prompts:
             raise ValueError("decoder was built for %d prompts, got %d" % (self.n_prompts, n))
         cons = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, n, length, self.eng.sh, "%d prompts" % n,
-                                  templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
+                                  templates, rhyme_scheme, rhyme_classes, rhyme_distinct, refrain_scheme)
+        refrain_without_keywords(keywords, cons.lines)
         kw = check_keywords(keywords, n, self.nb, self.eng.sh.V, self.eng.sh.msl + 2, prefix=cons.prefix)
         cons = cons.repeat(self.nb)
         rep = {k: (v.repeat_interleave(self.nb, 0) if torch.is_tensor(v) else v) for k, v in batch.items()}
@@ -1037,13 +1135,15 @@ class BeamDecoder(GreedyDecoder):
     @torch.no_grad()
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None, no_repeat_ngram_size=0,
                  line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False,
-                 return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, return_groups=False, keywords=None, return_met=False):
+                 return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, return_groups=False, keywords=None, return_met=False,
+                 refrain_scheme=None):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_beams, 1 + length] in
         GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row.
         prefix: one per prompt (check_prefix), shared by its beams.  no_repeat_ngram_size: as GreedyDecoder.generate, per beam
         on its own (reordered) history.  line_lengths / line_end_ids / templates: as GreedyDecoder.generate, one per prompt, shared by
         its beams (a given column adds nothing to a score).  rhyme_scheme / rhyme_classes / rhyme_distinct: as GreedyDecoder.generate,
-        one scheme per prompt; each beam rhymes with its own earlier lines.  return_logprobs=True raises ValueError before any device
+        one scheme per prompt; each beam rhymes with its own earlier lines.  refrain_scheme: as GreedyDecoder.generate, one scheme per
+        prompt; each beam repeats its own earlier line (not together with keywords: ValueError).  return_logprobs=True raises ValueError before any device
         work: the scores here are sums over the PROCESSED logits; generate.score_sequences gives a beam's raw log-probabilities.
         num_beam_groups / diversity_penalty: diverse beam search (``begin``): G groups of num_beams / G beams, a later group steered
         away from the ids earlier groups take at the same step.  The result keeps its form: all num_beams hypotheses of a prompt,
@@ -1062,7 +1162,7 @@ class BeamDecoder(GreedyDecoder):
                                prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths,
                                line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes,
                                rhyme_distinct=rhyme_distinct, **({"num_beam_groups": G, "diversity_penalty": lam} if G > 1 else {}),
-                               **({} if keywords is None else {"keywords": keywords}))
+                               **({} if keywords is None else {"keywords": keywords}), refrain_scheme=refrain_scheme)
         n, nb = self.n_prompts, self.nb
         ids = ids.view(n, nb, -1)
         sc = self.scores.view(n, nb).clone()

@@ -17,7 +17,8 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .constraints import BANNED, Constraints, _check_constraints, check_groups, check_keywords, check_prefix, sequence_scores
+from .constraints import (BANNED, Constraints, _check_constraints, check_groups, check_keywords, check_prefix, refrain_without_keywords,
+                          sequence_scores)
 from .decode import BeamDecoder, GreedyDecoder, _keywords_need_beams
 from .data import encode_line_end, encode_prefix, encode_rhyme_classes, encode_template  # noqa: F401  (public: the opening lines / the line-end sets / the line templates / the rhyme classes of generate_samples / generate_beams)
 
@@ -197,7 +198,7 @@ def rank_scored(scored, rank_by):
 def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperature=1.1, top_k=10, top_p=0.7,
                      repetition_penalty=1.5, max_batch=256, generator=None, decoder=None, prefixes=None, no_repeat_ngram_size=0,
                      line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False,
-                     return_scores=False, rank_by=None, keywords=None):
+                     return_scores=False, rank_by=None, keywords=None, refrain_scheme=None):
     """n_samples texts per prompt (generate.sh's loop, generate.py:205-235) on the batched, graph-replayed decoder:
     every prompt is replicated over n_samples rows, rows are decoded max_batch at a time with the device-side
     top-k / top-p sampler (one uniform per row and position from `generator`), each row is cut back to what
@@ -216,6 +217,9 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     rhyme_scheme / rhyme_classes / rhyme_distinct (optional, decode.check_lines; one scheme per prompt or one for all): lines that
     end on one rhyme, e.g. rhyme_scheme="AABB", rhyme_classes=encode_rhyme_classes(tokenizer, ["光忙香", "天年前"]); every sample
     chooses its own rhymes.  rhyme_distinct=True keeps a line from ending on the character an earlier line of its group ended on.
+    refrain_scheme (optional, constraints.check_refrain; one scheme per prompt or one for all): lines that repeat a line, e.g.
+    refrain_scheme="AB.A" makes line 3 the text of line 0 again, whatever the sample wrote there -- also under no_repeat_ngram_size.
+    A copy line takes no bounds, end set, template or rhyme letter of its own.
     return_scores: each prompt's entry is a list of (text, logprob_sum, n_tokens) instead -- the sum of the model's own token
     log-probabilities (raw logits: no penalty, no temperature, no bans, so comparable across sampling settings;
     GreedyDecoder.begin, return_logprobs) over the columns of the returned text that decode.chosen_mask counts, past the prompt's
@@ -233,7 +237,7 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     length = sh.max_seq_length if length is None else length
     n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
     cons = _check_constraints(prefixes, no_repeat_ngram_size, line_lengths, line_end_ids, n_prompts, length, sh, "%d prompts" % n_prompts,
-                              templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
+                              templates, rhyme_scheme, rhyme_classes, rhyme_distinct, refrain_scheme)
     bsz = min(max_batch, n_prompts * n_samples)
     dec = decoder if decoder is not None and decoder.B == bsz else GreedyDecoder(model, max_batch=bsz, max_len=length)
     texts = []
@@ -291,7 +295,7 @@ def score_sequences(model, rows, ids, max_batch=256):
 def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature=1.1, repetition_penalty=1.5, max_batch=256,
                    return_all=False, prefixes=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None,
                    rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_ids=False, num_beam_groups=1,
-                   diversity_penalty=0.0, best_per_group=False, keywords=None, return_met=False):
+                   diversity_penalty=0.0, best_per_group=False, keywords=None, return_met=False, refrain_scheme=None):
     """Beam search per prompt on the batched, graph-replayed decoder (BeamDecoder): prompts are decoded max_batch // num_beams at
     a time, every beam is cut back to what sample_sequence would have returned (GreedyDecoder.reference_return) and
     post-processed as generate_samples does.  rows: as generate_samples.  Returns one string per prompt (its best beam), or with
@@ -311,7 +315,9 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
     list for all prompts or one list per prompt (constraints.check_keywords; BeamDecoder.begin).  A prompt's beams are then ordered
     by (keywords met descending, score descending), so the text returned is the best hypothesis that holds the most keywords.  The
     search is best effort: return_met=True (with return_all) appends the number of keywords met to each beam's tuple.  Not together
-    with num_beam_groups > 1."""
+    with num_beam_groups > 1.
+    refrain_scheme: as generate_samples; every beam repeats its own earlier line, e.g.
+    generate_beams(..., refrain_scheme="AB.A", no_repeat_ngram_size=3).  Not together with keywords (ValueError)."""
     G, lam = check_groups(num_beams, num_beam_groups, diversity_penalty)
     BeamDecoder._keywords_alone(keywords, G)
     if return_met and (keywords is None or not return_all):
@@ -323,7 +329,8 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
     length = sh.max_seq_length if length is None else length
     n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
     cons = _check_constraints(prefixes, no_repeat_ngram_size, line_lengths, line_end_ids, n_prompts, length, sh, "%d prompts" % n_prompts,
-                              templates, rhyme_scheme, rhyme_classes, rhyme_distinct)
+                              templates, rhyme_scheme, rhyme_classes, rhyme_distinct, refrain_scheme)
+    refrain_without_keywords(keywords, cons.lines)
     kw = check_keywords(keywords, n_prompts, num_beams, sh.V, sh.msl + 2, prefix=cons.prefix)
     per = max(1, min(max_batch // num_beams, n_prompts))
     dec = BeamDecoder(model, per, num_beams, max_len=length)

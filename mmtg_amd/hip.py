@@ -131,6 +131,12 @@ _SIGS = {
                                  _vp, _vp, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_beam_candidates_rhyme": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
                                           _vp, _vp, _vp, _vp, _i, _vp], _i),
+    "mmtg_decode_select_refrain": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i,
+                                    _vp, _vp], _i),
+    "mmtg_decode_sample_refrain": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i,
+                                   _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
+    "mmtg_decode_beam_candidates_refrain": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
+                                            _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
     "mmtg_decode_logprob": ([_vp, _l, _i, _vp, _l, _vp, _i, _vp, _l, _i, _i, _vp], _i),
     "mmtg_decode_beam_candidates_kw": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
                                        _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp], _i),
@@ -901,11 +907,30 @@ def _rhyme(rhyme, tables, B, V):
     return _p(class_of), _p(lead), int(bool(distinct))
 
 
-def _rule_tail(form, B, V, fixed_end, ngram, tables, tmpl=None, sent=0, rhyme=None):
-    """What the selection entry of `form` ("" plain, "_fixed", "_ngram", "_lines", "_tmpl", "_rhyme") takes between its own arguments
-    and the stream (the template table of "_rhyme" may be None: a scheme without templates)."""
+def _refrain(src, tables, B):
+    """The refrain table of constraints.check_refrain on the device, int8 [rows >= B, n_lines] (of the line tables' width where there are
+    any), as the *_refrain entries' last argument before the stream (None is passed on: the library rejects it)."""
+    if src is not None:
+        if not (src.dtype == torch.int8 and src.dim() == 2 and src.shape[0] >= B and 1 <= src.shape[1] <= 128 and src.is_contiguous()
+                and (tables is None or src.shape[1] == tables[0].shape[1])):
+            raise ValueError("refrain table: src must be contiguous int8 [rows >= %d, n_lines]" % B)
+    return _p(src)
+
+
+def _rule_tail(form, B, V, fixed_end, ngram, tables, tmpl=None, sent=0, rhyme=None, refrain=None):
+    """What the selection entry of `form` ("" plain, "_fixed", "_ngram", "_lines", "_tmpl", "_rhyme", "_refrain") takes between its own
+    arguments and the stream (the template table of "_rhyme" may be None: a scheme without templates; "_refrain" is the rhyme form's
+    tail, whose tables may be None -- no line rule -- and whose rhyme may be None -- no rhyme scheme --, plus src)."""
     if form == "":
         return ()
+    if form == "_refrain":
+        if tables is None:
+            if rhyme is not None or tmpl is not None:
+                raise ValueError("refrain: templates / a rhyme scheme come with line tables")
+            rule = (0, 0, 0 if refrain is None else refrain.shape[1], 0, 0, 0, 0, 0, 0, 0)
+        else:
+            rule = _lines(tables, B, V) + (_template(tmpl, tables, B, sent),) + _rhyme(rhyme, tables, B, V)
+        return (_fixed(fixed_end, B), int(ngram)) + rule + (_refrain(refrain, tables, B),)
     tail = (_fixed(fixed_end, B),)
     if form != "_fixed":
         tail += (int(ngram),)
@@ -919,21 +944,21 @@ def _rule_tail(form, B, V, fixed_end, ngram, tables, tmpl=None, sent=0, rhyme=No
 
 
 def _select(form, logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, sampling=None, fixed_end=None, ngram=0,
-            tables=None, tmpl=None, rhyme=None):
+            tables=None, tmpl=None, rhyme=None, refrain=None):
     """mmtg_decode_select<form>, or with sampling = (top_k, top_p, uniforms) mmtg_decode_sample<form>."""
     name = ("decode_select" if sampling is None else "decode_sample") + form
     draw = () if sampling is None else (int(sampling[0]), float(sampling[1]), _p(sampling[2]), sampling[2].stride(0))
     _check(getattr(lib(), "mmtg_" + name)(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
                                           float(rep_penalty), *draw, B, _p(pos_next),
-                                          *_rule_tail(form, B, V, fixed_end, ngram, tables, tmpl, sent, rhyme), _stream()), name)
+                                          *_rule_tail(form, B, V, fixed_end, ngram, tables, tmpl, sent, rhyme, refrain), _stream()), name)
 
 
 def _beam_candidates(form, logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=None, ngram=0,
-                     tables=None, tmpl=None, rhyme=None):
+                     tables=None, tmpl=None, rhyme=None, refrain=None):
     name = "decode_beam_candidates" + form
     _check(getattr(lib(), "mmtg_" + name)(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
                                           float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B,
-                                          *_rule_tail(form, B, V, fixed_end, ngram, tables, tmpl, sent, rhyme), _stream()), name)
+                                          *_rule_tail(form, B, V, fixed_end, ngram, tables, tmpl, sent, rhyme, refrain), _stream()), name)
 
 
 def _beam_merge(form, cand_val, cand_id, scores, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next, fixed_end=None, groups=1,
@@ -1080,6 +1105,29 @@ def decode_beam_candidates_rhyme(logits, ldl, V, seq, pos, P, sent, temperature,
     """decode_beam_candidates_tmpl under the rhyme tables: every beam reads its own (reordered) history for its leader's rhyme."""
     _beam_candidates("_rhyme", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=fixed_end,
                      ngram=ngram, tables=tables, tmpl=tmpl, rhyme=rhyme)
+
+
+def decode_select_refrain(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, src, tables=None, rhyme=None, tmpl=None, ngram=0,
+                          fixed_end=None, pos_next=None):
+    """decode_select_rhyme (tables None: no line rule; rhyme None: no rhyme scheme) under the refrain table `src` of include/mmtg_hip.h:
+    on a copy column the row writes the id its own history holds at that column of the source line.  logits may be None (a step that
+    skipped the head): copy columns and the forced cadence are written, nothing else."""
+    _select("_refrain", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, fixed_end=fixed_end, ngram=ngram,
+            tables=tables, tmpl=tmpl, rhyme=rhyme, refrain=src)
+
+
+def decode_sample_refrain(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, uniforms, B, src, tables=None,
+                          rhyme=None, tmpl=None, ngram=0, fixed_end=None, pos_next=None):
+    _select("_refrain", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B, pos_next, (top_k, top_p, uniforms),
+            fixed_end=fixed_end, ngram=ngram, tables=tables, tmpl=tmpl, rhyme=rhyme, refrain=src)
+
+
+def decode_beam_candidates_refrain(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, src, tables=None,
+                                   rhyme=None, tmpl=None, ngram=0, fixed_end=None):
+    """decode_beam_candidates_rhyme under the refrain table: a row on a copy column offers the source's id the way a template's given id
+    is offered; every beam copies from its own (reordered) history."""
+    _beam_candidates("_refrain", logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=fixed_end,
+                     ngram=ngram, tables=tables, tmpl=tmpl, rhyme=rhyme, refrain=src)
 
 
 def _keywords(keywords, n_prompts):
