@@ -870,6 +870,55 @@ MMTG_API int mmtg_decode_beam_candidates_refrain(const float* logits, long ldl, 
                                        const int* tmpl, const short* class_of, const signed char* lead, int distinct,
                                        const signed char* src, void* stream);
 
+/* ---- contrastive search (ContrastiveDecoder, mmtg_amd/decode.py; Su et al. 2022, `penalty_alpha` / `top_k` of transformers'
+ * generate): among the model's k most probable next tokens, keep the one whose last-layer hidden state is least like the
+ * context's.  The reference has no such method (generate.py:117-142 is greedy / top-k / top-p); it is the deterministic answer to
+ * the repetition its repetition_penalty 1.5 fights on ids, made on representations.
+ * Layout.  A prompt owns k rows b0 .. b0 + k - 1 (k = top_k, 1..16, b0 = prompt * k: the beam decoder's layout, with its ancestry
+ *   table `rows`).  scores[b] is the processed log-probability at which the token in row b's NEWEST column was offered; a row at
+ *   -inf (or NaN) is dead.  Invariant: after every merge the k rows of a prompt agree in every column but the newest, which holds
+ *   the k candidates.  Token step `pos` embeds column pos of every row, runs the layers (and the head, where the beam decoder runs
+ *   it) and ends in three launches on one chain:
+ * 1. Candidates: the mmtg_decode_beam_candidates* entry the generation's rules name, with nb = k, unchanged, on a step with the
+ *   head: cand_val / cand_id [B, k].  Prefix, n-gram, line, template, rhyme and refrain rules act there and nowhere else.
+ * 2. Similarity, mmtg_decode_contrastive_sim: one workgroup of 256 threads per row b; nothing happens while pos < P.  x_b = x[b * ldx
+ *   + 0 .. D - 1] is the residual stream the last block left (what the head's LayerNorm-folded product reads; dtype MMTG_BF16 or
+ *   MMTG_F32).  h = gamma * (x_b - mean) / sqrt(var + eps) + beta with the population variance, u_b = h / ||h||_2 (the zero vector if
+ *   the norm is 0), fp32 throughout.  u_b is stored as fp32 into the hidden cache hc [B, hc_len, D] at [b, pos - P, :] (when pos - P >= hc_len or
+ *   pos is past a table's width, nothing is stored or read and sim[b] = 0), and
+ *     sim[b] = max over t in [P, pos) with keep[b, t] != 0 of dot(u_b, hc[rows[b, t], t - P, :]),   0 for an empty context.
+ *   The context is the row's own LYRIC columns through the ancestry table, [#START#] / [#EOS#] columns included and PAD columns
+ *   (keep 0) excluded.  The prompt's topic words are NOT context: the batched prefill leaves no last-layer states for them, and the
+ *   penalty is about the lyric repeating itself.  A dead row (scores given and scores[b] not above -inf) stores u_b and gets
+ *   sim[b] = 0 without reading its context; scores may be null (every row is read).  A table entry outside 0 .. B - 1 is skipped.
+ *   A dot product is summed in one fixed order and a max does not depend on the order: equal inputs give equal bits.
+ * 3. Merge, mmtg_decode_contrastive_merge: one workgroup per prompt; it publishes *pos_next = pos + 1 as the beam merge does.
+ *   pos < P (a decoder without prefill): the plain merge's identity, rows[b, pos + 1] = b, nothing else.  Otherwise:
+ *   choose   r* = argmax over the live rows r of (1 - alpha) * expf(scores[b0 + r]) - alpha * sim[b0 + r], the lowest r on a tie
+ *            (row 0 if no row is live); alpha = penalty_alpha in [0, 1].
+ *   column pos of seq, keep and rows of every row of the prompt becomes row b0 + r*'s (so rows[.., pos] = b0 + r*: the previous
+ *            merge pointed rows[b, pos] at b).  By the invariant no earlier column needs copying.
+ *   score    total[prompt] += scores[b0 + r*].
+ *   column pos + 1, the first case that applies: a prefix column (fixed_end given and pos + 1 < fixed_end[b0]) is left alone; a
+ *            forced [#EOS#] / [#START#] cadence column gets its token in every row; with candidates, row r gets
+ *            cand_id[b0 + r*, r]; without (a step that skipped the head) it is left alone.  scores[b0 + r] = cand_val[b0 + r*, r]
+ *            in the candidates case and [0, -inf, ...] in the others: what was not the model's choice is offered by row 0 alone,
+ *            which is also how the candidates offer a sticky PAD, a full line's PAD, a given id and a copy.
+ *   ancestry rows[b, pos + 1] = b.
+ * alpha = 0 is greedy decoding for any k (cand_val descends in r, ties go to the lowest r), and so is k = 1 for any alpha.  The
+ * host starts a prompt at scores [0, -inf, ...] and total 0; after the last step the lyric is row b0 and its score
+ * total[prompt] + scores[b0]: the last column keeps its most probable candidate, since no later step judges it.
+ * Null pointers (cand_val / cand_id, scores of the similarity entry and fixed_end may be null), k outside 1..16, alpha outside
+ * [0, 1], D not a multiple of 4 in 4..1024, hc_len < 1, a table narrower than P + 1 and pos_next == pos_ptr fail before any device
+ * call.  Two new kernels in a source file of their own; every other kernel compiles to the same code as before.                  */
+MMTG_API int mmtg_decode_contrastive_sim(int dtype, const void* x, long ldx, const float* gamma, const float* beta, float eps,
+                                float* hc, int hc_len, float* sim, const float* scores, const int* keep, long ldkeep,
+                                const int* rows, long ldrows, const int* pos_ptr, int P, int B, int D, void* stream);
+MMTG_API int mmtg_decode_contrastive_merge(const float* cand_val, const int* cand_id, float* scores, const float* sim, float* total,
+                                  float alpha, long long* seq, long ldseq, int* keep, long ldkeep, int* rows, long ldrows,
+                                  const int* pos_ptr, int P, int sent, int k, int n_prompts, int* pos_next,
+                                  const int* fixed_end, void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

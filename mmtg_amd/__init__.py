@@ -27,7 +27,7 @@ def __getattr__(name):
     if name in ("pack_token_table", "load_token_table"):
         from . import model
         return getattr(model, name)
-    if name in ("sample_sequence", "top_k_top_p_filtering", "generate_samples", "generate_beams", "postprocess_tokens",
+    if name in ("sample_sequence", "top_k_top_p_filtering", "generate_samples", "generate_beams", "generate_contrastive", "postprocess_tokens",
                 "score_sequences"):
         from . import generate
         return getattr(generate, name)

@@ -77,6 +77,23 @@ def check_groups(num_beams, num_beam_groups=1, diversity_penalty=0.0):
     return G, lam
 
 
+def check_contrastive(top_k, penalty_alpha):
+    """The settings of a contrastive search: (k, alpha).  k candidates per step, an integer in 1..16 (a prompt's rows, the beam
+    decoder's layout); alpha in [0, 1] weighs the degeneration penalty against the model's probability (0: greedy decoding)."""
+    if not _is_int(top_k):
+        raise ValueError("top_k must be an integer, got %r" % (top_k,))
+    k = int(top_k)
+    if not 1 <= k <= 16:
+        raise ValueError("top_k %d outside 1..16" % k)
+    try:
+        alpha = float(penalty_alpha)
+    except (TypeError, ValueError):
+        raise ValueError("penalty_alpha must be a number, got %r" % (penalty_alpha,)) from None
+    if not 0.0 <= alpha <= 1.0:                  # (NaN fails both comparisons)
+        raise ValueError("penalty_alpha must be in [0, 1], got %r" % (penalty_alpha,))
+    return k, alpha
+
+
 def chosen_mask(ids, sent=22, prefix_lens=None):
     """Which columns of generated lyric ids count towards a row's score: bool [B, 1 + length], host only.  Column j >= 1 of row b
     counts iff it is not a cadence column (j % sent not in {0, sent - 1}: the forced [#START#] / [#EOS#]), it lies past the row's

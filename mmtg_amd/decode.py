@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .constraints import (BANNED, KeywordTables, LineTables, _check_constraints, check_groups, check_keywords, check_lines,  # noqa: F401
+from .constraints import (BANNED, KeywordTables, LineTables, _check_constraints, check_contrastive, check_groups, check_keywords, check_lines,  # noqa: F401
                           check_ngram, check_prefix, check_refrain, chosen_mask, keywords_met, refrain_without_keywords,
                           sequence_scores)   # (the host-side checks keep their names here)
 
@@ -114,6 +114,7 @@ def _placement_ok(dev):
 
 class GreedyDecoder:
     _skips_copies = True            # a step whose every row copies (refrain_scheme=) or is held skips the head
+    _prefill_prompt_only = False    # with a prefix, prefill the prompt alone (ContrastiveDecoder: every lyric column through a step)
 
     def __init__(self, model, max_batch, max_len=None, use_graph=True, lanes=None, _parent=None, _lane=0):
         self.model = model
@@ -821,7 +822,8 @@ class GreedyDecoder:
         self.min_fixed = 0
         if pre is not None:
             lens = [len(p) for p in pre]
-            lmin = 1 if return_logprobs and min(lens) == length + 1 else min(lens)      # (scoring mode: the prompt only)
+            # (scoring mode, and a decoder that wants every lyric column from a token step: the prompt only)
+            lmin = 1 if (return_logprobs and min(lens) == length + 1) or self._prefill_prompt_only else min(lens)
             host = torch.zeros(B, max(lens), dtype=torch.long)
             for b, p in enumerate(pre):
                 host[b, :len(p)] = torch.tensor(p, dtype=torch.long)
@@ -1176,3 +1178,121 @@ class BeamDecoder(GreedyDecoder):
             return out + (torch.gather(met, 1, order),) if return_met else out
         out = torch.gather(ids, 1, order[:, :, None].expand_as(ids)), torch.gather(sc, 1, order)
         return out + (order // (nb // G),) if return_groups else out
+
+
+class ContrastiveDecoder(BeamDecoder):
+    """Contrastive search (Su et al. 2022; `penalty_alpha` / `top_k` of transformers' generate) on the beam decoder's machinery:
+    `top_k` rows per prompt advance in lock step, and the token step ends in three launches -- the beam candidates the generation's
+    rules name, unchanged; mmtg_decode_contrastive_sim; mmtg_decode_contrastive_merge (include/mmtg_hip.h states the rule).
+
+    The newest column of a prompt's rows holds the model's k most probable tokens; the step runs the model on each, and the merge
+    keeps the one with the best (1 - alpha) * p - alpha * s: p the processed probability the token was offered at, s the largest
+    cosine between its last-layer hidden state (ln_f of the final residual stream, unit length) and those of the lyric so far.
+    The context is the lyric alone, [#START#] / [#EOS#] columns included and PAD columns excluded; the prompt's topic words are not
+    part of it (the batched prefill leaves no last-layer states for them, and the penalty is about the lyric repeating itself).
+    One deterministic lyric per prompt, at about the cost of a k-beam search: no ban list, and every line rule composes, since the
+    rules act in the candidates.  alpha = 0 is greedy decoding bit for bit at any k, and so is k = 1 at any alpha.
+
+    The last column keeps its most probable candidate: no later step exists to judge it (at the usual lengths it is a forced
+    [#EOS#]).  The score is the sum of the processed log-probabilities of the chosen tokens, a beam score's scale."""
+
+    _prefill_prompt_only = True     # a prefix goes through token steps: every lyric column gets a hidden state
+
+    def __init__(self, model, max_prompts, top_k, max_len=None, use_graph=True, lanes=1):
+        k, _ = check_contrastive(top_k, 0.0)
+        super().__init__(model, max_prompts, k, max_len=max_len, use_graph=use_graph, lanes=lanes)
+        dev, D = self.eng.dev, self.eng.sh.D
+        if D % 4 or D > 1024:
+            raise ValueError("contrastive search holds n_embd up to 1024, a multiple of 4 (got %d)" % D)
+        self.Hc = torch.zeros(self.B, self.max_len + 1, D, dtype=torch.float32, device=dev)     # unit ln_f states per lyric column
+        self.sim = torch.zeros(self.B, dtype=torch.float32, device=dev)
+        self.total = torch.zeros(self.n_prompts, dtype=torch.float32, device=dev)
+        self.alpha = 0.0
+
+    @staticmethod
+    def _refuse(keywords=None, num_beam_groups=1, return_logprobs=False, diversity_penalty=0.0, top_k=1, top_p=0.0, generator=None):
+        """What contrastive search does not take, refused before any device work (the last four are arguments of the base
+        classes' ``begin`` that would otherwise be ignored in silence)."""
+        if diversity_penalty:
+            raise ValueError("contrastive search has no diversity_penalty: there are no beam groups to keep apart")
+        if not (int(top_k) == 1 and float(top_p) == 0.0) or generator is not None:
+            raise ValueError("contrastive search is deterministic: it takes no sampling top_k / top_p / generator (its top_k is "
+                             "the decoder's, given at construction)")
+        if keywords is not None:
+            raise ValueError("contrastive search takes no keywords=: it keeps one hypothesis per prompt, and a keyword needs banks "
+                             "of beams to be carried in (BeamDecoder / generate_beams)")
+        if num_beam_groups != 1:
+            raise ValueError("contrastive search has no num_beam_groups: its rows are one step's candidates, not beams to group")
+        if return_logprobs:
+            raise ValueError("contrastive search has no return_logprobs (the merge reorders rows after the selection); score the "
+                             "lyric with generate.score_sequences")
+
+    def _select(self, with_head):
+        """The step's last three launches: the candidates entry select_forms names (a step with the head), the similarity of every
+        row's hidden state to its lyric context, the contrastive merge."""
+        eng, sh = self.eng, self.eng.sh
+        temperature, rep, _, _ = self.params
+        tmpl, rhyme = getattr(self, "tmpl", None), getattr(self, "rhyme", None)
+        cand = _step_forms(self, with_head)[0]
+        fe = self.fixed_end if self.use_fixed else None
+        if with_head:
+            hip._beam_candidates(cand, self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2, temperature,
+                                 rep, self.nb, self.cand_val, self.cand_id, self.B, fixed_end=fe, ngram=self.ngram, tables=self.lines,
+                                 tmpl=tmpl, **({} if rhyme is None else {"rhyme": rhyme}),
+                                 **({"refrain": self.refrain} if cand == "_refrain" else {}))
+        pre = "decoder.gpt2.transformer."
+        # self.h: the residual stream the last block left, in every step variant (what the head's LayerNorm reads)
+        hip.decode_contrastive_sim(self.h, eng.P(pre + "ln_f.weight"), eng.P(pre + "ln_f.bias"), sh.eps, self.Hc, self.sim, self.keep,
+                                   self.rows, self.pos, sh.P, self.B, sh.D, scores=self.scores)
+        hip.decode_contrastive_merge(self.cand_val if with_head else None, self.cand_id if with_head else None, self.scores, self.sim,
+                                     self.total, self.alpha, self.seq, self.keep, self.rows, self.pos, sh.P, sh.msl + 2, self.nb,
+                                     self.n_prompts, pos_next=self.pos_next, fixed_end=fe)
+
+    def _graph_key(self, with_head, parity):
+        return super()._graph_key(with_head, parity) + (("contrastive", self.alpha),)       # (alpha is captured by value)
+
+    def _step_state(self):
+        return super()._step_state() + [self.total]
+
+    def describe(self):
+        return "contrastive search, %d candidates per prompt, " % self.nb + GreedyDecoder.describe(self)
+
+    @torch.no_grad()
+    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
+              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
+              rhyme_distinct=False, return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, keywords=None, refrain_scheme=None,
+              penalty_alpha=0.6):
+        """BeamDecoder.begin with the decoder's top_k rows per prompt, scores [0, -inf, ...] and total 0 per prompt.  `top_k`, `top_p`,
+        `generator` and `diversity_penalty` are the base signature's: anything but their defaults is refused.  With a prefix the prefill covers the prompt
+        only, so every lyric column gets its hidden state from a token step; the steps at which every row is held skip the head.
+        keywords=, num_beam_groups > 1, return_logprobs=True, a diversity penalty and sampling arguments are refused (ValueError)
+        before any device work."""
+        self._refuse(keywords, num_beam_groups, return_logprobs, diversity_penalty, top_k, top_p, generator)
+        _, alpha = check_contrastive(self.nb, penalty_alpha)
+        n_steps = super().begin(batch, length, temperature, repitition_penalty, prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size,
+                                line_lengths=line_lengths, line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme,
+                                rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct, refrain_scheme=refrain_scheme)
+        self.alpha = alpha
+        self.total.zero_()
+        self.sim.zero_()
+        if self.use_fixed:          # (the prefill stopped at the prompt; columns every row holds still need no head)
+            self.min_fixed = int(self.fixed_end.min().item())
+        return n_steps
+
+    @torch.no_grad()
+    def generate(self, batch, length, penalty_alpha=0.6, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None,
+                 no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
+                 rhyme_distinct=False, refrain_scheme=None, return_logprobs=False, num_beam_groups=1, keywords=None):
+        """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, 1 + length] in GreedyDecoder.generate's
+        column layout, scores [n] fp32): one lyric per prompt and the sum of the processed log-probabilities of its chosen tokens.
+        penalty_alpha in [0, 1]: the weight of the degeneration penalty (0: greedy decoding).  prefix, no_repeat_ngram_size,
+        line_lengths / line_end_ids, templates, rhyme_scheme / rhyme_classes / rhyme_distinct, refrain_scheme: as
+        BeamDecoder.generate, one per prompt.  keywords=, num_beam_groups > 1 and return_logprobs=True raise ValueError."""
+        self._refuse(keywords, num_beam_groups, return_logprobs)
+        ids = GreedyDecoder.generate(self, batch, length, temperature=temperature, repitition_penalty=repitition_penalty,
+                                     use_graph=use_graph, prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size,
+                                     line_lengths=line_lengths, line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme,
+                                     rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct, refrain_scheme=refrain_scheme,
+                                     penalty_alpha=penalty_alpha)
+        n, k = self.n_prompts, self.nb
+        return ids.view(n, k, -1)[:, 0].clone(), self.total + self.scores.view(n, k)[:, 0]

@@ -17,9 +17,9 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .constraints import (BANNED, Constraints, _check_constraints, check_groups, check_keywords, check_prefix, refrain_without_keywords,
+from .constraints import (BANNED, Constraints, _check_constraints, check_contrastive, check_groups, check_keywords, check_prefix, refrain_without_keywords,
                           sequence_scores)
-from .decode import BeamDecoder, GreedyDecoder, _keywords_need_beams
+from .decode import BeamDecoder, ContrastiveDecoder, GreedyDecoder, _keywords_need_beams
 from .data import encode_line_end, encode_prefix, encode_rhyme_classes, encode_template  # noqa: F401  (public: the opening lines / the line-end sets / the line templates / the rhyme classes of generate_samples / generate_beams)
 
 SENT_SLOT = 22  # generate.py:118-121
@@ -358,4 +358,42 @@ def generate_beams(model, rows, tokenizer, num_beams=4, length=None, temperature
                 out.append([beams[int(np.argmax(group[r] == g))] for g in range(G)])
             else:
                 out.append(beams if return_all else beams[0][0])
+    return out
+
+
+def generate_contrastive(model, rows, tokenizer, top_k=4, penalty_alpha=0.6, length=None, temperature=1.1, repetition_penalty=1.5,
+                         max_batch=256, prefixes=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None,
+                         rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, refrain_scheme=None, return_ids=False,
+                         keywords=None, num_beam_groups=1):
+    """Contrastive search per prompt on the batched, graph-replayed decoder (ContrastiveDecoder; Su et al. 2022): at every step the
+    model's top_k most probable characters are tried, and the one kept is the best by (1 - penalty_alpha) * probability -
+    penalty_alpha * (the largest cosine between its last-layer hidden state and those of the lyric so far).  One deterministic
+    lyric per prompt, at about the cost of a top_k-beam search; penalty_alpha=0 (or top_k=1) is greedy decoding.  Prompts are
+    decoded max_batch // top_k at a time; every lyric is cut back to what sample_sequence would have returned
+    (GreedyDecoder.reference_return) and post-processed as generate_samples does.  rows: as generate_samples.
+    Returns one (text, score) pair per prompt, or with return_ids=True (text, score, ids): score is the sum of the processed
+    log-probabilities of the chosen tokens (a beam score's scale), ids the 1 + length lyric ids -- a row score_sequences takes.
+    prefixes, no_repeat_ngram_size, line_lengths / line_end_ids, templates, rhyme_scheme / rhyme_classes / rhyme_distinct,
+    refrain_scheme: as generate_beams -- the rules act on the candidates, so the search chooses among characters they allow.
+    keywords= and num_beam_groups > 1 are refused with a ValueError that says why (ContrastiveDecoder); the model's raw token
+    log-probabilities of a returned lyric come from score_sequences on its ids."""
+    ContrastiveDecoder._refuse(keywords, num_beam_groups)
+    k, alpha = check_contrastive(top_k, penalty_alpha)
+    eng = model.engine()
+    sh = eng.sh
+    length = sh.max_seq_length if length is None else length
+    n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
+    cons = _check_constraints(prefixes, no_repeat_ngram_size, line_lengths, line_end_ids, n_prompts, length, sh, "%d prompts" % n_prompts,
+                              templates, rhyme_scheme, rhyme_classes, rhyme_distinct, refrain_scheme)
+    per = max(1, min(max_batch // k, n_prompts))
+    dec = ContrastiveDecoder(model, per, k, max_len=length)
+    out = []
+    for chunk, c, n in _chunks(_stack_rows(rows), cons, per, eng.dev):
+        ids, scores = dec.generate(chunk, length, penalty_alpha=alpha, temperature=temperature, repitition_penalty=repetition_penalty,
+                                   prefix=c.prefix, no_repeat_ngram_size=c.ngram, line_lengths=c.lines)
+        ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
+        for r in range(n):
+            seq = GreedyDecoder.reference_return(ids[r].tolist(), length, sent=sh.msl + 2)
+            out.append((postprocess_tokens(tokenizer.convert_ids_to_tokens(seq)), float(scores[r]))
+                       + ((ids[r].tolist(),) if return_ids else ()))
     return out

@@ -142,6 +142,8 @@ _SIGS = {
                                        _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp], _i),
     "mmtg_decode_beam_merge_kw": ([_vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _i, _vp], _i),
     "mmtg_decode_beam_merge_kw_fixed": ([_vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp], _i),
+    "mmtg_decode_contrastive_sim": ([_i, _vp, _l, _vp, _vp, _f, _vp, _i, _vp, _vp, _vp, _l, _vp, _l, _vp, _i, _i, _i, _vp], _i),
+    "mmtg_decode_contrastive_merge": ([_vp, _vp, _vp, _vp, _vp, _f, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
     "mmtg_decode_mlp_sync_words": ([], _i),
     "mmtg_decode_mlp_census": ([_vp, _vp], _i),
@@ -1197,6 +1199,27 @@ def decode_logprob(logits, ldl, V, seq, pos, P, out, B):
         raise ValueError("out must be fp32 [B, ncols] with unit column stride")
     _check(lib().mmtg_decode_logprob(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, _p(out), out.stride(0), out.shape[1], B,
                                      _stream()), "decode_logprob")
+
+
+def decode_contrastive_sim(x, gamma, beta, eps, hc, sim, keep, rows, pos, P, B, D, scores=None):
+    """Per row: u = unit(ln_f(x[b])) into hc[b, pos - P] and sim[b] = the largest dot(u, hc[rows[b, t], t - P]) over the row's kept
+    lyric columns t in [P, pos), 0 for none (include/mmtg_hip.h, mmtg_decode_contrastive_sim).  hc is fp32 [B, hc_len, D]."""
+    if hc.dtype != torch.float32 or hc.dim() != 3 or not hc.is_contiguous() or hc.shape[0] != B or hc.shape[2] != D:
+        raise ValueError("hc must be a contiguous fp32 [B, hc_len, D]")
+    if gamma.dtype != torch.float32 or beta.dtype != torch.float32 or sim.dtype != torch.float32:
+        raise ValueError("gamma, beta and sim must be fp32")
+    _check(lib().mmtg_decode_contrastive_sim(dt(x), _p(x), x.stride(0), _p(gamma), _p(beta), float(eps), _p(hc), hc.shape[1], _p(sim),
+                                             _p(scores), _p(keep), keep.stride(0), _p(rows), rows.stride(0), _p(pos), P, int(B), int(D),
+                                             _stream()), "decode_contrastive_sim")
+
+
+def decode_contrastive_merge(cand_val, cand_id, scores, sim, total, alpha, seq, keep, rows, pos, P, sent, k, n_prompts, pos_next=None,
+                             fixed_end=None):
+    """Per prompt: keep the row r* with the best (1 - alpha) * exp(score) - alpha * sim, give its column pos to every row, append the
+    next candidates (include/mmtg_hip.h, mmtg_decode_contrastive_merge)."""
+    _check(lib().mmtg_decode_contrastive_merge(_p(cand_val), _p(cand_id), _p(scores), _p(sim), _p(total), float(alpha), _p(seq),
+                                               seq.stride(0), _p(keep), keep.stride(0), _p(rows), rows.stride(0), _p(pos), P, sent, int(k),
+                                               int(n_prompts), _p(pos_next), _p(fixed_end), _stream()), "decode_contrastive_merge")
 
 
 def decode_advance(pos):
