@@ -465,6 +465,25 @@ MMTG_API int mmtg_logits_process_argmax(const float* logits, long ldl, int V, co
 MMTG_API int mmtg_logits_process_sample(const float* logits, long ldl, int V, const long long* generated, long ldg,
                                const int* gen_len, float temperature, float rep_penalty, int top_k, float top_p,
                                const float* uniforms, long long* next, float* filtered, int B, void* stream);
+/* The same with four more truncation stages between the nucleus filter and the draw (transformers' MinPLogitsWarper,
+ * TypicalLogitsWarper, EpsilonLogitsWarper and EtaLogitsWarper with min_tokens_to_keep = 1, in generate's warper order).  The reference
+ * has none of them (generate.py:64-94).  Each stage sees the softmax p over the survivors of everything before it (a dropped id has
+ * p = 0); pmax is p's largest value, H = -sum p log p with 0 log 0 = 0, and "the maximum" is the largest surviving logit:
+ *   min_p (0 = off, in [0, 1]):           drop ids with p < min_p * pmax.
+ *   typical_p (1 = off, in (0, 1]):       key = |-log p - H|; walk the survivors by ascending key accumulating p; keep every id whose
+ *                                         key is at most the key of the first id at which the mass reaches typical_p (ids tied at that
+ *                                         key stay; if the mass is never reached in floating point every survivor stays; p = 0 has key
+ *                                         +inf and is never kept).  The most probable id may go.
+ *   epsilon_cutoff (0 = off, in [0, 1)):  drop ids with p < epsilon_cutoff, but never the ids that hold the maximum.
+ *   eta_cutoff (0 = off, in [0, 1)):      eta = min(eta_cutoff, sqrt(eta_cutoff) * exp(-H)); drop ids with p < eta, but never the ids
+ *                                         that hold the maximum.
+ * No stage empties a row.  The draw is mmtg_logits_process_sample's, over the kept ids.  fp32 throughout: a kept set can differ from
+ * an exact evaluation only at an id within rounding of a stage's cut.  With all four off the result is mmtg_logits_process_sample's
+ * (from a kernel of its own: that entry's kernel is unchanged).  A value outside its range fails before any device call.           */
+MMTG_API int mmtg_logits_process_sample_warp(const float* logits, long ldl, int V, const long long* generated, long ldg,
+                               const int* gen_len, float temperature, float rep_penalty, int top_k, float top_p, float min_p,
+                               float typical_p, float epsilon_cutoff, float eta_cutoff, const float* uniforms, long long* next,
+                               float* filtered, int B, void* stream);
 
 /* ---------------------------------------------------------------- KV-cached decode step (generate.py:117-142)
  * Batched, lock-step: every row is at position *pos_ptr (a DEVICE int, so a captured hipGraph of
@@ -863,6 +882,19 @@ MMTG_API int mmtg_decode_sample_refrain(const float* logits, long ldl, int V, lo
                               const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets,
                               const short* set_of, const int* tmpl, const short* class_of, const signed char* lead, int distinct,
                               const signed char* src, void* stream);
+/* mmtg_decode_sample_refrain with the four truncation stages of mmtg_logits_process_sample_warp (min_p, typical_p, epsilon_cutoff,
+ * eta_cutoff after top_p; the rule is stated there) between the nucleus filter and the draw: the selection entry of a sampled
+ * generation with any of the four on, whatever its constraints.  One entry over the most general rule serves them all through that
+ * rule's "no rule" forms: fixed_end null (no prefix), ngram 0, lo / hi null (no line rule), tmpl null, class_of / lead null (no rhyme
+ * scheme), and a src table of -1 (no copy line; src itself and n_lines in 1 .. 128 are still required).  The stages act on the
+ * processed logits after every ban, so a banned id has p = 0 in all of them.  Logits and uniforms are required: a step without the
+ * head ends in the entry it always ended in.  A kernel of its own; the kernels of every earlier entry compile to the same code.   */
+MMTG_API int mmtg_decode_sample_warp(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                              int P, int sent, float temperature, float rep_penalty, int top_k, float top_p, float min_p,
+                              float typical_p, float epsilon_cutoff, float eta_cutoff, const float* uniforms, long ldu, int B,
+                              int* pos_next, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
+                              int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
+                              const short* class_of, const signed char* lead, int distinct, const signed char* src, void* stream);
 MMTG_API int mmtg_decode_beam_candidates_refrain(const float* logits, long ldl, int V, const long long* seq, long ldseq,
                                        const int* pos_ptr, int P, int sent, float temperature, float rep_penalty, int nb,
                                        float* cand_val, int* cand_id, int B, const int* fixed_end, int ngram, const unsigned char* lo,

@@ -94,6 +94,92 @@ def check_contrastive(top_k, penalty_alpha):
     return k, alpha
 
 
+WARP_OFF = (0.0, 1.0, 0.0, 0.0)        # (min_p, typical_p, epsilon_cutoff, eta_cutoff) at which every stage is off
+
+
+def check_warp(min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+    """The four truncation settings of a sampled generation beyond top_k / top_p, with the names, defaults and ranges of
+    transformers' generate: (min_p, typical_p, epsilon_cutoff, eta_cutoff) as floats.  min_p in [0, 1] (0 off), typical_p in (0, 1]
+    (1 off), epsilon_cutoff and eta_cutoff in [0, 1) (0 off); anything else (a NaN, a non-number) raises a ValueError that names the
+    argument.  include/mmtg_hip.h states the rule, ``warp_filter`` restates it."""
+    out = []
+    for name, v, ok, rng in (("min_p", min_p, lambda a: 0.0 <= a <= 1.0, "[0, 1]"),
+                             ("typical_p", typical_p, lambda a: 0.0 < a <= 1.0, "(0, 1]"),
+                             ("epsilon_cutoff", epsilon_cutoff, lambda a: 0.0 <= a < 1.0, "[0, 1)"),
+                             ("eta_cutoff", eta_cutoff, lambda a: 0.0 <= a < 1.0, "[0, 1)")):
+        try:
+            if isinstance(v, (bool, np.bool_, str, bytes)):
+                raise TypeError
+            a = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number in %s, got %r" % (name, rng, v)) from None
+        if not ok(a):                            # (NaN fails every comparison)
+            raise ValueError("%s must be in %s, got %r" % (name, rng, v))
+        out.append(a)
+    return tuple(out)
+
+
+def _warp_row(x, min_p, typical_p, epsilon_cutoff, eta_cutoff, margins):
+    keep = x > -np.inf
+
+    def softmax():
+        """p, log p and the entropy over the survivors (a dropped id has p = 0; 0 log 0 = 0), and who holds their maximum"""
+        m = x[keep].max()
+        e = np.where(keep, np.exp(np.where(keep, x - m, 0.0)), 0.0)
+        tot = e.sum()
+        logp = np.where(keep, (x - m) - np.log(tot), -np.inf)
+        p = e / tot
+        pos = p > 0.0
+        return p, logp, -(p[pos] * logp[pos]).sum(), keep & (x == m)
+
+    def cut_probabilities(thr, what):
+        nonlocal keep
+        p, _, _, top = softmax()
+        if margins is not None and thr > 0.0:
+            margins.append((what, "probability", float(np.abs(p[keep] - thr).min() / thr)))
+        keep = keep & ((p >= thr) | top)
+
+    if min_p > 0.0:
+        cut_probabilities(min_p * softmax()[0].max(), "min_p")
+    if typical_p < 1.0:
+        p, logp, H, _ = softmax()
+        key = np.where(p > 0.0, np.abs(-logp - H), np.inf)
+        order = np.flatnonzero(keep)
+        order = order[np.argsort(key[order], kind="stable")]
+        cum = np.cumsum(p[order])
+        reached = np.flatnonzero(cum >= typical_p)
+        if margins is not None:
+            ends = np.append(key[order][1:] != key[order][:-1], True)          # the mass as the ids of one key arrive together
+            margins.append(("typical_p", "mass", float(np.abs(cum[ends] - typical_p).min())))
+        if reached.size:
+            cut = key[order[reached[0]]]
+            if margins is not None:
+                away = np.abs(key[order] - cut)[key[order] != cut]
+                margins.append(("typical_p", "key", float(away.min()) if away.size else np.inf))
+            keep = keep & (key <= cut)
+    if epsilon_cutoff > 0.0:
+        cut_probabilities(epsilon_cutoff, "epsilon_cutoff")
+    if eta_cutoff > 0.0:
+        H = softmax()[2]
+        cut_probabilities(min(eta_cutoff, math.sqrt(eta_cutoff) * math.exp(-H)), "eta_cutoff")
+    return np.where(keep, x, -np.inf)
+
+
+def warp_filter(logits, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, margins=None):
+    """The four truncation stages of the *_warp entries (include/mmtg_hip.h) in float64 numpy, the host's statement of the rule and the
+    tests' oracle: transformers' MinPLogitsWarper, TypicalLogitsWarper, EpsilonLogitsWarper and EtaLogitsWarper with
+    min_tokens_to_keep = 1, chained in that order.  logits [V] or [rows, V]: the processed logits after the top-k / top-p filters
+    (-inf where dropped or banned).  Returns a float64 array of the same shape, -inf where a stage dropped the id.  Each stage sees the
+    softmax over the survivors of the stages before it.  margins (a list, optional) receives (argument, kind, distance) per row and
+    active stage -- how far the nearest id lies from the stage's cut: "probability" relative to the cut, the typical stage's "key"
+    absolute (ids at the cut key itself aside) and its accumulated "mass" absolute -- for tests that compare an fp32 evaluation."""
+    warp = check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+    x = np.asarray(logits, dtype=np.float64)
+    rows = x.reshape(-1, x.shape[-1])
+    out = np.stack([r.copy() if not (r > -np.inf).any() else _warp_row(r, *warp, margins) for r in rows])
+    return out.reshape(x.shape)
+
+
 def chosen_mask(ids, sent=22, prefix_lens=None):
     """Which columns of generated lyric ids count towards a row's score: bool [B, 1 + length], host only.  Column j >= 1 of row b
     counts iff it is not a cadence column (j % sent not in {0, sent - 1}: the forced [#START#] / [#EOS#]), it lies past the row's

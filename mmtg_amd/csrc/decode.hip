@@ -289,7 +289,305 @@ __global__ __launch_bounds__(256) void logits_sample_kernel(const float* __restr
     if (tid == 0) next[b] = pick;
 }
 
+// ------------------------------------------------------------------ truncation beyond top-k / top-p (the *_warp entries)
+// sample_row with four more stages between the nucleus filter and the draw, in transformers' warper order: min-p, locally typical,
+// epsilon, eta (include/mmtg_hip.h states the rule).  A function of its own: sample_row and its instantiations are untouched, and this
+// one is inlined by force into its two kernels, so the module gets no out-of-line function that uses LDS (sample_row's comment).
+// No per-id memory beyond px: with e(v) = exp(px[v] - mx) and the stage's survivor mass tot, p = e / tot and log p = px[v] - mx -
+// log(tot) are recomputed where needed.  Every stage is block reductions over its survivors (mass, sum of e * (px - mx) for the
+// entropy, the survivors' maximum) that give one scalar cut; the typical cut is a 4-pass radix select by accumulated mass over the
+// integer image of key = |-log p - H|, ascending, so ids tied at the cut key stay.  The cuts combine into `kept`, which the
+// stages after them, `filtered` and the CDF pass evaluate.
+struct WarpCuts {
+    unsigned keyt;      // top-k / top-p: integer image of the smallest kept logit
+    float mx;           // the row's largest processed logit
+    float emin;         // min-p: e >= emin
+    bool typ;           // the typical cut is set
+    float lt, H;        // typical: log of the stage's mass, its entropy
+    unsigned tkey;      // typical: integer image of the largest kept key
+    float msurv;        // the largest logit among the typical stage's survivors (the epsilon and eta stages always keep it)
+    float eps_e, eta_e; // epsilon / eta: e >= cut (p >= cutoff, times the stage's mass)
+    __device__ __forceinline__ float tkeyf(float x) const { return fabsf((lt - (x - mx)) - H); }
+    __device__ __forceinline__ bool kept(float x) const {
+        if (!(fkey(x) >= keyt && x > -INFINITY)) return false;
+        const float e = expf(x - mx);
+        if (e < emin) return false;
+        if (typ && fkey(tkeyf(x)) > tkey) return false;
+        return x >= msurv || (e >= eps_e && e >= eta_e);
+    }
+};
+
+template <bool NG = false, bool LN = false>
+__device__ __forceinline__ int sample_row_warp(const float* row, int V, const unsigned* cnt, float* px, float temperature,
+                                               float rep_penalty, int top_k, float top_p, float min_p, float typical_p,
+                                               float epsilon_cutoff, float eta_cutoff, float u, int tid, float* filtered) {
+    __shared__ unsigned hcnt[256];
+    __shared__ float hmass[256];
+    __shared__ float sred[4];
+    __shared__ unsigned s_prefix, s_rem;
+    __shared__ float s_acc;
+    __shared__ int s_pick;
+    for (int v = tid; v < V; v += 256) {
+        float x = row[v];
+        if ((LN || v != 0) && v != 102) {
+            const int c = (cnt[v >> 1] >> (16 * (v & 1))) & 0xFFFF;
+            x = penalize<NG>(x, c, rep_penalty);
+        }
+        x = x / temperature;
+        if (v == 1 || v == 2 || v == 100 || v == 102) x = -INFINITY;
+        px[v] = x;
+    }
+    __syncthreads();
+    // block reductions (every thread of the block calls; the result is uniform)
+    auto block_sum = [&](float a) {
+        a = wave_sum(a);
+        if ((tid & 63) == 0) sred[tid >> 6] = a;
+        __syncthreads();
+        a = sred[0] + sred[1] + sred[2] + sred[3];
+        __syncthreads();
+        return a;
+    };
+    auto block_max = [&](float a) {
+        a = wave_max(a);
+        if ((tid & 63) == 0) sred[tid >> 6] = a;
+        __syncthreads();
+        a = fmaxf(fmaxf(sred[0], sred[1]), fmaxf(sred[2], sred[3]));
+        __syncthreads();
+        return a;
+    };
+    // ---- top-k and top-p, as sample_row computes them
+    unsigned keyk = 0u;
+    if (top_k > 0 && top_k < V) {
+        if (tid == 0) { s_prefix = 0u; s_rem = (unsigned)top_k; }
+        unsigned mask = 0u;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hcnt[tid] = 0u;
+            __syncthreads();
+            const unsigned prefix = s_prefix;
+            for (int v = tid; v < V; v += 256) {
+                const unsigned k = fkey(px[v]);
+                if ((k & mask) == prefix) atomicAdd(hcnt + ((k >> shift) & 255u), 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned rem = s_rem;
+                int bin = 255;
+                for (; bin > 0; --bin) {
+                    if (hcnt[bin] >= rem) break;
+                    rem -= hcnt[bin];
+                }
+                s_rem = rem;
+                s_prefix = prefix | ((unsigned)bin << shift);
+            }
+            mask |= 255u << shift;
+            __syncthreads();
+        }
+        keyk = s_prefix;
+    }
+    float mx = -INFINITY;
+    for (int v = tid; v < V; v += 256)
+        if (fkey(px[v]) >= keyk) mx = fmaxf(mx, px[v]);
+    mx = block_max(mx);
+    float tot = 0.f;
+    for (int v = tid; v < V; v += 256)
+        if (fkey(px[v]) >= keyk) tot += expf(px[v] - mx);
+    tot = block_sum(tot);
+    unsigned keyp = 0u;
+    if (top_p > 0.f) {
+        const float P = top_p * tot;
+        if (tid == 0) { s_prefix = 0u; s_acc = 0.f; s_pick = 1; }
+        unsigned mask = 0u;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hmass[tid] = 0.f;
+            __syncthreads();
+            const unsigned prefix = s_prefix;
+            if (s_pick)
+                for (int v = tid; v < V; v += 256) {
+                    const unsigned k = fkey(px[v]);
+                    if (k >= keyk && (k & mask) == prefix) atomicAdd(hmass + ((k >> shift) & 255u), expf(px[v] - mx));
+                }
+            __syncthreads();
+            if (tid == 0 && s_pick) {
+                float acc = s_acc;
+                int bin = 255;
+                for (; bin >= 0; --bin) {
+                    if (acc + hmass[bin] > P) break;
+                    acc += hmass[bin];
+                }
+                if (bin < 0) s_pick = 0;
+                else { s_acc = acc; s_prefix = prefix | ((unsigned)bin << shift); }
+            }
+            mask |= 255u << shift;
+            __syncthreads();
+        }
+        keyp = s_pick ? s_prefix : 0u;
+        __syncthreads();
+    }
+    WarpCuts w = {keyk > keyp ? keyk : keyp, mx, 0.f, false, 0.f, 0.f, 0u, mx, 0.f, 0.f};
+    // ---- min-p: p < min_p * pmax, and pmax = 1 / tot, so e < min_p (the maximum has e = 1 >= min_p)
+    w.emin = min_p;
+    // ---- locally typical: the ids nearest the entropy, by ascending key, until their mass reaches typical_p
+    if (typical_p < 1.f) {
+        float m = 0.f, s = 0.f;
+        for (int v = tid; v < V; v += 256)
+            if (w.kept(px[v])) { const float e = expf(px[v] - mx); m += e; if (e > 0.f) s += e * (px[v] - mx); }
+        m = block_sum(m);
+        s = block_sum(s);
+        const float lt = logf(m), H = lt - s / m, P = typical_p * m;
+        if (tid == 0) { s_prefix = 0u; s_acc = 0.f; s_pick = 1; }
+        unsigned mask = 0u;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hmass[tid] = 0.f;
+            __syncthreads();
+            const unsigned prefix = s_prefix;
+            if (s_pick)
+                for (int v = tid; v < V; v += 256) {
+                    const float x = px[v];
+                    if (!w.kept(x)) continue;
+                    const unsigned k = fkey(fabsf((lt - (x - mx)) - H));
+                    if ((k & mask) == prefix) atomicAdd(hmass + ((k >> shift) & 255u), expf(x - mx));
+                }
+            __syncthreads();
+            if (tid == 0 && s_pick) {
+                float acc = s_acc;
+                int bin = 0;
+                for (; bin < 256; ++bin) {
+                    if (acc + hmass[bin] >= P) break;
+                    acc += hmass[bin];
+                }
+                if (bin == 256 && shift == 24) s_pick = 0;     // the mass is never reached in fp32: keep every survivor
+                else {
+                    if (bin == 256) bin = 255;                 // reached at the end of the bin above (the sums round apart): all of it
+                    s_acc = acc;
+                    s_prefix = prefix | ((unsigned)bin << shift);
+                }
+            }
+            mask |= 255u << shift;
+            __syncthreads();
+        }
+        if (s_pick) { w.lt = lt; w.H = H; w.tkey = s_prefix; w.typ = true; }
+        __syncthreads();
+        if (w.typ && (epsilon_cutoff > 0.f || eta_cutoff > 0.f)) {     // the head may be gone: the later stages keep the survivors' maximum
+            float ms = -INFINITY;
+            for (int v = tid; v < V; v += 256)
+                if (w.kept(px[v])) ms = fmaxf(ms, px[v]);
+            w.msurv = block_max(ms);
+        }
+    }
+    // ---- epsilon: p < epsilon_cutoff over the survivors
+    if (epsilon_cutoff > 0.f) {
+        float m = 0.f;
+        for (int v = tid; v < V; v += 256)
+            if (w.kept(px[v])) m += expf(px[v] - mx);
+        m = block_sum(m);
+        w.eps_e = epsilon_cutoff * m;
+    }
+    // ---- eta: p < min(eta_cutoff, sqrt(eta_cutoff) * exp(-H)) over the survivors
+    if (eta_cutoff > 0.f) {
+        float m = 0.f, s = 0.f;
+        for (int v = tid; v < V; v += 256)
+            if (w.kept(px[v])) { const float e = expf(px[v] - mx); m += e; if (e > 0.f) s += e * (px[v] - mx); }
+        m = block_sum(m);
+        s = block_sum(s);
+        const float H = logf(m) - s / m;
+        w.eta_e = fminf(eta_cutoff, sqrtf(eta_cutoff) * expf(-H)) * m;
+    }
+    if (filtered)
+        for (int v = tid; v < V; v += 256) filtered[v] = w.kept(px[v]) ? px[v] : -INFINITY;
+    // ---- inverse CDF over the kept ids in index order (sample_row's)
+    const int chunk = (V + 255) / 256, v0 = tid * chunk, v1 = min(V, v0 + chunk);
+    float mine = 0.f;
+    for (int v = v0; v < v1; ++v)
+        if (w.kept(px[v])) mine += expf(px[v] - mx);
+    hmass[tid] = mine;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const float add = tid >= o ? hmass[tid - o] : 0.f;
+        __syncthreads();
+        hmass[tid] += add;
+        __syncthreads();
+    }
+    const float Z = hmass[255], target = u * Z;
+    if (tid == 0) s_pick = 0x7fffffff;
+    __syncthreads();
+    const float before = tid ? hmass[tid - 1] : 0.f;
+    if (mine > 0.f && target < hmass[tid] && target >= before) {
+        float acc = before;
+        int pick = -1;
+        for (int v = v0; v < v1; ++v)
+            if (w.kept(px[v])) {
+                acc += expf(px[v] - mx);
+                pick = v;
+                if (target < acc) break;
+            }
+        if (pick >= 0) atomicMin(&s_pick, pick);
+    }
+    __syncthreads();
+    if (s_pick == 0x7fffffff) {          // rounding at the upper end: the last kept id
+        int last = -1;
+        for (int v = v0; v < v1; ++v)
+            if (w.kept(px[v])) last = v;
+        __syncthreads();
+        if (tid == 0) s_pick = -1;
+        __syncthreads();
+        if (last >= 0) atomicMax(&s_pick, last);
+        __syncthreads();
+    }
+    return s_pick < 0 ? 0 : s_pick;
+}
+
+__global__ __launch_bounds__(256) void logits_sample_warp_kernel(const float* __restrict__ logits, long ldl, int V,
+        const long long* __restrict__ generated, long ldg, const int* __restrict__ gen_len,
+        float temperature, float rep_penalty, int top_k, float top_p, float min_p, float typical_p, float epsilon_cutoff,
+        float eta_cutoff, const float* __restrict__ uniforms, long long* __restrict__ next, float* __restrict__ filtered) {
+    extern __shared__ unsigned cnt[];
+    float* px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = min(gen_len[b], MAXGEN);
+    const long long* gen = generated + (long)b * ldg;
+    if (n > 0 && gen[n - 1] == 0) {  // sticky PAD (generate.py:137-138)
+        if (tid == 0) next[b] = 0;
+        return;
+    }
+    count_ids(cnt, V, gen, n, tid);
+    const int pick = sample_row_warp(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k, top_p, min_p, typical_p,
+                                     epsilon_cutoff, eta_cutoff, uniforms[b], tid, filtered ? filtered + (long)b * ldl : nullptr);
+    if (tid == 0) next[b] = pick;
+}
+
+// (what both *_warp entries ask of the four cuts; a NaN fails every test)
+static int warp_args_check(const char* what, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff) {
+    MMTG_REQUIRE(min_p >= 0.f && min_p <= 1.f, "%s: min_p must be in [0, 1]", what);
+    MMTG_REQUIRE(typical_p > 0.f && typical_p <= 1.f, "%s: typical_p must be in (0, 1]", what);
+    MMTG_REQUIRE(epsilon_cutoff >= 0.f && epsilon_cutoff < 1.f, "%s: epsilon_cutoff must be in [0, 1)", what);
+    MMTG_REQUIRE(eta_cutoff >= 0.f && eta_cutoff < 1.f, "%s: eta_cutoff must be in [0, 1)", what);
+    return MMTG_OK;
+}
+
 }  // namespace
+
+extern "C" int mmtg_logits_process_sample_warp(const float* logits, long ldl, int V, const long long* generated, long ldg,
+                                               const int* gen_len, float temperature, float rep_penalty, int top_k, float top_p,
+                                               float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff,
+                                               const float* uniforms, long long* next, float* filtered, int B, void* stream) {
+    MMTG_REQUIRE(logits && generated && gen_len && uniforms && next && B > 0 && V > 0 && ldl >= V, "logits_process_sample_warp: bad args");
+    MMTG_REQUIRE(temperature > 0.f && rep_penalty > 0.f && top_k >= 0 && top_p >= 0.f, "logits_process_sample_warp: bad sampling parameters");
+    if (int e = warp_args_check("logits_process_sample_warp", min_p, typical_p, epsilon_cutoff, eta_cutoff)) return e;
+    MMTG_REQUIRE(V <= 24000, "logits_process_sample_warp: vocabulary of %d exceeds the LDS row image (24000)", V);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, 40.0 * B * V, 4.0 * B * V);
+    const size_t shm = (size_t)((V + 1) / 2) * 4 + (size_t)V * 4;
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute((const void*)logits_sample_warp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
+            MMTG_FAIL(MMTG_ERR_HIP, "logits_process_sample_warp: cannot raise dynamic LDS");
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(logits_sample_warp_kernel, dim3(B), dim3(256), shm, s, logits, ldl, V, generated, ldg, gen_len, temperature,
+                       rep_penalty, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, uniforms, next, filtered);
+    MMTG_LAUNCH_CHECK("logits_process_sample_warp");
+    return MMTG_OK;
+}
 
 extern "C" int mmtg_logits_process_argmax(const float* logits, long ldl, int V, const long long* generated,
                                           long ldg, const int* gen_len, float temperature, float rep_penalty,
@@ -1428,6 +1726,42 @@ __global__ __launch_bounds__(256) void decode_select_kernel(const float* __restr
             if (sval[w] > best || (sval[w] == best && sidx[w] < besti)) { best = sval[w]; besti = sidx[w]; }
         gen[j] = besti == 0x7fffffff ? 0 : besti;
     }
+}
+
+// decode_select_kernel<RefrainRule>'s sampling path with sample_row_warp for the draw (mmtg_decode_sample_warp): a kernel of its
+// own over the most general rule, whose "no rule" forms serve every generation, so the kernels above stay what they were.  Always
+// with logits and uniforms (a step without the head runs the entry it always ran).
+__global__ __launch_bounds__(256) void decode_select_warp_kernel(const float* __restrict__ logits, long ldl, int V,
+        long long* __restrict__ seq, long ldseq, const int* __restrict__ pos_ptr, int P, int sent,
+        float temperature, float rep_penalty, int top_k, float top_p, float min_p, float typical_p, float epsilon_cutoff,
+        float eta_cutoff, const float* __restrict__ uniforms, long ldu, int* __restrict__ pos_next, RefrainRule rule) {
+    extern __shared__ unsigned cnt[];
+    const int b = blockIdx.x, tid = threadIdx.x, pos = *pos_ptr;
+    if (pos_next && b == 0 && tid == 0) *pos_next = pos + 1;
+    if (rule.held(b, pos)) return;
+    const int j = pos + 1 - P;                 // lyric index of the token to append
+    if (j < 1) return;                         // still inside the prompt / the initial [#START#]
+    long long* gen = seq + (long)b * ldseq + P;
+    if (j > 1 && (j + 1) % sent == 0) { if (tid == 0) gen[j] = 2; return; }     // [#EOS#]
+    if (j > 1 && (j + 1) % sent == 1) { if (tid == 0) gen[j] = 1; return; }     // [#START#]
+    const int q = rule.copy_from(b, j, sent);
+    if (q >= 0) { const long long v = gen[q]; if (tid == 0) gen[j] = v; return; }
+    const int n = min(j, MAXGEN);
+    if (gen[n - 1] == 0) { if (tid == 0) gen[j] = 0; return; }                   // sticky PAD
+    bool rhymes = false;
+    const LineCol lc = rule.col(b, j, sent, gen, &rhymes);
+    if (lc.force_pad) { if (tid == 0) gen[j] = 0; return; }
+    const TmplCol tc = rule.sym(b, j, sent);
+    if (tc.given >= 0) { if (tid == 0) gen[j] = tc.given; return; }
+    count_ids(cnt, V, gen, n, tid);
+    const NgramBan ng = rule.bans();
+    if (ng.n > 0) ban_ngrams(cnt, reinterpret_cast<int*>(cnt + (V + 1) / 2 + V), V, gen, min(n, ng.hist_cap), ng.n, tid);
+    ban_line_tmpl(cnt, V, lc, tc.cls, tid);
+    rule.ban_distinct(cnt, b, j, sent, gen, lc, rhymes, tid);
+    float* px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
+    const int pick = sample_row_warp<true, true>(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k, top_p, min_p,
+                                                 typical_p, epsilon_cutoff, eta_cutoff, uniforms[(long)pos * ldu + b], tid, nullptr);
+    if (tid == 0) gen[j] = pick;
 }
 
 __global__ void decode_advance_kernel(int* pos_ptr) { *pos_ptr += 1; }
@@ -2579,6 +2913,39 @@ extern "C" int mmtg_decode_sample_refrain(const float* logits, long ldl, int V, 
     if (int e = sample_args_check("decode_sample_refrain", uniforms, ldu, B, top_k, top_p)) return e;
     return decode_select_launch("decode_sample_refrain", logits, ldl, V, seq, ldseq, pos_ptr, P, sent, temperature, rep_penalty, top_k, top_p,
                                 uniforms, ldu, B, pos_next, stream, rf);
+}
+
+extern "C" int mmtg_decode_sample_warp(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                       int P, int sent, float temperature, float rep_penalty, int top_k, float top_p, float min_p,
+                                       float typical_p, float epsilon_cutoff, float eta_cutoff, const float* uniforms, long ldu, int B,
+                                       int* pos_next, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
+                                       int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
+                                       const short* class_of, const signed char* lead, int distinct, const signed char* src,
+                                       void* stream) {
+    RefrainRule rf;
+    MMTG_REQUIRE(logits, "decode_sample_warp: a draw needs logits");
+    if (int e = refrain_check("decode_sample_warp", V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, tmpl,
+                              class_of, lead, distinct, src, &rf))
+        return e;
+    if (int e = sample_args_check("decode_sample_warp", uniforms, ldu, B, top_k, top_p)) return e;
+    if (int e = warp_args_check("decode_sample_warp", min_p, typical_p, epsilon_cutoff, eta_cutoff)) return e;
+    MMTG_REQUIRE(seq && pos_ptr && B > 0, "decode_sample_warp: bad args");
+    MMTG_REQUIRE(pos_next != pos_ptr, "decode_sample_warp: pos_next must not alias pos_ptr (blocks read the position while block 0 writes the next)");
+    MMTG_REQUIRE(V > 0 && ldl >= V && temperature > 0.f && rep_penalty > 0.f, "decode_sample_warp: bad logits args");
+    MMTG_REQUIRE(V <= 24000, "decode_sample_warp: vocabulary of %d exceeds the LDS tables", V);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, 40.0 * B * V, 4.0 * B * V);
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute((const void*)decode_select_warp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
+            MMTG_FAIL(MMTG_ERR_HIP, "decode_sample_warp: cannot raise dynamic LDS");
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(decode_select_warp_kernel, dim3(B), dim3(256), select_lds(V, true, rf), s, logits, ldl, V, seq, ldseq, pos_ptr, P,
+                       sent, temperature, rep_penalty, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, uniforms, ldu, pos_next,
+                       rf);
+    MMTG_LAUNCH_CHECK("decode_sample_warp");
+    return MMTG_OK;
 }
 
 extern "C" int mmtg_decode_beam_candidates_refrain(const float* logits, long ldl, int V, const long long* seq, long ldseq,

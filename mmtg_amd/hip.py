@@ -12,6 +12,8 @@ import os
 
 import torch
 
+from .constraints import check_warp
+
 F32, BF16 = 0, 1
 ABI_VERSION = 12
 EPI_NONE, EPI_GELU, EPI_TANH, EPI_RESID, EPI_DGELU, EPI_DTANH, EPI_ATOMIC, EPI_ROWDOT = range(8)
@@ -99,6 +101,7 @@ _SIGS = {
     "mmtg_decode_attn": ([_i, _vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mmtg_decode_attn_split": ([_i, _vp, _i, _vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mmtg_logits_process_sample": ([_vp, _l, _i, _vp, _l, _vp, _f, _f, _i, _f, _vp, _vp, _vp, _i, _vp], _i),
+    "mmtg_logits_process_sample_warp": ([_vp, _l, _i, _vp, _l, _vp, _f, _f, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_sample": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp], _i),
     "mmtg_decode_select": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp], _i),
     "mmtg_decode_advance": ([_vp, _vp], _i),
@@ -135,6 +138,8 @@ _SIGS = {
                                     _vp, _vp], _i),
     "mmtg_decode_sample_refrain": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i,
                                    _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
+    "mmtg_decode_sample_warp": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _f, _f, _f, _f, _vp, _l, _i, _vp, _vp, _i, _vp, _vp, _i,
+                                _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
     "mmtg_decode_beam_candidates_refrain": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
                                             _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
     "mmtg_decode_logprob": ([_vp, _l, _i, _vp, _l, _vp, _i, _vp, _l, _i, _i, _vp], _i),
@@ -778,6 +783,16 @@ def logits_process_sample(logits, ldl, V, generated, ldg, gen_len, temperature, 
                                             B, _stream()), "logits_process_sample")
 
 
+def logits_process_sample_warp(logits, ldl, V, generated, ldg, gen_len, temperature, rep_penalty, top_k, top_p, uniforms, nxt, B,
+                               min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, filtered=None):
+    """logits_process_sample with the min-p, typical, epsilon and eta stages between the nucleus filter and the draw
+    (include/mmtg_hip.h; constraints.warp_filter restates them)."""
+    warp = check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+    _check(lib().mmtg_logits_process_sample_warp(_p(logits), ldl, V, _p(generated), ldg, _p(gen_len), float(temperature),
+                                                 float(rep_penalty), int(top_k), float(top_p), *warp, _p(uniforms), _p(nxt),
+                                                 _p(filtered), B, _stream()), "logits_process_sample_warp")
+
+
 # ------------------------------------------------------------------ KV-cached decode step
 def decode_embed(table, seq, c, x, pos, tpw_type, tpw_mask, type_out, keep, B, P, S, E, two_sents, V, sent, max_sent_num):
     _check(lib().mmtg_decode_embed(dt(table), _p(table), _p(seq), seq.stride(0), _p(c), _p(x), _p(pos), _p(tpw_type),
@@ -953,6 +968,17 @@ def _select(form, logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, B
     _check(getattr(lib(), "mmtg_" + name)(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
                                           float(rep_penalty), *draw, B, _p(pos_next),
                                           *_rule_tail(form, B, V, fixed_end, ngram, tables, tmpl, sent, rhyme, refrain), _stream()), name)
+
+
+def decode_sample_warp(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, warp, uniforms, B, src, tables=None,
+                       rhyme=None, tmpl=None, ngram=0, pos_next=None, fixed_end=None):
+    """mmtg_decode_sample_warp: the refrain form's draw with warp = (min_p, typical_p, epsilon_cutoff, eta_cutoff) (include/mmtg_hip.h).
+    src is required (int8 [rows >= B, n_lines], all -1 without a refrain); every other table may be None."""
+    _check(lib().mmtg_decode_sample_warp(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                         float(rep_penalty), int(top_k), float(top_p), *check_warp(*warp), _p(uniforms),
+                                         0 if uniforms is None else uniforms.stride(0), B, _p(pos_next),
+                                         *_rule_tail("_refrain", B, V, fixed_end, ngram, tables, tmpl, sent, rhyme, src), _stream()),
+           "decode_sample_warp")
 
 
 def _beam_candidates(form, logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=None, ngram=0,
