@@ -484,6 +484,24 @@ MMTG_API int mmtg_logits_process_sample_warp(const float* logits, long ldl, int 
                                const int* gen_len, float temperature, float rep_penalty, int top_k, float top_p, float min_p,
                                float typical_p, float epsilon_cutoff, float eta_cutoff, const float* uniforms, long long* next,
                                float* filtered, int B, void* stream);
+/* The same with Mirostat (Basu et al. 2021, version 2, llama.cpp's `mirostat = 2`) as the last stage, behind top-k, top-p, min-p,
+ * typical, epsilon and eta: a cut that adapts after every draw so that the observed surprise of the text stays near mirostat_tau bits
+ * per token.  The state is mu[b], one fp32 per row, in bits; the caller starts it at 2 * mirostat_tau.  On a row that draws, with S
+ * the survivors of every earlier stage and p the softmax over S:
+ *   1. keep v in S when -log2 p(v) <= mu[b], and every id that holds S's largest logit (so no row is emptied);
+ *   2. q = softmax over the kept ids; draw x by inverse CDF over the kept ids in index order with uniforms[b];
+ *   3. s = -log2 q(x);  mu[b] <- mu[b] - mirostat_eta * (s - mirostat_tau).
+ * llama.cpp keeps only the first id of its sorted list when mu lies below every surprise; this rule keeps every id tied at the
+ * maximum.  The two differ only on an exact tie at the top.  Version 1 (a Zipf exponent estimate) is not built.
+ * mirostat_tau in (0, 32], mirostat_eta in [0, 1] (0 freezes mu: the stage is then epsilon_cutoff = 2^-mu sampling); mu [B] is read and
+ * written and required; surprise (nullable, [B]) receives the step's s.  A sticky-PAD row writes next = 0 and surprise = 0 and leaves
+ * mu alone.  A value outside its range fails before any device call.  fp32 throughout: the mass and the scan's total come from
+ * fixed-order reductions, so with top_p and typical_p off the mu trajectory is reproducible bit for bit.  A kernel of its own.  */
+MMTG_API int mmtg_logits_process_sample_mirostat(const float* logits, long ldl, int V, const long long* generated, long ldg,
+                               const int* gen_len, float temperature, float rep_penalty, int top_k, float top_p, float min_p,
+                               float typical_p, float epsilon_cutoff, float eta_cutoff, const float* uniforms, long long* next,
+                               float* filtered, int B, float mirostat_tau, float mirostat_eta, float* mu, float* surprise,
+                               void* stream);
 
 /* ---------------------------------------------------------------- KV-cached decode step (generate.py:117-142)
  * Batched, lock-step: every row is at position *pos_ptr (a DEVICE int, so a captured hipGraph of
@@ -895,6 +913,18 @@ MMTG_API int mmtg_decode_sample_warp(const float* logits, long ldl, int V, long 
                               int* pos_next, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
                               int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
                               const short* class_of, const signed char* lead, int distinct, const signed char* src, void* stream);
+/* mmtg_decode_sample_warp with the Mirostat stage of mmtg_logits_process_sample_mirostat (the rule is stated there) behind its four:
+ * the selection entry of every head step of a generation with mirostat_tau on, whatever its other sampling values and constraints.
+ * mu [B] (required) is row b's state; only a column that the row draws updates it.  The forced [#START#] / [#EOS#] cadence, a held
+ * prefix column, a refrain's copy column, a template's given id, a full line's PAD and sticky PAD leave mu[b] exactly as it was;
+ * columns narrowed by bans draw and update.  A kernel of its own over the refrain rule.                                         */
+MMTG_API int mmtg_decode_sample_mirostat(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                              int P, int sent, float temperature, float rep_penalty, int top_k, float top_p, float min_p,
+                              float typical_p, float epsilon_cutoff, float eta_cutoff, const float* uniforms, long ldu, int B,
+                              int* pos_next, const int* fixed_end, int ngram, const unsigned char* lo, const unsigned char* hi,
+                              int n_lines, const unsigned* sets, int n_sets, const short* set_of, const int* tmpl,
+                              const short* class_of, const signed char* lead, int distinct, const signed char* src,
+                              float mirostat_tau, float mirostat_eta, float* mu, void* stream);
 MMTG_API int mmtg_decode_beam_candidates_refrain(const float* logits, long ldl, int V, const long long* seq, long ldseq,
                                        const int* pos_ptr, int P, int sent, float temperature, float rep_penalty, int nb,
                                        float* cand_val, int* cand_id, int B, const int* fixed_end, int ngram, const unsigned char* lo,

@@ -180,6 +180,60 @@ def warp_filter(logits, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff
     return out.reshape(x.shape)
 
 
+MIROSTAT_OFF = (0.0, 0.1)              # (mirostat_tau, mirostat_eta): tau = 0 is off, eta is llama.cpp's default
+
+
+def check_mirostat(mirostat_tau=0.0, mirostat_eta=0.1):
+    """The two Mirostat settings of a sampled generation, with llama.cpp's names: (mirostat_tau, mirostat_eta) as floats.  mirostat_tau
+    is 0 (off) or in (0, 32], mirostat_eta in [0, 1]; anything else (a NaN, a non-number) raises a ValueError that names the argument.
+    include/mmtg_hip.h states the rule, ``mirostat_filter`` and ``mirostat_update`` restate it."""
+    out = []
+    for name, v, ok, rng in (("mirostat_tau", mirostat_tau, lambda a: 0.0 <= a <= 32.0, "0 (off) or (0, 32]"),
+                             ("mirostat_eta", mirostat_eta, lambda a: 0.0 <= a <= 1.0, "[0, 1]")):
+        try:
+            if isinstance(v, (bool, np.bool_, str, bytes)):
+                raise TypeError
+            a = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number, %s, got %r" % (name, rng, v)) from None
+        if not ok(a):                            # (NaN fails every comparison)
+            raise ValueError("%s must be %s, got %r" % (name, rng, v))
+        out.append(a)
+    return tuple(out)
+
+
+def mirostat_filter(x, mu, margins=None):
+    """The Mirostat v2 cut of the *_mirostat entries (include/mmtg_hip.h) in float64 numpy: x [V] is a row of processed logits after
+    every earlier stage (``warp_filter``'s result; -inf where dropped), mu the row's state in bits.  With p the softmax over the
+    survivors, an id stays when -log2 p <= mu or when it holds the survivors' largest logit.  Returns the filtered row.  margins (a
+    list, optional) receives ("mirostat_tau", "surprise", |-log2 p - mu|) for every survivor, in index order -- how far each lies
+    from the cut, in bits, for tests that compare an fp32 evaluation."""
+    x = np.asarray(x, dtype=np.float64)
+    keep = x > -np.inf
+    if not keep.any():
+        return x.copy()
+    m = x[keep].max()
+    surprise = -((x[keep] - m) - np.log(np.exp(x[keep] - m).sum())) / math.log(2.0)
+    if margins is not None:
+        margins.extend(("mirostat_tau", "surprise", float(d)) for d in np.abs(surprise - float(mu)))
+    out = np.full_like(x, -np.inf)
+    stay = np.flatnonzero(keep)[(surprise <= float(mu)) | (x[keep] == m)]
+    out[stay] = x[stay]
+    return out
+
+
+def mirostat_update(filtered, pick, mu, tau, eta):
+    """What drawing id `pick` from the row ``mirostat_filter`` returned does to the state: (s, mu') with s = -log2 q(pick) under the
+    softmax q over the kept ids and mu' = mu - eta * (s - tau), in float64."""
+    f = np.asarray(filtered, dtype=np.float64)
+    keep = f > -np.inf
+    if not keep[pick]:
+        raise ValueError("mirostat_update: id %d is not in the kept set" % pick)
+    m = f[keep].max()
+    s = (math.log(np.exp(f[keep] - m).sum()) - (f[pick] - m)) / math.log(2.0)
+    return float(s), float(mu) - float(eta) * (float(s) - float(tau))
+
+
 def chosen_mask(ids, sent=22, prefix_lens=None):
     """Which columns of generated lyric ids count towards a row's score: bool [B, 1 + length], host only.  Column j >= 1 of row b
     counts iff it is not a cadence column (j % sent not in {0, sent - 1}: the forced [#START#] / [#EOS#]), it lies past the row's

@@ -298,6 +298,9 @@ __global__ __launch_bounds__(256) void logits_sample_kernel(const float* __restr
 // entropy, the survivors' maximum) that give one scalar cut; the typical cut is a 4-pass radix select by accumulated mass over the
 // integer image of key = |-log p - H|, ascending, so ids tied at the cut key stay.  The cuts combine into `kept`, which the
 // stages after them, `filtered` and the CDF pass evaluate.
+// MS adds Mirostat v2 as the last stage (the *_mirostat entries): one more survivor mass gives the cut e >= 2^-mu * m, which joins
+// `kept` beside the epsilon and eta cuts and keeps the survivors' maximum as they do; the pick's surprise comes from the scan's total.
+template <bool MS = false>
 struct WarpCuts {
     unsigned keyt;      // top-k / top-p: integer image of the smallest kept logit
     float mx;           // the row's largest processed logit
@@ -307,20 +310,23 @@ struct WarpCuts {
     unsigned tkey;      // typical: integer image of the largest kept key
     float msurv;        // the largest logit among the typical stage's survivors (the epsilon and eta stages always keep it)
     float eps_e, eta_e; // epsilon / eta: e >= cut (p >= cutoff, times the stage's mass)
+    float mu_e;         // Mirostat (MS only): e >= 2^-mu times the stage's mass
     __device__ __forceinline__ float tkeyf(float x) const { return fabsf((lt - (x - mx)) - H); }
     __device__ __forceinline__ bool kept(float x) const {
         if (!(fkey(x) >= keyt && x > -INFINITY)) return false;
         const float e = expf(x - mx);
         if (e < emin) return false;
         if (typ && fkey(tkeyf(x)) > tkey) return false;
-        return x >= msurv || (e >= eps_e && e >= eta_e);
+        if constexpr (MS) return x >= msurv || (e >= eps_e && e >= eta_e && e >= mu_e);
+        else return x >= msurv || (e >= eps_e && e >= eta_e);
     }
 };
 
-template <bool NG = false, bool LN = false>
+template <bool NG = false, bool LN = false, bool MS = false>
 __device__ __forceinline__ int sample_row_warp(const float* row, int V, const unsigned* cnt, float* px, float temperature,
                                                float rep_penalty, int top_k, float top_p, float min_p, float typical_p,
-                                               float epsilon_cutoff, float eta_cutoff, float u, int tid, float* filtered) {
+                                               float epsilon_cutoff, float eta_cutoff, float u, int tid, float* filtered,
+                                               [[maybe_unused]] float mu = 0.f, [[maybe_unused]] float* surprise = nullptr) {
     __shared__ unsigned hcnt[256];
     __shared__ float hmass[256];
     __shared__ float sred[4];
@@ -423,7 +429,7 @@ __device__ __forceinline__ int sample_row_warp(const float* row, int V, const un
         keyp = s_pick ? s_prefix : 0u;
         __syncthreads();
     }
-    WarpCuts w = {keyk > keyp ? keyk : keyp, mx, 0.f, false, 0.f, 0.f, 0u, mx, 0.f, 0.f};
+    WarpCuts<MS> w = {keyk > keyp ? keyk : keyp, mx, 0.f, false, 0.f, 0.f, 0u, mx, 0.f, 0.f, 0.f};
     // ---- min-p: p < min_p * pmax, and pmax = 1 / tot, so e < min_p (the maximum has e = 1 >= min_p)
     w.emin = min_p;
     // ---- locally typical: the ids nearest the entropy, by ascending key, until their mass reaches typical_p
@@ -467,7 +473,7 @@ __device__ __forceinline__ int sample_row_warp(const float* row, int V, const un
         }
         if (s_pick) { w.lt = lt; w.H = H; w.tkey = s_prefix; w.typ = true; }
         __syncthreads();
-        if (w.typ && (epsilon_cutoff > 0.f || eta_cutoff > 0.f)) {     // the head may be gone: the later stages keep the survivors' maximum
+        if (w.typ && (MS || epsilon_cutoff > 0.f || eta_cutoff > 0.f)) {     // the head may be gone: the later stages keep the survivors' maximum
             float ms = -INFINITY;
             for (int v = tid; v < V; v += 256)
                 if (w.kept(px[v])) ms = fmaxf(ms, px[v]);
@@ -491,6 +497,14 @@ __device__ __forceinline__ int sample_row_warp(const float* row, int V, const un
         s = block_sum(s);
         const float H = logf(m) - s / m;
         w.eta_e = fminf(eta_cutoff, sqrtf(eta_cutoff) * expf(-H)) * m;
+    }
+    // ---- Mirostat v2: -log2 p > mu over the survivors, that is e < 2^-mu * m (mu is the row's, read before any barrier above)
+    if constexpr (MS) {
+        float m = 0.f;
+        for (int v = tid; v < V; v += 256)
+            if (w.kept(px[v])) m += expf(px[v] - mx);
+        m = block_sum(m);
+        w.mu_e = exp2f(-mu) * m;
     }
     if (filtered)
         for (int v = tid; v < V; v += 256) filtered[v] = w.kept(px[v]) ? px[v] : -INFINITY;
@@ -533,6 +547,8 @@ __device__ __forceinline__ int sample_row_warp(const float* row, int V, const un
         if (last >= 0) atomicMax(&s_pick, last);
         __syncthreads();
     }
+    if constexpr (MS)          // the pick's surprise in bits under the kept set's softmax: Z is the kept set's mass already
+        *surprise = (logf(Z) - (px[s_pick < 0 ? 0 : s_pick] - mx)) * 1.44269504088896341f;
     return s_pick < 0 ? 0 : s_pick;
 }
 
@@ -555,6 +571,35 @@ __global__ __launch_bounds__(256) void logits_sample_warp_kernel(const float* __
     if (tid == 0) next[b] = pick;
 }
 
+// logits_sample_warp_kernel with the Mirostat stage: mu[b] is the row's state, read by every thread before the first barrier and
+// stored by thread 0 after the draw; a sticky-PAD row leaves it alone.
+__global__ __launch_bounds__(256) void logits_sample_mirostat_kernel(const float* __restrict__ logits, long ldl, int V,
+        const long long* __restrict__ generated, long ldg, const int* __restrict__ gen_len,
+        float temperature, float rep_penalty, int top_k, float top_p, float min_p, float typical_p, float epsilon_cutoff,
+        float eta_cutoff, float tau, float eta, const float* __restrict__ uniforms, long long* __restrict__ next,
+        float* __restrict__ filtered, float* mu, float* __restrict__ surprise) {
+    extern __shared__ unsigned cnt[];
+    float* px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = min(gen_len[b], MAXGEN);
+    const long long* gen = generated + (long)b * ldg;
+    if (n > 0 && gen[n - 1] == 0) {  // sticky PAD: no draw, no update
+        if (tid == 0) { next[b] = 0; if (surprise) surprise[b] = 0.f; }
+        return;
+    }
+    const float mub = mu[b];
+    count_ids(cnt, V, gen, n, tid);
+    float s;
+    const int pick = sample_row_warp<false, false, true>(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k, top_p,
+                                                         min_p, typical_p, epsilon_cutoff, eta_cutoff, uniforms[b], tid,
+                                                         filtered ? filtered + (long)b * ldl : nullptr, mub, &s);
+    if (tid == 0) {
+        next[b] = pick;
+        mu[b] = mub - eta * (s - tau);
+        if (surprise) surprise[b] = s;
+    }
+}
+
 // (what both *_warp entries ask of the four cuts; a NaN fails every test)
 static int warp_args_check(const char* what, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff) {
     MMTG_REQUIRE(min_p >= 0.f && min_p <= 1.f, "%s: min_p must be in [0, 1]", what);
@@ -564,7 +609,41 @@ static int warp_args_check(const char* what, float min_p, float typical_p, float
     return MMTG_OK;
 }
 
+// (what both *_mirostat entries ask; 0 is "off" on the Python surface and has no meaning here)
+static int mirostat_args_check(const char* what, float tau, float eta, const float* mu) {
+    MMTG_REQUIRE(tau > 0.f && tau <= 32.f, "%s: mirostat_tau must be in (0, 32]", what);
+    MMTG_REQUIRE(eta >= 0.f && eta <= 1.f, "%s: mirostat_eta must be in [0, 1]", what);
+    MMTG_REQUIRE(mu, "%s: mirostat needs the mu buffer", what);
+    return MMTG_OK;
+}
+
 }  // namespace
+
+extern "C" int mmtg_logits_process_sample_mirostat(const float* logits, long ldl, int V, const long long* generated, long ldg,
+                                                   const int* gen_len, float temperature, float rep_penalty, int top_k, float top_p,
+                                                   float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff,
+                                                   const float* uniforms, long long* next, float* filtered, int B,
+                                                   float mirostat_tau, float mirostat_eta, float* mu, float* surprise, void* stream) {
+    if (int e = mirostat_args_check("logits_process_sample_mirostat", mirostat_tau, mirostat_eta, mu)) return e;
+    MMTG_REQUIRE(logits && generated && gen_len && uniforms && next && B > 0 && V > 0 && ldl >= V, "logits_process_sample_mirostat: bad args");
+    MMTG_REQUIRE(temperature > 0.f && rep_penalty > 0.f && top_k >= 0 && top_p >= 0.f, "logits_process_sample_mirostat: bad sampling parameters");
+    if (int e = warp_args_check("logits_process_sample_mirostat", min_p, typical_p, epsilon_cutoff, eta_cutoff)) return e;
+    MMTG_REQUIRE(V <= 24000, "logits_process_sample_mirostat: vocabulary of %d exceeds the LDS row image (24000)", V);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, 44.0 * B * V, 4.0 * B * V);
+    const size_t shm = (size_t)((V + 1) / 2) * 4 + (size_t)V * 4;
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute((const void*)logits_sample_mirostat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
+            MMTG_FAIL(MMTG_ERR_HIP, "logits_process_sample_mirostat: cannot raise dynamic LDS");
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(logits_sample_mirostat_kernel, dim3(B), dim3(256), shm, s, logits, ldl, V, generated, ldg, gen_len, temperature,
+                       rep_penalty, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, mirostat_tau, mirostat_eta, uniforms, next,
+                       filtered, mu, surprise);
+    MMTG_LAUNCH_CHECK("logits_process_sample_mirostat");
+    return MMTG_OK;
+}
 
 extern "C" int mmtg_logits_process_sample_warp(const float* logits, long ldl, int V, const long long* generated, long ldg,
                                                const int* gen_len, float temperature, float rep_penalty, int top_k, float top_p,
@@ -1764,6 +1843,45 @@ __global__ __launch_bounds__(256) void decode_select_warp_kernel(const float* __
     if (tid == 0) gen[j] = pick;
 }
 
+// decode_select_warp_kernel with the Mirostat stage (mmtg_decode_sample_mirostat).  mu[b] changes only on a column the row
+// draws: every early return leaves it alone.
+__global__ __launch_bounds__(256) void decode_select_mirostat_kernel(const float* __restrict__ logits, long ldl, int V,
+        long long* __restrict__ seq, long ldseq, const int* __restrict__ pos_ptr, int P, int sent,
+        float temperature, float rep_penalty, int top_k, float top_p, float min_p, float typical_p, float epsilon_cutoff,
+        float eta_cutoff, float tau, float eta, float* mu, const float* __restrict__ uniforms, long ldu, int* __restrict__ pos_next,
+        RefrainRule rule) {
+    extern __shared__ unsigned cnt[];
+    const int b = blockIdx.x, tid = threadIdx.x, pos = *pos_ptr;
+    if (pos_next && b == 0 && tid == 0) *pos_next = pos + 1;
+    if (rule.held(b, pos)) return;
+    const int j = pos + 1 - P;                 // lyric index of the token to append
+    if (j < 1) return;                         // still inside the prompt / the initial [#START#]
+    long long* gen = seq + (long)b * ldseq + P;
+    if (j > 1 && (j + 1) % sent == 0) { if (tid == 0) gen[j] = 2; return; }     // [#EOS#]
+    if (j > 1 && (j + 1) % sent == 1) { if (tid == 0) gen[j] = 1; return; }     // [#START#]
+    const int q = rule.copy_from(b, j, sent);
+    if (q >= 0) { const long long v = gen[q]; if (tid == 0) gen[j] = v; return; }
+    const int n = min(j, MAXGEN);
+    if (gen[n - 1] == 0) { if (tid == 0) gen[j] = 0; return; }                   // sticky PAD
+    bool rhymes = false;
+    const LineCol lc = rule.col(b, j, sent, gen, &rhymes);
+    if (lc.force_pad) { if (tid == 0) gen[j] = 0; return; }
+    const TmplCol tc = rule.sym(b, j, sent);
+    if (tc.given >= 0) { if (tid == 0) gen[j] = tc.given; return; }
+    const float mub = mu[b];
+    count_ids(cnt, V, gen, n, tid);
+    const NgramBan ng = rule.bans();
+    if (ng.n > 0) ban_ngrams(cnt, reinterpret_cast<int*>(cnt + (V + 1) / 2 + V), V, gen, min(n, ng.hist_cap), ng.n, tid);
+    ban_line_tmpl(cnt, V, lc, tc.cls, tid);
+    rule.ban_distinct(cnt, b, j, sent, gen, lc, rhymes, tid);
+    float* px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
+    float s;
+    const int pick = sample_row_warp<true, true, true>(logits + (long)b * ldl, V, cnt, px, temperature, rep_penalty, top_k, top_p, min_p,
+                                                       typical_p, epsilon_cutoff, eta_cutoff, uniforms[(long)pos * ldu + b], tid, nullptr,
+                                                       mub, &s);
+    if (tid == 0) { gen[j] = pick; mu[b] = mub - eta * (s - tau); }
+}
+
 __global__ void decode_advance_kernel(int* pos_ptr) { *pos_ptr += 1; }
 
 // ------------------------------------------------------------------ beam search (the selection step of BeamDecoder)
@@ -2945,6 +3063,40 @@ extern "C" int mmtg_decode_sample_warp(const float* logits, long ldl, int V, lon
                        sent, temperature, rep_penalty, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, uniforms, ldu, pos_next,
                        rf);
     MMTG_LAUNCH_CHECK("decode_sample_warp");
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_decode_sample_mirostat(const float* logits, long ldl, int V, long long* seq, long ldseq, const int* pos_ptr,
+                                           int P, int sent, float temperature, float rep_penalty, int top_k, float top_p, float min_p,
+                                           float typical_p, float epsilon_cutoff, float eta_cutoff, const float* uniforms, long ldu,
+                                           int B, int* pos_next, const int* fixed_end, int ngram, const unsigned char* lo,
+                                           const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets, const short* set_of,
+                                           const int* tmpl, const short* class_of, const signed char* lead, int distinct,
+                                           const signed char* src, float mirostat_tau, float mirostat_eta, float* mu, void* stream) {
+    RefrainRule rf;
+    if (int e = mirostat_args_check("decode_sample_mirostat", mirostat_tau, mirostat_eta, mu)) return e;
+    MMTG_REQUIRE(logits, "decode_sample_mirostat: a draw needs logits");
+    if (int e = refrain_check("decode_sample_mirostat", V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, tmpl,
+                              class_of, lead, distinct, src, &rf))
+        return e;
+    if (int e = sample_args_check("decode_sample_mirostat", uniforms, ldu, B, top_k, top_p)) return e;
+    if (int e = warp_args_check("decode_sample_mirostat", min_p, typical_p, epsilon_cutoff, eta_cutoff)) return e;
+    MMTG_REQUIRE(seq && pos_ptr && B > 0, "decode_sample_mirostat: bad args");
+    MMTG_REQUIRE(pos_next != pos_ptr, "decode_sample_mirostat: pos_next must not alias pos_ptr (blocks read the position while block 0 writes the next)");
+    MMTG_REQUIRE(V > 0 && ldl >= V && temperature > 0.f && rep_penalty > 0.f, "decode_sample_mirostat: bad logits args");
+    MMTG_REQUIRE(V <= 24000, "decode_sample_mirostat: vocabulary of %d exceeds the LDS tables", V);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, 44.0 * B * V, 4.0 * B * V);
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute((const void*)decode_select_mirostat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096) != hipSuccess)
+            MMTG_FAIL(MMTG_ERR_HIP, "decode_sample_mirostat: cannot raise dynamic LDS");
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(decode_select_mirostat_kernel, dim3(B), dim3(256), select_lds(V, true, rf), s, logits, ldl, V, seq, ldseq, pos_ptr,
+                       P, sent, temperature, rep_penalty, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, mirostat_tau,
+                       mirostat_eta, mu, uniforms, ldu, pos_next, rf);
+    MMTG_LAUNCH_CHECK("decode_sample_mirostat");
     return MMTG_OK;
 }
 

@@ -19,8 +19,8 @@ import numpy as np
 import torch
 
 from . import hip
-from .constraints import (BANNED, WARP_OFF, KeywordTables, LineTables, _check_constraints, check_contrastive, check_groups, check_keywords, check_lines,  # noqa: F401
-                          check_ngram, check_prefix, check_refrain, check_warp, chosen_mask, keywords_met, refrain_without_keywords,
+from .constraints import (BANNED, MIROSTAT_OFF, WARP_OFF, KeywordTables, LineTables, _check_constraints, check_contrastive, check_groups, check_keywords, check_lines,  # noqa: F401
+                          check_mirostat, check_ngram, check_prefix, check_refrain, check_warp, chosen_mask, keywords_met, refrain_without_keywords,
                           sequence_scores)   # (the host-side checks keep their names here)
 
 _PLACEMENT = {}
@@ -98,6 +98,11 @@ def _warp_on(dec):
     """Whether decoder `dec`'s generation has any of min_p / typical_p / epsilon_cutoff / eta_cutoff on (a decoder without the field:
     none)."""
     return getattr(dec, "warp", WARP_OFF) != WARP_OFF
+
+
+def _mirostat_on(dec):
+    """Whether decoder `dec`'s generation runs Mirostat (mirostat_tau > 0; a decoder without the field: no)."""
+    return getattr(dec, "mirostat", MIROSTAT_OFF)[0] > 0.0
 
 
 def _fill(buf, src, fill, axis):
@@ -302,6 +307,11 @@ class GreedyDecoder:
         self.warp = WARP_OFF
         self.warp_src = None
         self._warp_buf = None
+        # Mirostat (mirostat_tau=, mirostat_eta=): (tau, eta); tau > 0 ends every step that calls the head in mmtg_decode_sample_mirostat.
+        # mirostat_mu: the rows' state, fp32 [B] in bits, this decoder's rows (allocated once: captured graphs hold its address; None
+        # until a generation asks for it); the selection kernel updates it on the columns a row draws
+        self.mirostat = MIROSTAT_OFF
+        self.mirostat_mu = None
         # token log-probabilities (return_logprobs=): fp32 [B, 1 + max_len], this decoder's rows; on, every step that calls the head
         # ends in one more launch, mmtg_decode_logprob, which writes the step's column (allocated once: captured graphs hold its address)
         self.return_logprobs = False
@@ -382,6 +392,12 @@ class GreedyDecoder:
             V = min(sh.V, 13317)
         # stochastic: the draw of each position reads its row of the pre-filled uniforms
         sampling = (top_k, top_p, self.uniforms) if with_head and not (top_k == 1 and top_p == 0.0) else None
+        if with_head and _mirostat_on(self):    # Mirostat behind the four cuts (on or off): the warp entry's launch plus the rows' state
+            hip.decode_sample_mirostat(logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, top_k, top_p, self.warp,
+                                       self.mirostat, self.mirostat_mu, self.uniforms, self.B,
+                                       self.warp_src if self.refrain is None else self.refrain, tables=self.lines, rhyme=rhyme, tmpl=tmpl,
+                                       ngram=self.ngram, pos_next=self.pos_next, fixed_end=self.fixed_end if self.use_fixed else None)
+            return
         if with_head and _warp_on(self):    # min_p / typical_p / epsilon_cutoff / eta_cutoff: one entry over the refrain form, whatever the rules
             hip.decode_sample_warp(logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, top_k, top_p, self.warp,
                                    self.uniforms, self.B, self.warp_src if self.refrain is None else self.refrain, tables=self.lines,
@@ -695,8 +711,10 @@ class GreedyDecoder:
             key += _rhyme_key(self)
         if form == "_refrain":
             key += _refrain_key(self)
-        if with_head and _warp_on(self):    # (the four cuts by value; which of the refrain form's tables the launch holds; a real src or none)
+        if with_head and (_warp_on(self) or _mirostat_on(self)):    # (the four cuts by value; which of the refrain form's tables the launch holds; a real src or none)
             key += (("warp",) + self.warp,) + _refrain_key(self) + (("src",) if getattr(self, "refrain", None) is not None else ())
+        if with_head and _mirostat_on(self):                        # (tau and eta by value; the state's address never changes)
+            key += (("mirostat",) + self.mirostat,)
         if logprob:
             key += ("logprob",)
         if merge.startswith("_groups"):     # (the grouped merge holds both by value)
@@ -708,8 +726,9 @@ class GreedyDecoder:
         return key
 
     def _step_state(self):
-        """What a token step changes besides the caches' slot `pos` (rewound around the warm-up step of a graph capture)."""
-        return [self.pos_all, self.seq, self.keep]
+        """What a token step changes besides the caches' slot `pos` (rewound around the warm-up step of a graph capture).  With
+        Mirostat that includes the rows' mu: without it the first step of every new graph key would update mu twice."""
+        return [self.pos_all, self.seq, self.keep] + ([self.mirostat_mu] if _mirostat_on(self) else [])
 
     # ------------------------------------------------------------------ public
     def describe(self):
@@ -735,7 +754,7 @@ class GreedyDecoder:
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
               no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
               rhyme_distinct=False, return_logprobs=False, keywords=None, refrain_scheme=None, min_p=0.0, typical_p=1.0,
-              epsilon_cutoff=0.0, eta_cutoff=0.0):
+              epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
         """Everything of a generation that happens once: the settings, the uniforms of a stochastic run, fresh weight copies /
         LayerNorm folds, the experience encoder, the prompt (prefilled in one batched pass: ``first_pos`` = P afterwards) and the
         reset position.  Returns the end position n; ``step_at(pos)`` for pos = first_pos .. n - 1 then runs the token steps (``generate`` does both; tools/decode_lanes_threads.py drives
@@ -791,10 +810,20 @@ class GreedyDecoder:
         constraints there are; the values join the graph key.  A step without the head runs what it always ran.  All four at their
         defaults run exactly the launches, graphs and graph keys of a generation without the arguments.
 
+        mirostat_tau / mirostat_eta (check_mirostat states the ranges, include/mmtg_hip.h the rule, constraints.mirostat_filter and
+        mirostat_update restate it): Mirostat v2 as the last stage of the draw, behind top_k / top_p and the four above, with llama.cpp's
+        names.  mirostat_tau > 0 turns it on: the generation samples (uniforms are drawn, also at top_k=1, top_p=0), every step that
+        calls the head ends in mmtg_decode_sample_mirostat, whatever the other values and constraints, and ("mirostat", tau, eta) joins
+        the graph key.  The rows' state ``mirostat_mu`` (fp32 [B], bits) is filled with 2 * tau here and readable after the generation;
+        only a column that a row draws changes its entry.  mirostat_tau=0 runs exactly the launches, graphs and graph keys of a
+        generation without the arguments, and allocates nothing.
+
         keywords: refused here (ValueError).  A lyric that contains given words needs a search, and greedy decoding and sampling
         follow one path: BeamDecoder takes keywords=."""
         _keywords_need_beams(keywords)
         warp = check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+        mirostat = check_mirostat(mirostat_tau, mirostat_eta)
+        miro_on = mirostat[0] > 0.0
         eng, sh = self.eng, self.eng.sh
         B = batch["img_embs"].shape[0]
         if B != self.B:
@@ -805,7 +834,7 @@ class GreedyDecoder:
                                   templates, rhyme_scheme, rhyme_classes, rhyme_distinct, refrain_scheme)
         pre = cons.prefix
         self.params = (float(temperature), float(repitition_penalty), int(top_k), float(top_p))
-        if not (int(top_k) == 1 and float(top_p) == 0.0) or warp != WARP_OFF:
+        if not (int(top_k) == 1 and float(top_p) == 0.0) or warp != WARP_OFF or miro_on:
             if self.uniforms is None:
                 self.uniforms = torch.empty(sh.P + self.max_len + 1, self.B, device=eng.dev, dtype=torch.float32)
             self.uniforms.uniform_(0.0, 1.0, generator=generator)
@@ -836,7 +865,11 @@ class GreedyDecoder:
         lines, tmpl, rhyme = self._upload_lines(None if bare else cons.lines), self._upload_templates(cons.lines), self._upload_rhyme(cons.lines)
         refrain = self._upload_refrain(cons.lines)
         self.copy_cols = self._copy_columns(cons.lines, pre, length, return_logprobs)
-        if warp != WARP_OFF and self._warp_buf is None:         # the "no copy line" src of a generation without a refrain scheme
+        if miro_on:
+            if self.mirostat_mu is None:
+                self.mirostat_mu = torch.empty(B, dtype=torch.float32, device=eng.dev)
+            self.mirostat_mu.fill_(2.0 * mirostat[0])
+        if (warp != WARP_OFF or miro_on) and self._warp_buf is None:         # the "no copy line" src of a generation without a refrain scheme
             self._warp_buf = torch.full((B, (self.max_len - 1) // (sh.msl + 2) + 1), -1, dtype=torch.int8, device=eng.dev)
         self.skipped_steps = 0
         for i, d in enumerate([self] + self.children):
@@ -847,6 +880,9 @@ class GreedyDecoder:
             d.rhyme = None if rhyme is None else (rhyme[0], rhyme[1][a:z], rhyme[2])
             d.refrain, d.copy_step = None if refrain is None else refrain[a:z], False
             d.warp, d.warp_src = warp, None if self._warp_buf is None else self._warp_buf[a:z]
+            d.mirostat = mirostat if miro_on else MIROSTAT_OFF
+            if miro_on and d is not self:
+                d.mirostat_mu = self.mirostat_mu[a:z]
             d.return_logprobs = bool(return_logprobs)
             if return_logprobs and d is not self:
                 d.tok_lp = self.tok_lp[a:z]
@@ -929,7 +965,8 @@ class GreedyDecoder:
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None,
                  use_graph=None, teacher=None, tap=None, prefix=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None,
                  templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_logprobs=False,
-                 refrain_scheme=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, **begin_kw):
+                 refrain_scheme=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1,
+                 **begin_kw):
         """batch: dict with topic_ids/tpw_* [B,P], topic_emb, img_embs, r_embs (no targets needed).
         Runs `length` iterations of the reference loop and returns the lyric ids
         [B, 1 + length] (column 0 is the initial [#START#]).  top_k = 1, top_p = 0 is the greedy setting;
@@ -959,6 +996,9 @@ class GreedyDecoder:
         min_p / typical_p / epsilon_cutoff / eta_cutoff: min-p, locally typical, epsilon and eta sampling (``begin``), transformers'
         arguments of those names: typical_p=0.9 keeps the ids whose surprise is nearest the entropy, min_p=0.05 drops what is under
         a twentieth of the best id's probability.  They act behind top_k / top_p, so top_k=0, top_p=0 leaves the choice to them.
+        mirostat_tau / mirostat_eta: Mirostat v2 (``begin``), llama.cpp's arguments of those names: mirostat_tau=2.0 holds the observed
+        surprise of the text near 2 bits per drawn token by adapting the cut after every draw, at learning rate mirostat_eta.  It acts
+        last, so top_k=0, top_p=0 leaves the choice to it.  Afterwards ``mirostat_mu`` holds every row's state.
         begin_kw: what a subclass's ``begin`` takes beyond these (BeamDecoder: the beam groups); ``begin`` here takes none."""
         n_steps = self.begin(batch, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix,
                              no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths, line_end_ids=line_end_ids,
@@ -967,6 +1007,8 @@ class GreedyDecoder:
                              **({} if refrain_scheme is None else {"refrain_scheme": refrain_scheme}),
                              **({} if (min_p, typical_p, epsilon_cutoff, eta_cutoff) == WARP_OFF else
                                 {"min_p": min_p, "typical_p": typical_p, "epsilon_cutoff": epsilon_cutoff, "eta_cutoff": eta_cutoff}),
+                             **({} if mirostat_tau == 0 and mirostat_eta == MIROSTAT_OFF[1] else
+                                {"mirostat_tau": mirostat_tau, "mirostat_eta": mirostat_eta}),
                              **begin_kw)
         eng, sh = self.eng, self.eng.sh
         saved_mode = self.use_graph
@@ -1124,6 +1166,13 @@ class BeamDecoder(GreedyDecoder):
             raise ValueError("a search draws nothing: min_p / typical_p / epsilon_cutoff / eta_cutoff shape the distribution a sampled "
                              "generation draws from (GreedyDecoder / generate_samples), and no sampling runs inside a beam or contrastive search")
 
+    @staticmethod
+    def _no_mirostat(mirostat_tau=0.0, mirostat_eta=0.1):
+        """As ``_no_warp``: Mirostat adapts the cut of a draw, and a search draws nothing."""
+        if check_mirostat(mirostat_tau, mirostat_eta)[0] > 0.0:
+            raise ValueError("a search draws nothing: mirostat_tau / mirostat_eta steer the surprise of what a sampled generation "
+                             "draws (GreedyDecoder / generate_samples), and no sampling runs inside a beam or contrastive search")
+
     def describe(self):
         return "%d beams per prompt, " % self.nb + super().describe()
 
@@ -1131,7 +1180,7 @@ class BeamDecoder(GreedyDecoder):
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
               no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
               rhyme_distinct=False, return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, keywords=None, refrain_scheme=None,
-              min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+              min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
         """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill, the prefix, the line
         constraints, the templates and the rhyme scheme: one per prompt; every beam finds its leader's rhyme in its own history), the
         ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at the free positions
@@ -1157,9 +1206,11 @@ class BeamDecoder(GreedyDecoder):
         known remainder here.  Beam groups need nothing.  keywords= together with a scheme is a ValueError: the one combination
         left out.
 
-        min_p / typical_p / epsilon_cutoff / eta_cutoff: refused at anything but their defaults (``_no_warp``)."""
+        min_p / typical_p / epsilon_cutoff / eta_cutoff: refused at anything but their defaults (``_no_warp``); mirostat_tau > 0
+        likewise (``_no_mirostat``)."""
         self._no_logprobs(return_logprobs)
         self._no_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+        self._no_mirostat(mirostat_tau, mirostat_eta)
         G, lam = check_groups(self.nb, num_beam_groups, diversity_penalty)
         self._keywords_alone(keywords, G)
         n = batch["img_embs"].shape[0]
@@ -1186,7 +1237,7 @@ class BeamDecoder(GreedyDecoder):
     def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None, no_repeat_ngram_size=0,
                  line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False,
                  return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, return_groups=False, keywords=None, return_met=False,
-                 refrain_scheme=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+                 refrain_scheme=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_beams, 1 + length] in
         GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row.
         prefix: one per prompt (check_prefix), shared by its beams.  no_repeat_ngram_size: as GreedyDecoder.generate, per beam
@@ -1203,9 +1254,11 @@ class BeamDecoder(GreedyDecoder):
         (number of keywords met descending, score descending, stable); return_met=True adds an int64 [n, num_beams] tensor, that
         number for each hypothesis returned (``constraints.keywords_met`` of its ids).  Best effort: a keyword may stay unmet, and
         is reported so.  Not together with num_beam_groups > 1 or return_logprobs (ValueError).
-        min_p / typical_p / epsilon_cutoff / eta_cutoff: refused at anything but their defaults (ValueError): a search draws nothing."""
+        min_p / typical_p / epsilon_cutoff / eta_cutoff, mirostat_tau > 0: refused at anything but their defaults (ValueError): a
+        search draws nothing."""
         self._no_logprobs(return_logprobs)
         self._no_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+        self._no_mirostat(mirostat_tau, mirostat_eta)
         G, lam = check_groups(self.nb, num_beam_groups, diversity_penalty)
         self._keywords_alone(keywords, G)
         if return_met and keywords is None:
@@ -1261,10 +1314,11 @@ class ContrastiveDecoder(BeamDecoder):
 
     @staticmethod
     def _refuse(keywords=None, num_beam_groups=1, return_logprobs=False, diversity_penalty=0.0, top_k=1, top_p=0.0, generator=None,
-                min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
-        """What contrastive search does not take, refused before any device work (the last four are arguments of the base
+                min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
+        """What contrastive search does not take, refused before any device work (the last six are arguments of the base
         classes' ``begin`` that would otherwise be ignored in silence)."""
         BeamDecoder._no_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+        BeamDecoder._no_mirostat(mirostat_tau, mirostat_eta)
         if diversity_penalty:
             raise ValueError("contrastive search has no diversity_penalty: there are no beam groups to keep apart")
         if not (int(top_k) == 1 and float(top_p) == 0.0) or generator is not None:
@@ -1313,14 +1367,14 @@ class ContrastiveDecoder(BeamDecoder):
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
               no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
               rhyme_distinct=False, return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, keywords=None, refrain_scheme=None,
-              penalty_alpha=0.6, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+              penalty_alpha=0.6, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
         """BeamDecoder.begin with the decoder's top_k rows per prompt, scores [0, -inf, ...] and total 0 per prompt.  `top_k`, `top_p`,
         `generator` and `diversity_penalty` are the base signature's: anything but their defaults is refused.  With a prefix the prefill covers the prompt
         only, so every lyric column gets its hidden state from a token step; the steps at which every row is held skip the head.
         keywords=, num_beam_groups > 1, return_logprobs=True, a diversity penalty and sampling arguments are refused (ValueError)
         before any device work."""
         self._refuse(keywords, num_beam_groups, return_logprobs, diversity_penalty, top_k, top_p, generator, min_p, typical_p,
-                     epsilon_cutoff, eta_cutoff)
+                     epsilon_cutoff, eta_cutoff, mirostat_tau, mirostat_eta)
         _, alpha = check_contrastive(self.nb, penalty_alpha)
         n_steps = super().begin(batch, length, temperature, repitition_penalty, prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size,
                                 line_lengths=line_lengths, line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme,
@@ -1336,14 +1390,14 @@ class ContrastiveDecoder(BeamDecoder):
     def generate(self, batch, length, penalty_alpha=0.6, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None,
                  no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
                  rhyme_distinct=False, refrain_scheme=None, return_logprobs=False, num_beam_groups=1, keywords=None, min_p=0.0,
-                 typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+                 typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, 1 + length] in GreedyDecoder.generate's
         column layout, scores [n] fp32): one lyric per prompt and the sum of the processed log-probabilities of its chosen tokens.
         penalty_alpha in [0, 1]: the weight of the degeneration penalty (0: greedy decoding).  prefix, no_repeat_ngram_size,
         line_lengths / line_end_ids, templates, rhyme_scheme / rhyme_classes / rhyme_distinct, refrain_scheme: as
         BeamDecoder.generate, one per prompt.  keywords=, num_beam_groups > 1 and return_logprobs=True raise ValueError."""
         self._refuse(keywords, num_beam_groups, return_logprobs, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff,
-                     eta_cutoff=eta_cutoff)
+                     eta_cutoff=eta_cutoff, mirostat_tau=mirostat_tau, mirostat_eta=mirostat_eta)
         ids = GreedyDecoder.generate(self, batch, length, temperature=temperature, repitition_penalty=repitition_penalty,
                                      use_graph=use_graph, prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size,
                                      line_lengths=line_lengths, line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme,

@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .constraints import (BANNED, WARP_OFF, Constraints, _check_constraints, check_warp, check_contrastive, check_groups, check_keywords, check_prefix, refrain_without_keywords,
+from .constraints import (BANNED, WARP_OFF, Constraints, _check_constraints, check_mirostat, check_warp, check_contrastive, check_groups, check_keywords, check_prefix, refrain_without_keywords,
                           sequence_scores)
 from .decode import BeamDecoder, ContrastiveDecoder, GreedyDecoder, _keywords_need_beams
 from .data import encode_line_end, encode_prefix, encode_rhyme_classes, encode_template  # noqa: F401  (public: the opening lines / the line-end sets / the line templates / the rhyme classes of generate_samples / generate_beams)
@@ -76,22 +76,27 @@ def _cached_decoder(model, start_input, length):
 
 
 def sample_sequence(model, start_input, length, tokenizer, temperature=1.0, top_k=30, top_p=0.0,
-                    repitition_penalty=1.0, device="cuda", *, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+                    repitition_penalty=1.0, device="cuda", *, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0,
+                    mirostat_tau=0.0, mirostat_eta=0.1):
     """generate.py:97-145.  When the call is the reference's own (see _cached_decoder) the loop runs on the KV-cached decoder:
     one captured token step replayed per position instead of a full forward over the growing prefix per token; the returned
     list is what the reference loop returns (the sequence before the last model call's append).  Greedy ids are the same as
     the re-run loop's bit for bit in the f32 mode (tests/test_decode_gpu.py).
     min_p / typical_p / epsilon_cutoff / eta_cutoff (keyword only, so the reference's positional signature stands): min-p, locally
-    typical, epsilon and eta sampling behind top_k / top_p (constraints.check_warp, include/mmtg_hip.h); any of them on samples."""
+    typical, epsilon and eta sampling behind top_k / top_p (constraints.check_warp, include/mmtg_hip.h); any of them on samples.
+    mirostat_tau / mirostat_eta (keyword only; constraints.check_mirostat, include/mmtg_hip.h): Mirostat v2 behind all of them, the
+    sequence's surprise state carried from draw to draw; mirostat_tau > 0 samples."""
     _check_tokenizer(tokenizer)
     warp = check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
     warp_kw = {} if warp == WARP_OFF else dict(zip(("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"), warp))
+    tau, eta = check_mirostat(mirostat_tau, mirostat_eta)
+    miro_kw = {"mirostat_tau": tau, "mirostat_eta": eta} if tau > 0.0 else {}
     dec = _cached_decoder(model, start_input, length)
     if dec is not None:
         m = getattr(model, "module", model)
         batch = {k: torch.as_tensor(np.asarray(v)).unsqueeze(0) for k, v in start_input.items() if k not in ("targets", "rating")}
         ids = dec.generate(batch, int(length), temperature=temperature, repitition_penalty=repitition_penalty,
-                           top_k=int(top_k), top_p=float(top_p), **warp_kw)
+                           top_k=int(top_k), top_p=float(top_p), **warp_kw, **miro_kw)
         return dec.reference_return(ids[0].tolist(), int(length), sent=m.shapes.msl + 2)
     inputs = {}
     for k, v in start_input.items():
@@ -100,7 +105,8 @@ def sample_sequence(model, start_input, length, tokenizer, temperature=1.0, top_
         else:
             inputs[k] = torch.tensor(np.asarray(v), dtype=torch.float32, device=device).unsqueeze(0)
     generated = inputs["targets"]
-    greedy = top_k == 1 and top_p == 0.0 and not warp_kw
+    greedy = top_k == 1 and top_p == 0.0 and not warp_kw and not miro_kw
+    mu = torch.full((1,), 2.0 * tau, dtype=torch.float32, device=device) if miro_kw else None
     nxt = torch.zeros(1, dtype=torch.long, device=device)
     glen = torch.zeros(1, dtype=torch.int32, device=device)
     with torch.no_grad():
@@ -123,9 +129,14 @@ def sample_sequence(model, start_input, length, tokenizer, temperature=1.0, top_
                 row = outputs[0, -1, :]
                 glen.fill_(generated.shape[1])
                 u = torch.rand(1, device=device).clamp_(max=1.0 - 2.0 ** -24)
-                draw = hip.logits_process_sample_warp if warp_kw else hip.logits_process_sample
-                draw(row, row.shape[0], min(row.shape[0], 13317), generated.contiguous(),
-                     generated.shape[1], glen, temperature, repitition_penalty, top_k, top_p, u, nxt, 1, **warp_kw)
+                if miro_kw:
+                    hip.logits_process_sample_mirostat(row, row.shape[0], min(row.shape[0], 13317), generated.contiguous(),
+                                                       generated.shape[1], glen, temperature, repitition_penalty, top_k, top_p, u, nxt, 1,
+                                                       tau, eta, mu, **warp_kw)
+                else:
+                    draw = hip.logits_process_sample_warp if warp_kw else hip.logits_process_sample
+                    draw(row, row.shape[0], min(row.shape[0], 13317), generated.contiguous(),
+                         generated.shape[1], glen, temperature, repitition_penalty, top_k, top_p, u, nxt, 1, **warp_kw)
                 next_token = nxt.view(1, 1).clone()
             inputs["targets"] = torch.cat((generated, next_token), dim=-1)
     return generated.tolist()[0]
@@ -204,7 +215,7 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
                      repetition_penalty=1.5, max_batch=256, generator=None, decoder=None, prefixes=None, no_repeat_ngram_size=0,
                      line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False,
                      return_scores=False, rank_by=None, keywords=None, refrain_scheme=None, *, min_p=0.0, typical_p=1.0,
-                     epsilon_cutoff=0.0, eta_cutoff=0.0):
+                     epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
     """n_samples texts per prompt (generate.sh's loop, generate.py:205-235) on the batched, graph-replayed decoder:
     every prompt is replicated over n_samples rows, rows are decoded max_batch at a time with the device-side
     top-k / top-p sampler (one uniform per row and position from `generator`), each row is cut back to what
@@ -236,10 +247,16 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     keywords: refused (ValueError): a lyric that contains given words needs a search over beams -- generate_beams(keywords=).
     min_p / typical_p / epsilon_cutoff / eta_cutoff (keyword only; constraints.check_warp, include/mmtg_hip.h): min-p, locally typical,
     epsilon and eta sampling, transformers' arguments of those names, behind top_k / top_p and under every constraint above, e.g.
-    typical_p=0.9, min_p=0.05 with top_k=0, top_p=0.  At their defaults the call is the call without them."""
+    typical_p=0.9, min_p=0.05 with top_k=0, top_p=0.  At their defaults the call is the call without them.
+    mirostat_tau / mirostat_eta (keyword only; constraints.check_mirostat, include/mmtg_hip.h): Mirostat v2, llama.cpp's arguments of
+    those names, behind all of the above: mirostat_tau=2.0 with top_k=0, top_p=0 holds every sample's surprise near 2 bits per drawn
+    character.  Each of the n_samples rows of a prompt has its own state.  mirostat_tau=0 (the default) is the call without them."""
     _keywords_need_beams(keywords)
     warp = check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
     warp_kw = {} if warp == WARP_OFF else dict(zip(("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"), warp))
+    tau, eta = check_mirostat(mirostat_tau, mirostat_eta)
+    if tau > 0.0:
+        warp_kw = dict(warp_kw, mirostat_tau=tau, mirostat_eta=eta)
     if rank_by is not None and rank_by not in ("sum", "mean"):
         raise ValueError('rank_by must be "sum", "mean" or None, got %r' % (rank_by,))
     scoring = bool(return_scores) or rank_by is not None

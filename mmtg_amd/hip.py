@@ -12,7 +12,7 @@ import os
 
 import torch
 
-from .constraints import check_warp
+from .constraints import check_mirostat, check_warp
 
 F32, BF16 = 0, 1
 ABI_VERSION = 12
@@ -102,6 +102,8 @@ _SIGS = {
     "mmtg_decode_attn_split": ([_i, _vp, _i, _vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "mmtg_logits_process_sample": ([_vp, _l, _i, _vp, _l, _vp, _f, _f, _i, _f, _vp, _vp, _vp, _i, _vp], _i),
     "mmtg_logits_process_sample_warp": ([_vp, _l, _i, _vp, _l, _vp, _f, _f, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _i, _vp], _i),
+    "mmtg_logits_process_sample_mirostat": ([_vp, _l, _i, _vp, _l, _vp, _f, _f, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _i, _f, _f, _vp, _vp,
+                                             _vp], _i),
     "mmtg_decode_sample": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _vp, _l, _i, _vp, _vp], _i),
     "mmtg_decode_select": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp], _i),
     "mmtg_decode_advance": ([_vp, _vp], _i),
@@ -140,6 +142,8 @@ _SIGS = {
                                    _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
     "mmtg_decode_sample_warp": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _f, _f, _f, _f, _vp, _l, _i, _vp, _vp, _i, _vp, _vp, _i,
                                 _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
+    "mmtg_decode_sample_mirostat": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _f, _f, _f, _f, _f, _vp, _l, _i, _vp, _vp, _i, _vp, _vp, _i,
+                                    _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _f, _vp, _vp], _i),
     "mmtg_decode_beam_candidates_refrain": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
                                             _vp, _vp, _vp, _vp, _i, _vp, _vp], _i),
     "mmtg_decode_logprob": ([_vp, _l, _i, _vp, _l, _vp, _i, _vp, _l, _i, _i, _vp], _i),
@@ -793,6 +797,21 @@ def logits_process_sample_warp(logits, ldl, V, generated, ldg, gen_len, temperat
                                                  _p(filtered), B, _stream()), "logits_process_sample_warp")
 
 
+def logits_process_sample_mirostat(logits, ldl, V, generated, ldg, gen_len, temperature, rep_penalty, top_k, top_p, uniforms, nxt, B,
+                                   mirostat_tau, mirostat_eta, mu, surprise=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0,
+                                   eta_cutoff=0.0, filtered=None):
+    """logits_process_sample_warp with Mirostat v2 as the last stage (include/mmtg_hip.h; constraints.mirostat_filter and
+    mirostat_update restate it).  mu: f32 [B], read and written; surprise: f32 [B] or None."""
+    warp = check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+    tau, eta = check_mirostat(mirostat_tau, mirostat_eta)
+    if tau == 0.0:
+        raise ValueError("mirostat_tau must be in (0, 32] here: 0 (off) is logits_process_sample_warp")
+    _check(lib().mmtg_logits_process_sample_mirostat(_p(logits), ldl, V, _p(generated), ldg, _p(gen_len), float(temperature),
+                                                     float(rep_penalty), int(top_k), float(top_p), *warp, _p(uniforms), _p(nxt),
+                                                     _p(filtered), B, tau, eta, _p(mu), _p(surprise), _stream()),
+           "logits_process_sample_mirostat")
+
+
 # ------------------------------------------------------------------ KV-cached decode step
 def decode_embed(table, seq, c, x, pos, tpw_type, tpw_mask, type_out, keep, B, P, S, E, two_sents, V, sent, max_sent_num):
     _check(lib().mmtg_decode_embed(dt(table), _p(table), _p(seq), seq.stride(0), _p(c), _p(x), _p(pos), _p(tpw_type),
@@ -979,6 +998,21 @@ def decode_sample_warp(logits, ldl, V, seq, pos, P, sent, temperature, rep_penal
                                          0 if uniforms is None else uniforms.stride(0), B, _p(pos_next),
                                          *_rule_tail("_refrain", B, V, fixed_end, ngram, tables, tmpl, sent, rhyme, src), _stream()),
            "decode_sample_warp")
+
+
+def decode_sample_mirostat(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, top_k, top_p, warp, mirostat, mu, uniforms, B, src,
+                           tables=None, rhyme=None, tmpl=None, ngram=0, pos_next=None, fixed_end=None):
+    """mmtg_decode_sample_mirostat: decode_sample_warp's draw with mirostat = (tau, eta) and the rows' state mu (f32 [B], read and
+    written) behind the four stages of warp (include/mmtg_hip.h)."""
+    tau, eta = check_mirostat(*mirostat)
+    if tau == 0.0:
+        raise ValueError("mirostat_tau must be in (0, 32] here: 0 (off) is decode_sample_warp")
+    _check(lib().mmtg_decode_sample_mirostat(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                             float(rep_penalty), int(top_k), float(top_p), *check_warp(*warp), _p(uniforms),
+                                             0 if uniforms is None else uniforms.stride(0), B, _p(pos_next),
+                                             *_rule_tail("_refrain", B, V, fixed_end, ngram, tables, tmpl, sent, rhyme, src), tau, eta,
+                                             _p(mu), _stream()),
+           "decode_sample_mirostat")
 
 
 def _beam_candidates(form, logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, B, fixed_end=None, ngram=0,
