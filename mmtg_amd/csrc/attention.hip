@@ -555,6 +555,15 @@ __device__ __forceinline__ void dma_wait_chunk(int c) {
 // request (vmcnt(0)) and serialise the streamed chunks; LDS stores of this wave are drained explicitly
 __device__ __forceinline__ void raw_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// LSE of a query row in log2 units, as the backward kernels subtract it from the scaled score.  A row with no visible key carries
+// lse = -inf (the forward's contract: out = 0): +inf here makes every exponent of the row -inf and every p exactly 0, so the row adds
+// nothing to dK / dV and its own dQ is 0 -- scaled as it is, -inf would give exp2(+inf), or inf - inf against a padded key's bias.
+// The comparison with -INFINITY must survive compilation: never build this file with -ffast-math / -ffinite-math-only
+__device__ __forceinline__ float lse_log2(float l) { return l == -INFINITY ? INFINITY : l * LOG2E; }
+// x under a bit mask: all ones keeps x, the sign bit alone leaves the zero that x * 0.f gives for a finite x -- and a zero where x
+// is inf or NaN, which the product with 0 turns into NaN
+__device__ __forceinline__ float and_bits(float x, uint32_t m) { return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, x) & m); }
+
 // keep-bit matrix of one head: sMask[row * 8 + w] bit j <-> (query row, key 32 w + j); bit = 1 keeps the element.
 // Only words at or below the diagonal of rows < Tn are ever read (a word is one work item: compacted index i ->
 // row-major enumeration of the pairs (row, w <= row / 32), 4 x 32 rows + 8 ... per 32-row band).
@@ -915,14 +924,17 @@ __device__ __forceinline__ void bwd_small_keys_store(const BwdKeys& st, int t, i
     const long ld = 3L * D;
     const bool kin = key < Tn;
     // a padded key never receives attention: its probabilities are zero for every query, hence dK = dV = 0.  Each lane
-    // owns one key's column of both products, so the sweep runs unmasked and the column is zeroed here.
-    const float kz = kpok ? 1.f : 0.f, vz = kpok ? inv_keep : 0.f;
+    // owns one key's column of both products, so the sweep runs unmasked and the column is zeroed here -- by a bit mask, not a
+    // product with 0: the unmasked exp2 of a padded key's score can overflow, and inf * 0 is NaN.
+    const uint32_t km = kpok ? 0xFFFFFFFFu : 0x80000000u;
     bf16x4 kk[4], vv[4];
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-        kk[dt] = bf16x4{(bf16)(st.dk[dt][0] * kz), (bf16)(st.dk[dt][1] * kz), (bf16)(st.dk[dt][2] * kz), (bf16)(st.dk[dt][3] * kz)};
-        vv[dt] = bf16x4{(bf16)(st.dv[dt][0] * vz), (bf16)(st.dv[dt][1] * vz), (bf16)(st.dv[dt][2] * vz), (bf16)(st.dv[dt][3] * vz)};
-    }
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            kk[dt][r] = (bf16)and_bits(st.dk[dt][r], km);
+            vv[dt][r] = (bf16)and_bits(st.dv[dt][r] * inv_keep, km);
+        }
     if (kin) {
         bf16* dst = dqkv + ((long)b * Tn + key) * ld + h * DH;
 #pragma unroll
@@ -1014,7 +1026,7 @@ __global__ __launch_bounds__(64 * NW, (NW / (MT == 256 ? 2 : 4))) void attn_bwd_
             raw_barrier();
             if (c < 2) dma_issue_chunk<NW, MT>(sQ, rq, ld, sO, ro, D, c + 2, nchunk, wave, lane);
             if (c == 0) {
-                for (int i = tid; i < MT; i += 64 * NW) { sLse[i] *= LOG2E; sDel[i] *= 0.125f; }
+                for (int i = tid; i < MT; i += 64 * NW) { sLse[i] = lse_log2(sLse[i]); sDel[i] *= 0.125f; }
                 raw_barrier();
                 if (trace) ts[2] = __builtin_amdgcn_s_memrealtime();
             }
@@ -1170,14 +1182,17 @@ __device__ __forceinline__ void bwd_small_keys2_store(const BwdKeys (&st)[2], in
         const int key = 32 * u + 16 * j + l15;
         const bool kin = key < Tn, kpok = sKeep[key & mt_mask] != 0;
         // a padded key never receives attention: its probabilities are zero for every query, hence dK = dV = 0.  Each lane
-        // owns one key's column of both products, so the sweep runs unmasked and the column is zeroed here.
-        const float kz = kpok ? 1.f : 0.f, vz = kpok ? inv_keep : 0.f;
+        // owns one key's column of both products, so the sweep runs unmasked and the column is zeroed here -- by a bit mask, not a
+        // product with 0: the unmasked exp2 of a padded key's score can overflow, and inf * 0 is NaN.
+        const uint32_t km = kpok ? 0xFFFFFFFFu : 0x80000000u;
         bf16x4 kk[4], vv[4];
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            kk[dt] = bf16x4{(bf16)(st[j].dk[dt][0] * kz), (bf16)(st[j].dk[dt][1] * kz), (bf16)(st[j].dk[dt][2] * kz), (bf16)(st[j].dk[dt][3] * kz)};
-            vv[dt] = bf16x4{(bf16)(st[j].dv[dt][0] * vz), (bf16)(st[j].dv[dt][1] * vz), (bf16)(st[j].dv[dt][2] * vz), (bf16)(st[j].dv[dt][3] * vz)};
-        }
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                kk[dt][r] = (bf16)and_bits(st[j].dk[dt][r], km);
+                vv[dt][r] = (bf16)and_bits(st[j].dv[dt][r] * inv_keep, km);
+            }
         if (kin) {
             bf16* dst = dqkv + ((long)b * Tn + key) * ld + h * DH;
 #pragma unroll
@@ -1274,7 +1289,7 @@ __global__ __launch_bounds__(MT, (MT == 256 ? 2 : 1)) void attn_bwd_small_kv2_ke
         raw_barrier();
         if (c < 2) dma_issue_chunk<NW, MT>(sQ, rq, ld, sO, ro, D, c + 2, nchunk, wave, lane);
         if (c == 0) {
-            for (int i = tid; i < MT; i += 64 * NW) { sLse[i] *= LOG2E; sDel[i] *= 0.125f; }
+            for (int i = tid; i < MT; i += 64 * NW) { sLse[i] = lse_log2(sLse[i]); sDel[i] *= 0.125f; }
             raw_barrier();
             if (trace) ts[2] = __builtin_amdgcn_s_memrealtime();
         }
@@ -1461,7 +1476,7 @@ __global__ __launch_bounds__(2 * MT, 4) void attn_bwd_small_q_kernel(const bf16*
         if (c < 2) dma_issue_chunk<NW, MT>(sK, rk, ld, sV, rv, ld, c + 2, nchunk, wave, lane);
         if (c == 0) {
             if (tid < MT) sBias[tid] = sKeep[tid] != 0 ? 0.f : -INFINITY;      // (in place: thread tid owns word tid)
-            lseB = sLse[qb_ & (MT - 1)] * LOG2E;                                // (rows beyond the tensor: the DMA's bounds check left 0)
+            lseB = lse_log2(sLse[qb_ & (MT - 1)]);                               // (rows beyond the tensor: the DMA's bounds check left 0)
             delB = sDel[qb_ & (MT - 1)] * 0.125f;
             raw_barrier();
             if (trace) ts[2] = __builtin_amdgcn_s_memrealtime();
@@ -1487,7 +1502,7 @@ __global__ __launch_bounds__(2 * MT, 4) void attn_bwd_small_q_kernel(const bf16*
         bwd_small_queries_store(dq, tB, lane, b, h, Tn, nH, dqkv, dbias != nullptr, cq);
         if (tA != tB) {
             if (!(qa < Tn)) { qfA[0] = qfA[1] = ofA[0] = ofA[1] = zero16<bf16>(); }
-            const float lseA = sLse[qa & (MT - 1)] * LOG2E, delA = sDel[qa & (MT - 1)] * 0.125f;
+            const float lseA = lse_log2(sLse[qa & (MT - 1)]), delA = sDel[qa & (MT - 1)] * 0.125f;
 #pragma unroll
             for (int i = 0; i < 4; ++i) dq[i] = f32x4{0.f, 0.f, 0.f, 0.f};
             int j0 = 0;
