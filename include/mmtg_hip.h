@@ -981,6 +981,28 @@ MMTG_API int mmtg_decode_contrastive_merge(const float* cand_val, const int* can
                                   const int* pos_ptr, int P, int sent, int k, int n_prompts, int* pos_next,
                                   const int* fixed_end, void* stream);
 
+/* ---- classifier-free guidance (GuidedDecoder, mmtg_amd/decode.py; generate_samples / sample_sequence with guidance_scale=): how
+ * strongly the text follows its inputs.  The reference has no such control (generate.py:117-142 runs one prompt); the rule is
+ * transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor.  The decoder runs 2 N rows: rows 0 .. N - 1 are the prompts, rows
+ * N .. 2 N - 1 their negatives; a step with the head puts mmtg_decode_guidance between the head and the selection entry, which then
+ * reads `out` over N rows, and every step ends in mmtg_decode_mirror, which keeps the negatives on the prompts' text.
+ * mmtg_decode_guidance: one workgroup of 256 threads per pair b < N.  With c = cond[b * ldl + 0 .. V - 1], u = uncond[b * ldl + 0 ..
+ *   V - 1] (RAW logits) and L(x) = max x + log(sum_v exp(x[v] - max x)), fp32 throughout and in this order of operations:
+ *     lc = c[v] - L(c)      lu = u[v] - L(u)      out[b * ldo + v] = lu + scale * (lc - lu)           for v < V,
+ *   so c == u gives out = lu bit for bit at any scale, scale 1 follows c and scale 0 follows u.  An id where c or u is -inf gets
+ *   -inf, never NaN; a row whose V entries are all -inf (either row) gives all -inf.  Columns V .. ldo - 1 of `out` and the input
+ *   columns >= V are not touched.  Each row is read once from HBM for the (max, sum) pair (16-byte aligned rows as float4, others
+ *   one logit at a time: ldl may be odd) and once more for the combine, which finds it in the L2 the first pass left it in; wave
+ *   shuffles and static LDS words reduce in a fixed order, without atomics: equal inputs give equal bits.
+ *   Fails before any device call: a null pointer, N < 1, V < 1, ldl < V, ldo < V, scale not finite or < 0, `out` overlapping
+ *   `cond` or `uncond`.
+ * mmtg_decode_mirror: with pos = *pos_ptr (the slot the selection leaves alone), seq[(N + b) * ldseq + pos + 1] =
+ *   seq[b * ldseq + pos + 1] for b < N when pos + 1 < ldseq (and pos + 1 >= 0); nothing otherwise.  Nothing else is written.
+ *   Fails before any device call: a null pointer, N < 1, ldseq < 1.                                                              */
+MMTG_API int mmtg_decode_guidance(const float* cond, const float* uncond, long ldl, int V, float scale, float* out, long ldo, int N,
+                         void* stream);
+MMTG_API int mmtg_decode_mirror(long long* seq, long ldseq, const int* pos_ptr, int N, void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

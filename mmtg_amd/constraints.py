@@ -234,6 +234,50 @@ def mirostat_update(filtered, pick, mu, tau, eta):
     return float(s), float(mu) - float(eta) * (float(s) - float(tau))
 
 
+GUIDANCE_OFF = 1.0                     # guidance_scale at which the surface runs the plain decoder
+
+
+def check_guidance(guidance_scale=GUIDANCE_OFF):
+    """The scale of classifier-free guidance, transformers' argument of that name, as a float: a finite real number >= 0 (0 follows the
+    negative prompt alone, 1 the prompt alone, more sharpens the prompt against the negative).  Anything else (a bool, a string, None,
+    NaN, inf, a negative) raises a ValueError that names the argument.  include/mmtg_hip.h states the rule, ``guidance_scores``
+    restates it."""
+    try:
+        if isinstance(guidance_scale, (bool, np.bool_, str, bytes)):
+            raise TypeError
+        a = float(guidance_scale)
+    except (TypeError, ValueError):
+        raise ValueError("guidance_scale must be a number, finite and >= 0, got %r" % (guidance_scale,)) from None
+    if not (0.0 <= a < math.inf):               # (NaN fails every comparison)
+        raise ValueError("guidance_scale must be finite and >= 0, got %r" % (guidance_scale,))
+    return a
+
+
+def _log_softmax64(x):
+    """Row-wise log-softmax in float64; a row without a finite entry comes back all -inf."""
+    m = x.max(axis=-1, keepdims=True)
+    safe = np.where(np.isfinite(m), m, 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lse = safe + np.log(np.exp(x - safe).sum(axis=-1, keepdims=True))
+        return np.where(np.isfinite(m), x - lse, -np.inf)
+
+
+def guidance_scores(cond, uncond, scale):
+    """The rule of mmtg_decode_guidance (include/mmtg_hip.h) in float64 numpy: cond / uncond [..., V] are the raw logits of the prompts
+    and of their negatives, already cut to the columns the selection reads.  Returns lu + scale * (lc - lu) with lc / lu their
+    log-softmax over the last axis; an id where either is -inf gets -inf (never NaN), and so does every id of a pair one of whose rows
+    is all -inf."""
+    c, u = np.asarray(cond, dtype=np.float64), np.asarray(uncond, dtype=np.float64)
+    if c.shape != u.shape:
+        raise ValueError("guidance_scores: cond %r and uncond %r differ in shape" % (c.shape, u.shape))
+    s = check_guidance(scale)
+    lc, lu = _log_softmax64(c), _log_softmax64(u)
+    out_ = np.isneginf(lc) | np.isneginf(lu)
+    with np.errstate(invalid="ignore"):
+        g = lu + s * (lc - lu)
+    return np.where(out_, -np.inf, g)
+
+
 def chosen_mask(ids, sent=22, prefix_lens=None):
     """Which columns of generated lyric ids count towards a row's score: bool [B, 1 + length], host only.  Column j >= 1 of row b
     counts iff it is not a cadence column (j % sent not in {0, sent - 1}: the forced [#START#] / [#EOS#]), it lies past the row's

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .constraints import (BANNED, MIROSTAT_OFF, WARP_OFF, KeywordTables, LineTables, _check_constraints, check_contrastive, check_groups, check_keywords, check_lines,  # noqa: F401
+from .constraints import (BANNED, GUIDANCE_OFF, MIROSTAT_OFF, WARP_OFF, KeywordTables, LineTables, _check_constraints, check_contrastive, check_groups, check_guidance, check_keywords, check_lines,  # noqa: F401
                           check_mirostat, check_ngram, check_prefix, check_refrain, check_warp, chosen_mask, keywords_met, refrain_without_keywords,
                           sequence_scores)   # (the host-side checks keep their names here)
 
@@ -348,6 +348,7 @@ class GreedyDecoder:
             self._step_x3(with_head)
             self._select(with_head)
             self._logprob(with_head)
+            self._end_step(with_head)
             return
         hip.decode_embed(eng.table, self.seq, self.c, self.x, self.pos, self.tpw_type, self.tpw_mask, self.types,
                          self.keep, B, sh.P, sh.S, E, sh.two_sents, eng.table.shape[0], sent,
@@ -375,6 +376,20 @@ class GreedyDecoder:
             hip.gemm(self.a, eng.Wp("wte"), self.logits, B, eng.layout.Vpad, D, transB=True, ldb=D, out_f32=True)
         self._select(with_head)
         self._logprob(with_head)
+        self._end_step(with_head)
+
+    def _end_step(self, with_head):
+        """What a subclass launches behind the selection and the log-probabilities of every step (GuidedDecoder: the mirror).  Here:
+        nothing."""
+
+    def _begin_lead(self, batch, length):
+        """The leading positional arguments ``generate`` hands ``begin``: (batch, length) here; GuidedDecoder's begin takes the negative
+        batch and the scale among them."""
+        return batch, length
+
+    def _result_rows(self):
+        """How many of the decoder's rows ``generate`` returns: all of them here; GuidedDecoder's prompts, not their negatives."""
+        return self.B
 
     def _select(self, with_head):
         """The step's last launch: logits processing + arg-max / draw + the forced cadence + the next position (generate.py:117-142),
@@ -387,24 +402,26 @@ class GreedyDecoder:
         temperature, rep, top_k, top_p = self.params
         tmpl, rhyme = getattr(self, "tmpl", None), getattr(self, "rhyme", None)
         form = _step_forms(self, with_head)[0]
-        logits, ldl, V = (self.logits, self.eng.layout.Vpad, min(sh.V, 13317)) if with_head else (None, 0, 0)
+        # (the step's own logits over every row; GuidedDecoder selects for its prompts' rows only, from the guided scores)
+        B = getattr(self, "select_rows", self.B)
+        logits, ldl, V = (getattr(self, "select_logits", self.logits), self.eng.layout.Vpad, min(sh.V, 13317)) if with_head else (None, 0, 0)
         if form == "_refrain":              # (the tables' shapes are held against the cut with or without logits)
             V = min(sh.V, 13317)
         # stochastic: the draw of each position reads its row of the pre-filled uniforms
         sampling = (top_k, top_p, self.uniforms) if with_head and not (top_k == 1 and top_p == 0.0) else None
         if with_head and _mirostat_on(self):    # Mirostat behind the four cuts (on or off): the warp entry's launch plus the rows' state
             hip.decode_sample_mirostat(logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, top_k, top_p, self.warp,
-                                       self.mirostat, self.mirostat_mu, self.uniforms, self.B,
+                                       self.mirostat, self.mirostat_mu, self.uniforms, B,
                                        self.warp_src if self.refrain is None else self.refrain, tables=self.lines, rhyme=rhyme, tmpl=tmpl,
                                        ngram=self.ngram, pos_next=self.pos_next, fixed_end=self.fixed_end if self.use_fixed else None)
             return
         if with_head and _warp_on(self):    # min_p / typical_p / epsilon_cutoff / eta_cutoff: one entry over the refrain form, whatever the rules
             hip.decode_sample_warp(logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, top_k, top_p, self.warp,
-                                   self.uniforms, self.B, self.warp_src if self.refrain is None else self.refrain, tables=self.lines,
+                                   self.uniforms, B, self.warp_src if self.refrain is None else self.refrain, tables=self.lines,
                                    rhyme=rhyme, tmpl=tmpl, ngram=self.ngram, pos_next=self.pos_next,
                                    fixed_end=self.fixed_end if self.use_fixed else None)
             return
-        hip._select(form, logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, self.B, self.pos_next, sampling,
+        hip._select(form, logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, B, self.pos_next, sampling,
                     fixed_end=self.fixed_end if self.use_fixed else None, ngram=self.ngram, tables=self.lines, tmpl=tmpl,
                     **({} if rhyme is None else {"rhyme": rhyme}), **({"refrain": self.refrain} if form == "_refrain" else {}))
 
@@ -415,7 +432,8 @@ class GreedyDecoder:
         were.  Off, nothing is launched."""
         if _step_forms(self, with_head)[2]:
             sh = self.eng.sh
-            hip.decode_logprob(self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, self.tok_lp, self.B)
+            hip.decode_logprob(self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, self.tok_lp,
+                               getattr(self, "select_rows", self.B))
 
     def _upload_lines(self, tables):
         """The line tables into this decoder's device buffers (allocated once, so captured graphs keep their addresses; a `sets`
@@ -1000,7 +1018,7 @@ class GreedyDecoder:
         surprise of the text near 2 bits per drawn token by adapting the cut after every draw, at learning rate mirostat_eta.  It acts
         last, so top_k=0, top_p=0 leaves the choice to it.  Afterwards ``mirostat_mu`` holds every row's state.
         begin_kw: what a subclass's ``begin`` takes beyond these (BeamDecoder: the beam groups); ``begin`` here takes none."""
-        n_steps = self.begin(batch, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix,
+        n_steps = self.begin(*self._begin_lead(batch, length), temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix,
                              no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths, line_end_ids=line_end_ids,
                              templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct,
                              **({"return_logprobs": True} if return_logprobs else {}),
@@ -1029,8 +1047,9 @@ class GreedyDecoder:
         finally:
             self.use_graph = saved_mode
         self.check_mlp_error()
-        ids = self.seq[:, sh.P:sh.P + 1 + length].clone()
-        return (ids, self.tok_lp[:, :1 + length].clone()) if return_logprobs else ids
+        n = self._result_rows()
+        ids = self.seq[:n, sh.P:sh.P + 1 + length].clone()
+        return (ids, self.tok_lp[:n, :1 + length].clone()) if return_logprobs else ids
 
     def check_mlp_error(self):
         """Raise if a mmtg_decode_mlp launch of this generation reported a bounded wait that ran out or a hand-off group split over
@@ -1405,3 +1424,97 @@ class ContrastiveDecoder(BeamDecoder):
                                      penalty_alpha=penalty_alpha)
         n, k = self.n_prompts, self.nb
         return ids.view(n, k, -1)[:, 0].clone(), self.total + self.scores.view(n, k)[:, 0]
+
+
+class GuidedDecoder(GreedyDecoder):
+    """Classifier-free guidance on the KV-cached, graph-replayed token step: how strongly the text follows its inputs.  Built for
+    `max_prompts` = N prompts, the decoder runs 2 N rows: rows 0 .. N - 1 are the prompts, rows N .. 2 N - 1 their negatives (another
+    prompt, or the same one without its images and texts: generate.without_experience).  Rows never interact, so the prompt prefill
+    and the token step see 2 N ordinary rows; a step that calls the head then ends in
+
+        mmtg_decode_guidance   glogits[b] = lu + s * (lc - lu) over the log-softmax of the raw logits rows b and N + b, b < N
+        the selection entry a plain decoder would pick, over N rows, reading glogits -- penalty, temperature, bans, every
+            constraint, top-k / top-p, the four cuts and Mirostat all act on the guided scores
+        mmtg_decode_logprob    (with return_logprobs) over the N raw prompt rows: the log-probability stays the model's own
+        mmtg_decode_mirror     seq[N + b, pos + 1] = seq[b, pos + 1]: the negatives stay on the prompts' text
+
+    and a step without the head in the selection it always ended in, over N rows, and the mirror.  Only the first N rows of the
+    constraint tables, the uniforms, ``mirostat_mu`` and ``tok_lp`` are ever read or written by a selection.  The guided scores are
+    log-probabilities, never positive, where raw logits have either sign, and the per-occurrence repetition penalty (a division,
+    whatever the sign: generate.py:127-131) acts on the number it finds: guidance_scale = 1 with a penalty is not the plain decoder
+    (without one it is, up to rounding: log-softmax keeps the order).  One lane (the halves must meet in one launch)."""
+
+    def __init__(self, model, max_prompts, max_len=None, use_graph=True, lanes=1):
+        if lanes != 1:
+            raise ValueError("guided decoding runs on one lane (got lanes=%r)" % (lanes,))
+        n = int(max_prompts)
+        if n < 1:
+            raise ValueError("max_prompts %r must be at least 1" % (max_prompts,))
+        super().__init__(model, 2 * n, max_len=max_len, use_graph=use_graph, lanes=1)
+        self.n_prompts = n
+        self.guidance_scale = GUIDANCE_OFF
+        # the guided scores, allocated once: captured graphs hold the address.  Columns V .. Vpad - 1 are never written nor read.
+        self.glogits = torch.zeros(n, self.eng.layout.Vpad, dtype=torch.float32, device=self.eng.dev)
+        # what GreedyDecoder._select / _logprob read in place of the step's own logits and row count
+        self.select_rows, self.select_logits = n, self.glogits
+
+    def _select(self, with_head):
+        if with_head:
+            hip.decode_guidance(self.logits, self.logits[self.n_prompts:], self.eng.layout.Vpad, min(self.eng.sh.V, 13317),
+                                self.guidance_scale, self.glogits, self.n_prompts)
+        super()._select(with_head)
+
+    def _end_step(self, with_head):
+        hip.decode_mirror(self.seq, self.pos, self.n_prompts)      # the step's last launch; it reads the slot the selection left alone
+
+    def _begin_lead(self, batch, length):
+        return (batch,) + self._negative_and_scale[:1] + (length,) + self._negative_and_scale[1:]
+
+    def _result_rows(self):
+        return self.n_prompts
+
+    def _graph_key(self, with_head, parity):
+        return super()._graph_key(with_head, parity) + (("guidance", self.guidance_scale),)
+
+    def describe(self):
+        return super().describe() + ", %d prompts beside their negatives (guidance_scale %g)" % (self.n_prompts, self.guidance_scale)
+
+    @torch.no_grad()
+    def begin(self, batch, negative_batch, length, guidance_scale=GUIDANCE_OFF, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0,
+              generator=None, prefix=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None,
+              rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_logprobs=False, keywords=None, refrain_scheme=None,
+              **sampler_kw):
+        """GreedyDecoder.begin for N prompts (batch) and their N negatives (negative_batch, the same keys): the two are concatenated,
+        the constraints and prefixes -- one per prompt -- are doubled, and guidance_scale (check_guidance) is kept for the steps.
+        sampler_kw: min_p / typical_p / epsilon_cutoff / eta_cutoff / mirostat_tau / mirostat_eta, as GreedyDecoder.begin takes them."""
+        _keywords_need_beams(keywords)
+        scale = check_guidance(guidance_scale)
+        n, sh = self.n_prompts, self.eng.sh
+        for name, b in (("batch", batch), ("negative_batch", negative_batch)):
+            if b["img_embs"].shape[0] != n:
+                raise ValueError("decoder was built for %d prompts, %s has %d" % (n, name, b["img_embs"].shape[0]))
+        dev = self.eng.dev
+        # (an input the negative does not name is the prompt's own: a negative differs in what it is given to differ in)
+        both = {k: torch.cat([torch.as_tensor(batch[k]).to(dev), torch.as_tensor(negative_batch.get(k, batch[k])).to(dev)]) for k in batch
+                if k not in ("targets", "rating")}
+        cons = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, n, length, sh, "%d prompts" % n, templates,
+                                  rhyme_scheme, rhyme_classes, rhyme_distinct, refrain_scheme).take(list(range(n)) * 2)
+        self.guidance_scale = scale
+        return super().begin(both, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=cons.prefix,
+                             no_repeat_ngram_size=cons.ngram, line_lengths=cons.lines, return_logprobs=return_logprobs, **sampler_kw)
+
+    @torch.no_grad()
+    def generate(self, batch, negative_batch, length, guidance_scale=GUIDANCE_OFF, **kw):
+        """batch / negative_batch: N prompts and their N negatives (GreedyDecoder.generate's keys).  Returns the prompts' lyric ids
+        [N, 1 + length] -- with return_logprobs (ids, tok_lp [N, 1 + length]), the log-probability the RAW logits of the prompt's own
+        row give each id.  guidance_scale: 0 follows the negative alone, 1 the prompt alone, more sharpens the prompt against the
+        negative.  kw: everything else GreedyDecoder.generate takes but `teacher` (temperature, repitition_penalty, top_k, top_p,
+        generator, use_graph, tap, prefix, the constraints, the samplers, return_logprobs), one per prompt.  `tap(j, with_head, picked
+        [2 N], logits [2 N, Vpad] or None)` receives the raw logits of both halves.  The loop is GreedyDecoder.generate's own."""
+        if kw.get("teacher") is not None:
+            raise ValueError("guided decoding takes no teacher: the two halves of the batch follow one text, the prompts' own")
+        self._negative_and_scale = (negative_batch, guidance_scale)
+        try:
+            return super().generate(batch, length, **kw)
+        finally:
+            self._negative_and_scale = None

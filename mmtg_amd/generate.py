@@ -17,9 +17,9 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .constraints import (BANNED, WARP_OFF, Constraints, _check_constraints, check_mirostat, check_warp, check_contrastive, check_groups, check_keywords, check_prefix, refrain_without_keywords,
+from .constraints import (BANNED, GUIDANCE_OFF, WARP_OFF, Constraints, _check_constraints, check_guidance, check_mirostat, check_warp, check_contrastive, check_groups, check_keywords, check_prefix, refrain_without_keywords,
                           sequence_scores)
-from .decode import BeamDecoder, ContrastiveDecoder, GreedyDecoder, _keywords_need_beams
+from .decode import BeamDecoder, ContrastiveDecoder, GreedyDecoder, GuidedDecoder, _keywords_need_beams
 from .data import encode_line_end, encode_prefix, encode_rhyme_classes, encode_template  # noqa: F401  (public: the opening lines / the line-end sets / the line templates / the rhyme classes of generate_samples / generate_beams)
 
 SENT_SLOT = 22  # generate.py:118-121
@@ -50,10 +50,11 @@ def _check_tokenizer(tokenizer):
         raise ValueError("tokenizer special ids %s differ from the reference vocabulary's %s" % (got, BANNED))
 
 
-def _cached_decoder(model, start_input, length):
+def _cached_decoder(model, start_input, length, guided=False):
     """The KV-cached, graph-replayed decoder for this call, or None when the call is not the one the reference's
     generate.py makes (an MMTG in inference mode on the GPU -- possibly inside the nn.DataParallel wrapper of generate.py:191 --
-    started from the single [#START#] token, generate.py:207-209).  MMTG_SAMPLE_RERUN=1 forces the prefix re-run loop."""
+    started from the single [#START#] token, generate.py:207-209).  MMTG_SAMPLE_RERUN=1 forces the prefix re-run loop.
+    guided: a GuidedDecoder of one prompt (two rows) instead."""
     from .model import MMTG
     m = getattr(model, "module", model)
     if not isinstance(m, MMTG) or m.train_flag or not m._flat.is_cuda or os.environ.get("MMTG_SAMPLE_RERUN"):
@@ -67,17 +68,17 @@ def _cached_decoder(model, start_input, length):
     if t.shape[0] != 1 or int(t[0]) != 1 or length < 1 or sh.P + length + 1 > sh.NP:
         return None
     cache = m.__dict__.setdefault("_sample_decoders", {})
-    key = (m._flat.data_ptr(), int(length))
+    key = (m._flat.data_ptr(), int(length)) + (("guided",) if guided else ())
     dec = cache.get(key)
     if dec is None:
         cache.clear()                       # one decoder (KV caches + graphs) at a time
-        dec = cache[key] = GreedyDecoder(m, max_batch=1, max_len=int(length))
+        dec = cache[key] = (GuidedDecoder(m, 1, max_len=int(length)) if guided else GreedyDecoder(m, max_batch=1, max_len=int(length)))
     return dec
 
 
 def sample_sequence(model, start_input, length, tokenizer, temperature=1.0, top_k=30, top_p=0.0,
                     repitition_penalty=1.0, device="cuda", *, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0,
-                    mirostat_tau=0.0, mirostat_eta=0.1):
+                    mirostat_tau=0.0, mirostat_eta=0.1, guidance_scale=1.0, negative_input=None):
     """generate.py:97-145.  When the call is the reference's own (see _cached_decoder) the loop runs on the KV-cached decoder:
     one captured token step replayed per position instead of a full forward over the growing prefix per token; the returned
     list is what the reference loop returns (the sequence before the last model call's append).  Greedy ids are the same as
@@ -85,16 +86,32 @@ def sample_sequence(model, start_input, length, tokenizer, temperature=1.0, top_
     min_p / typical_p / epsilon_cutoff / eta_cutoff (keyword only, so the reference's positional signature stands): min-p, locally
     typical, epsilon and eta sampling behind top_k / top_p (constraints.check_warp, include/mmtg_hip.h); any of them on samples.
     mirostat_tau / mirostat_eta (keyword only; constraints.check_mirostat, include/mmtg_hip.h): Mirostat v2 behind all of them, the
-    sequence's surprise state carried from draw to draw; mirostat_tau > 0 samples."""
+    sequence's surprise state carried from draw to draw; mirostat_tau > 0 samples.
+    guidance_scale / negative_input (keyword only; constraints.check_guidance, include/mmtg_hip.h): classifier-free guidance,
+    transformers' argument of that name.  Any scale but 1 runs the model on start_input and on negative_input (the same keys; default:
+    start_input with img_embs and r_embs zeroed) and selects from lu + guidance_scale * (lc - lu) of their log-softmaxed logits: on
+    the cached path a GuidedDecoder of one prompt, in the re-run loop a second forward and mmtg_decode_guidance on the two last rows.
+    guidance_scale=1 (the default) is the call without the arguments; negative_input beside it is a ValueError."""
     _check_tokenizer(tokenizer)
+    scale = check_guidance(guidance_scale)
+    guided = scale != GUIDANCE_OFF
+    if not guided and negative_input is not None:
+        raise ValueError("negative_input needs a guidance_scale other than 1 (1 is the unguided call)")
+    if guided and negative_input is None:
+        negative_input = {k: (np.zeros_like(np.asarray(v)) if k in ("img_embs", "r_embs") else v) for k, v in start_input.items()}
     warp = check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
     warp_kw = {} if warp == WARP_OFF else dict(zip(("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"), warp))
     tau, eta = check_mirostat(mirostat_tau, mirostat_eta)
     miro_kw = {"mirostat_tau": tau, "mirostat_eta": eta} if tau > 0.0 else {}
-    dec = _cached_decoder(model, start_input, length)
+    dec = _cached_decoder(model, start_input, length, guided=guided)
     if dec is not None:
         m = getattr(model, "module", model)
         batch = {k: torch.as_tensor(np.asarray(v)).unsqueeze(0) for k, v in start_input.items() if k not in ("targets", "rating")}
+        if guided:
+            neg = {k: torch.as_tensor(np.asarray(negative_input[k])).unsqueeze(0) for k in batch}
+            ids = dec.generate(batch, neg, int(length), scale, temperature=temperature, repitition_penalty=repitition_penalty,
+                               top_k=int(top_k), top_p=float(top_p), **warp_kw, **miro_kw)
+            return dec.reference_return(ids[0].tolist(), int(length), sent=m.shapes.msl + 2)
         ids = dec.generate(batch, int(length), temperature=temperature, repitition_penalty=repitition_penalty,
                            top_k=int(top_k), top_p=float(top_p), **warp_kw, **miro_kw)
         return dec.reference_return(ids[0].tolist(), int(length), sent=m.shapes.msl + 2)
@@ -104,6 +121,10 @@ def sample_sequence(model, start_input, length, tokenizer, temperature=1.0, top_
             inputs[k] = torch.tensor(np.asarray(v), dtype=torch.long, device=device).unsqueeze(0)
         else:
             inputs[k] = torch.tensor(np.asarray(v), dtype=torch.float32, device=device).unsqueeze(0)
+    neg_inputs = None
+    if guided:      # the negative prompt beside the prompt: its own conditioning, the same growing targets
+        neg_inputs = {k: torch.tensor(np.asarray(negative_input[k]), dtype=torch.float32, device=device).unsqueeze(0)
+                      for k in start_input if k != "targets"}
     generated = inputs["targets"]
     greedy = top_k == 1 and top_p == 0.0 and not warp_kw and not miro_kw
     mu = torch.full((1,), 2.0 * tau, dtype=torch.float32, device=device) if miro_kw else None
@@ -119,6 +140,14 @@ def sample_sequence(model, start_input, length, tokenizer, temperature=1.0, top_
                 continue
             _, _, outputs = model.forward(inputs)
             generated = inputs["targets"]
+            if guided:
+                # the guided scores of the two last rows take the raw logits' place (columns past the cut are never read)
+                cond = outputs[0, -1, :].float().clone()       # (a copy: the engine's next forward may write the same buffer)
+                _, _, outputs_u = model.forward(dict(neg_inputs, targets=generated))
+                uncond = outputs_u[0, -1, :].float().contiguous()
+                guided_row = torch.zeros(1, cond.shape[0], dtype=torch.float32, device=cond.device)
+                hip.decode_guidance(cond, uncond, cond.shape[0], min(cond.shape[0], 13317), scale, guided_row, 1)
+                outputs = guided_row.view(1, 1, -1)
             if greedy:
                 row = outputs[0, -1, :]
                 glen.fill_(generated.shape[1])
@@ -191,6 +220,14 @@ def _stack_rows(rows):
     return {k: torch.as_tensor(np.stack([np.asarray(r[k]) for r in rows])) for k in keys}
 
 
+def without_experience(rows):
+    """The default negative prompt of classifier-free guidance: `rows` (as generate_samples takes them) stacked, with the images and
+    texts of the experience (img_embs, r_embs) zeroed and the topic kept -- what the model would write about the topic alone."""
+    out = _stack_rows(rows)
+    out["img_embs"], out["r_embs"] = torch.zeros_like(out["img_embs"]), torch.zeros_like(out["r_embs"])
+    return out
+
+
 def _chunks(stacked, cons, size, dev, copies=1):
     """The prompts of `stacked`, each `copies` times in a row, cut into decoder batches of exactly `size` rows on `dev`: yields
     (batch, the rows' Constraints, the number of real rows).  The decoder's batch is fixed, so the last chunk is padded by repeating
@@ -215,7 +252,7 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
                      repetition_penalty=1.5, max_batch=256, generator=None, decoder=None, prefixes=None, no_repeat_ngram_size=0,
                      line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False,
                      return_scores=False, rank_by=None, keywords=None, refrain_scheme=None, *, min_p=0.0, typical_p=1.0,
-                     epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
+                     epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1, guidance_scale=1.0, negative_rows=None):
     """n_samples texts per prompt (generate.sh's loop, generate.py:205-235) on the batched, graph-replayed decoder:
     every prompt is replicated over n_samples rows, rows are decoded max_batch at a time with the device-side
     top-k / top-p sampler (one uniform per row and position from `generator`), each row is cut back to what
@@ -250,8 +287,19 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     typical_p=0.9, min_p=0.05 with top_k=0, top_p=0.  At their defaults the call is the call without them.
     mirostat_tau / mirostat_eta (keyword only; constraints.check_mirostat, include/mmtg_hip.h): Mirostat v2, llama.cpp's arguments of
     those names, behind all of the above: mirostat_tau=2.0 with top_k=0, top_p=0 holds every sample's surprise near 2 bits per drawn
-    character.  Each of the n_samples rows of a prompt has its own state.  mirostat_tau=0 (the default) is the call without them."""
+    character.  Each of the n_samples rows of a prompt has its own state.  mirostat_tau=0 (the default) is the call without them.
+    guidance_scale / negative_rows (keyword only; constraints.check_guidance, include/mmtg_hip.h, decode.GuidedDecoder): classifier-free
+    guidance, transformers' argument of that name: guidance_scale=3.0 makes every sample follow its prompt's images and texts more
+    closely than the model alone would, by sharpening each step's distribution against that of a negative prompt -- negative_rows (rows
+    as above, one per prompt or one for all; default without_experience(rows): the topic alone).  Every other argument works as
+    before, on the guided scores; the scores of return_scores stay the model's own log-probabilities under the real prompt.  A
+    guided chunk holds max_batch // 2 rows beside their negatives.  guidance_scale=1 (the default) is the call without the
+    arguments; negative_rows beside it is a ValueError."""
     _keywords_need_beams(keywords)
+    scale = check_guidance(guidance_scale)
+    guided = scale != GUIDANCE_OFF
+    if not guided and negative_rows is not None:
+        raise ValueError("negative_rows needs a guidance_scale other than 1 (1 is the unguided call)")
     warp = check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
     warp_kw = {} if warp == WARP_OFF else dict(zip(("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"), warp))
     tau, eta = check_mirostat(mirostat_tau, mirostat_eta)
@@ -266,11 +314,25 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
     cons = _check_constraints(prefixes, no_repeat_ngram_size, line_lengths, line_end_ids, n_prompts, length, sh, "%d prompts" % n_prompts,
                               templates, rhyme_scheme, rhyme_classes, rhyme_distinct, refrain_scheme)
-    bsz = min(max_batch, n_prompts * n_samples)
-    dec = decoder if decoder is not None and decoder.B == bsz else GreedyDecoder(model, max_batch=bsz, max_len=length)
+    stacked = _stack_rows(rows)
+    if guided:
+        neg = without_experience(rows) if negative_rows is None else _stack_rows(negative_rows)
+        n_neg = neg["topic_ids"].shape[0]
+        if n_neg == 1 and n_prompts > 1:
+            neg = {k: v.expand(n_prompts, *v.shape[1:]) for k, v in neg.items()}
+        elif n_neg != n_prompts:
+            raise ValueError("negative_rows: one row per prompt (%d) or one for all, got %d" % (n_prompts, n_neg))
+        bsz = max(1, min(max_batch // 2, n_prompts * n_samples))
+        dec = (decoder if isinstance(decoder, GuidedDecoder) and decoder.n_prompts == bsz
+               else GuidedDecoder(model, bsz, max_len=length))
+        negs = _chunks(neg, cons, bsz, eng.dev, copies=n_samples)       # (the prompts' chunks, row for row)
+    else:
+        bsz = min(max_batch, n_prompts * n_samples)
+        dec = decoder if decoder is not None and decoder.B == bsz else GreedyDecoder(model, max_batch=bsz, max_len=length)
     texts = []
-    for chunk, c, n in _chunks(_stack_rows(rows), cons, bsz, eng.dev, copies=n_samples):
-        ids = dec.generate(chunk, length, temperature=temperature, repitition_penalty=repetition_penalty,
+    for chunk, c, n in _chunks(stacked, cons, bsz, eng.dev, copies=n_samples):
+        ids = dec.generate(chunk, *((next(negs)[0], length, scale) if guided else (length,)), temperature=temperature,
+                           repitition_penalty=repetition_penalty,
                            top_k=top_k, top_p=top_p, generator=generator, prefix=c.prefix, no_repeat_ngram_size=c.ngram,
                            line_lengths=c.lines, **({"return_logprobs": True} if scoring else {}), **warp_kw)
         if scoring:

@@ -153,6 +153,8 @@ _SIGS = {
     "mmtg_decode_beam_merge_kw_fixed": ([_vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_contrastive_sim": ([_i, _vp, _l, _vp, _vp, _f, _vp, _i, _vp, _vp, _vp, _l, _vp, _l, _vp, _i, _i, _i, _vp], _i),
     "mmtg_decode_contrastive_merge": ([_vp, _vp, _vp, _vp, _vp, _f, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "mmtg_decode_guidance": ([_vp, _vp, _l, _i, _f, _vp, _l, _i, _vp], _i),
+    "mmtg_decode_mirror": ([_vp, _l, _vp, _i, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
     "mmtg_decode_mlp_sync_words": ([], _i),
     "mmtg_decode_mlp_census": ([_vp, _vp], _i),
@@ -1280,6 +1282,25 @@ def decode_contrastive_merge(cand_val, cand_id, scores, sim, total, alpha, seq, 
     _check(lib().mmtg_decode_contrastive_merge(_p(cand_val), _p(cand_id), _p(scores), _p(sim), _p(total), float(alpha), _p(seq),
                                                seq.stride(0), _p(keep), keep.stride(0), _p(rows), rows.stride(0), _p(pos), P, sent, int(k),
                                                int(n_prompts), _p(pos_next), _p(fixed_end), _stream()), "decode_contrastive_merge")
+
+
+def decode_guidance(cond, uncond, ldl, V, scale, out, N):
+    """out[b, :V] = lu + scale * (lc - lu), lc / lu the log-softmax of cond[b, :V] / uncond[b, :V], for b < N (include/mmtg_hip.h,
+    mmtg_decode_guidance).  cond and uncond are fp32 row starts ldl apart; out is fp32 [>= N, >= V]; columns V .. stay as they are."""
+    if cond.dtype != torch.float32 or uncond.dtype != torch.float32 or out.dtype != torch.float32:
+        raise ValueError("cond, uncond and out must be fp32")
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < N:
+        raise ValueError("out must be fp32 [>= N, >= V] with unit column stride")
+    _check(lib().mmtg_decode_guidance(_p(cond), _p(uncond), int(ldl), int(V), float(scale), _p(out), out.stride(0), int(N), _stream()),
+           "decode_guidance")
+
+
+def decode_mirror(seq, pos, N):
+    """seq[N + b, pos + 1] = seq[b, pos + 1] for b < N, where the column exists (include/mmtg_hip.h, mmtg_decode_mirror).  seq is
+    int64 [>= 2 N, ld]; pos is the position slot the selection left alone."""
+    if seq.dtype != torch.long or seq.dim() != 2 or seq.stride(1) != 1 or seq.shape[0] < 2 * N:
+        raise ValueError("seq must be int64 [>= 2 N, ld] with unit column stride")
+    _check(lib().mmtg_decode_mirror(_p(seq), seq.stride(0), _p(pos), int(N), _stream()), "decode_mirror")
 
 
 def decode_advance(pos):
