@@ -981,6 +981,67 @@ MMTG_API int mmtg_decode_contrastive_merge(const float* cand_val, const int* can
                                   const int* pos_ptr, int P, int sent, int k, int n_prompts, int* pos_next,
                                   const int* fixed_end, void* stream);
 
+/* ---- stochastic beam search (StochasticBeamDecoder, mmtg_amd/decode.py; Kool, van Hoof and Welling 2019, "Stochastic Beams and
+ * Where to Find Them"): nb DIFFERENT lyrics per prompt, an exact sample of size nb without replacement from the distribution the
+ * sampler draws from -- the processed logits: penalty, temperature, bans and every line rule.  The reference has no such method
+ * (generate.py:117-142 draws its samples independently, so they can coincide).  Log-probabilities are perturbed with Gumbel noise,
+ * every child conditioned on its parent's perturbed value, and a beam search of width nb runs over the perturbed values.
+ * State.  A prompt owns nb rows b0 .. b0 + nb - 1 (nb in 1..16, b0 = prompt * nb: the beam decoder's layout, its ancestry table
+ *   `rows` and its `scores`).  scores[b] is the sum of the processed log-probabilities of row b's tokens, a beam score's scale.
+ *   gum[b] (fp32) is the row's perturbed value; a row with gum[b] or scores[b] not above -inf (NaN included) is dead.  The host
+ *   starts a prompt at scores = [0, -inf, ...] and gum = [0, -inf, ...].
+ * Noise.  Counter-based and stateless, from hash_u32 of csrc/common.h (the murmur3 finaliser the dropout uses):
+ *     h = hash_u32(hash_u32(row_seed[b], (uint32) pos), (uint32) v)      row_seed uint32 [B], written by the host
+ *     u = ((h >> 9) + 0.5f) * 2^-23                                      exact in fp32, strictly inside (0, 1)
+ *     n_v = -logf(-logf(u))
+ *   pos is read from pos_ptr, so a replayed graph draws fresh noise at every step.
+ * Candidates, mmtg_decode_gumbel_candidates: one workgroup of 256 threads per row, at a step where mmtg_decode_beam_candidates*
+ *   would offer candidates (nothing is written on a forced cadence column, a held prefix column or while pos + 1 - P < 1).  With x
+ *   the processed logits exactly as those kernels compute them (the refrain form's rule, whose "no rule" forms serve every
+ *   generation: fixed_end null, ngram 0, lo / hi / tmpl / class_of / lead null, a src table of -1):
+ *     lp_v = log_softmax(x)[v] in fp32 = (x_v - max x) - logf(sum exp(x - max x)), the beam candidates' own expressions and order
+ *     t_v  = lp_v + n_v   over the ids with x_v > -inf;     Zt = max_v t_v
+ *   The row offers its nb largest t_v, by t descending and then id ascending: cand_id, cand_val = lp_v, and cand_g [B, nb]:
+ *     G  = scores[b] + t_v
+ *     w  = (gum[b] - G) + log1mexp(t_v - Zt)
+ *     cand_g = gum[b] - fmaxf(0, w) - log1pf(expf(-fabsf(w)))
+ *     log1mexp(a) = a > -ln 2 ? logf(-expm1f(a)) : log1pf(-expf(a))          log1mexp(0) = -inf
+ *   the numerically stable form of -log(exp(-T) - exp(-Z) + exp(-G)) (T = gum[b], Z = scores[b] + Zt) of the paper's appendix,
+ *   with logf / expf / log1pf / expm1f, not the fast intrinsics.  The transform is monotone in t_v, so the order by t is the order
+ *   by cand_g.  The child at Zt gets cand_g == gum[b] bit for bit, and every cand_g <= gum[b].  cand_val of an id has the bits
+ *   mmtg_decode_beam_candidates_refrain gives that id: the winners' lp is computed again from the logits; the noise is never
+ *   subtracted back out.  Slots past the allowed ids hold -inf in both tables and id 0.
+ *   Single-choice columns -- a refrain's copy, sticky PAD, a full line's PAD, a template's given id, in that order: slot 0 offers
+ *   that id with cand_val = 0 and cand_g = gum[b] (a continuation of probability 1); the other slots hold -inf and id 0.
+ *   Rows that offer nothing: a dead row (tested before everything but the forced / held columns), and a row with every id banned,
+ *   offer -inf in both tables and id 0.  No table ever holds a NaN.
+ *   LDS: the count words and one V-float image (x, then t): what the beam candidates request.  Fixed-order reductions, no atomics
+ *   beyond the count table's: equal inputs give equal bits.
+ * Merge, mmtg_decode_gumbel_merge: one workgroup per prompt over its nb * nb candidates; it publishes *pos_next = pos + 1.
+ *   The nb largest cand_g are kept, ordered by cand_g descending, then parent ascending, then rank ascending (a strict total
+ *   order; a NaN counts as -inf).  The kept candidates become rows 0 .. nb - 1 in that order: seq / keep / rows are reordered in
+ *   place as mmtg_decode_beam_merge reorders them, seq[b, pos + 1] = the id, rows[b, pos + 1] = b,
+ *   scores[b] = scores[parent] + cand_val (a NaN sum counts as -inf) and gum[b] = cand_g.
+ *   A forced cadence column, a held prefix column (fixed_end given, nullable: one prefix per prompt, pos + 1 < fixed_end[b0]) and
+ *   null candidates (a step that skipped the head) do what mmtg_decode_beam_merge_fixed does, and gum is left as it was: a
+ *   continuation of probability 1 inherits its parent's value.
+ * Invariants: after every merge gum[b0] == 0.0 exactly; gum is non-increasing over a prompt's rows; the live rows of a prompt are
+ *   pairwise different sequences; nb = 1 is ancestral sampling by the Gumbel-max trick.
+ * Fail before any device call: nb outside 1..16, null scores / gum / row_seed / cand_g (cand_val / cand_id / cand_g of the merge
+ *   may be null together; fixed_end may be null), the refrain form's table checks, pos_next == pos_ptr.
+ * Two new kernels (the candidates behind every other function of decode.hip, the merge in a source file of its own); every other
+ * kernel compiles to the same code as before.                                                                                    */
+MMTG_API int mmtg_decode_gumbel_candidates(const float* logits, long ldl, int V, const long long* seq, long ldseq,
+                                  const int* pos_ptr, int P, int sent, float temperature, float rep_penalty, int nb,
+                                  float* cand_val, int* cand_id, int B, const int* fixed_end, int ngram, const unsigned char* lo,
+                                  const unsigned char* hi, int n_lines, const unsigned* sets, int n_sets, const short* set_of,
+                                  const int* tmpl, const short* class_of, const signed char* lead, int distinct,
+                                  const signed char* src, const float* scores, const float* gum, const unsigned* row_seed,
+                                  float* cand_g, void* stream);
+MMTG_API int mmtg_decode_gumbel_merge(const float* cand_val, const int* cand_id, const float* cand_g, float* scores, float* gum,
+                             long long* seq, long ldseq, int* keep, long ldkeep, int* rows, long ldrows, const int* pos_ptr,
+                             int P, int sent, int nb, int n_prompts, int* pos_next, const int* fixed_end, void* stream);
+
 /* ---- classifier-free guidance (GuidedDecoder, mmtg_amd/decode.py; generate_samples / sample_sequence with guidance_scale=): how
  * strongly the text follows its inputs.  The reference has no such control (generate.py:117-142 runs one prompt); the rule is
  * transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor.  The decoder runs 2 N rows: rows 0 .. N - 1 are the prompts, rows

@@ -234,6 +234,147 @@ def mirostat_update(filtered, pick, mu, tau, eta):
     return float(s), float(mu) - float(eta) * (float(s) - float(tau))
 
 
+def check_stochastic(num_samples, seed=0):
+    """The settings of a stochastic beam search: (nb, seed).  nb samples without replacement per prompt, an integer in 1..16 (a
+    prompt's rows, the beam decoder's layout); seed an integer in 0 .. 2^32 - 1, the word every row's noise is derived from
+    (``stochastic_row_seeds``).  Anything else raises a ValueError that names the argument."""
+    if not _is_int(num_samples):
+        raise ValueError("num_samples must be an integer, got %r" % (num_samples,))
+    nb = int(num_samples)
+    if not 1 <= nb <= 16:
+        raise ValueError("num_samples %d outside 1..16" % nb)
+    if not _is_int(seed):
+        raise ValueError("seed must be an integer, got %r" % (seed,))
+    if not 0 <= int(seed) < 2 ** 32:
+        raise ValueError("seed %d outside 0 .. 2^32 - 1" % int(seed))
+    return nb, int(seed)
+
+
+def _hash_u32(seed, idx):
+    """hash_u32 of csrc/common.h (the murmur3 finaliser over seed + idx * 0x9E3779B1) on numpy uint32 arrays, bit-exact."""
+    with np.errstate(over="ignore"):
+        h = np.asarray(idx, dtype=np.uint32) * np.uint32(0x9E3779B1) + np.asarray(seed, dtype=np.uint32)
+        h = h ^ (h >> np.uint32(16))
+        h = h * np.uint32(0x85EBCA6B)
+        h = h ^ (h >> np.uint32(13))
+        h = h * np.uint32(0xC2B2AE35)
+        return h ^ (h >> np.uint32(16))
+
+
+def stochastic_row_seeds(seed, first_prompt, n_prompts, nb):
+    """The row_seed words of mmtg_decode_gumbel_candidates for prompts first_prompt .. first_prompt + n_prompts - 1 of a call, uint32
+    [n_prompts * nb] in the decoder's row order: hash(hash(seed, 1 + the prompt's index in the whole call), 1 + the beam slot) (from
+    1: the hash maps (0, 0) to 0).  The batch chunk is not an input, so how a call is cut into batches does not change a prompt's
+    noise."""
+    nb, seed = check_stochastic(nb, seed)
+    prompts = np.arange(int(first_prompt), int(first_prompt) + int(n_prompts), dtype=np.uint64) + np.uint64(1)
+    return _hash_u32(_hash_u32(np.uint32(seed), prompts.astype(np.uint32))[:, None],
+                     np.arange(1, nb + 1, dtype=np.uint32)[None, :]).reshape(-1)
+
+
+def gumbel_uniforms(seed_words, pos, V):
+    """u of the noise rule (include/mmtg_hip.h) as float32 [rows, V], the kernel's bits: h = hash(hash(row_seed[b], pos), v),
+    u = ((h >> 9) + 0.5) * 2^-23 -- exact in fp32 and strictly inside (0, 1)."""
+    words = np.asarray(seed_words, dtype=np.uint32).reshape(-1)
+    h = _hash_u32(_hash_u32(words, np.uint32(int(pos) & 0xFFFFFFFF))[:, None], np.arange(int(V), dtype=np.uint32)[None, :])
+    return ((h >> np.uint32(9)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -23)
+
+
+def gumbel_noise(seed_words, pos, V):
+    """n_v = -log(-log(u)) of the noise rule in float64 [rows, V], from the exact u of ``gumbel_uniforms``: nothing random is left."""
+    return -np.log(-np.log(gumbel_uniforms(seed_words, pos, V).astype(np.float64)))
+
+
+def _log1mexp(a):
+    """log(1 - exp(a)) for a <= 0 in float64; log1mexp(0) = -inf."""
+    a = np.asarray(a, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        return np.where(a > -math.log(2.0), np.log(-np.expm1(a)), np.log1p(-np.exp(np.minimum(a, 0.0))))
+
+
+def gumbel_candidates(x, scores, gum, seed_words, pos, nb, only=None, gaps=None):
+    """mmtg_decode_gumbel_candidates (include/mmtg_hip.h) in float64 numpy, the host's statement of the rule and the tests' oracle.
+    x [rows, V]: the processed logits of every row (penalty, temperature and every ban applied; -inf where banned); scores / gum
+    [rows]; seed_words uint32 [rows]; pos the step's position.  only (optional) [rows]: the id of a row that sits on a single-choice
+    column (a copy, a sticky or full-line PAD, a given id), -1 elsewhere.  Returns (cand_id int64, cand_val, cand_g float64), each
+    [rows, nb]: per row the nb largest t = log_softmax(x) + noise by (t descending, id ascending), their log-probabilities and the
+    children's perturbed values; a dead row (gum or score not above -inf) and a row with every id banned offer -inf and id 0.
+    gaps (a list, optional) receives per row the gap between its nb-th and (nb + 1)-th t (inf where nothing was to decide)."""
+    x = np.asarray(x, dtype=np.float64)
+    x = x.reshape(-1, x.shape[-1])
+    R, V = x.shape
+    scores, gum = np.asarray(scores, dtype=np.float64).reshape(R), np.asarray(gum, dtype=np.float64).reshape(R)
+    noise = gumbel_noise(seed_words, pos, V)
+    ids = np.zeros((R, nb), dtype=np.int64)
+    val, g = np.full((R, nb), -np.inf), np.full((R, nb), -np.inf)
+    for b in range(R):
+        gap = np.inf
+        live = gum[b] > -np.inf and scores[b] > -np.inf
+        if live and only is not None and only[b] >= 0:
+            ids[b, 0], val[b, 0], g[b, 0] = int(only[b]), 0.0, gum[b]
+        elif live and (x[b] > -np.inf).any():
+            ok = x[b] > -np.inf
+            m = x[b][ok].max()
+            lp = np.where(ok, (x[b] - m) - math.log(np.exp(x[b][ok] - m).sum()), -np.inf)
+            t = np.where(ok, lp + noise[b], -np.inf)
+            order = np.lexsort((np.arange(V), -t))
+            zt = t[order[0]]
+            for r, v in enumerate(order[:nb]):
+                if not ok[v]:
+                    break
+                w = (gum[b] - (scores[b] + t[v])) + float(_log1mexp(t[v] - zt))
+                ids[b, r], val[b, r] = v, lp[v]
+                g[b, r] = gum[b] - max(0.0, w) - math.log1p(math.exp(-abs(w)))
+            if V > nb and ok[order[nb - 1]]:
+                gap = t[order[nb - 1]] - t[order[nb]]
+        if gaps is not None:
+            gaps.append(float(gap))
+    return ids, val, g
+
+
+def gumbel_merge(cand_val, cand_id, cand_g, scores, gum, seq, keep, rows, pos, P, sent, nb, fixed_end=None, gaps=None):
+    """mmtg_decode_gumbel_merge (include/mmtg_hip.h) on numpy arrays, in place: cand_val / cand_id / cand_g [B, nb] (all None: a step
+    without candidates), scores / gum [B], seq / keep / rows [B, width], B a multiple of nb.  Per prompt the nb candidates with the
+    largest cand_g by (cand_g descending, parent ascending, rank ascending; a NaN counts as -inf) become its rows in that order:
+    columns 0 .. pos of seq / keep / rows are the parent's, seq[b, pos + 1] the id, rows[b, pos + 1] = b, scores[b] = scores[parent] +
+    cand_val (a NaN counts as -inf), gum[b] = cand_g.  A held prompt, a forced cadence column and a step without candidates keep
+    every row (and gum) and append the forced token, if any.  gaps (a list, optional) receives per merged prompt the gap between
+    its nb-th and (nb + 1)-th cand_g (inf where there is no (nb + 1)-th or the nb-th is -inf).  Returns the parents int64 [B] (the
+    identity where nothing was merged)."""
+    B = scores.shape[0]
+    j = pos + 1 - P
+    forced = j > 1 and ((j + 1) % sent == 0 or (j + 1) % sent == 1)
+    par = np.arange(B, dtype=np.int64)
+    for b0 in range(0, B, nb):
+        blk = slice(b0, b0 + nb)
+        if fixed_end is not None and pos + 1 < fixed_end[b0]:
+            rows[blk, pos + 1] = np.arange(b0, b0 + nb)
+            continue
+        if j < 1 or forced or cand_val is None:
+            if j >= 1 and forced:
+                seq[blk, pos + 1] = 2 if (j + 1) % sent == 0 else 1
+            rows[blk, pos + 1] = np.arange(b0, b0 + nb)
+            continue
+        cg = np.asarray(cand_g[blk], dtype=np.float64).reshape(-1).copy()
+        cg[np.isnan(cg)] = -np.inf
+        order = np.lexsort((np.arange(nb * nb), -cg))[:nb]
+        if gaps is not None:
+            rest = np.lexsort((np.arange(nb * nb), -cg))
+            gaps.append(float(cg[rest[nb - 1]] - cg[rest[nb]]) if nb * nb > nb and cg[rest[nb - 1]] > -np.inf else float("inf"))
+        p, k = order // nb, order % nb
+        with np.errstate(invalid="ignore"):
+            sc = (scores[blk][p] + cand_val[blk][p, k]).astype(scores.dtype)
+        sc[np.isnan(sc)] = -np.inf
+        for t in (seq, keep, rows):
+            t[blk, :pos + 1] = t[blk, :pos + 1][p]
+        seq[blk, pos + 1] = cand_id[blk][p, k]
+        rows[blk, pos + 1] = np.arange(b0, b0 + nb)
+        scores[blk] = sc
+        gum[blk] = cg[order].astype(gum.dtype)
+        par[blk] = b0 + p
+    return par
+
+
 GUIDANCE_OFF = 1.0                     # guidance_scale at which the surface runs the plain decoder
 
 

@@ -3517,3 +3517,199 @@ extern "C" int mmtg_decode_logprob(const float* logits, long ldl, int V, const l
     MMTG_LAUNCH_CHECK("decode_logprob");
     return MMTG_OK;
 }
+
+// ------------------------------------------------------------------ stochastic beam search (StochasticBeamDecoder)
+// The candidates of mmtg_decode_gumbel_candidates (include/mmtg_hip.h states the rule; the merge is csrc/decode_stochastic.hip).
+// beam_candidates_kernel<RefrainRule> with Gumbel noise: the row's nb largest t_v = log_softmax(x)[v] + n_v, each with its
+// log-probability and the perturbed value of the child, conditioned on the row's own.  One kernel over the most general rule, whose
+// "no rule" forms serve every generation, as decode_select_warp_kernel is; a template, so that it is emitted behind every other
+// function of the code object and the kernels above stay the code they were.
+// LDS: the count words and ONE V-float image, which holds x and then t (select_lds(V, true, rule), what the beam candidates ask
+// for).  lp is not kept beside t: the nb winners' are recomputed from the logits by the beam kernel's own expressions, so cand_val
+// has the bits that kernel gives the id, and the footprint stays at 80 KB for V = 13317 instead of 133 KB.
+namespace {
+
+// log(1 - exp(a)) for a <= 0 (Maechler 2012): log1mexp(0) = -inf
+__device__ __forceinline__ float gumbel_log1mexp(float a) { return a > -0.69314718f ? logf(-expm1f(a)) : log1pf(-expf(a)); }
+
+template <typename R>
+__global__ __launch_bounds__(256) void gumbel_candidates_kernel(const float* __restrict__ logits, long ldl, int V,
+        const long long* __restrict__ seq, long ldseq, const int* __restrict__ pos_ptr, int P, int sent,
+        float temperature, float rep_penalty, int nb, float* __restrict__ cand_val, int* __restrict__ cand_id,
+        const float* __restrict__ scores, const float* __restrict__ gum, const unsigned* __restrict__ row_seed,
+        float* __restrict__ cand_g, R rule) {
+    extern __shared__ unsigned cnt[];          // (V + 1) / 2 count words | V floats: the processed logits, then t
+    float* const px = reinterpret_cast<float*>(cnt + (V + 1) / 2);
+    __shared__ float sval[4], sx[BEAM_MAX];
+    __shared__ int sidx[4], si[BEAM_MAX];
+    const int b = blockIdx.x, tid = threadIdx.x, pos = *pos_ptr;
+    const int j = pos + 1 - P;
+    if (j < 1 || beam_forced(j, sent)) return;             // the merge appends the forced token without candidates
+    if (rule.held(b, pos)) return;                         // a prefix column: nothing to offer (the merge keeps the prompt)
+    float* const cv = cand_val + (long)b * nb;
+    float* const cg = cand_g + (long)b * nb;
+    int* const ci = cand_id + (long)b * nb;
+    const float gb = gum[b], sb = scores[b];
+    if (!(gb > -INFINITY) || !(sb > -INFINITY)) {          // a dead row offers nothing (NaN counts as dead)
+        if (tid < nb) { cv[tid] = -INFINITY; cg[tid] = -INFINITY; ci[tid] = 0; }
+        return;
+    }
+    const long long* gen = seq + (long)b * ldseq + P;
+    // the single-choice columns: slot 0 alone, at log-probability 0, with the row's own perturbed value (probability 1)
+    int only = -1;
+    const int q = rule.copy_from(b, j, sent);
+    const int n = min(j, MAXGEN);
+    LineCol lc = {false, false, nullptr};
+    bool rhymes = false;
+    TmplCol tc = {-1, nullptr};
+    if (q >= 0) only = (int)gen[q];                        // a refrain's copy
+    else if (gen[n - 1] == 0) only = 0;                    // sticky PAD
+    else {
+        lc = rule.col(b, j, sent, gen, &rhymes);
+        if (lc.force_pad) only = 0;                        // a full line's PAD
+        else {
+            tc = rule.sym(b, j, sent);
+            if (tc.given >= 0) only = tc.given;            // a template's given id
+        }
+    }
+    if (q >= 0 || only >= 0) {
+        if (tid < nb) { cv[tid] = tid == 0 ? 0.f : -INFINITY; cg[tid] = tid == 0 ? gb : -INFINITY; ci[tid] = tid == 0 ? only : 0; }
+        return;
+    }
+    count_ids(cnt, V, gen, n, tid);
+    const NgramBan ng = rule.bans();
+    if (ng.n > 0) ban_ngrams(cnt, reinterpret_cast<int*>(px + V), V, gen, min(n, ng.hist_cap), ng.n, tid);
+    ban_line_tmpl(cnt, V, lc, tc.cls, tid);
+    rule.ban_distinct(cnt, b, j, sent, gen, lc, rhymes, tid);
+    const float* row = logits + (long)b * ldl;
+    float mx = -INFINITY;
+    for (int v = tid; v < V; v += 256) {                   // (beam_candidates_kernel's expressions, in its order: cand_val's bits)
+        float x = row[v];
+        if (v != 102) {
+            const int c = (cnt[v >> 1] >> (16 * (v & 1))) & 0xFFFF;
+            x = penalize<true>(x, c, rep_penalty);
+        }
+        x = x / temperature;
+        if (v == 1 || v == 2 || v == 100 || v == 102) x = -INFINITY;
+        px[v] = x;
+        mx = fmaxf(mx, x);
+    }
+    mx = wave_max(mx);
+    if ((tid & 63) == 0) sval[tid >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(sval[0], sval[1]), fmaxf(sval[2], sval[3]));
+    if (!(mx > -INFINITY)) {                               // every id banned: nothing to offer, as a dead row
+        if (tid < nb) { cv[tid] = -INFINITY; cg[tid] = -INFINITY; ci[tid] = 0; }
+        return;
+    }
+    float sum = 0.f;
+    for (int v = tid; v < V; v += 256) sum += expf(px[v] - mx);
+    sum = wave_sum(sum);
+    __syncthreads();
+    if ((tid & 63) == 0) sval[tid >> 6] = sum;
+    __syncthreads();
+    const float lsum = logf(sval[0] + sval[1] + sval[2] + sval[3]);
+    // t_v = lp_v + n_v in place of x_v (a thread rewrites the entries it wrote); -inf stays -inf: the noise is finite
+    const unsigned hs = hash_u32(row_seed[b], (unsigned)pos);
+    float zt = -INFINITY;
+    for (int v = tid; v < V; v += 256) {
+        const float x = px[v];
+        float t = -INFINITY;
+        if (x > -INFINITY) {
+            const unsigned h = hash_u32(hs, (unsigned)v);
+            const float u = ((float)(h >> 9) + 0.5f) * 1.1920928955078125e-07f;          // 2^-23: exact, inside (0, 1)
+            t = ((x - mx) - lsum) + -logf(-logf(u));
+        }
+        px[v] = t;
+        zt = fmaxf(zt, t);
+    }
+    zt = wave_max(zt);
+    __syncthreads();                                       // (sval's sums are read)
+    if ((tid & 63) == 0) sval[tid >> 6] = zt;
+    __syncthreads();
+    zt = fmaxf(fmaxf(sval[0], sval[1]), fmaxf(sval[2], sval[3]));
+    // nb rounds of the block arg-max over t (lowest id wins ties); a taken id is marked NaN, which no comparison selects again
+    for (int r = 0; r < nb; ++r) {
+        __syncthreads();
+        float best = -INFINITY;
+        int besti = 0x7fffffff;
+        for (int v = tid; v < V; v += 256) {
+            const float x = px[v];
+            if (x > best || (x == best && v < besti)) { best = x; besti = v; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(best, o, 64);
+            const int oi = __shfl_xor(besti, o, 64);
+            if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        }
+        if ((tid & 63) == 0) { sval[tid >> 6] = best; sidx[tid >> 6] = besti; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < 4; ++w)
+                if (sval[w] > best || (sval[w] == best && sidx[w] < besti)) { best = sval[w]; besti = sidx[w]; }
+            sx[r] = best;
+            si[r] = besti;
+            if (besti >= 0 && besti < V) px[besti] = __int_as_float(0x7fc00000);
+        }
+    }
+    __syncthreads();
+    if (tid < nb) {
+        const float t = sx[tid];
+        const int v = si[tid];
+        const bool ok = v >= 0 && v < V && t > -INFINITY;
+        float lp = -INFINITY, g = -INFINITY;
+        if (ok) {
+            float x = row[v];                              // the winner's log-probability again, from the logits
+            if (v != 102) {
+                const int c = (cnt[v >> 1] >> (16 * (v & 1))) & 0xFFFF;
+                x = penalize<true>(x, c, rep_penalty);
+            }
+            x = x / temperature;
+            lp = (x - mx) - lsum;
+            const float G = sb + t;
+            const float w = (gb - G) + gumbel_log1mexp(t - zt);
+            g = gb - fmaxf(0.f, w) - log1pf(expf(-fabsf(w)));
+        }
+        cv[tid] = lp;
+        cg[tid] = g;
+        ci[tid] = ok ? v : 0;
+    }
+}
+
+}  // namespace
+
+extern "C" int mmtg_decode_gumbel_candidates(const float* logits, long ldl, int V, const long long* seq, long ldseq,
+                                             const int* pos_ptr, int P, int sent, float temperature, float rep_penalty, int nb,
+                                             float* cand_val, int* cand_id, int B, const int* fixed_end, int ngram,
+                                             const unsigned char* lo, const unsigned char* hi, int n_lines, const unsigned* sets,
+                                             int n_sets, const short* set_of, const int* tmpl, const short* class_of,
+                                             const signed char* lead, int distinct, const signed char* src, const float* scores,
+                                             const float* gum, const unsigned* row_seed, float* cand_g, void* stream) {
+    const char* what = "decode_gumbel_candidates";
+    RefrainRule rf;
+    MMTG_REQUIRE(nb >= 1 && nb <= BEAM_MAX, "%s: nb = %d rows per prompt (1..%d)", what, nb, BEAM_MAX);
+    MMTG_REQUIRE(scores, "%s: scores [B] is null", what);
+    MMTG_REQUIRE(gum, "%s: gum [B] is null", what);
+    MMTG_REQUIRE(row_seed, "%s: row_seed [B] is null", what);
+    MMTG_REQUIRE(cand_g, "%s: cand_g [B, nb] is null", what);
+    if (int e = refrain_check(what, V, ldseq, P, sent, fixed_end, ngram, lo, hi, n_lines, sets, n_sets, set_of, tmpl, class_of, lead,
+                              distinct, src, &rf))
+        return e;
+    MMTG_REQUIRE(logits && seq && pos_ptr && cand_val && cand_id && B > 0 && V > 0 && ldl >= V, "%s: bad args", what);
+    MMTG_REQUIRE(temperature > 0.f && rep_penalty > 0.f, "%s: temperature / penalty must be > 0", what);
+    MMTG_REQUIRE(V <= 24000, "%s: vocabulary of %d exceeds the LDS row image (24000)", what, V);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_DECODE, s, 60.0 * B * V, 4.0 * B * V);
+    static bool attr_done = false;
+    if (!attr_done) {
+        if (hipFuncSetAttribute((const void*)gumbel_candidates_kernel<RefrainRule>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024 - 4096) != hipSuccess)
+            MMTG_FAIL(MMTG_ERR_HIP, "%s: cannot raise dynamic LDS", what);
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(gumbel_candidates_kernel<RefrainRule>, dim3(B), dim3(256), select_lds(V, true, rf), s, logits, ldl, V, seq, ldseq,
+                       pos_ptr, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, scores, gum, row_seed, cand_g, rf);
+    MMTG_LAUNCH_CHECK(what);
+    return MMTG_OK;
+}

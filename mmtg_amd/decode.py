@@ -20,8 +20,8 @@ import torch
 
 from . import hip
 from .constraints import (BANNED, GUIDANCE_OFF, MIROSTAT_OFF, WARP_OFF, KeywordTables, LineTables, _check_constraints, check_contrastive, check_groups, check_guidance, check_keywords, check_lines,  # noqa: F401
-                          check_mirostat, check_ngram, check_prefix, check_refrain, check_warp, chosen_mask, keywords_met, refrain_without_keywords,
-                          sequence_scores)   # (the host-side checks keep their names here)
+                          check_mirostat, check_ngram, check_prefix, check_refrain, check_stochastic, check_warp, chosen_mask, keywords_met, refrain_without_keywords,
+                          sequence_scores, stochastic_row_seeds)   # (the host-side checks keep their names here)
 
 _PLACEMENT = {}
 
@@ -1424,6 +1424,131 @@ class ContrastiveDecoder(BeamDecoder):
                                      penalty_alpha=penalty_alpha)
         n, k = self.n_prompts, self.nb
         return ids.view(n, k, -1)[:, 0].clone(), self.total + self.scores.view(n, k)[:, 0]
+
+
+class StochasticBeamDecoder(BeamDecoder):
+    """Stochastic beam search (Kool, van Hoof and Welling 2019, "Stochastic Beams and Where to Find Them") on the beam decoder's
+    machinery: `num_samples` rows per prompt advance in lock step, and a token step that calls the head ends in
+    mmtg_decode_gumbel_candidates and mmtg_decode_gumbel_merge (include/mmtg_hip.h states the rule; constraints.gumbel_candidates
+    and gumbel_merge restate it).
+
+    Every row keeps, beside its beam score, a perturbed value `gum`: its log-probability plus Gumbel noise, conditioned on its
+    parent's.  The candidates offer a row's `num_samples` best perturbed children, the merge keeps the prompt's `num_samples` best
+    overall.  The result is `num_samples` DIFFERENT lyrics per prompt, an exact sample without replacement from the distribution a
+    sampled generation draws from -- the processed logits: penalty, temperature, bans and every line rule, which act in the
+    candidates -- in the order they were drawn: row 0 is an ordinary sample (gum exactly 0), the later rows are what further draws
+    would give were repeats thrown away.  One row is ancestral sampling by the Gumbel-max trick.  The noise is a counter-based hash
+    of (the row's seed word, the position, the id), so a generation is a function of its seed and a replayed graph draws fresh
+    noise at every step."""
+
+    def __init__(self, model, max_prompts, num_samples, max_len=None, use_graph=True, lanes=1):
+        nb, _ = check_stochastic(num_samples, 0)
+        super().__init__(model, max_prompts, nb, max_len=max_len, use_graph=use_graph, lanes=lanes)
+        dev, sent = self.eng.dev, self.eng.sh.msl + 2
+        # allocated once: captured graphs hold their addresses
+        self.gum = torch.zeros(self.B, dtype=torch.float32, device=dev)
+        self.row_seed = torch.zeros(self.B, dtype=torch.int32, device=dev)         # (the library reads the words as uint32)
+        self.cand_g = torch.zeros(self.B, nb, dtype=torch.float32, device=dev)
+        self._no_src = torch.full((self.B, (self.max_len - 1) // sent + 1), -1, dtype=torch.int8, device=dev)      # "no copy line"
+
+    @staticmethod
+    def _refuse(keywords=None, num_beam_groups=1, return_logprobs=False, diversity_penalty=0.0, top_k=1, top_p=0.0, generator=None,
+                min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
+        """What stochastic beam search does not take, refused before any device work with the reason."""
+        if check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff) != WARP_OFF:
+            raise ValueError("stochastic beam search samples from the whole processed distribution: min_p / typical_p / "
+                             "epsilon_cutoff / eta_cutoff would truncate it before the perturbation, which is not built (a sampled "
+                             "generation takes them: GreedyDecoder / generate_samples)")
+        if check_mirostat(mirostat_tau, mirostat_eta)[0] > 0.0:
+            raise ValueError("stochastic beam search has no mirostat_tau / mirostat_eta: Mirostat adapts a cut per row and draw, and "
+                             "the rows here are reordered by the merge (GreedyDecoder / generate_samples take it)")
+        if not (int(top_k) == 1 and float(top_p) == 0.0) or generator is not None:
+            raise ValueError("stochastic beam search takes no sampling top_k / top_p / generator: it samples from the whole "
+                             "processed distribution, and its noise comes from seed=")
+        if keywords is not None:
+            raise ValueError("stochastic beam search takes no keywords=: its rows are samples in draw order, not banks of beams to "
+                             "carry a keyword in (BeamDecoder / generate_beams)")
+        if num_beam_groups != 1 or diversity_penalty:
+            raise ValueError("stochastic beam search has no num_beam_groups / diversity_penalty: a penalty between groups would "
+                             "change the distribution the samples come from")
+        if return_logprobs:
+            raise ValueError("stochastic beam search has no return_logprobs (the merge reorders rows after the selection); score the "
+                             "samples with generate.score_sequences")
+
+    def _select(self, with_head):
+        """The step's last launches: on a step with the head the Gumbel candidates (one entry over the refrain form, whatever rules
+        the generation has or none) and the Gumbel merge; otherwise the merge with null candidates."""
+        eng, sh = self.eng, self.eng.sh
+        temperature, rep, _, _ = self.params
+        fe = self.fixed_end if self.use_fixed else None
+        if with_head:
+            hip.decode_gumbel_candidates(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2, temperature,
+                                         rep, self.nb, self.cand_val, self.cand_id, self.cand_g, self.scores, self.gum, self.row_seed,
+                                         self.B, self._no_src if self.refrain is None else self.refrain, tables=self.lines,
+                                         rhyme=getattr(self, "rhyme", None), tmpl=getattr(self, "tmpl", None), ngram=self.ngram,
+                                         fixed_end=fe)
+        hip.decode_gumbel_merge(self.cand_val if with_head else None, self.cand_id if with_head else None,
+                                self.cand_g if with_head else None, self.scores, self.gum, self.seq, self.keep, self.rows, self.pos, sh.P,
+                                sh.msl + 2, self.nb, self.n_prompts, pos_next=self.pos_next, fixed_end=fe)
+
+    def _graph_key(self, with_head, parity):
+        # (on a head step: which of the refrain form's tables the launch holds, and a real src or none)
+        held = _refrain_key(self) + (("src",) if self.refrain is not None else ()) if with_head else ()
+        return super()._graph_key(with_head, parity) + (("stochastic",) + held,)
+
+    def _step_state(self):
+        """BeamDecoder's state plus gum: without it the warm-up step of a graph capture would merge twice."""
+        return super()._step_state() + [self.gum]
+
+    def describe(self):
+        return "stochastic beam search, %d samples per prompt, " % self.nb + GreedyDecoder.describe(self)
+
+    @torch.no_grad()
+    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
+              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
+              rhyme_distinct=False, return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, keywords=None, refrain_scheme=None,
+              min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1, seed=0, first_prompt=0):
+        """BeamDecoder.begin with the decoder's num_samples rows per prompt, scores and gum at [0, -inf, ...] per prompt, and the rows'
+        seed words written from `seed` (``stochastic_row_seeds``: a word per prompt and beam slot; `first_prompt` is the index of
+        this batch's first prompt in the whole call, so that cutting a call into batches does not change a prompt's noise).
+        keywords=, num_beam_groups > 1, a diversity penalty, return_logprobs=True, sampling top_k / top_p / generator, the four
+        truncation stages and Mirostat are refused (ValueError) before any device work."""
+        StochasticBeamDecoder._refuse(keywords, num_beam_groups, return_logprobs, diversity_penalty, top_k, top_p, generator, min_p,
+                                      typical_p, epsilon_cutoff, eta_cutoff, mirostat_tau, mirostat_eta)
+        _, seed = check_stochastic(self.nb, seed)
+        n_steps = super().begin(batch, length, temperature, repitition_penalty, prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size,
+                                line_lengths=line_lengths, line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme,
+                                rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct, refrain_scheme=refrain_scheme)
+        self.gum.copy_(self.scores)                             # [0, -inf, ...] per prompt
+        words = stochastic_row_seeds(seed, first_prompt, self.n_prompts, self.nb)
+        self.row_seed.copy_(torch.from_numpy(words.view(np.int32)))
+        self.cand_g.fill_(float("-inf"))
+        return n_steps
+
+    @torch.no_grad()
+    def generate(self, batch, length, seed=0, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None,
+                 no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
+                 rhyme_distinct=False, refrain_scheme=None, first_prompt=0, return_logprobs=False, num_beam_groups=1,
+                 diversity_penalty=0.0, keywords=None, top_k=1, top_p=0.0, generator=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0,
+                 eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
+        """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_samples, 1 + length] in
+        GreedyDecoder.generate's column layout, scores [n, num_samples] fp32, gum [n, num_samples] fp32) in draw order: the samples
+        of a prompt are pairwise different, scores are the sums of the processed log-probabilities of their tokens (a beam score's
+        scale), gum their perturbed values (0 for the first, then non-increasing).  A prompt whose rules leave fewer than
+        num_samples different lyrics has dead rows at the end: score and gum -inf.  seed: an integer in 0 .. 2^32 - 1; equal seeds
+        give equal bits.  prefix, no_repeat_ngram_size, line_lengths / line_end_ids, templates, rhyme_scheme / rhyme_classes /
+        rhyme_distinct, refrain_scheme: as BeamDecoder.generate, one per prompt.  What ``begin`` refuses raises ValueError."""
+        StochasticBeamDecoder._refuse(keywords, num_beam_groups, return_logprobs, diversity_penalty, top_k, top_p, generator, min_p,
+                                      typical_p, epsilon_cutoff, eta_cutoff, mirostat_tau, mirostat_eta)
+        ids = GreedyDecoder.generate(self, batch, length, temperature=temperature, repitition_penalty=repitition_penalty,
+                                     use_graph=use_graph, prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size,
+                                     line_lengths=line_lengths, line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme,
+                                     rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct, refrain_scheme=refrain_scheme,
+                                     seed=seed, first_prompt=first_prompt)
+        n, nb = self.n_prompts, self.nb
+        gum = self.gum.view(n, nb).clone()
+        sc = torch.where(gum > float("-inf"), self.scores.view(n, nb), torch.full_like(gum, float("-inf")))
+        return ids.view(n, nb, -1).clone(), sc, gum
 
 
 class GuidedDecoder(GreedyDecoder):

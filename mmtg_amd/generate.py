@@ -17,9 +17,9 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .constraints import (BANNED, GUIDANCE_OFF, WARP_OFF, Constraints, _check_constraints, check_guidance, check_mirostat, check_warp, check_contrastive, check_groups, check_keywords, check_prefix, refrain_without_keywords,
+from .constraints import (BANNED, GUIDANCE_OFF, WARP_OFF, Constraints, _check_constraints, check_guidance, check_mirostat, check_warp, check_contrastive, check_groups, check_keywords, check_prefix, check_stochastic, refrain_without_keywords,
                           sequence_scores)
-from .decode import BeamDecoder, ContrastiveDecoder, GreedyDecoder, GuidedDecoder, _keywords_need_beams
+from .decode import BeamDecoder, ContrastiveDecoder, GreedyDecoder, GuidedDecoder, StochasticBeamDecoder, _keywords_need_beams
 from .data import encode_line_end, encode_prefix, encode_rhyme_classes, encode_template  # noqa: F401  (public: the opening lines / the line-end sets / the line templates / the rhyme classes of generate_samples / generate_beams)
 
 SENT_SLOT = 22  # generate.py:118-121
@@ -486,4 +486,54 @@ def generate_contrastive(model, rows, tokenizer, top_k=4, penalty_alpha=0.6, len
             seq = GreedyDecoder.reference_return(ids[r].tolist(), length, sent=sh.msl + 2)
             out.append((postprocess_tokens(tokenizer.convert_ids_to_tokens(seq)), float(scores[r]))
                        + ((ids[r].tolist(),) if return_ids else ()))
+    return out
+
+
+def generate_stochastic_beams(model, rows, tokenizer, num_samples=4, seed=0, length=None, temperature=1.1, repetition_penalty=1.5,
+                              max_batch=256, prefixes=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None,
+                              rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, refrain_scheme=None, return_ids=False,
+                              return_perturbed=False, keywords=None, num_beam_groups=1, diversity_penalty=0.0, return_logprobs=False,
+                              top_k=1, top_p=0.0, generator=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0,
+                              mirostat_tau=0.0, mirostat_eta=0.1):
+    """num_samples DIFFERENT lyrics per prompt by stochastic beam search on the batched, graph-replayed decoder (StochasticBeamDecoder;
+    Kool, van Hoof and Welling 2019): an exact sample without replacement from the distribution generate_samples draws from at
+    top_k=0, top_p=0 -- the processed logits: repetition penalty, temperature, bans and every line rule -- where generate_samples
+    draws its n_samples independently and may return one lyric several times.  The cost is about that of a num_samples-beam search.
+    Prompts are decoded max_batch // num_samples at a time; a prompt's noise depends on seed, its index among `rows` and the beam
+    slot, not on max_batch.  Every lyric is cut back to what sample_sequence would have returned (GreedyDecoder.reference_return)
+    and post-processed as generate_samples does.  rows: as generate_samples.
+    Returns, per prompt, a list of num_samples tuples in draw order (the first is an ordinary sample): (text, score), score the sum
+    of the processed log-probabilities of the lyric's tokens (a beam score's scale); return_ids=True appends the 1 + length lyric
+    ids (a row score_sequences takes), return_perturbed=True then the sample's perturbed value (0 for the first, non-increasing).
+    A prompt whose rules leave fewer than num_samples different lyrics returns only those it has.
+    prefixes, no_repeat_ngram_size, line_lengths / line_end_ids, templates, rhyme_scheme / rhyme_classes / rhyme_distinct,
+    refrain_scheme: as generate_contrastive -- the rules act on the candidates, so the samples come from what they allow.
+    keywords=, num_beam_groups > 1, a diversity penalty, return_logprobs, sampling top_k / top_p / generator, min_p / typical_p /
+    epsilon_cutoff / eta_cutoff and Mirostat are refused with a ValueError that says why (StochasticBeamDecoder)."""
+    StochasticBeamDecoder._refuse(keywords, num_beam_groups, return_logprobs, diversity_penalty, top_k, top_p, generator, min_p, typical_p,
+                                  epsilon_cutoff, eta_cutoff, mirostat_tau, mirostat_eta)
+    nb, seed = check_stochastic(num_samples, seed)
+    eng = model.engine()
+    sh = eng.sh
+    length = sh.max_seq_length if length is None else length
+    n_prompts = len(rows["topic_ids"]) if isinstance(rows, dict) else len(rows)
+    cons = _check_constraints(prefixes, no_repeat_ngram_size, line_lengths, line_end_ids, n_prompts, length, sh, "%d prompts" % n_prompts,
+                              templates, rhyme_scheme, rhyme_classes, rhyme_distinct, refrain_scheme)
+    per = max(1, min(max_batch // nb, n_prompts))
+    dec = StochasticBeamDecoder(model, per, nb, max_len=length)
+    out, first = [], 0
+    for chunk, c, n in _chunks(_stack_rows(rows), cons, per, eng.dev):
+        ids, scores, gum = dec.generate(chunk, length, seed=seed, temperature=temperature, repitition_penalty=repetition_penalty,
+                                        prefix=c.prefix, no_repeat_ngram_size=c.ngram, line_lengths=c.lines, first_prompt=first)
+        first += per
+        ids, scores, gum = ids.cpu().numpy(), scores.cpu().numpy(), gum.cpu().numpy()
+        for r in range(n):
+            got = []
+            for s in range(nb):
+                if not gum[r, s] > -np.inf:
+                    continue
+                seq = GreedyDecoder.reference_return(ids[r, s].tolist(), length, sent=sh.msl + 2)
+                got.append((postprocess_tokens(tokenizer.convert_ids_to_tokens(seq)), float(scores[r, s]))
+                           + ((ids[r, s].tolist(),) if return_ids else ()) + ((float(gum[r, s]),) if return_perturbed else ()))
+            out.append(got)
     return out

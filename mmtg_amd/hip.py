@@ -153,6 +153,9 @@ _SIGS = {
     "mmtg_decode_beam_merge_kw_fixed": ([_vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp], _i),
     "mmtg_decode_contrastive_sim": ([_i, _vp, _l, _vp, _vp, _f, _vp, _i, _vp, _vp, _vp, _l, _vp, _l, _vp, _i, _i, _i, _vp], _i),
     "mmtg_decode_contrastive_merge": ([_vp, _vp, _vp, _vp, _vp, _f, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
+    "mmtg_decode_gumbel_candidates": ([_vp, _l, _i, _vp, _l, _vp, _i, _i, _f, _f, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i,
+                                      _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "mmtg_decode_gumbel_merge": ([_vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
     "mmtg_decode_guidance": ([_vp, _vp, _l, _i, _f, _vp, _l, _i, _vp], _i),
     "mmtg_decode_mirror": ([_vp, _l, _vp, _i, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
@@ -1282,6 +1285,38 @@ def decode_contrastive_merge(cand_val, cand_id, scores, sim, total, alpha, seq, 
     _check(lib().mmtg_decode_contrastive_merge(_p(cand_val), _p(cand_id), _p(scores), _p(sim), _p(total), float(alpha), _p(seq),
                                                seq.stride(0), _p(keep), keep.stride(0), _p(rows), rows.stride(0), _p(pos), P, sent, int(k),
                                                int(n_prompts), _p(pos_next), _p(fixed_end), _stream()), "decode_contrastive_merge")
+
+
+def _gumbel_state(what, B, nb, scores, gum, row_seed, cand_g):
+    """The per-row state of stochastic beam search: scores / gum fp32 [>= B], row_seed int32 [>= B] (the library reads its words as
+    uint32), cand_g fp32 [>= B, nb] (None for the merge of a step without candidates).  None is passed on: the library rejects it."""
+    for name, t, dtype, n in (("scores", scores, torch.float32, B), ("gum", gum, torch.float32, B), ("row_seed", row_seed, torch.int32, B),
+                              ("cand_g", cand_g, torch.float32, B * nb)):
+        if t is not None and (t.dtype != dtype or t.numel() < n or not t.is_contiguous()):
+            raise ValueError("%s: %s must be a contiguous %s tensor of at least %d entries" % (what, name, dtype, n))
+
+
+def decode_gumbel_candidates(logits, ldl, V, seq, pos, P, sent, temperature, rep_penalty, nb, cand_val, cand_id, cand_g, scores, gum,
+                             row_seed, B, src, tables=None, rhyme=None, tmpl=None, ngram=0, fixed_end=None):
+    """Per row: its nb largest t_v = log_softmax(x)[v] + Gumbel noise, as (cand_id, cand_val = the log-probability, cand_g = the
+    child's perturbed value given the row's own gum[b]) (include/mmtg_hip.h, mmtg_decode_gumbel_candidates).  The rule is the refrain
+    form's: src is required (int8 [rows >= B, n_lines], all -1 without a refrain); every other table may be None."""
+    _gumbel_state("decode_gumbel_candidates", B, nb, scores, gum, row_seed, cand_g)
+    _check(lib().mmtg_decode_gumbel_candidates(_p(logits), ldl, V, _p(seq), seq.stride(0), _p(pos), P, sent, float(temperature),
+                                               float(rep_penalty), int(nb), _p(cand_val), _p(cand_id), B,
+                                               *_rule_tail("_refrain", B, V, fixed_end, ngram, tables, tmpl, sent, rhyme, src),
+                                               _p(scores), _p(gum), _p(row_seed), _p(cand_g), _stream()), "decode_gumbel_candidates")
+
+
+def decode_gumbel_merge(cand_val, cand_id, cand_g, scores, gum, seq, keep, rows, pos, P, sent, nb, n_prompts, pos_next=None,
+                        fixed_end=None):
+    """Per prompt: keep the nb candidates with the largest cand_g (then parent, then rank), reorder seq / keep / rows as the beam merge
+    does, append the ids, scores[b] = scores[parent] + cand_val, gum[b] = cand_g (include/mmtg_hip.h, mmtg_decode_gumbel_merge).
+    cand_val / cand_id / cand_g None: a step without candidates (the beam merge's identity; gum untouched)."""
+    _gumbel_state("decode_gumbel_merge", n_prompts * nb, nb, scores, gum, None, cand_g)
+    _check(lib().mmtg_decode_gumbel_merge(_p(cand_val), _p(cand_id), _p(cand_g), _p(scores), _p(gum), _p(seq), seq.stride(0), _p(keep),
+                                          keep.stride(0), _p(rows), rows.stride(0), _p(pos), P, sent, int(nb), int(n_prompts),
+                                          _p(pos_next), _fixed(fixed_end, n_prompts * nb), _stream()), "decode_gumbel_merge")
 
 
 def decode_guidance(cond, uncond, ldl, V, scale, out, N):
