@@ -13,6 +13,7 @@ only because it never batches; identical at batch 1).
 """
 from __future__ import annotations
 
+import inspect
 import os
 
 import numpy as np
@@ -51,58 +52,113 @@ def select_forms(with_head, prefix, ngram, lines, templates=False, rhymes=False,
             "_groups" + held if groups else held)
 
 
-def _step_forms(dec, with_head):
-    """select_forms' answer for a step of decoder `dec`, and whether mmtg_decode_logprob follows it: (selection form, merge form,
-    logprob).  A decoder without the newer fields (tmpl, rhyme, groups, return_logprobs) is one whose generation does not use them."""
-    return select_forms(with_head, dec.use_fixed, dec.ngram, dec.lines is not None, templates=getattr(dec, "tmpl", None) is not None,
-                        rhymes=getattr(dec, "rhyme", None) is not None, groups=getattr(dec, "groups", 1) > 1,
-                        keywords=getattr(dec, "kw", None) is not None, refrain=getattr(dec, "refrain", None) is not None,
-                        copies=getattr(dec, "copy_step", False)) + (
-        bool(with_head and getattr(dec, "return_logprobs", False)),)
+class StepRules:
+    """What one generation decided about its token steps: built once, in ``begin``, and not changed afterwards.  Every field's default
+    is "off", so ``StepRules()`` is a generation without rules: the plain entries and nothing in the graph key.  What changes from
+    step to step (whether the step calls the head, whether it is a copy step) is an argument of the methods; the rows' state
+    (uniforms, mirostat_mu, tok_lp, gum) and fixed_end, a view each decoder holds since its construction, stay on the decoder.
+
+    prefix: the generation has one: the steps end in the *_fixed selection entries.  ngram: no_repeat_ngram_size.
+    lines: the device tables (lo, hi, sets or None, set_of or None) of line_lengths= / line_end_ids=.  tmpl: the int32 symbol table
+    [B, lines, sent - 2] of templates=.  rhyme: (class_of int16 [V], lead int8 [B, lines], distinct) of rhyme_scheme=.  refrain: src
+    int8 [B, lines] of refrain_scheme=.  Each of them, when not None, ends every step that calls the head in the selection entries
+    of its form (``select_forms``).
+    warp: (min_p, typical_p, epsilon_cutoff, eta_cutoff); any of them on ends every step that calls the head in
+    mmtg_decode_sample_warp.  warp_src: an all -1 src table, what that entry takes without a refrain scheme.
+    mirostat: (tau, eta); tau > 0 ends every step that calls the head in mmtg_decode_sample_mirostat.
+    return_logprobs: every step that calls the head ends in one more launch, mmtg_decode_logprob.
+    groups, diversity_penalty: the beam groups of a diverse beam search.  kw: (phrases int32 [prompts, 8, 4], lens int8 [prompts, 8],
+    K, the longest phrase) of keywords=; not None ends every step that calls the head in the *_kw entries."""
+    __slots__ = ("prefix", "ngram", "lines", "tmpl", "rhyme", "refrain", "warp", "warp_src", "mirostat", "return_logprobs", "groups",
+                 "diversity_penalty", "kw")
+
+    def __init__(self, prefix=False, ngram=0, lines=None, tmpl=None, rhyme=None, refrain=None, warp=WARP_OFF, warp_src=None,
+                 mirostat=MIROSTAT_OFF, return_logprobs=False, groups=1, diversity_penalty=0.0, kw=None):
+        self.prefix, self.ngram, self.lines, self.tmpl, self.rhyme, self.refrain = prefix, ngram, lines, tmpl, rhyme, refrain
+        self.warp, self.warp_src, self.mirostat, self.return_logprobs = warp, warp_src, mirostat, return_logprobs
+        self.groups, self.diversity_penalty, self.kw = groups, diversity_penalty, kw
+
+    def rows(self, a, z):
+        """The record of rows a .. z - 1 of the batch (a lane's): views of the per-row tables, the shared ones (sets, class_of) as
+        they are."""
+        cut = lambda t: None if t is None else t[a:z]                           # noqa: E731
+        lines, rhyme = self.lines, self.rhyme
+        return StepRules(self.prefix, self.ngram, None if lines is None else (lines[0][a:z], lines[1][a:z], lines[2], cut(lines[3])),
+                         cut(self.tmpl), None if rhyme is None else (rhyme[0], rhyme[1][a:z], rhyme[2]), cut(self.refrain), self.warp,
+                         cut(self.warp_src), self.mirostat, self.return_logprobs, self.groups, self.diversity_penalty, self.kw)
+
+    def forms(self, with_head, copies=False):
+        """select_forms' answer for a step of this generation, and whether mmtg_decode_logprob follows it: (selection form, merge
+        form, logprob).  copies: the step skipped the head because every row copies or is held."""
+        return select_forms(with_head, self.prefix, self.ngram, self.lines is not None, templates=self.tmpl is not None,
+                            rhymes=self.rhyme is not None, groups=self.groups > 1, keywords=self.kw is not None,
+                            refrain=self.refrain is not None, copies=copies) + (bool(with_head and self.return_logprobs),)
+
+    def _rhyme_key(self):
+        """What a captured launch of the rhyme form holds by value: end sets or bounds only, the template table or none, a scheme's
+        distinct flag (the "_kw" candidates run the form with line tables but possibly without a scheme: "lines" then)."""
+        return (("lines" if self.rhyme is None else "rhyme", "sets" if self.lines[2] is not None else "bounds")
+                + (("tmpl",) if self.tmpl is not None else ()) + (("distinct",) if self.rhyme is not None and self.rhyme[2] else ()))
+
+    def _refrain_key(self):
+        """What a captured launch of the refrain form holds by value: which of the rhyme form's tables are there at all (line tables
+        with end sets or bounds only, the template table, a rhyme scheme and its distinct flag)."""
+        return (("refrain",) + (("sets" if self.lines[2] is not None else "bounds",) if self.lines is not None else ())
+                + (("tmpl",) if self.tmpl is not None else ())
+                + ((("rhyme",) + (("distinct",) if self.rhyme[2] else ())) if self.rhyme is not None else ()))
+
+    def src_key(self):
+        """The same for an entry over the refrain form that always takes a src (the warp, Mirostat and Gumbel entries): the refrain
+        form's tables, and whether src is a scheme's or the all -1 one."""
+        return self._refrain_key() + (("src",) if self.refrain is not None else ())
+
+    def key(self, with_head, copies=False):
+        """What a decoder's graph key holds behind (with_head, parity, params): the rules as far as select_forms lets them reach
+        this step (a step without the head runs the launches it always ran), each by what the captured launches hold by value."""
+        form, merge, logprob = self.forms(with_head, copies)
+        key = (("prefix",) if self.prefix else ()) + (("ngram", self.ngram) if self.ngram else ())
+        if form in ("_lines", "_tmpl"):
+            key += (form[1:], "sets" if self.lines[2] is not None else "bounds")
+        if form == "_rhyme":
+            key += self._rhyme_key()
+        if form == "_refrain":
+            key += self._refrain_key()
+        mirostat = with_head and self.mirostat[0] > 0.0
+        if with_head and (mirostat or self.warp != WARP_OFF):       # (the four cuts by value, whichever of the two entries runs)
+            key += (("warp",) + self.warp,) + self.src_key()
+        if mirostat:                                                # (tau and eta by value; the state's address never changes)
+            key += (("mirostat",) + self.mirostat,)
+        if logprob:
+            key += ("logprob",)
+        if merge.startswith("_groups"):     # (the grouped merge holds both by value)
+            key += (("groups", self.groups, float(self.diversity_penalty)),)
+        if form == "_kw":                   # (K and the phrase bound by value; then what the rhyme form under them holds by value)
+            key += (("kw", self.kw[2]), ("cap", self.kw[3]))
+            if self.lines is not None:
+                key += self._rhyme_key()
+        return key
+
+    def tail(self, fixed_end, entry="form", spare=None):
+        """The trailing keyword arguments of the hip selection and candidate calls; fixed_end: the decoder's own view, passed on with
+        a prefix only.  entry "form": an entry select_forms names -- it takes the refrain table as refrain= (and reads it in the
+        "_refrain" form only).  "src": an entry over the refrain form that always takes a src -- the scheme's table, or without a
+        scheme an all -1 one: `spare` if given, else warp_src.  "kw": the keyword candidates, which run the rhyme form -- line tables
+        without a scheme get `spare`, a rhyme triple whose lead table names no leader."""
+        kw = {"fixed_end": fixed_end if self.prefix else None, "ngram": self.ngram, "tables": self.lines, "tmpl": self.tmpl,
+              "rhyme": self.rhyme}
+        if entry == "form":
+            kw["refrain"] = self.refrain
+        elif entry == "src":
+            kw["src"] = self.refrain if self.refrain is not None else self.warp_src if spare is None else spare
+        elif self.rhyme is None and self.lines is not None:
+            kw["rhyme"] = spare
+        return kw
 
 
 def _keywords_need_beams(keywords):
     if keywords is not None:
         raise ValueError("keywords= needs beams: a lyric that contains given words is found by a search over several hypotheses "
                          "(BeamDecoder / generate_beams), not by greedy decoding or sampling")
-
-
-def _rhyme_key(dec):
-    """What a captured launch of the rhyme form holds by value, for decoder `dec`'s graph key: end sets or bounds only, the template
-    table or none, a scheme's distinct flag (the "_kw" candidates run the form with line tables but possibly without a scheme:
-    "lines" then)."""
-    rhyme = getattr(dec, "rhyme", None)
-    key = ("lines" if rhyme is None else "rhyme", "sets" if dec.lines[2] is not None else "bounds")
-    if getattr(dec, "tmpl", None) is not None:
-        key += ("tmpl",)
-    if rhyme is not None and rhyme[2]:
-        key += ("distinct",)
-    return key
-
-
-def _refrain_key(dec):
-    """What a captured launch of the refrain form holds by value, for decoder `dec`'s graph key: which of the rhyme form's tables
-    are there at all (line tables with end sets or bounds only, the template table, a rhyme scheme and its distinct flag)."""
-    key = ("refrain",)
-    if dec.lines is not None:
-        key += ("sets" if dec.lines[2] is not None else "bounds",)
-    if getattr(dec, "tmpl", None) is not None:
-        key += ("tmpl",)
-    rhyme = getattr(dec, "rhyme", None)
-    if rhyme is not None:
-        key += ("rhyme",) + (("distinct",) if rhyme[2] else ())
-    return key
-
-
-def _warp_on(dec):
-    """Whether decoder `dec`'s generation has any of min_p / typical_p / epsilon_cutoff / eta_cutoff on (a decoder without the field:
-    none)."""
-    return getattr(dec, "warp", WARP_OFF) != WARP_OFF
-
-
-def _mirostat_on(dec):
-    """Whether decoder `dec`'s generation runs Mirostat (mirostat_tau > 0; a decoder without the field: no)."""
-    return getattr(dec, "mirostat", MIROSTAT_OFF)[0] > 0.0
 
 
 def _fill(buf, src, fill, axis):
@@ -278,44 +334,26 @@ class GreedyDecoder:
         self.graphs = {}
         self.params = None
         self.rows = None            # the ancestry table of beam search (BeamDecoder); None: row b attends over its own cache row
-        self.use_fixed = False      # this generation has a prefix: the step ends in the *_fixed selection entries
+        # what the generation decided about its steps (``begin`` builds it once; a lane holds the record of its own rows)
+        self.rules = StepRules()
         self.min_fixed = 0          # min over rows of fixed_end (a step below it appends nothing: no head needed)
-        self.ngram = 0              # no_repeat_ngram_size: > 0 ends every step that calls the head in the *_ngram selection entries
-        # line constraints (line_lengths= / line_end_ids=): the device tables (lo, hi, sets or None, set_of or None) of this
-        # decoder's rows; not None ends every step that calls the head in the *_lines selection entries
-        self.lines = None
-        self._line_buf = None       # (lo, hi, set_of) [B, lines of max_len] and the growing `sets` buffer: fixed addresses for the graphs
-        # line templates (templates=): this decoder's rows of the int32 symbol table [B, lines of max_len, sent - 2]; not None ends
-        # every step that calls the head in the *_tmpl selection entries
-        self.tmpl = None
-        self._tmpl_buf = None
-        # rhyme scheme (rhyme_scheme=): (class_of int16 [V], this decoder's rows of lead int8 [B, lines of max_len], distinct); not None
-        # ends every step that calls the head in the *_rhyme selection entries
-        self.rhyme = None
-        self._rhyme_buf = None
-        # refrain scheme (refrain_scheme=): this decoder's rows of src int8 [B, lines of max_len]; not None ends every step that calls
-        # the head in the *_refrain selection entries.  copy_cols (host, bool [1 + length], the parent's): the lyric columns at which
-        # every row is held by its prefix or copies, so the step skips the head; copy_step: the step being run is one of those (it ends
-        # in mmtg_decode_select_refrain with null logits); skipped_steps counts them per generation
-        self.refrain = None
-        self._refrain_buf = None
+        # the rules' device tables, all rows, each allocated once by its _upload_*: captured graphs hold the addresses.  _line_buf:
+        # (lo, hi, set_of) [B, lines of max_len] and the growing `sets` buffer; _warp_buf: the all -1 src of StepRules.warp_src
+        self._line_buf = self._tmpl_buf = self._rhyme_buf = self._refrain_buf = self._warp_buf = None
+        # copy_cols (host, bool [1 + length], the parent's): the lyric columns at which every row is held by its prefix or copies
+        # under the refrain scheme, so the step skips the head; copy_step: the step being run is one of those (it ends in
+        # mmtg_decode_select_refrain with null logits); skipped_steps counts them per generation
         self.copy_cols = None
         self.copy_step = False
         self.skipped_steps = 0
-        # min_p / typical_p / epsilon_cutoff / eta_cutoff: the four cuts; any of them on ends every step that calls the head in
-        # mmtg_decode_sample_warp.  warp_src: this decoder's rows of an all -1 src table, what that entry takes without a refrain scheme
-        self.warp = WARP_OFF
-        self.warp_src = None
-        self._warp_buf = None
-        # Mirostat (mirostat_tau=, mirostat_eta=): (tau, eta); tau > 0 ends every step that calls the head in mmtg_decode_sample_mirostat.
-        # mirostat_mu: the rows' state, fp32 [B] in bits, this decoder's rows (allocated once: captured graphs hold its address; None
+        # Mirostat's state of the rows, fp32 [B] in bits, this decoder's rows (allocated once: captured graphs hold its address; None
         # until a generation asks for it); the selection kernel updates it on the columns a row draws
-        self.mirostat = MIROSTAT_OFF
         self.mirostat_mu = None
-        # token log-probabilities (return_logprobs=): fp32 [B, 1 + max_len], this decoder's rows; on, every step that calls the head
-        # ends in one more launch, mmtg_decode_logprob, which writes the step's column (allocated once: captured graphs hold its address)
-        self.return_logprobs = False
+        # token log-probabilities (return_logprobs=): fp32 [B, 1 + max_len], this decoder's rows; mmtg_decode_logprob writes the step's
+        # column (allocated once: captured graphs hold its address)
         self.tok_lp = None
+        # what _select / _logprob read: the step's own logits over every row (GuidedDecoder: the guided scores, its prompts' rows)
+        self.select_rows, self.select_logits = B, None if self.children else self.logits
 
     def _conv1d(self, x, wkey, out, **kw):
         # bf16: Engine._fwd routes Conv1D weights through their [out,in] copies (NT layout), which is
@@ -398,42 +436,35 @@ class GreedyDecoder:
         ones (n possibly 0) add the line-length bounds and line-end sets of include/mmtg_hip.h, the *_tmpl ones the line templates,
         the *_rhyme ones (templates or none) the rhyme scheme, the *_refrain ones (any of these or none) the copy lines -- also on a
         step that skipped the head because every row copies or is held (null logits: the copies and nothing else are written)."""
-        sh = self.eng.sh
+        sh, rules = self.eng.sh, self.rules
         temperature, rep, top_k, top_p = self.params
-        tmpl, rhyme = getattr(self, "tmpl", None), getattr(self, "rhyme", None)
-        form = _step_forms(self, with_head)[0]
-        # (the step's own logits over every row; GuidedDecoder selects for its prompts' rows only, from the guided scores)
-        B = getattr(self, "select_rows", self.B)
-        logits, ldl, V = (getattr(self, "select_logits", self.logits), self.eng.layout.Vpad, min(sh.V, 13317)) if with_head else (None, 0, 0)
+        form = rules.forms(with_head, self.copy_step)[0]
+        B = self.select_rows
+        logits, ldl, V = (self.select_logits, self.eng.layout.Vpad, min(sh.V, 13317)) if with_head else (None, 0, 0)
         if form == "_refrain":              # (the tables' shapes are held against the cut with or without logits)
             V = min(sh.V, 13317)
         # stochastic: the draw of each position reads its row of the pre-filled uniforms
         sampling = (top_k, top_p, self.uniforms) if with_head and not (top_k == 1 and top_p == 0.0) else None
-        if with_head and _mirostat_on(self):    # Mirostat behind the four cuts (on or off): the warp entry's launch plus the rows' state
-            hip.decode_sample_mirostat(logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, top_k, top_p, self.warp,
-                                       self.mirostat, self.mirostat_mu, self.uniforms, B,
-                                       self.warp_src if self.refrain is None else self.refrain, tables=self.lines, rhyme=rhyme, tmpl=tmpl,
-                                       ngram=self.ngram, pos_next=self.pos_next, fixed_end=self.fixed_end if self.use_fixed else None)
+        if with_head and rules.mirostat[0] > 0.0:   # Mirostat behind the four cuts (on or off): the warp entry's launch plus the rows' state
+            hip.decode_sample_mirostat(logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, top_k, top_p, rules.warp,
+                                       rules.mirostat, self.mirostat_mu, self.uniforms, B, pos_next=self.pos_next,
+                                       **rules.tail(self.fixed_end, "src"))
             return
-        if with_head and _warp_on(self):    # min_p / typical_p / epsilon_cutoff / eta_cutoff: one entry over the refrain form, whatever the rules
-            hip.decode_sample_warp(logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, top_k, top_p, self.warp,
-                                   self.uniforms, B, self.warp_src if self.refrain is None else self.refrain, tables=self.lines,
-                                   rhyme=rhyme, tmpl=tmpl, ngram=self.ngram, pos_next=self.pos_next,
-                                   fixed_end=self.fixed_end if self.use_fixed else None)
+        if with_head and rules.warp != WARP_OFF:    # min_p / typical_p / epsilon_cutoff / eta_cutoff: one entry over the refrain form, whatever the rules
+            hip.decode_sample_warp(logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, top_k, top_p, rules.warp,
+                                   self.uniforms, B, pos_next=self.pos_next, **rules.tail(self.fixed_end, "src"))
             return
         hip._select(form, logits, ldl, V, self.seq, self.pos, sh.P, sh.msl + 2, temperature, rep, B, self.pos_next, sampling,
-                    fixed_end=self.fixed_end if self.use_fixed else None, ngram=self.ngram, tables=self.lines, tmpl=tmpl,
-                    **({} if rhyme is None else {"rhyme": rhyme}), **({"refrain": self.refrain} if form == "_refrain" else {}))
+                    **rules.tail(self.fixed_end))
 
     def _logprob(self, with_head):
         """With return_logprobs, after the selection of a step that called the head: tok_lp[b, pos + 1 - P] = log_softmax of the row's
         raw logits at the id column pos + 1 now holds (include/mmtg_hip.h, mmtg_decode_logprob).  A node of its own behind the
         selection, on the same stream: it reads self.pos, which the selection leaves alone, and the selection kernels stay what they
         were.  Off, nothing is launched."""
-        if _step_forms(self, with_head)[2]:
+        if self.rules.forms(with_head, self.copy_step)[2]:
             sh = self.eng.sh
-            hip.decode_logprob(self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, self.tok_lp,
-                               getattr(self, "select_rows", self.B))
+            hip.decode_logprob(self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, self.tok_lp, self.select_rows)
 
     def _upload_lines(self, tables):
         """The line tables into this decoder's device buffers (allocated once, so captured graphs keep their addresses; a `sets`
@@ -719,34 +750,13 @@ class GreedyDecoder:
         g.replay()
 
     def _graph_key(self, with_head, parity):
-        """What the step's launches depend on: the settings, and the constraints as far as select_forms lets them reach this step
-        (a step without the head runs the launches it always ran)."""
-        key = (with_head, parity, self.params) + (("prefix",) if self.use_fixed else ()) + (("ngram", self.ngram) if self.ngram else ())
-        form, merge, logprob = _step_forms(self, with_head)
-        if form in ("_lines", "_tmpl"):
-            key += (form[1:], "sets" if self.lines[2] is not None else "bounds")
-        if form == "_rhyme":
-            key += _rhyme_key(self)
-        if form == "_refrain":
-            key += _refrain_key(self)
-        if with_head and (_warp_on(self) or _mirostat_on(self)):    # (the four cuts by value; which of the refrain form's tables the launch holds; a real src or none)
-            key += (("warp",) + self.warp,) + _refrain_key(self) + (("src",) if getattr(self, "refrain", None) is not None else ())
-        if with_head and _mirostat_on(self):                        # (tau and eta by value; the state's address never changes)
-            key += (("mirostat",) + self.mirostat,)
-        if logprob:
-            key += ("logprob",)
-        if merge.startswith("_groups"):     # (the grouped merge holds both by value)
-            key += (("groups", self.groups, float(self.diversity_penalty)),)
-        if form == "_kw":                   # (K and the phrase bound by value; then what the rhyme form under them holds by value)
-            key += (("kw", self.kw[2]), ("cap", self.kw[3]))
-            if self.lines is not None:
-                key += _rhyme_key(self)
-        return key
+        """What the step's launches depend on: the settings, and the rules as far as they reach this step (StepRules.key)."""
+        return (with_head, parity, self.params) + self.rules.key(with_head, self.copy_step)
 
     def _step_state(self):
         """What a token step changes besides the caches' slot `pos` (rewound around the warm-up step of a graph capture).  With
         Mirostat that includes the rows' mu: without it the first step of every new graph key would update mu twice."""
-        return [self.pos_all, self.seq, self.keep] + ([self.mirostat_mu] if _mirostat_on(self) else [])
+        return [self.pos_all, self.seq, self.keep] + ([self.mirostat_mu] if self.rules.mirostat[0] > 0.0 else [])
 
     # ------------------------------------------------------------------ public
     def describe(self):
@@ -772,7 +782,7 @@ class GreedyDecoder:
     def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
               no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
               rhyme_distinct=False, return_logprobs=False, keywords=None, refrain_scheme=None, min_p=0.0, typical_p=1.0,
-              epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
+              epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1, _search=None):
         """Everything of a generation that happens once: the settings, the uniforms of a stochastic run, fresh weight copies /
         LayerNorm folds, the experience encoder, the prompt (prefilled in one batched pass: ``first_pos`` = P afterwards) and the
         reset position.  Returns the end position n; ``step_at(pos)`` for pos = first_pos .. n - 1 then runs the token steps (``generate`` does both; tools/decode_lanes_threads.py drives
@@ -837,7 +847,10 @@ class GreedyDecoder:
         generation without the arguments, and allocates nothing.
 
         keywords: refused here (ValueError).  A lyric that contains given words needs a search, and greedy decoding and sampling
-        follow one path: BeamDecoder takes keywords=."""
+        follow one path: BeamDecoder takes keywords=.
+
+        _search: the StepRules fields a search decoder decides (BeamDecoder.begin: groups, diversity_penalty, kw), for the one
+        record built here."""
         _keywords_need_beams(keywords)
         warp = check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
         mirostat = check_mirostat(mirostat_tau, mirostat_eta)
@@ -877,11 +890,6 @@ class GreedyDecoder:
             if self.tok_lp is None:
                 self.tok_lp = torch.zeros(B, 1 + self.max_len, dtype=torch.float32, device=eng.dev)
             self.tok_lp.zero_()
-        # the generation's constraints, on the decoder and its lanes: a lane's _select reads its own flags, its slice of fixed_end
-        # (a view since construction) and its rows of the line tables (the sets are shared)
-        bare = cons.lines is not None and cons.lines.bare       # (tables made for a refrain alone: no line rule to upload)
-        lines, tmpl, rhyme = self._upload_lines(None if bare else cons.lines), self._upload_templates(cons.lines), self._upload_rhyme(cons.lines)
-        refrain = self._upload_refrain(cons.lines)
         self.copy_cols = self._copy_columns(cons.lines, pre, length, return_logprobs)
         if miro_on:
             if self.mirostat_mu is None:
@@ -890,20 +898,21 @@ class GreedyDecoder:
         if (warp != WARP_OFF or miro_on) and self._warp_buf is None:         # the "no copy line" src of a generation without a refrain scheme
             self._warp_buf = torch.full((B, (self.max_len - 1) // (sh.msl + 2) + 1), -1, dtype=torch.int8, device=eng.dev)
         self.skipped_steps = 0
-        for i, d in enumerate([self] + self.children):
-            a, z = (0, B) if d is self else ((i - 1) * d.B, i * d.B)
-            d.use_fixed, d.ngram = pre is not None, cons.ngram
-            d.lines = None if lines is None else tuple(t if t is None or t is lines[2] else t[a:z] for t in lines)
-            d.tmpl = None if tmpl is None else tmpl[a:z]
-            d.rhyme = None if rhyme is None else (rhyme[0], rhyme[1][a:z], rhyme[2])
-            d.refrain, d.copy_step = None if refrain is None else refrain[a:z], False
-            d.warp, d.warp_src = warp, None if self._warp_buf is None else self._warp_buf[a:z]
-            d.mirostat = mirostat if miro_on else MIROSTAT_OFF
-            if miro_on and d is not self:
-                d.mirostat_mu = self.mirostat_mu[a:z]
-            d.return_logprobs = bool(return_logprobs)
-            if return_logprobs and d is not self:
-                d.tok_lp = self.tok_lp[a:z]
+        # the generation's rules, on the decoder and its lanes: a lane's _select reads the record of its own rows (the sets are shared),
+        # its slice of fixed_end (a view since construction) and its rows of the state
+        bare = cons.lines is not None and cons.lines.bare       # (tables made for a refrain alone: no line rule to upload)
+        self.rules = StepRules(prefix=pre is not None, ngram=cons.ngram, lines=self._upload_lines(None if bare else cons.lines),
+                               tmpl=self._upload_templates(cons.lines), rhyme=self._upload_rhyme(cons.lines),
+                               refrain=self._upload_refrain(cons.lines), warp=warp, warp_src=self._warp_buf,
+                               mirostat=mirostat if miro_on else MIROSTAT_OFF, return_logprobs=bool(return_logprobs), **(_search or {}))
+        self.copy_step = False
+        for i, ch in enumerate(self.children):
+            a, z = i * ch.B, (i + 1) * ch.B
+            ch.rules, ch.copy_step = self.rules.rows(a, z), False
+            if miro_on:
+                ch.mirostat_mu = self.mirostat_mu[a:z]
+            if return_logprobs:
+                ch.tok_lp = self.tok_lp[a:z]
         self.min_fixed = 0
         if pre is not None:
             lens = [len(p) for p in pre]
@@ -968,7 +977,7 @@ class GreedyDecoder:
         sh = self.eng.sh
         j = pos + 1 - sh.P                                      # lyric index appended after this step
         forced = j < 1 or (j > 1 and (j + 1) % (sh.msl + 2) in (0, 1))
-        if self.use_fixed and pos + 1 < self.min_fixed and not self.return_logprobs:
+        if self.rules.prefix and pos + 1 < self.min_fixed and not self.rules.return_logprobs:
             forced = True                                       # every row's column pos + 1 is a prefix id: no model call
         copies = bool(not forced and self.copy_cols is not None and 0 <= j < len(self.copy_cols) and self.copy_cols[j])
         if copies:                                              # every row copies or is held: no model call, the selection copies
@@ -1017,17 +1026,14 @@ class GreedyDecoder:
         mirostat_tau / mirostat_eta: Mirostat v2 (``begin``), llama.cpp's arguments of those names: mirostat_tau=2.0 holds the observed
         surprise of the text near 2 bits per drawn token by adapting the cut after every draw, at learning rate mirostat_eta.  It acts
         last, so top_k=0, top_p=0 leaves the choice to it.  Afterwards ``mirostat_mu`` holds every row's state.
-        begin_kw: what a subclass's ``begin`` takes beyond these (BeamDecoder: the beam groups); ``begin`` here takes none."""
-        n_steps = self.begin(*self._begin_lead(batch, length), temperature, repitition_penalty, top_k, top_p, generator, prefix=prefix,
-                             no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths, line_end_ids=line_end_ids,
-                             templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct,
-                             **({"return_logprobs": True} if return_logprobs else {}),
-                             **({} if refrain_scheme is None else {"refrain_scheme": refrain_scheme}),
-                             **({} if (min_p, typical_p, epsilon_cutoff, eta_cutoff) == WARP_OFF else
-                                {"min_p": min_p, "typical_p": typical_p, "epsilon_cutoff": epsilon_cutoff, "eta_cutoff": eta_cutoff}),
-                             **({} if mirostat_tau == 0 and mirostat_eta == MIROSTAT_OFF[1] else
-                                {"mirostat_tau": mirostat_tau, "mirostat_eta": mirostat_eta}),
-                             **begin_kw)
+        begin_kw: what a subclass's ``begin`` takes beyond these (BeamDecoder: the beam groups); ``begin`` here takes none.  Every
+        argument above goes to ``begin`` by name, at its default too: a search decoder's ``begin`` runs them through its refusals."""
+        n_steps = self.begin(*self._begin_lead(batch, length), temperature=temperature, repitition_penalty=repitition_penalty, top_k=top_k,
+                             top_p=top_p, generator=generator, prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size,
+                             line_lengths=line_lengths, line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme,
+                             rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct, return_logprobs=return_logprobs,
+                             refrain_scheme=refrain_scheme, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff,
+                             eta_cutoff=eta_cutoff, mirostat_tau=mirostat_tau, mirostat_eta=mirostat_eta, **begin_kw)
         eng, sh = self.eng, self.eng.sh
         saved_mode = self.use_graph
         if use_graph is not None:
@@ -1068,6 +1074,44 @@ class GreedyDecoder:
         return list(ids_row[:1 + last_call])
 
 
+# ---------------------------------------------------------------------- what a search refuses
+# The search decoders' begin / generate name what they add or use and take the rest as **settings.  What a search cannot honour is
+# refused by a table, (names, whether their values are all "off", the reason) per row, before any device work and before anything of
+# `self` is read; the rest is forwarded towards GreedyDecoder's explicit signatures, which document the arguments.
+_SETTINGS = frozenset(inspect.signature(GreedyDecoder.generate).parameters) - {"self", "batch", "length", "teacher", "tap", "begin_kw"}
+_WARP_NAMES = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
+_MIROSTAT_NAMES = ("mirostat_tau", "mirostat_eta")
+_DRAW_NAMES = ("top_k", "top_p", "generator")
+
+
+def _no_draw(top_k=1, top_p=0.0, generator=None):
+    return int(top_k) == 1 and float(top_p) == 0.0 and generator is None
+
+
+def _no_warp(**cuts):
+    return check_warp(**cuts) == WARP_OFF
+
+
+def _no_mirostat(**tau_eta):
+    return check_mirostat(**tau_eta)[0] == 0.0        # (eta alone turns nothing on)
+
+
+def _run_refusals(table, settings):
+    """`settings` through a search decoder's refusal table: TypeError for a name that neither a row of the table nor
+    GreedyDecoder.generate knows (as Python's own check of an explicit signature), ValueError with the row's reason for a value that
+    is not "off" (an out-of-range value is said first, by check_warp / check_mirostat).  Returns the settings without the table's
+    names -- they are at their defaults -- for the caller to forward."""
+    named = {k for names, _, _ in table for k in names}
+    for k in settings:
+        if k not in named and k not in _SETTINGS:
+            raise TypeError("got an unexpected keyword argument %r" % k)
+    for names, off, reason in table:
+        given = {k: settings[k] for k in names if k in settings}
+        if given and not off(**given):
+            raise ValueError(reason)
+    return {k: v for k, v in settings.items() if k not in named}
+
+
 class BeamDecoder(GreedyDecoder):
     """Beam search on the KV-cached, graph-replayed token step: `num_beams` rows per prompt advance in lock step, and the step's
     last two launches (mmtg_decode_beam_candidates, mmtg_decode_beam_merge) replace decode_select.
@@ -1104,40 +1148,32 @@ class BeamDecoder(GreedyDecoder):
         self.scores = torch.zeros(self.B, dtype=torch.float32, device=dev)
         self.cand_val = torch.zeros(self.B, nb, dtype=torch.float32, device=dev)
         self.cand_id = torch.zeros(self.B, nb, dtype=torch.int32, device=dev)
-        self.groups, self.diversity_penalty = 1, 0.0
-        # keywords (keywords=): (phrases int32 [prompts, 8, 4], lens int8 [prompts, 8], K, the longest phrase) on the device; not
-        # None ends every step that calls the head in the *_kw entries, over the nb + K wide candidate tables of _kw_cand
-        self.kw = None
-        self._kw_buf = None         # the two tables, the wide candidate storage and the rhyme form's empty tables: allocated once
+        # keywords=: the two tables of StepRules.kw, the wide candidate storage and the rhyme form's empty tables: allocated once
+        self._kw_buf = None
         self._kw_cand = None        # (cand_val, cand_id, cand_bank) [B, nb + K]: views of that storage
 
     def _select(self, with_head):
         """The step's last two launches, through the entries select_forms names: the bans (and a full line's PAD, offered as sticky
         PAD is) act in the candidates; the merge is the prefix-aware one or the plain one -- with beam groups, on a step with the
         head, the grouped one of either (the candidates do not know of groups)."""
-        sh = self.eng.sh
+        sh, rules = self.eng.sh, self.rules
         temperature, rep, _, _ = self.params
-        tmpl, rhyme = getattr(self, "tmpl", None), getattr(self, "rhyme", None)
-        cand, merge, _ = _step_forms(self, with_head)
-        fe = self.fixed_end if self.use_fixed else None
+        cand, merge, _ = rules.forms(with_head)
+        fe = self.fixed_end if rules.prefix else None
         if cand == "_kw":
             # the rhyme form serves every rule or none; line tables without a scheme get a lead table that names no leader
             cv, ci, cb = self._kw_cand
             hip.decode_beam_candidates_kw(self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2,
-                                          temperature, rep, self.nb, cv, ci, cb, self.B, self.kw, tables=self.lines, tmpl=tmpl,
-                                          rhyme=(rhyme if rhyme is not None else self._kw_buf[3]) if self.lines is not None else None,
-                                          ngram=self.ngram, fixed_end=fe)
+                                          temperature, rep, self.nb, cv, ci, cb, self.B, rules.kw, **rules.tail(self.fixed_end, "kw", self._kw_buf[3]))
             hip.decode_beam_merge_kw(cv, ci, cb, self.scores, self.seq, self.keep, self.rows, self.pos, sh.P, sh.msl + 2, self.nb,
-                                     self.n_prompts, self.kw[2], fixed_end=fe, pos_next=self.pos_next)
+                                     self.n_prompts, rules.kw[2], fixed_end=fe, pos_next=self.pos_next)
             return
         if with_head:
             hip._beam_candidates(cand, self.logits, self.eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2, temperature,
-                                 rep, self.nb, self.cand_val, self.cand_id, self.B, fixed_end=fe, ngram=self.ngram, tables=self.lines,
-                                 tmpl=tmpl, **({} if rhyme is None else {"rhyme": rhyme}),
-                                 **({"refrain": self.refrain} if cand == "_refrain" else {}))
+                                 rep, self.nb, self.cand_val, self.cand_id, self.B, **rules.tail(self.fixed_end))
         hip._beam_merge(merge, self.cand_val if with_head else None, self.cand_id if with_head else None, self.scores, self.seq, self.keep,
                         self.rows, self.pos, sh.P, sh.msl + 2, self.nb, self.n_prompts, self.pos_next, fixed_end=fe,
-                        groups=getattr(self, "groups", 1), diversity_penalty=getattr(self, "diversity_penalty", 0.0))
+                        groups=rules.groups, diversity_penalty=rules.diversity_penalty)
 
     def _step_state(self):
         return super()._step_state() + [self.rows, self.scores]
@@ -1170,40 +1206,36 @@ class BeamDecoder(GreedyDecoder):
         if keywords is not None and G > 1:
             raise ValueError("keywords= and num_beam_groups > 1 both allocate the beams: ask for one of them")
 
-    @staticmethod
-    def _no_logprobs(return_logprobs):
-        """Beam search keeps no token log-probabilities: the merge reorders the rows after the selection, and tok_lp would have to be
-        reordered with seq.  Beams are scored afterwards, through generate.score_sequences."""
-        if return_logprobs:
-            raise ValueError("beam search has no return_logprobs (the merge reorders rows after the selection); score the beams "
-                             "with generate.score_sequences")
+    # Beam search keeps no token log-probabilities: the merge reorders the rows after the selection, and tok_lp would have to be
+    # reordered with seq; beams are scored afterwards, through generate.score_sequences.  A search is deterministic: the truncation
+    # stages of a draw and Mirostat (GreedyDecoder.begin) have nothing to act on.
+    _REFUSED = (
+        (("return_logprobs",), lambda return_logprobs: not return_logprobs,
+         "beam search has no return_logprobs (the merge reorders rows after the selection); score the beams with generate.score_sequences"),
+        (_WARP_NAMES, _no_warp,
+         "a search draws nothing: min_p / typical_p / epsilon_cutoff / eta_cutoff shape the distribution a sampled generation draws from "
+         "(GreedyDecoder / generate_samples), and no sampling runs inside a beam or contrastive search"),
+        (_MIROSTAT_NAMES, _no_mirostat,
+         "a search draws nothing: mirostat_tau / mirostat_eta steer the surprise of what a sampled generation draws (GreedyDecoder / "
+         "generate_samples), and no sampling runs inside a beam or contrastive search"))
 
-    @staticmethod
-    def _no_warp(min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
-        """A search is deterministic: the truncation stages of a draw (GreedyDecoder.begin) have nothing to act on."""
-        if check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff) != WARP_OFF:
-            raise ValueError("a search draws nothing: min_p / typical_p / epsilon_cutoff / eta_cutoff shape the distribution a sampled "
-                             "generation draws from (GreedyDecoder / generate_samples), and no sampling runs inside a beam or contrastive search")
-
-    @staticmethod
-    def _no_mirostat(mirostat_tau=0.0, mirostat_eta=0.1):
-        """As ``_no_warp``: Mirostat adapts the cut of a draw, and a search draws nothing."""
-        if check_mirostat(mirostat_tau, mirostat_eta)[0] > 0.0:
-            raise ValueError("a search draws nothing: mirostat_tau / mirostat_eta steer the surprise of what a sampled generation "
-                             "draws (GreedyDecoder / generate_samples), and no sampling runs inside a beam or contrastive search")
+    @classmethod
+    def _refuse(cls, **settings):
+        """What this search does not take, refused with the reason (``_run_refusals`` over the class's table); returns the rest."""
+        return _run_refusals(cls._REFUSED, settings)
 
     def describe(self):
         return "%d beams per prompt, " % self.nb + super().describe()
 
     @torch.no_grad()
-    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
-              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
-              rhyme_distinct=False, return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, keywords=None, refrain_scheme=None,
-              min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
+    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, prefix=None, no_repeat_ngram_size=0, line_lengths=None,
+              line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, refrain_scheme=None,
+              num_beam_groups=1, diversity_penalty=0.0, keywords=None, **settings):
         """GreedyDecoder.begin on every prompt replicated over its beams (encoder inputs, prompt prefill, the prefix, the line
         constraints, the templates and the rhyme scheme: one per prompt; every beam finds its leader's rhyme in its own history), the
         ancestry table as the identity and the beam scores at [0, -inf, ...] per prompt.  Scores only accumulate at the free positions
-        after a prompt's prefix.  return_logprobs=True raises ValueError (``_no_logprobs``).
+        after a prompt's prefix.  settings: whatever else GreedyDecoder.begin takes, through ``_refuse``: return_logprobs=True raises
+        ValueError, and so do min_p / typical_p / epsilon_cutoff / eta_cutoff and mirostat_tau at anything but their defaults.
 
         num_beam_groups / diversity_penalty (``check_groups``; the rule's home is include/mmtg_hip.h): G > 1 splits a prompt's beams
         into G groups of s = num_beams / G rows, each started at [0, -inf, ...] and searched on its own; at every step that calls
@@ -1223,13 +1255,10 @@ class BeamDecoder(GreedyDecoder):
         history.  A copy is offered by the candidates the way a template's given id is (mmtg_decode_beam_candidates_refrain), so the
         merge and the scores are untouched -- and so every copy column still calls the head: head skipping is GreedyDecoder's, the
         known remainder here.  Beam groups need nothing.  keywords= together with a scheme is a ValueError: the one combination
-        left out.
-
-        min_p / typical_p / epsilon_cutoff / eta_cutoff: refused at anything but their defaults (``_no_warp``); mirostat_tau > 0
-        likewise (``_no_mirostat``)."""
-        self._no_logprobs(return_logprobs)
-        self._no_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
-        self._no_mirostat(mirostat_tau, mirostat_eta)
+        left out."""
+        settings = BeamDecoder._refuse(**settings)
+        for k in _DRAW_NAMES:       # (the base signature's sampling arguments: a beam search draws nothing and never read them)
+            settings.pop(k, None)
         G, lam = check_groups(self.nb, num_beam_groups, diversity_penalty)
         self._keywords_alone(keywords, G)
         n = batch["img_embs"].shape[0]
@@ -1241,23 +1270,21 @@ class BeamDecoder(GreedyDecoder):
         kw = check_keywords(keywords, n, self.nb, self.eng.sh.V, self.eng.sh.msl + 2, prefix=cons.prefix)
         cons = cons.repeat(self.nb)
         rep = {k: (v.repeat_interleave(self.nb, 0) if torch.is_tensor(v) else v) for k, v in batch.items()}
-        n_steps = super().begin(rep, length, temperature, repitition_penalty, 1, 0.0, prefix=cons.prefix,
-                                no_repeat_ngram_size=cons.ngram, line_lengths=cons.lines)
+        n_steps = super().begin(rep, length, temperature, repitition_penalty, prefix=cons.prefix, no_repeat_ngram_size=cons.ngram,
+                                line_lengths=cons.lines, _search={"groups": G, "diversity_penalty": lam, "kw": self._upload_keywords(kw)},
+                                **settings)
         B, dev = self.B, self.eng.dev
         self.rows.copy_(torch.arange(B, dtype=torch.int32, device=dev)[:, None].expand(B, self.Tmax))
-        self.groups, self.diversity_penalty = G, lam
-        self.kw = self._upload_keywords(kw)
         sc = torch.full((n, self.nb), float("-inf"), dtype=torch.float32, device=dev)
         sc[:, ::self.nb // G] = 0.0                              # the first row of every group
         self.scores.copy_(sc.view(-1))
         return n_steps
 
     @torch.no_grad()
-    def generate(self, batch, length, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None, no_repeat_ngram_size=0,
-                 line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False,
-                 return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, return_groups=False, keywords=None, return_met=False,
-                 refrain_scheme=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
-        """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_beams, 1 + length] in
+    def generate(self, batch, length, num_beam_groups=1, diversity_penalty=0.0, return_groups=False, keywords=None, return_met=False,
+                 **settings):
+        """batch: n = max_prompts prompts (GreedyDecoder.generate's keys); settings: temperature, repitition_penalty, use_graph and the
+        constraints, as GreedyDecoder.generate takes them (``_refuse`` says what of the rest a search refuses).  Returns (ids [n, num_beams, 1 + length] in
         GreedyDecoder.generate's column layout, scores [n, num_beams] fp32), best first; ties go to the lower final row.
         prefix: one per prompt (check_prefix), shared by its beams.  no_repeat_ngram_size: as GreedyDecoder.generate, per beam
         on its own (reordered) history.  line_lengths / line_end_ids / templates: as GreedyDecoder.generate, one per prompt, shared by
@@ -1275,18 +1302,12 @@ class BeamDecoder(GreedyDecoder):
         is reported so.  Not together with num_beam_groups > 1 or return_logprobs (ValueError).
         min_p / typical_p / epsilon_cutoff / eta_cutoff, mirostat_tau > 0: refused at anything but their defaults (ValueError): a
         search draws nothing."""
-        self._no_logprobs(return_logprobs)
-        self._no_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
-        self._no_mirostat(mirostat_tau, mirostat_eta)
+        settings = BeamDecoder._refuse(**settings)
         G, lam = check_groups(self.nb, num_beam_groups, diversity_penalty)
         self._keywords_alone(keywords, G)
         if return_met and keywords is None:
             raise ValueError("return_met reports the keywords a hypothesis holds: give keywords=")
-        ids = super().generate(batch, length, temperature=temperature, repitition_penalty=repitition_penalty, use_graph=use_graph,
-                               prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size, line_lengths=line_lengths,
-                               line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme, rhyme_classes=rhyme_classes,
-                               rhyme_distinct=rhyme_distinct, **({"num_beam_groups": G, "diversity_penalty": lam} if G > 1 else {}),
-                               **({} if keywords is None else {"keywords": keywords}), refrain_scheme=refrain_scheme)
+        ids = super().generate(batch, length, num_beam_groups=G, diversity_penalty=lam, keywords=keywords, **settings)
         n, nb = self.n_prompts, self.nb
         ids = ids.view(n, nb, -1)
         sc = self.scores.view(n, nb).clone()
@@ -1331,40 +1352,31 @@ class ContrastiveDecoder(BeamDecoder):
         self.total = torch.zeros(self.n_prompts, dtype=torch.float32, device=dev)
         self.alpha = 0.0
 
-    @staticmethod
-    def _refuse(keywords=None, num_beam_groups=1, return_logprobs=False, diversity_penalty=0.0, top_k=1, top_p=0.0, generator=None,
-                min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
-        """What contrastive search does not take, refused before any device work (the last six are arguments of the base
-        classes' ``begin`` that would otherwise be ignored in silence)."""
-        BeamDecoder._no_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
-        BeamDecoder._no_mirostat(mirostat_tau, mirostat_eta)
-        if diversity_penalty:
-            raise ValueError("contrastive search has no diversity_penalty: there are no beam groups to keep apart")
-        if not (int(top_k) == 1 and float(top_p) == 0.0) or generator is not None:
-            raise ValueError("contrastive search is deterministic: it takes no sampling top_k / top_p / generator (its top_k is "
-                             "the decoder's, given at construction)")
-        if keywords is not None:
-            raise ValueError("contrastive search takes no keywords=: it keeps one hypothesis per prompt, and a keyword needs banks "
-                             "of beams to be carried in (BeamDecoder / generate_beams)")
-        if num_beam_groups != 1:
-            raise ValueError("contrastive search has no num_beam_groups: its rows are one step's candidates, not beams to group")
-        if return_logprobs:
-            raise ValueError("contrastive search has no return_logprobs (the merge reorders rows after the selection); score the "
-                             "lyric with generate.score_sequences")
+    # What contrastive search does not take (the sampling arguments are the base classes', and would otherwise be ignored in silence)
+    _REFUSED = BeamDecoder._REFUSED[1:] + (
+        (("diversity_penalty",), lambda diversity_penalty: not diversity_penalty,
+         "contrastive search has no diversity_penalty: there are no beam groups to keep apart"),
+        (_DRAW_NAMES, _no_draw,
+         "contrastive search is deterministic: it takes no sampling top_k / top_p / generator (its top_k is the decoder's, given at "
+         "construction)"),
+        (("keywords",), lambda keywords: keywords is None,
+         "contrastive search takes no keywords=: it keeps one hypothesis per prompt, and a keyword needs banks of beams to be carried in "
+         "(BeamDecoder / generate_beams)"),
+        (("num_beam_groups",), lambda num_beam_groups: num_beam_groups == 1,
+         "contrastive search has no num_beam_groups: its rows are one step's candidates, not beams to group"),
+        (("return_logprobs",), lambda return_logprobs: not return_logprobs,
+         "contrastive search has no return_logprobs (the merge reorders rows after the selection); score the lyric with "
+         "generate.score_sequences"))
 
     def _select(self, with_head):
         """The step's last three launches: the candidates entry select_forms names (a step with the head), the similarity of every
         row's hidden state to its lyric context, the contrastive merge."""
-        eng, sh = self.eng, self.eng.sh
+        eng, sh, rules = self.eng, self.eng.sh, self.rules
         temperature, rep, _, _ = self.params
-        tmpl, rhyme = getattr(self, "tmpl", None), getattr(self, "rhyme", None)
-        cand = _step_forms(self, with_head)[0]
-        fe = self.fixed_end if self.use_fixed else None
+        fe = self.fixed_end if rules.prefix else None
         if with_head:
-            hip._beam_candidates(cand, self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2, temperature,
-                                 rep, self.nb, self.cand_val, self.cand_id, self.B, fixed_end=fe, ngram=self.ngram, tables=self.lines,
-                                 tmpl=tmpl, **({} if rhyme is None else {"rhyme": rhyme}),
-                                 **({"refrain": self.refrain} if cand == "_refrain" else {}))
+            hip._beam_candidates(rules.forms(with_head)[0], self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P,
+                                 sh.msl + 2, temperature, rep, self.nb, self.cand_val, self.cand_id, self.B, **rules.tail(self.fixed_end))
         pre = "decoder.gpt2.transformer."
         # self.h: the residual stream the last block left, in every step variant (what the head's LayerNorm reads)
         hip.decode_contrastive_sim(self.h, eng.P(pre + "ln_f.weight"), eng.P(pre + "ln_f.bias"), sh.eps, self.Hc, self.sim, self.keep,
@@ -1383,45 +1395,32 @@ class ContrastiveDecoder(BeamDecoder):
         return "contrastive search, %d candidates per prompt, " % self.nb + GreedyDecoder.describe(self)
 
     @torch.no_grad()
-    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
-              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
-              rhyme_distinct=False, return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, keywords=None, refrain_scheme=None,
-              penalty_alpha=0.6, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
-        """BeamDecoder.begin with the decoder's top_k rows per prompt, scores [0, -inf, ...] and total 0 per prompt.  `top_k`, `top_p`,
-        `generator` and `diversity_penalty` are the base signature's: anything but their defaults is refused.  With a prefix the prefill covers the prompt
+    def begin(self, batch, length, penalty_alpha=0.6, **settings):
+        """BeamDecoder.begin with the decoder's top_k rows per prompt, scores [0, -inf, ...] and total 0 per prompt.  settings:
+        temperature, repitition_penalty and the constraints, as BeamDecoder.begin takes them.  With a prefix the prefill covers the prompt
         only, so every lyric column gets its hidden state from a token step; the steps at which every row is held skip the head.
-        keywords=, num_beam_groups > 1, return_logprobs=True, a diversity penalty and sampling arguments are refused (ValueError)
-        before any device work."""
-        self._refuse(keywords, num_beam_groups, return_logprobs, diversity_penalty, top_k, top_p, generator, min_p, typical_p,
-                     epsilon_cutoff, eta_cutoff, mirostat_tau, mirostat_eta)
+        keywords=, num_beam_groups > 1, return_logprobs=True, a diversity penalty and sampling arguments (`top_k`, `top_p`, `generator`
+        are the base signature's) are refused (ValueError, ``_refuse``) before any device work."""
+        settings = ContrastiveDecoder._refuse(**settings)
         _, alpha = check_contrastive(self.nb, penalty_alpha)
-        n_steps = super().begin(batch, length, temperature, repitition_penalty, prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size,
-                                line_lengths=line_lengths, line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme,
-                                rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct, refrain_scheme=refrain_scheme)
+        n_steps = super().begin(batch, length, **settings)
         self.alpha = alpha
         self.total.zero_()
         self.sim.zero_()
-        if self.use_fixed:          # (the prefill stopped at the prompt; columns every row holds still need no head)
+        if self.rules.prefix:       # (the prefill stopped at the prompt; columns every row holds still need no head)
             self.min_fixed = int(self.fixed_end.min().item())
         return n_steps
 
     @torch.no_grad()
-    def generate(self, batch, length, penalty_alpha=0.6, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None,
-                 no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
-                 rhyme_distinct=False, refrain_scheme=None, return_logprobs=False, num_beam_groups=1, keywords=None, min_p=0.0,
-                 typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
+    def generate(self, batch, length, penalty_alpha=0.6, **settings):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, 1 + length] in GreedyDecoder.generate's
         column layout, scores [n] fp32): one lyric per prompt and the sum of the processed log-probabilities of its chosen tokens.
-        penalty_alpha in [0, 1]: the weight of the degeneration penalty (0: greedy decoding).  prefix, no_repeat_ngram_size,
-        line_lengths / line_end_ids, templates, rhyme_scheme / rhyme_classes / rhyme_distinct, refrain_scheme: as
-        BeamDecoder.generate, one per prompt.  keywords=, num_beam_groups > 1 and return_logprobs=True raise ValueError."""
-        self._refuse(keywords, num_beam_groups, return_logprobs, min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff,
-                     eta_cutoff=eta_cutoff, mirostat_tau=mirostat_tau, mirostat_eta=mirostat_eta)
-        ids = GreedyDecoder.generate(self, batch, length, temperature=temperature, repitition_penalty=repitition_penalty,
-                                     use_graph=use_graph, prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size,
-                                     line_lengths=line_lengths, line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme,
-                                     rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct, refrain_scheme=refrain_scheme,
-                                     penalty_alpha=penalty_alpha)
+        penalty_alpha in [0, 1]: the weight of the degeneration penalty (0: greedy decoding).  settings: temperature,
+        repitition_penalty, use_graph, prefix, no_repeat_ngram_size, line_lengths / line_end_ids, templates, rhyme_scheme /
+        rhyme_classes / rhyme_distinct, refrain_scheme: as BeamDecoder.generate, one per prompt.  What ``begin`` refuses raises
+        ValueError."""
+        settings = ContrastiveDecoder._refuse(**settings)
+        ids = GreedyDecoder.generate(self, batch, length, penalty_alpha=penalty_alpha, **settings)
         n, k = self.n_prompts, self.nb
         return ids.view(n, k, -1)[:, 0].clone(), self.total + self.scores.view(n, k)[:, 0]
 
@@ -1451,50 +1450,44 @@ class StochasticBeamDecoder(BeamDecoder):
         self.cand_g = torch.zeros(self.B, nb, dtype=torch.float32, device=dev)
         self._no_src = torch.full((self.B, (self.max_len - 1) // sent + 1), -1, dtype=torch.int8, device=dev)      # "no copy line"
 
-    @staticmethod
-    def _refuse(keywords=None, num_beam_groups=1, return_logprobs=False, diversity_penalty=0.0, top_k=1, top_p=0.0, generator=None,
-                min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
-        """What stochastic beam search does not take, refused before any device work with the reason."""
-        if check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff) != WARP_OFF:
-            raise ValueError("stochastic beam search samples from the whole processed distribution: min_p / typical_p / "
-                             "epsilon_cutoff / eta_cutoff would truncate it before the perturbation, which is not built (a sampled "
-                             "generation takes them: GreedyDecoder / generate_samples)")
-        if check_mirostat(mirostat_tau, mirostat_eta)[0] > 0.0:
-            raise ValueError("stochastic beam search has no mirostat_tau / mirostat_eta: Mirostat adapts a cut per row and draw, and "
-                             "the rows here are reordered by the merge (GreedyDecoder / generate_samples take it)")
-        if not (int(top_k) == 1 and float(top_p) == 0.0) or generator is not None:
-            raise ValueError("stochastic beam search takes no sampling top_k / top_p / generator: it samples from the whole "
-                             "processed distribution, and its noise comes from seed=")
-        if keywords is not None:
-            raise ValueError("stochastic beam search takes no keywords=: its rows are samples in draw order, not banks of beams to "
-                             "carry a keyword in (BeamDecoder / generate_beams)")
-        if num_beam_groups != 1 or diversity_penalty:
-            raise ValueError("stochastic beam search has no num_beam_groups / diversity_penalty: a penalty between groups would "
-                             "change the distribution the samples come from")
-        if return_logprobs:
-            raise ValueError("stochastic beam search has no return_logprobs (the merge reorders rows after the selection); score the "
-                             "samples with generate.score_sequences")
+    # What stochastic beam search does not take
+    _REFUSED = (
+        (_WARP_NAMES, _no_warp,
+         "stochastic beam search samples from the whole processed distribution: min_p / typical_p / epsilon_cutoff / eta_cutoff would "
+         "truncate it before the perturbation, which is not built (a sampled generation takes them: GreedyDecoder / generate_samples)"),
+        (_MIROSTAT_NAMES, _no_mirostat,
+         "stochastic beam search has no mirostat_tau / mirostat_eta: Mirostat adapts a cut per row and draw, and the rows here are "
+         "reordered by the merge (GreedyDecoder / generate_samples take it)"),
+        (_DRAW_NAMES, _no_draw,
+         "stochastic beam search takes no sampling top_k / top_p / generator: it samples from the whole processed distribution, and its "
+         "noise comes from seed="),
+        (("keywords",), lambda keywords: keywords is None,
+         "stochastic beam search takes no keywords=: its rows are samples in draw order, not banks of beams to carry a keyword in "
+         "(BeamDecoder / generate_beams)"),
+        (("num_beam_groups", "diversity_penalty"), lambda num_beam_groups=1, diversity_penalty=0.0: num_beam_groups == 1 and not diversity_penalty,
+         "stochastic beam search has no num_beam_groups / diversity_penalty: a penalty between groups would change the distribution the "
+         "samples come from"),
+        (("return_logprobs",), lambda return_logprobs: not return_logprobs,
+         "stochastic beam search has no return_logprobs (the merge reorders rows after the selection); score the samples with "
+         "generate.score_sequences"))
 
     def _select(self, with_head):
         """The step's last launches: on a step with the head the Gumbel candidates (one entry over the refrain form, whatever rules
         the generation has or none) and the Gumbel merge; otherwise the merge with null candidates."""
-        eng, sh = self.eng, self.eng.sh
+        eng, sh, rules = self.eng, self.eng.sh, self.rules
         temperature, rep, _, _ = self.params
-        fe = self.fixed_end if self.use_fixed else None
+        fe = self.fixed_end if rules.prefix else None
         if with_head:
             hip.decode_gumbel_candidates(self.logits, eng.layout.Vpad, min(sh.V, 13317), self.seq, self.pos, sh.P, sh.msl + 2, temperature,
                                          rep, self.nb, self.cand_val, self.cand_id, self.cand_g, self.scores, self.gum, self.row_seed,
-                                         self.B, self._no_src if self.refrain is None else self.refrain, tables=self.lines,
-                                         rhyme=getattr(self, "rhyme", None), tmpl=getattr(self, "tmpl", None), ngram=self.ngram,
-                                         fixed_end=fe)
+                                         self.B, **rules.tail(self.fixed_end, "src", self._no_src))
         hip.decode_gumbel_merge(self.cand_val if with_head else None, self.cand_id if with_head else None,
                                 self.cand_g if with_head else None, self.scores, self.gum, self.seq, self.keep, self.rows, self.pos, sh.P,
                                 sh.msl + 2, self.nb, self.n_prompts, pos_next=self.pos_next, fixed_end=fe)
 
     def _graph_key(self, with_head, parity):
         # (on a head step: which of the refrain form's tables the launch holds, and a real src or none)
-        held = _refrain_key(self) + (("src",) if self.refrain is not None else ()) if with_head else ()
-        return super()._graph_key(with_head, parity) + (("stochastic",) + held,)
+        return super()._graph_key(with_head, parity) + (("stochastic",) + (self.rules.src_key() if with_head else ()),)
 
     def _step_state(self):
         """BeamDecoder's state plus gum: without it the warm-up step of a graph capture would merge twice."""
@@ -1504,21 +1497,16 @@ class StochasticBeamDecoder(BeamDecoder):
         return "stochastic beam search, %d samples per prompt, " % self.nb + GreedyDecoder.describe(self)
 
     @torch.no_grad()
-    def begin(self, batch, length, temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0, generator=None, prefix=None,
-              no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
-              rhyme_distinct=False, return_logprobs=False, num_beam_groups=1, diversity_penalty=0.0, keywords=None, refrain_scheme=None,
-              min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1, seed=0, first_prompt=0):
+    def begin(self, batch, length, seed=0, first_prompt=0, **settings):
         """BeamDecoder.begin with the decoder's num_samples rows per prompt, scores and gum at [0, -inf, ...] per prompt, and the rows'
         seed words written from `seed` (``stochastic_row_seeds``: a word per prompt and beam slot; `first_prompt` is the index of
         this batch's first prompt in the whole call, so that cutting a call into batches does not change a prompt's noise).
-        keywords=, num_beam_groups > 1, a diversity penalty, return_logprobs=True, sampling top_k / top_p / generator, the four
-        truncation stages and Mirostat are refused (ValueError) before any device work."""
-        StochasticBeamDecoder._refuse(keywords, num_beam_groups, return_logprobs, diversity_penalty, top_k, top_p, generator, min_p,
-                                      typical_p, epsilon_cutoff, eta_cutoff, mirostat_tau, mirostat_eta)
+        settings: temperature, repitition_penalty and the constraints, as BeamDecoder.begin takes them.  keywords=,
+        num_beam_groups > 1, a diversity penalty, return_logprobs=True, sampling top_k / top_p / generator, the four truncation stages
+        and Mirostat are refused (ValueError, ``_refuse``) before any device work."""
+        settings = StochasticBeamDecoder._refuse(**settings)
         _, seed = check_stochastic(self.nb, seed)
-        n_steps = super().begin(batch, length, temperature, repitition_penalty, prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size,
-                                line_lengths=line_lengths, line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme,
-                                rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct, refrain_scheme=refrain_scheme)
+        n_steps = super().begin(batch, length, **settings)
         self.gum.copy_(self.scores)                             # [0, -inf, ...] per prompt
         words = stochastic_row_seeds(seed, first_prompt, self.n_prompts, self.nb)
         self.row_seed.copy_(torch.from_numpy(words.view(np.int32)))
@@ -1526,25 +1514,17 @@ class StochasticBeamDecoder(BeamDecoder):
         return n_steps
 
     @torch.no_grad()
-    def generate(self, batch, length, seed=0, temperature=1.0, repitition_penalty=1.0, use_graph=None, prefix=None,
-                 no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None,
-                 rhyme_distinct=False, refrain_scheme=None, first_prompt=0, return_logprobs=False, num_beam_groups=1,
-                 diversity_penalty=0.0, keywords=None, top_k=1, top_p=0.0, generator=None, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0,
-                 eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
+    def generate(self, batch, length, seed=0, first_prompt=0, **settings):
         """batch: n = max_prompts prompts (GreedyDecoder.generate's keys).  Returns (ids [n, num_samples, 1 + length] in
         GreedyDecoder.generate's column layout, scores [n, num_samples] fp32, gum [n, num_samples] fp32) in draw order: the samples
         of a prompt are pairwise different, scores are the sums of the processed log-probabilities of their tokens (a beam score's
         scale), gum their perturbed values (0 for the first, then non-increasing).  A prompt whose rules leave fewer than
         num_samples different lyrics has dead rows at the end: score and gum -inf.  seed: an integer in 0 .. 2^32 - 1; equal seeds
-        give equal bits.  prefix, no_repeat_ngram_size, line_lengths / line_end_ids, templates, rhyme_scheme / rhyme_classes /
-        rhyme_distinct, refrain_scheme: as BeamDecoder.generate, one per prompt.  What ``begin`` refuses raises ValueError."""
-        StochasticBeamDecoder._refuse(keywords, num_beam_groups, return_logprobs, diversity_penalty, top_k, top_p, generator, min_p,
-                                      typical_p, epsilon_cutoff, eta_cutoff, mirostat_tau, mirostat_eta)
-        ids = GreedyDecoder.generate(self, batch, length, temperature=temperature, repitition_penalty=repitition_penalty,
-                                     use_graph=use_graph, prefix=prefix, no_repeat_ngram_size=no_repeat_ngram_size,
-                                     line_lengths=line_lengths, line_end_ids=line_end_ids, templates=templates, rhyme_scheme=rhyme_scheme,
-                                     rhyme_classes=rhyme_classes, rhyme_distinct=rhyme_distinct, refrain_scheme=refrain_scheme,
-                                     seed=seed, first_prompt=first_prompt)
+        give equal bits.  settings: temperature, repitition_penalty, use_graph, prefix, no_repeat_ngram_size, line_lengths /
+        line_end_ids, templates, rhyme_scheme / rhyme_classes / rhyme_distinct, refrain_scheme: as BeamDecoder.generate, one per
+        prompt.  What ``begin`` refuses raises ValueError."""
+        settings = StochasticBeamDecoder._refuse(**settings)
+        ids = GreedyDecoder.generate(self, batch, length, seed=seed, first_prompt=first_prompt, **settings)
         n, nb = self.n_prompts, self.nb
         gum = self.gum.view(n, nb).clone()
         sc = torch.where(gum > float("-inf"), self.scores.view(n, nb), torch.full_like(gum, float("-inf")))

@@ -300,11 +300,8 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     guided = scale != GUIDANCE_OFF
     if not guided and negative_rows is not None:
         raise ValueError("negative_rows needs a guidance_scale other than 1 (1 is the unguided call)")
-    warp = check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
-    warp_kw = {} if warp == WARP_OFF else dict(zip(("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"), warp))
-    tau, eta = check_mirostat(mirostat_tau, mirostat_eta)
-    if tau > 0.0:
-        warp_kw = dict(warp_kw, mirostat_tau=tau, mirostat_eta=eta)
+    warp_kw = dict(zip(("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"), check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)))
+    warp_kw["mirostat_tau"], warp_kw["mirostat_eta"] = check_mirostat(mirostat_tau, mirostat_eta)
     if rank_by is not None and rank_by not in ("sum", "mean"):
         raise ValueError('rank_by must be "sum", "mean" or None, got %r' % (rank_by,))
     scoring = bool(return_scores) or rank_by is not None
@@ -334,7 +331,7 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
         ids = dec.generate(chunk, *((next(negs)[0], length, scale) if guided else (length,)), temperature=temperature,
                            repitition_penalty=repetition_penalty,
                            top_k=top_k, top_p=top_p, generator=generator, prefix=c.prefix, no_repeat_ngram_size=c.ngram,
-                           line_lengths=c.lines, **({"return_logprobs": True} if scoring else {}), **warp_kw)
+                           line_lengths=c.lines, return_logprobs=scoring, **warp_kw)
         if scoring:
             ids, lp = ids[0].cpu().numpy(), ids[1].cpu().numpy()
             upto = len(GreedyDecoder.reference_return(ids[0].tolist(), length, sent=sh.msl + 2))        # 1 + the last model call
@@ -467,7 +464,7 @@ def generate_contrastive(model, rows, tokenizer, top_k=4, penalty_alpha=0.6, len
     refrain_scheme: as generate_beams -- the rules act on the candidates, so the search chooses among characters they allow.
     keywords= and num_beam_groups > 1 are refused with a ValueError that says why (ContrastiveDecoder); the model's raw token
     log-probabilities of a returned lyric come from score_sequences on its ids."""
-    ContrastiveDecoder._refuse(keywords, num_beam_groups)
+    ContrastiveDecoder._refuse(keywords=keywords, num_beam_groups=num_beam_groups)
     k, alpha = check_contrastive(top_k, penalty_alpha)
     eng = model.engine()
     sh = eng.sh
@@ -510,8 +507,10 @@ def generate_stochastic_beams(model, rows, tokenizer, num_samples=4, seed=0, len
     refrain_scheme: as generate_contrastive -- the rules act on the candidates, so the samples come from what they allow.
     keywords=, num_beam_groups > 1, a diversity penalty, return_logprobs, sampling top_k / top_p / generator, min_p / typical_p /
     epsilon_cutoff / eta_cutoff and Mirostat are refused with a ValueError that says why (StochasticBeamDecoder)."""
-    StochasticBeamDecoder._refuse(keywords, num_beam_groups, return_logprobs, diversity_penalty, top_k, top_p, generator, min_p, typical_p,
-                                  epsilon_cutoff, eta_cutoff, mirostat_tau, mirostat_eta)
+    StochasticBeamDecoder._refuse(keywords=keywords, num_beam_groups=num_beam_groups, return_logprobs=return_logprobs,
+                                  diversity_penalty=diversity_penalty, top_k=top_k, top_p=top_p, generator=generator, min_p=min_p,
+                                  typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, mirostat_tau=mirostat_tau,
+                                  mirostat_eta=mirostat_eta)
     nb, seed = check_stochastic(num_samples, seed)
     eng = model.engine()
     sh = eng.sh

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from mmtg_amd import hip
-from mmtg_amd.decode import BeamDecoder, GreedyDecoder, check_groups, select_forms
+from mmtg_amd.decode import BeamDecoder, GreedyDecoder, StepRules, check_groups, select_forms
 from oracle import mmtg_oracle as O
 from test_beam_cpu import NEG, SENT, _fork, comparable_length, cpu_beam_search, setup_case, start_row
 from test_ngram_cpu import _Eng, _Model
@@ -267,11 +267,11 @@ def test_select_forms_names_the_grouped_merge_on_head_steps_only(monkeypatch):
             for ngram in (0, 3):
                 for G, lam in ((1, 0.0), (2, 0.5), (4, 0.0)):
                     fe = i32(B)
-                    dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb, use_fixed=prefix,
-                             ngram=ngram, lines=None, tmpl=None, rhyme=None, fixed_end=fe, logits=torch.zeros(B, V),
+                    dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb,
+                             rules=StepRules(prefix=prefix, ngram=ngram, groups=G, diversity_penalty=lam), copy_step=False, fixed_end=fe,
+                             logits=torch.zeros(B, V),
                              seq=torch.zeros(B, 64, dtype=torch.long), pos=i32(1), pos_next=i32(1), keep=i32(B, 64), rows=i32(B, 64),
-                             scores=torch.zeros(B), cand_val=torch.zeros(B, nb), cand_id=i32(B, nb), params=(1.1, 1.5, 1, 0.0),
-                             groups=G, diversity_penalty=lam)
+                             scores=torch.zeros(B), cand_val=torch.zeros(B, nb), cand_id=i32(B, nb), params=(1.1, 1.5, 1, 0.0))
                     held = "_fixed" if prefix else ""
                     base = (with_head, 0, dec.params) + (("prefix",) if prefix else ()) + (("ngram", 3) if ngram else ())
                     key = GreedyDecoder._graph_key(dec, with_head, 0)

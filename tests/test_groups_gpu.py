@@ -206,7 +206,7 @@ def test_one_group_is_exactly_the_call_without_the_argument():
     assert new and all(k[0] and ("groups", 2, 0.5) in k for k in new)      # head steps only; the others replay the graphs they had
     assert not torch.equal(i2, i0)
     i3, s3 = dec.generate(tb, 66, temperature=T, repitition_penalty=REP)                      # and back
-    assert torch.equal(i3, i0) and torch.equal(s3, s0) and dec.groups == 1
+    assert torch.equal(i3, i0) and torch.equal(s3, s0) and dec.rules.groups == 1
 
 
 # ------------------------------------------------------------------ 7. with the constraints

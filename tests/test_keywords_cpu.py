@@ -14,7 +14,7 @@ import torch
 
 from mmtg_amd import hip
 from mmtg_amd.constraints import (KeywordTables, check_keywords, keyword_bank, keyword_met_mask, keyword_select, keywords_met)
-from mmtg_amd.decode import BeamDecoder, GreedyDecoder, select_forms
+from mmtg_amd.decode import BeamDecoder, GreedyDecoder, StepRules, select_forms
 from mmtg_amd.generate import encode_keywords, generate_beams, generate_samples
 from oracle import mmtg_oracle as O
 from test_beam_cpu import NEG, SENT, _fork, comparable_length, cpu_beam_search, setup_case, start_row
@@ -198,11 +198,11 @@ def test_select_forms_names_the_keyword_entries_on_head_steps_only(monkeypatch):
                 fe = i32(B)
                 kw = (i32(B // nb, 8, 4), torch.zeros(B // nb, 8, dtype=torch.int8), K, 4) if kw_on else None
                 wide = (torch.zeros(B, nb + K), i32(B, nb + K), i32(B, nb + K))
-                dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb, use_fixed=prefix,
-                         ngram=3, lines=None, tmpl=None, rhyme=None, fixed_end=fe, logits=torch.zeros(B, V),
+                dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb,
+                         rules=StepRules(prefix=prefix, ngram=3, kw=kw), copy_step=False, fixed_end=fe, logits=torch.zeros(B, V),
                          seq=torch.zeros(B, 64, dtype=torch.long), pos=i32(1), pos_next=i32(1), keep=i32(B, 64), rows=i32(B, 64),
                          scores=torch.zeros(B), cand_val=torch.zeros(B, nb), cand_id=i32(B, nb), params=(1.1, 1.5, 1, 0.0),
-                         groups=1, diversity_penalty=0.0, kw=kw, _kw_cand=wide, _kw_buf=None)
+                         _kw_cand=wide, _kw_buf=(None, None, None, None))          # (no line tables: the no-leader table is not read)
                 held = "_fixed" if prefix else ""
                 base = (with_head, 0, dec.params) + (("prefix",) if prefix else ()) + ("ngram", 3)
                 assert GreedyDecoder._graph_key(dec, with_head, 0) == base + ((("kw", K), ("cap", 4)) if with_head and kw_on else ())

@@ -236,7 +236,7 @@ def test_keyword_surfaces():
     # keywords=None is the call without the argument: ids, scores, graph keys
     i0, s0 = fresh.generate(tb, length, temperature=T, repitition_penalty=REP)
     i1, s1 = dec.generate(tb, length, temperature=T, repitition_penalty=REP, keywords=None)
-    assert torch.equal(i0, i1) and torch.equal(s0, s1) and set(dec.graphs) == set(fresh.graphs) and dec.kw is None
+    assert torch.equal(i0, i1) and torch.equal(s0, s1) and set(dec.graphs) == set(fresh.graphs) and dec.rules.kw is None
     keys = set(dec.graphs)
     ids, scores, met = dec.generate(tb, length, temperature=T, repitition_penalty=REP, keywords=kws, return_met=True)
     new = set(dec.graphs) - keys
@@ -250,7 +250,7 @@ def test_keyword_surfaces():
     assert int(met[:, 0].min()) == 2                                  # every prompt's first hypothesis holds both
     assert torch.isfinite(scores).all() and not torch.equal(ids, i0)
     i3, s3 = dec.generate(tb, length, temperature=T, repitition_penalty=REP)                  # and back
-    assert torch.equal(i3, i0) and torch.equal(s3, s0) and dec.kw is None
+    assert torch.equal(i3, i0) and torch.equal(s3, s0) and dec.rules.kw is None
     # a whole given first line that holds a keyword: met from the start, and not written again
     line = [1, 30, KEYWORDS[0][0], KEYWORDS[0][1], 31] + [0] * (CAP - 4) + [2]
     ids, scores, met = dec.generate(tb, length, temperature=T, repitition_penalty=REP, keywords=kws, return_met=True, prefix=[line] * n)

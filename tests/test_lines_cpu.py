@@ -430,7 +430,7 @@ def test_every_step_ends_in_the_entry_the_dispatch_table_names(monkeypatch):
     held to the ABI's), against the table written out here."""
     from types import SimpleNamespace as NS
 
-    from mmtg_amd.decode import select_forms
+    from mmtg_amd.decode import StepRules, select_forms
     #        with_head prefix ngram lines   select / sample / candidates   merge
     table = [(True, False, 0, False,        "",                            ""),
              (True, True, 0, False,         "_fixed",                      "_fixed"),
@@ -466,8 +466,10 @@ def test_every_step_ends_in_the_entry_the_dispatch_table_names(monkeypatch):
     for with_head, prefix, ngram, with_lines, want, want_merge in table:
         assert select_forms(with_head, prefix, ngram, with_lines) == (want, want_merge)
         fe = i32(B)
-        dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb, use_fixed=prefix, ngram=ngram,
-                 lines=lines if with_lines else None, fixed_end=fe, logits=torch.zeros(B, V), seq=torch.zeros(B, 64, dtype=torch.long),
+        logits = torch.zeros(B, V)
+        dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb,
+                 rules=StepRules(prefix=prefix, ngram=ngram, lines=lines if with_lines else None), copy_step=False, fixed_end=fe,
+                 logits=logits, select_rows=B, select_logits=logits, seq=torch.zeros(B, 64, dtype=torch.long),
                  pos=i32(1), pos_next=i32(1), uniforms=torch.zeros(70, B), keep=i32(B, 64), rows=i32(B, 64), scores=torch.zeros(B),
                  cand_val=torch.zeros(B, nb), cand_id=i32(B, nb))
         # the graph key comes from the same answer: "prefix", then ("ngram", n), then "lines" exactly on a head step under line constraints

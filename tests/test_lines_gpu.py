@@ -321,7 +321,7 @@ def test_none_is_exactly_the_call_without_the_arguments_and_unconstrained_tables
     a = fresh.generate(tb, 220, temperature=T, repitition_penalty=REP)
     b = dec.generate(tb, 220, temperature=T, repitition_penalty=REP, line_lengths=None, line_end_ids=None)
     assert torch.equal(a, b) and set(dec.graphs) == set(fresh.graphs) and all("lines" not in k for k in dec.graphs)
-    assert dec.kernel_name() == fresh.kernel_name() and dec.describe() == fresh.describe() and dec.lines is None
+    assert dec.kernel_name() == fresh.kernel_name() and dec.describe() == fresh.describe() and dec.rules.lines is None
     c = dec.generate(tb, 220, temperature=T, repitition_penalty=REP, line_lengths=[None])           # the *_lines entries, no bounds
     assert torch.equal(a, c) and any("lines" in k for k in dec.graphs)
     kw = dict(temperature=T, repitition_penalty=REP, top_k=10, top_p=0.7)
@@ -338,7 +338,7 @@ def test_none_is_exactly_the_call_without_the_arguments_and_unconstrained_tables
     assert torch.equal(ia, ic) and torch.equal(sa, sc)
     # after a constrained run, None is the plain decoder again
     dec.generate(tb, 220, temperature=T, repitition_penalty=REP, line_lengths=7)
-    assert torch.equal(dec.generate(tb, 220, temperature=T, repitition_penalty=REP), a) and dec.lines is None
+    assert torch.equal(dec.generate(tb, 220, temperature=T, repitition_penalty=REP), a) and dec.rules.lines is None
 
 
 # ------------------------------------------------------------------ 5. full size

@@ -201,7 +201,7 @@ def test_the_python_surface_names_the_argument_out_of_range(name, value):
     with pytest.raises(ValueError, match=name):
         GreedyDecoder.begin(None, None, 8, **a)                                  # the first thing begin looks at after keywords
     with pytest.raises(ValueError, match=name):
-        BeamDecoder._no_mirostat(**a)
+        BeamDecoder._refuse(**a)
 
 
 def test_check_mirostat_takes_the_ends_of_the_ranges_and_refuses_what_is_no_number():
@@ -267,15 +267,16 @@ def test_the_entries_are_declared_bound_and_exported_and_the_abi_version_is_12()
 def test_the_search_decoders_refuse_the_arguments_with_a_reason():
     for kw in (dict(mirostat_tau=2.0), dict(mirostat_tau=0.5, mirostat_eta=0.0)):
         with pytest.raises(ValueError, match="search draws nothing"):
-            BeamDecoder._no_mirostat(**kw)
+            BeamDecoder._refuse(**kw)
         with pytest.raises(ValueError, match="search draws nothing"):
             ContrastiveDecoder._refuse(**kw)
-    BeamDecoder._no_mirostat(*MIROSTAT_OFF)
-    BeamDecoder._no_mirostat(0.0, 0.5)                                           # eta alone turns nothing on
+    BeamDecoder._refuse(mirostat_tau=MIROSTAT_OFF[0], mirostat_eta=MIROSTAT_OFF[1])
+    BeamDecoder._refuse(mirostat_tau=0.0, mirostat_eta=0.5)                                           # eta alone turns nothing on
     ContrastiveDecoder._refuse(mirostat_tau=0.0, mirostat_eta=0.1)
     with pytest.raises(ValueError, match="mirostat_tau"):                        # out of range is said first, by name
         ContrastiveDecoder._refuse(mirostat_tau=77.0)
-    import inspect
-    for cls in (BeamDecoder, ContrastiveDecoder):
+    for cls in (BeamDecoder, ContrastiveDecoder):                                # begin and generate take the names, and refuse them
+        assert {"mirostat_tau", "mirostat_eta"} <= {k for names, _, _ in cls._REFUSED for k in names}
         for fn in (cls.begin, cls.generate):
-            assert {"mirostat_tau", "mirostat_eta"} <= set(inspect.signature(fn).parameters)
+            with pytest.raises(ValueError, match="search draws nothing"):
+                fn(None, {}, 8, mirostat_tau=2.0, mirostat_eta=0.1)

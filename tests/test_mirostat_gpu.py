@@ -456,7 +456,7 @@ def test_mirostat_tau_zero_is_exactly_the_call_without_the_arguments(monkeypatch
     assert new and set(mirostat_keys(dec)) == new and all(k[0] for k in new)     # head steps only; the others replay the graphs they had
     assert dec.mirostat_mu is not None and dec.mirostat_mu.dtype == torch.float32 and tuple(dec.mirostat_mu.shape) == (3,)
     c = dec.generate(tb, 2 * SENT, temperature=T, repitition_penalty=REP, top_k=10, top_p=0.7, generator=torch.Generator(device=DEV).manual_seed(5))
-    assert torch.equal(c, a) and dec.mirostat == (0.0, 0.1) and set(dec.graphs) == keys | new
+    assert torch.equal(c, a) and dec.rules.mirostat == (0.0, 0.1) and set(dec.graphs) == keys | new
 
 
 # ------------------------------------------------------------------ 12. text surface

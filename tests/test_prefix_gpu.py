@@ -306,7 +306,7 @@ def test_full_size_prefixed_decode_is_bit_stable_and_row_independent():
     assert int(i1.min()) >= 0 and int(i1.max()) < V
     # no prefix afterwards: the plain launches and graphs again, as a fresh decoder computes
     plain = dec.generate(batch, Ln, temperature=T, repitition_penalty=REP)
-    assert not dec.use_fixed
+    assert not dec.rules.prefix
     assert torch.equal(plain, GreedyDecoder(model, B, max_len=Ln).generate(batch, Ln, temperature=T, repitition_penalty=REP))
 
 

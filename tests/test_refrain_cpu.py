@@ -14,7 +14,7 @@ import torch
 import test_lines_cpu as L
 from mmtg_amd import hip
 from mmtg_amd.constraints import _check_constraints, check_refrain
-from mmtg_amd.decode import BeamDecoder, GreedyDecoder, LineTables, check_lines, select_forms
+from mmtg_amd.decode import BeamDecoder, GreedyDecoder, StepRules, LineTables, check_lines, select_forms
 from test_beam_cpu import SENT, comparable_length, setup_case, start_row
 from test_lines_cpu import CAP
 from test_ngram_cpu import _Eng, _Model, banned_ids
@@ -244,8 +244,10 @@ def test_select_forms_names_the_refrain_entries_exactly_when_a_scheme_is_given(m
                                (lines, torch.full((B, 3, CAP), -1, dtype=torch.int32), None), (lines, None, (cof, lead, True)),
                                (lines, None, (cof, lead, False))):
                 fe = i32(B)
-                dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb, use_fixed=prefix, ngram=3,
-                         lines=ln, tmpl=tm, rhyme=rh, refrain=src, copy_step=copies, fixed_end=fe, logits=torch.zeros(B, V),
+                logits = torch.zeros(B, V)
+                dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb,
+                         rules=StepRules(prefix=prefix, ngram=3, lines=ln, tmpl=tm, rhyme=rh, refrain=src), copy_step=copies, fixed_end=fe,
+                         logits=logits, select_rows=B, select_logits=logits,
                          seq=torch.zeros(B, 64, dtype=torch.long), pos=i32(1), pos_next=i32(1), uniforms=torch.zeros(70, B),
                          keep=i32(B, 64), rows=i32(B, 64), scores=torch.zeros(B), cand_val=torch.zeros(B, nb), cand_id=i32(B, nb),
                          params=(1.1, 1.5, 1, 0.0))
@@ -278,13 +280,12 @@ def test_select_forms_names_the_refrain_entries_exactly_when_a_scheme_is_given(m
                 assert [c[0] for c in calls] == (["mmtg_decode_beam_candidates_refrain"] if with_head else []) + ["mmtg_decode_beam_merge" + held]
                 if with_head:
                     assert calls[0][1][-2:] == (src.data_ptr(), 0)
-    # a decoder without the attribute (or with None) takes the entries and keys it always took
-    dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, use_fixed=False, ngram=0, lines=lines, tmpl=None, rhyme=(cof, lead, False),
-             fixed_end=i32(B), logits=torch.zeros(B, V), seq=torch.zeros(B, 64, dtype=torch.long), pos=i32(1), pos_next=i32(1),
-             params=(1.1, 1.5, 1, 0.0))
-    for extra in ({}, {"refrain": None}, {"copy_step": True}):
-        for k, v in extra.items():
-            setattr(dec, k, v)
+    # a record built without the argument (or with None) takes the entries and keys it always took, on a copy step too
+    logits = torch.zeros(B, V)
+    dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, fixed_end=i32(B), logits=logits, select_rows=B, select_logits=logits,
+             seq=torch.zeros(B, 64, dtype=torch.long), pos=i32(1), pos_next=i32(1), params=(1.1, 1.5, 1, 0.0))
+    for extra, copies in (({}, False), ({"refrain": None}, False), ({"refrain": None}, True)):
+        dec.rules, dec.copy_step = StepRules(lines=lines, rhyme=(cof, lead, False), **extra), copies
         for with_head in (True, False):
             del calls[:]
             GreedyDecoder._select(dec, with_head)

@@ -204,7 +204,7 @@ def test_decoders_repeat_line_0_as_line_3_under_ngram_blocking(mode):
     dec = GreedyDecoder(model, 3, max_len=LENGTH)
     plain = dec.generate(tb, LENGTH, **args)
     greedy = dec.generate(tb, LENGTH, refrain_scheme=scheme, **args)
-    assert dec.refrain is not None and dec.lines is None and any("refrain" in k for k in dec.graphs)
+    assert dec.rules.refrain is not None and dec.rules.lines is None and any("refrain" in k for k in dec.graphs)
     assert _holds(greedy, tabs, n) == 3 * CAP and torch.equal(greedy[:, :first], plain[:, :first])
     assert all(lines_of(r)[3] == lines_of(r)[0] and any(lines_of(r)[0]) for r in greedy.cpu().tolist())
     assert not all(lines_of(r)[3] == lines_of(r)[0] for r in plain.cpu().tolist())              # blocking alone: the line cannot come back
@@ -300,7 +300,7 @@ def test_schemes_compose_with_a_partial_prefix_bounds_a_template_a_rhyme_scheme_
     assert not tabs.bare and tabs.src[:, 3].tolist() == [0, 0, 0]
     dec = GreedyDecoder(model, 3, max_len=length)
     ids, lp = dec.generate(tb, length, temperature=T, repitition_penalty=REP, refrain_scheme=scheme, return_logprobs=True, **kw)
-    assert dec.skipped_steps == 0 and dec.lines is not None and dec.tmpl is not None and dec.rhyme is not None
+    assert dec.skipped_steps == 0 and dec.rules.lines is not None and dec.rules.tmpl is not None and dec.rules.rhyme is not None
     rows = ids.cpu().tolist()
     for b, p in enumerate(pre):
         assert rows[b][:len(p)] == p
@@ -359,7 +359,7 @@ def test_refrain_scheme_none_is_exactly_the_call_without_the_argument(monkeypatc
                             generator=torch.Generator(device=DEV).manual_seed(5), **kw)
         bids, sc = BeamDecoder(model, 3, 4, use_graph=False).generate(tb, 220, temperature=T, repitition_penalty=REP, **kw)
         runs.append((list(names), ids, sids, bids, sc))
-        assert dec.refrain is None and dec.rhyme is None and dec.tmpl is None and dec.lines is None and dec.copy_cols is None
+        assert dec.rules.refrain is None and dec.rules.rhyme is None and dec.rules.tmpl is None and dec.rules.lines is None and dec.copy_cols is None
         assert dec.skipped_steps == 0
     assert runs[0][0] == runs[1][0] and not any("_refrain" in x or "_rhyme" in x or "_lines" in x for x in runs[0][0])
     assert all(torch.equal(a, b) for a, b in zip(runs[0][1:], runs[1][1:]))
@@ -374,12 +374,12 @@ def test_refrain_scheme_none_is_exactly_the_call_without_the_argument(monkeypatc
     assert torch.equal(a, b) and torch.equal(a, runs[0][1]) and set(dec.graphs) == set(fresh.graphs)
     keys = set(dec.graphs)
     c = dec.generate(tb, 220, temperature=T, repitition_penalty=REP, refrain_scheme="..........")       # the *_refrain entries, nothing asked
-    assert torch.equal(a, c) and dec.refrain is not None and dec.copy_cols is None and dec.skipped_steps == 0
+    assert torch.equal(a, c) and dec.rules.refrain is not None and dec.copy_cols is None and dec.skipped_steps == 0
     new = set(dec.graphs) - keys
     assert new and all("refrain" in k and k[0] for k in new)                   # head steps only; the others replay the graphs they had
     d = dec.generate(tb, 220, temperature=T, repitition_penalty=REP, refrain_scheme="AA")
     assert not torch.equal(a, d) and dec.skipped_steps == CAP
-    assert torch.equal(dec.generate(tb, 220, temperature=T, repitition_penalty=REP), a) and dec.refrain is None and dec.lines is None
+    assert torch.equal(dec.generate(tb, 220, temperature=T, repitition_penalty=REP), a) and dec.rules.refrain is None and dec.rules.lines is None
 
 
 # ------------------------------------------------------------------ 8. full size
@@ -409,3 +409,40 @@ def test_full_size_bf16_under_a_scheme_is_bit_stable_and_repeats_its_lines():
     assert torch.equal(dec.generate(batch, Ln, top_k=10, top_p=0.7, generator=torch.Generator(device=DEV).manual_seed(21), **args), s1)
     sb = s1[:, 1:].reshape(B, 10, SENT)[:, :, :CAP]
     assert all(torch.equal(sb[:, l], sb[:, int(src[l])]) for l in range(10) if src[l] >= 0) and not torch.equal(s1, g1)
+
+
+# ------------------------------------------------------------------ 9. lanes
+@pytest.mark.parametrize("use_graph", [True, False])
+def test_two_lanes_read_their_own_rows_of_every_table(use_graph):
+    """Four rows whose prefix lengths, bounds, templates, rhyme and refrain schemes all differ between rows 0-1 and rows 2-3, under
+    no_repeat_ngram_size=3 and a min_p draw: a decoder of two lanes gives every row a view of its own rows of each table (and of the
+    uniforms), so its ids are those of the one-lane decoder bit for bit, replayed and eager.  Three lines: the third carries the
+    copies."""
+    fx, sh, w, table, batch = setup_case("tiny_s5")
+    model, tb = build("tiny_s5", "bf16")
+    tb4 = {k: torch.cat([v, v[:1]], 0) for k, v in tb.items()}
+    cid = content_ids(fx)
+    classes, _ = fixture_rhymes(fx)
+    length = 3 * SENT
+    pre = [[1], [1, cid[22], cid[23]], [1, cid[20]], [1, cid[21], cid[5], cid[22], cid[23]]]
+    kw = dict(temperature=T, repitition_penalty=REP, top_k=0, top_p=0.0, min_p=0.05, prefix=pre, no_repeat_ngram_size=3,
+              line_lengths=[[(3, 8), (3, 8), (3, 8)], [(2, 6), (3, 8), None], [(3, 8), (2, 9), (3, 8)], [(4, 7), (3, 8), (3, 8)]],
+              line_end_ids=[None, [None, [cid[7], cid[8], cid[9]], None], None, None],
+              templates=[None, [None, (cid[5], Ellipsis)], [None, (cid[22], None, Ellipsis)], None],
+              rhyme_scheme=["AA", "A.A", "AA", "AA"], rhyme_classes=classes, refrain_scheme=["A.A", None, "A.A", ".AA"])
+    tabs = refrain_tables(sh, 4, length, kw["refrain_scheme"], 3, **{k: kw[k] for k in ("prefix", "line_lengths", "line_end_ids", "templates",
+                                                                                       "rhyme_scheme", "rhyme_classes")})
+    for t in (tabs.lo, tabs.hi, tabs.set_of, tabs.tmpl, tabs.lead, tabs.src):   # (rows 2-3 are not rows 0-1 in any table)
+        assert not np.array_equal(t[:2], t[2:])
+    gen = lambda: torch.Generator(device=DEV).manual_seed(17)                    # noqa: E731
+    one = GreedyDecoder(model, 4, max_len=length, lanes=1, use_graph=use_graph)
+    two = GreedyDecoder(model, 4, max_len=length, lanes=2, use_graph=use_graph)
+    a = one.generate(tb4, length, generator=gen(), **kw)
+    b = two.generate(tb4, length, generator=gen(), **kw)
+    assert torch.equal(a, b), (a.tolist(), b.tolist())
+    assert bool(two.graphs) == use_graph and len(two.children) == 2
+    rows = a.cpu().tolist()
+    for r, p in enumerate(pre):
+        assert rows[r][:len(p)] == p and rhyme_violations(rows[r], tabs, r, start=len(p)) == [], r
+    assert lines_of(rows[0])[2] == lines_of(rows[0])[0] and lines_of(rows[3])[2] == lines_of(rows[3])[1]
+    assert not torch.equal(a[0], a[3])                                          # (the same prompt under other rules and draws)

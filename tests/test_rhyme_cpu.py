@@ -16,7 +16,7 @@ import torch
 
 import test_lines_cpu as L
 from mmtg_amd import hip
-from mmtg_amd.decode import BeamDecoder, GreedyDecoder, LineTables, check_lines, select_forms
+from mmtg_amd.decode import BeamDecoder, GreedyDecoder, StepRules, LineTables, check_lines, select_forms
 from test_beam_cpu import SENT, setup_case, start_row
 from test_lines_cpu import CAP, line_lengths_of, line_rule
 from test_ngram_cpu import _Eng, _Model, banned_ids
@@ -404,8 +404,10 @@ def test_select_forms_names_the_rhyme_entries_on_head_steps_only(monkeypatch):
             for tm in (None, torch.full((B, 3, CAP), -1, dtype=torch.int32)):
                 for distinct in (False, True):
                     fe = i32(B)
-                    dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb, use_fixed=prefix,
-                             ngram=3, lines=lines, tmpl=tm, rhyme=(cof, lead, distinct), fixed_end=fe, logits=torch.zeros(B, V),
+                    logits = torch.zeros(B, V)
+                    dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb,
+                             rules=StepRules(prefix=prefix, ngram=3, lines=lines, tmpl=tm, rhyme=(cof, lead, distinct)), copy_step=False,
+                             fixed_end=fe, logits=logits, select_rows=B, select_logits=logits,
                              seq=torch.zeros(B, 64, dtype=torch.long), pos=i32(1), pos_next=i32(1), uniforms=torch.zeros(70, B),
                              keep=i32(B, 64), rows=i32(B, 64), scores=torch.zeros(B), cand_val=torch.zeros(B, nb), cand_id=i32(B, nb),
                              params=(1.1, 1.5, 1, 0.0))
@@ -430,13 +432,12 @@ def test_select_forms_names_the_rhyme_entries_on_head_steps_only(monkeypatch):
                     assert [c[0] for c in calls] == (["mmtg_decode_beam_candidates_rhyme"] if with_head else []) + ["mmtg_decode_beam_merge" + held]
                     if with_head:
                         assert calls[0][1][-4:-1] == (cof.data_ptr(), lead.data_ptr(), int(distinct))
-    # a decoder without the attribute (or with None) takes the entries and keys it always took
-    dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, use_fixed=False, ngram=0, lines=lines[:2] + (None, None), tmpl=None,
-             fixed_end=i32(B), logits=torch.zeros(B, V), seq=torch.zeros(B, 64, dtype=torch.long), pos=i32(1), pos_next=i32(1),
-             params=(1.1, 1.5, 1, 0.0))
+    # a record built without the argument (or with None) takes the entries and keys it always took
+    logits = torch.zeros(B, V)
+    dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, copy_step=False, fixed_end=i32(B), logits=logits, select_rows=B,
+             select_logits=logits, seq=torch.zeros(B, 64, dtype=torch.long), pos=i32(1), pos_next=i32(1), params=(1.1, 1.5, 1, 0.0))
     for extra in ({}, {"rhyme": None}):
-        for k, v in extra.items():
-            setattr(dec, k, v)
+        dec.rules = StepRules(lines=lines[:2] + (None, None), **extra)
         del calls[:]
         GreedyDecoder._select(dec, True)
         assert [c[0] for c in calls] == ["mmtg_decode_select_lines"]

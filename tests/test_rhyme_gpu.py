@@ -403,7 +403,7 @@ def test_rhyme_scheme_none_is_exactly_the_call_without_the_argument(monkeypatch)
                             generator=torch.Generator(device=DEV).manual_seed(5), **kw)
         bids, sc = BeamDecoder(model, 3, 4, use_graph=False).generate(tb, 220, temperature=T, repitition_penalty=REP, **kw)
         runs.append((list(names), ids, sids, bids, sc))
-        assert dec.rhyme is None and dec.tmpl is None and dec.lines is None
+        assert dec.rules.rhyme is None and dec.rules.tmpl is None and dec.rules.lines is None
     assert runs[0][0] == runs[1][0] and not any("_rhyme" in x or "_tmpl" in x or "_lines" in x for x in runs[0][0])
     assert all(torch.equal(a, b) for a, b in zip(runs[0][1:], runs[1][1:]))
     monkeypatch.undo()
@@ -413,12 +413,12 @@ def test_rhyme_scheme_none_is_exactly_the_call_without_the_argument(monkeypatch)
     assert torch.equal(a, b) and torch.equal(a, runs[0][1]) and set(dec.graphs) == set(fresh.graphs)
     keys = set(dec.graphs)
     c = dec.generate(tb, 220, temperature=T, repitition_penalty=REP, rhyme_scheme="..........", rhyme_classes=classes)   # the *_rhyme entries, nothing asked
-    assert torch.equal(a, c) and dec.rhyme is not None
+    assert torch.equal(a, c) and dec.rules.rhyme is not None
     new = set(dec.graphs) - keys
     assert new and all("rhyme" in k and k[0] for k in new)                     # head steps only; the others replay the graphs they had
     d = dec.generate(tb, 220, temperature=T, repitition_penalty=REP, line_lengths=bounds, rhyme_scheme="AA", rhyme_classes=classes)
     assert not torch.equal(a, d)
-    assert torch.equal(dec.generate(tb, 220, temperature=T, repitition_penalty=REP), a) and dec.rhyme is None and dec.lines is None
+    assert torch.equal(dec.generate(tb, 220, temperature=T, repitition_penalty=REP), a) and dec.rules.rhyme is None and dec.rules.lines is None
 
 
 # ------------------------------------------------------------------ 5. full size

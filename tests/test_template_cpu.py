@@ -15,7 +15,7 @@ import torch
 
 import test_lines_cpu as L
 from mmtg_amd import hip
-from mmtg_amd.decode import BeamDecoder, GreedyDecoder, LineTables, check_lines, select_forms
+from mmtg_amd.decode import BeamDecoder, GreedyDecoder, StepRules, LineTables, check_lines, select_forms
 from test_beam_cpu import SENT, setup_case, start_row
 from test_lines_cpu import CAP, line_lengths_of, line_rule
 from test_ngram_cpu import _Eng, _Model, banned_ids
@@ -332,8 +332,10 @@ def test_select_forms_names_the_template_entries_on_head_steps_only(monkeypatch)
         for prefix in (False, True):
             for ngram in (0, 3):
                 fe = i32(B)
-                dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb, use_fixed=prefix,
-                         ngram=ngram, lines=lines, tmpl=tm, fixed_end=fe, logits=torch.zeros(B, V), seq=torch.zeros(B, 64, dtype=torch.long),
+                logits = torch.zeros(B, V)
+                dec = NS(eng=NS(sh=NS(P=5, msl=SENT - 2, V=V), layout=NS(Vpad=V)), B=B, nb=nb, n_prompts=B // nb,
+                         rules=StepRules(prefix=prefix, ngram=ngram, lines=lines, tmpl=tm), copy_step=False, fixed_end=fe, logits=logits,
+                         select_rows=B, select_logits=logits, seq=torch.zeros(B, 64, dtype=torch.long),
                          pos=i32(1), pos_next=i32(1), uniforms=torch.zeros(70, B), keep=i32(B, 64), rows=i32(B, 64),
                          scores=torch.zeros(B), cand_val=torch.zeros(B, nb), cand_id=i32(B, nb), params=(1.1, 1.5, 1, 0.0))
                 held = "_fixed" if prefix else ""

@@ -366,7 +366,7 @@ def test_templates_none_is_exactly_the_call_without_the_argument(monkeypatch):
                             generator=torch.Generator(device=DEV).manual_seed(5), **kw)
         bids, sc = BeamDecoder(model, 3, 4, use_graph=False).generate(tb, 220, temperature=T, repitition_penalty=REP, **kw)
         runs.append((list(names), ids, sids, bids, sc))
-        assert dec.tmpl is None and dec.lines is None
+        assert dec.rules.tmpl is None and dec.rules.lines is None
     assert runs[0][0] == runs[1][0] and not any("_tmpl" in x or "_lines" in x for x in runs[0][0])
     assert all(torch.equal(a, b) for a, b in zip(runs[0][1:], runs[1][1:]))
     monkeypatch.undo()
@@ -375,10 +375,10 @@ def test_templates_none_is_exactly_the_call_without_the_argument(monkeypatch):
     b = dec.generate(tb, 220, temperature=T, repitition_penalty=REP, templates=None)
     assert torch.equal(a, b) and torch.equal(a, runs[0][1]) and set(dec.graphs) == set(fresh.graphs)
     c = dec.generate(tb, 220, temperature=T, repitition_penalty=REP, templates=[None])           # the *_tmpl entries, nothing asked
-    assert torch.equal(a, c) and any("tmpl" in k for k in dec.graphs) and dec.tmpl is not None
+    assert torch.equal(a, c) and any("tmpl" in k for k in dec.graphs) and dec.rules.tmpl is not None
     d = dec.generate(tb, 220, temperature=T, repitition_penalty=REP, templates=[(50, Ellipsis)])
     assert int(d[0, 1]) == 50 and not torch.equal(a, d)
-    assert torch.equal(dec.generate(tb, 220, temperature=T, repitition_penalty=REP), a) and dec.tmpl is None and dec.lines is None
+    assert torch.equal(dec.generate(tb, 220, temperature=T, repitition_penalty=REP), a) and dec.rules.tmpl is None and dec.rules.lines is None
 
 
 # ------------------------------------------------------------------ 5. full size

@@ -173,10 +173,10 @@ def test_the_entries_are_declared_bound_and_exported_and_the_abi_version_is_12()
 @pytest.mark.parametrize("kw", [dict(min_p=0.05), dict(typical_p=0.9), dict(epsilon_cutoff=1e-3), dict(eta_cutoff=1e-3)])
 def test_the_search_decoders_refuse_the_arguments_with_a_reason(kw):
     with pytest.raises(ValueError, match="search draws nothing"):
-        BeamDecoder._no_warp(**kw)
+        BeamDecoder._refuse(**kw)
     with pytest.raises(ValueError, match="search draws nothing"):
         ContrastiveDecoder._refuse(**kw)
-    BeamDecoder._no_warp(*WARP_OFF)
+    BeamDecoder._refuse(**dict(zip(NAMES, WARP_OFF)))
     ContrastiveDecoder._refuse(**dict(zip(NAMES, WARP_OFF)))
     with pytest.raises(ValueError, match=next(iter(kw))):                        # out of range is said first, by name
-        BeamDecoder._no_warp(**{next(iter(kw)): 7.0})
+        BeamDecoder._refuse(**{next(iter(kw)): 7.0})

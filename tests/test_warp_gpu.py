@@ -342,7 +342,7 @@ def test_the_four_defaults_are_exactly_the_call_without_the_arguments(monkeypatc
     new = set(dec.graphs) - keys
     assert new and set(warp_keys(dec)) == new and all(k[0] for k in new)         # head steps only; the others replay the graphs they had
     c = dec.generate(tb, 2 * SENT, temperature=T, repitition_penalty=REP, top_k=10, top_p=0.7, generator=torch.Generator(device=DEV).manual_seed(5))
-    assert torch.equal(c, a) and dec.warp == WARP_OFF
+    assert torch.equal(c, a) and dec.rules.warp == WARP_OFF
 
 
 # ------------------------------------------------------------------ 7. the greedy limits

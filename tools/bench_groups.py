@@ -62,7 +62,7 @@ def main():
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         steps = n_steps - dec.first_pos
-        return dict(leg=leg, groups=dec.groups, penalty=dec.diversity_penalty, prompts=a.prompts, beams=a.beams, length=a.length,
+        return dict(leg=leg, groups=dec.rules.groups, penalty=dec.rules.diversity_penalty, prompts=a.prompts, beams=a.beams, length=a.length,
                     steps=steps, us_per_step=1e6 * (t2 - t1) / steps)
 
     names = tuple(a.legs.split(","))
