@@ -434,7 +434,11 @@ MMTG_API int mmtg_slab_sum(const float* part, int splits, long stride, float* ds
  *           lo plane planeA / planeB ELEMENTS behind the hi plane -- and every K slice is walked three times,
  *           A_hi^T B_hi + A_lo^T B_hi + A_hi^T B_lo (see mmtg_gemm_x3); planeA / planeB are ignored otherwise.
  * config 6 (= 2 | 4): the same products on combined stages -- a 64 KB stage holds the K tile of all four planes and every fragment
- *           pair feeds the three MFMA passes (two workgroups per CU; a third fewer bytes through the L2 -> LDS port).      */
+ *           pair feeds the three MFMA passes (two workgroups per CU; a third fewer bytes through the L2 -> LDS port).
+ * config 8: 256x256 tiles, ONE 1024-thread workgroup per CU (sixteen waves, a 64x64 quadrant each) over a ring of three 32-k
+ *           stages (96 KB of LDS), two stages in flight while one is read (65536 floats and 16 counters per tile and split; K
+ *           slices are multiples of 64).  Same summation order per element as config 0: bit-equal to it at an equal split
+ *           count.  (bf16 operands only: not combined with 2 / 4.)                                                          */
 typedef struct mmtg_wgrad_problem {
     const void* A; long lda;
     const void* B; long ldb;

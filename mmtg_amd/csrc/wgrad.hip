@@ -22,7 +22,9 @@
 // The last arriver resets its counter: the counter buffer is zero before and after every launch.
 //
 // Main loop = the single-stage, four-workgroups-per-CU kernel of gemm.hip (gemm_occ4_kernel<true, true>): one
-// 32 KB LDS stage per 128x128 workgroup filled by LDS-DMA, K-strided images read with ds_read_b64_tr_b16.
+// 32 KB LDS stage per 128x128 workgroup filled by LDS-DMA, K-strided images read with ds_read_b64_tr_b16.  The bf16 training
+// step runs the ring form at the end of the file instead (wgrad_group_ring_kernel, config 8): the same tiles of work per wave,
+// the same sum order and epilogue, sixteen waves of a CU as one workgroup over three stages.
 #include "gemm_common.h"
 #include <stdlib.h>
 
@@ -455,6 +457,120 @@ __global__ __launch_bounds__(512, 1) void wgrad_group_p8_kernel(WgArgs a) {
     wg_reduce_store<false, 8, 256 * 256>(a, P.C, P.ldc, M, N, m0 + wr * 128, n0 + wc * 64, t, split, 8, wave, lane, acc, smem + wave * 4096);
 }
 
+// ------------------------------------------------------------------ 256x256 ring form (one 16-wave workgroup per CU)
+// The loop of the 128x128 kernel is held by fill LATENCY: each of the four workgroups of a CU owns one 32 KB stage and can
+// request K tile t + 1 only after all its waves have read tile t (<= 64 KB in flight per CU).  Here the sixteen waves of a CU
+// are ONE 1024-thread workgroup on a 256x256 tile (4x4 waves, a 64x64 quadrant each: the accumulators and the transposed
+// fragment reads of the 128x128 kernel), over a ring of three 32-k stages -- a stage = an A image of 32 k-rows x 256 columns
+// (16 KB, K-strided, the swizzle of gemm_common.h at 512-byte rows) + a B image of the same size.  Every wave issues two 1 KB
+// LDS-DMA requests per stage (its two k-rows of A and of B); while stage s is read, stages s + 1 and s + 2 are in flight or
+// landed; half the fill bytes per MAC of the 128x128 tiles.  Per stage: a counted vmcnt(2) (my share of stage s has landed),
+// ONE raw barrier (everybody's has; everybody is done reading stage s - 1), the requests of stage s + 2 into the slot of
+// stage s - 1, eight fragment pairs, sixteen MFMAs.  Requests past the K slice go out of range per lane (zeros), so the count
+// is the same in every iteration.  Per output element k ascends in 32-deep MFMA blocks exactly as in the 128x128 kernel and
+// the epilogue is the same: for an equal split count the results are bit-equal to config 0.
+__device__ __forceinline__ void wg_raw_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// The sixteen transposed reads of a stage (A fragments at o + 0 / + 4 k-rows, B fragments IMG = 16 KB behind) and their wait as
+// ONE assembly statement.  hipcc orders every LDS read it can see behind ALL outstanding LDS-DMA requests (an LDS-DMA is a
+// pending LDS write it cannot tell apart by address): a vmcnt(0) in front of the first read of every stage, which would drain
+// the two stages the ring keeps in flight.  The ring's own protocol (counted vmcnt + barrier, see the kernel) orders these reads.
+__device__ __forceinline__ void wgr_read_stage(unsigned base, const int (&oa)[4], const int (&ob)[4], bf16x8 (&fa)[4], bf16x8 (&fb)[4]) {
+    s16x4 al[4], ah[4], bl[4], bh[4];
+    unsigned pa[4], pb[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { pa[i] = base + (unsigned)oa[i]; pb[i] = base + (unsigned)ob[i]; }
+    asm volatile(
+        "ds_read_b64_tr_b16 %0, %16\n\t"
+        "ds_read_b64_tr_b16 %1, %16 offset:2048\n\t"
+        "ds_read_b64_tr_b16 %2, %17\n\t"
+        "ds_read_b64_tr_b16 %3, %17 offset:2048\n\t"
+        "ds_read_b64_tr_b16 %4, %18\n\t"
+        "ds_read_b64_tr_b16 %5, %18 offset:2048\n\t"
+        "ds_read_b64_tr_b16 %6, %19\n\t"
+        "ds_read_b64_tr_b16 %7, %19 offset:2048\n\t"
+        "ds_read_b64_tr_b16 %8, %20 offset:16384\n\t"
+        "ds_read_b64_tr_b16 %9, %20 offset:18432\n\t"
+        "ds_read_b64_tr_b16 %10, %21 offset:16384\n\t"
+        "ds_read_b64_tr_b16 %11, %21 offset:18432\n\t"
+        "ds_read_b64_tr_b16 %12, %22 offset:16384\n\t"
+        "ds_read_b64_tr_b16 %13, %22 offset:18432\n\t"
+        "ds_read_b64_tr_b16 %14, %23 offset:16384\n\t"
+        "ds_read_b64_tr_b16 %15, %23 offset:18432\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&v"(al[0]), "=&v"(ah[0]), "=&v"(al[1]), "=&v"(ah[1]), "=&v"(al[2]), "=&v"(ah[2]), "=&v"(al[3]), "=&v"(ah[3]),
+          "=&v"(bl[0]), "=&v"(bh[0]), "=&v"(bl[1]), "=&v"(bh[1]), "=&v"(bl[2]), "=&v"(bh[2]), "=&v"(bl[3]), "=&v"(bh[3])
+        : "v"(pa[0]), "v"(pa[1]), "v"(pa[2]), "v"(pa[3]), "v"(pb[0]), "v"(pb[1]), "v"(pb[2]), "v"(pb[3])
+        : "memory");
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        fa[i] = __builtin_shufflevector(__builtin_bit_cast(bf16x4, al[i]), __builtin_bit_cast(bf16x4, ah[i]), 0, 1, 2, 3, 4, 5, 6, 7);
+        fb[i] = __builtin_shufflevector(__builtin_bit_cast(bf16x4, bl[i]), __builtin_bit_cast(bf16x4, bh[i]), 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+}
+
+__global__ __launch_bounds__(1024, 1) void wgrad_group_ring_kernel(WgArgs a) {
+    constexpr int TB = 256, BK = 32, IMG = BK * TB * 2, STAGE = 2 * IMG;      // bytes: 16 KB per image, 32 KB per stage
+    extern __shared__ __attribute__((aligned(16))) char smem[];    // three stages
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 2, wn = wave & 3;
+    int t, split, m0, n0;
+    const WgProb& P = a.pr[wg_locate<TB>(a, t, split, m0, n0)];
+    const int M = P.M, N = P.N;
+    const long lda = P.lda, ldb = P.ldb;
+    const int kbeg = split * a.kper;
+    const int klen = max(0, min(a.K, kbeg + a.kper) - kbeg);
+    const int ns = (klen + BK - 1) / BK;
+    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(P.A), 0, P.bytesA, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(P.B), 0, P.bytesB, 0x00020000);
+    const int sa0 = (int)(((long)kbeg * lda + m0) * 2), sb0 = (int)(((long)kbeg * ldb + n0) * 2);
+    const int stepa = (int)((long)BK * lda * 2), stepb = (int)((long)BK * ldb * 2);
+    // block `wave` of an image = k-rows 2 wave, 2 wave + 1 (512 bytes each); a row at or past the end of the K slice is requested
+    // out of range PER LANE (the stage's row offset travels in the scalar offset, which the descriptor's range check does not see)
+    const int va = dma_voff<true, TB>(lda, m0, M, BK, wave, lane);
+    const int vb = dma_voff<true, TB>(ldb, n0, N, BK, wave, lane);
+    const int kl = wave * 2 + (lane >> 5);
+    int oa[4], ob[4];
+    ks_offsets<TB, 4>(wm * 64, lane, oa);
+    ks_offsets<TB, 4>(wn * 64, lane, ob);
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // requests of stage st into the ring slot at byte offset slot (wave-uniform)
+    auto issue = [&](int st, int slot) {
+        const bool in = st < ns, ok = st * BK + kl < klen;
+        const int soa = __builtin_amdgcn_readfirstlane(in ? sa0 + st * stepa : 0);
+        const int sob = __builtin_amdgcn_readfirstlane(in ? sb0 + st * stepb : 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, LDS_PTR(void, smem + slot + wave * 1024), 16, ok ? va : OOB, soa, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, LDS_PTR(void, smem + slot + IMG + wave * 1024), 16, ok ? vb : OOB, sob, 0, 0);
+    };
+    issue(0, 0);
+    issue(1, STAGE);
+    const unsigned lds0 = (unsigned)(unsigned long)LDS_PTR(char, smem);
+    int rd = 0, wr = 2 * STAGE;                        // slots of stage s and of stage s + 2 (= the slot of stage s - 1)
+    for (int s = 0; s < ns; ++s) {
+        wait_vmcnt<2>();                               // my two requests of stage s have landed
+        wg_raw_barrier();                              // ... everybody's have, and every wave is done reading stage s - 1:
+        issue(s + 2, wr);                              // its slot is re-requested only behind this barrier
+        bf16x8 fa[4], fb[4];
+        wgr_read_stage(lds0 + rd, oa, ob, fa, fb);
+        // (swapped operands: a lane then holds 4 consecutive columns of row l15 -- row-contiguous stores)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) mma16(fb[j], fa[i], acc[i][j]);
+        wr = rd;
+        rd = rd == 2 * STAGE ? 0 : rd + STAGE;
+    }
+    wait_vmcnt<0>();                                   // the zero-fill requests past the slice
+    wg_raw_barrier();                                  // every wave is done with the ring: it becomes the waves' private epilogue scratch
+    wg_reduce_store<false, 4, TB * TB>(a, P.C, P.ldc, M, N, m0 + wm * 64, n0 + wn * 64, t, split, 16, wave, lane, acc, smem + wave * 4096);
+}
+
 }  // namespace
 
 extern "C" int mmtg_wgrad_group(int config, int n, const mmtg_wgrad_problem* probs, int K, int splits, float* ws, long ws_floats,
@@ -462,9 +578,9 @@ extern "C" int mmtg_wgrad_group(int config, int n, const mmtg_wgrad_problem* pro
     const bool x3 = (config & 2) != 0;             // split-precision operands (plane pairs), 128x128 tiles only
     const bool x3c = x3 && (config & 4) != 0;      // ... on combined stages (all four planes of a K tile per stage, two workgroups per CU)
     config &= ~6;
-    MMTG_REQUIRE(config == 0 || (config == 1 && !x3),
-                 "wgrad_group: config 0 (128x128 tiles), 1 (256x256 eight-phase tiles), 2 (128x128 tiles, x3 operands) or 6 (x3, combined stages)");
-    const int TB = config ? 256 : 128, NWV = config ? 8 : 4, KQ = config ? 128 : 64;
+    MMTG_REQUIRE(config == 0 || ((config == 1 || config == 8) && !x3),
+                 "wgrad_group: config 0 (128x128 tiles), 1 (256x256 eight-phase tiles), 8 (256x256 tiles, 16-wave ring), 2 (128x128 tiles, x3 operands) or 6 (x3, combined stages)");
+    const int TB = config ? 256 : 128, NWV = config == 8 ? 16 : config ? 8 : 4, KQ = config == 1 ? 128 : 64;
     MMTG_REQUIRE(n >= 1 && n <= WG_MAXP && probs, "wgrad_group: 1..%d problems", WG_MAXP);
     MMTG_REQUIRE(K > 0 && splits >= 1, "wgrad_group: K and splits must be positive");
     WgArgs a;
@@ -515,6 +631,18 @@ extern "C" int mmtg_wgrad_group(int config, int n, const mmtg_wgrad_problem* pro
             attr8_done = true;
         }
         hipLaunchKernelGGL(wgrad_group_p8_kernel, dim3(tiles * splits), dim3(512), shm8, s, a);
+        MMTG_LAUNCH_CHECK("wgrad_group");
+        return MMTG_OK;
+    }
+    if (config == 8) {
+        const size_t shmr = 3 * 2 * 32 * 256 * 2;          // three stages of (A | B) images, 32 k-rows x 256 columns each
+        static bool attrr_done = false;
+        if (!attrr_done) {
+            if (hipFuncSetAttribute((const void*)wgrad_group_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmr) != hipSuccess)
+                MMTG_FAIL(MMTG_ERR_HIP, "wgrad_group: cannot raise dynamic LDS to %zu bytes", shmr);
+            attrr_done = true;
+        }
+        hipLaunchKernelGGL(wgrad_group_ring_kernel, dim3(tiles * splits), dim3(1024), shmr, s, a);
         MMTG_LAUNCH_CHECK("wgrad_group");
         return MMTG_OK;
     }

@@ -249,7 +249,17 @@ _ENC_STREAMS = _os.environ.get("MMTG_ENC_STREAMS", "0") != "0"
 # bf16x3f: the encoder / fuser backward on the bf16 kernels as well (MMTG_HYBRID_ENC_BF16=0: exact fp32, the round's first version)
 _HYBRID_ENC_BF16 = _os.environ.get("MMTG_HYBRID_ENC_BF16", "1") != "0"
 _X3_WG_CFG = 6 if _os.environ.get("MMTG_WGRAD_X3_COMBINED", "1") != "0" else 2
-_WGRAD_GROUP_CFG = int(_os.environ.get("MMTG_WGRAD_GROUP_CFG", "0"))          # 0: 128x128 tiles, four workgroups per CU; 1: 256x256 eight-phase
+# 0: 128x128 tiles, four workgroups per CU; 1: 256x256 eight-phase; 2: 256x256, one 16-wave workgroup per CU over a 3-deep ring of
+# 32-k stages (mmtg_wgrad_group's config 8 -- its 2 is the split-precision form).  Default 2: 14.71 -> 14.07 ms per step over three
+# alternating pairs, the launch 275 -> 228 us, parameters and gradients bit-equal to config 0's (docs/experiments.md, last section)
+_WGRAD_GROUP_CFG = int(_os.environ.get("MMTG_WGRAD_GROUP_CFG", "2"))
+
+
+def _group_cfg(D, x3=False):
+    """mmtg_wgrad_group configuration of the bf16 grouped launches (256x256 tiles need D >= 256 to fill them)."""
+    if x3 or D < 256 or _WGRAD_GROUP_CFG not in (1, 2):
+        return 0
+    return hip.WGRAD_RING if _WGRAD_GROUP_CFG == 2 else 1
 
 
 def _group_splits(tiles, K, slots=1024):
@@ -1266,9 +1276,10 @@ class Engine:
         elif _WGRAD_GROUP and _LMHEAD_GROUP and self.dtype == hip.BF16 and M >= 256 and D % 8 == 0 and Vp % 8 == 0:
             # the tied embedding's gradient through the grouped kernel too: no fp32 atomics (bit-reproducible), and the
             # gradient is WRITTEN, so the lazy zero_grad can skip its 41 MB (the type-embedding rows are added later)
-            tiles = hip.wgrad_group_sizes(((Vp, D),), 1, 0)[0]
-            hs = _LMHEAD_GROUP_SPLITS or _group_splits(tiles, M)
-            _, nws, ncnt = hip.wgrad_group_sizes(((Vp, D),), hs, 0)
+            hcfg = hip.WGRAD_RING if _group_cfg(D) == hip.WGRAD_RING else 0      # (the ring form: the same rule on its 256 slots)
+            tiles = hip.wgrad_group_sizes(((Vp, D),), 1, hcfg)[0]
+            hs = _LMHEAD_GROUP_SPLITS or _group_splits(tiles, M, 256 if hcfg else 1024)
+            _, nws, ncnt = hip.wgrad_group_sizes(((Vp, D),), hs, hcfg)
             # (a workspace of its own: under MMTG_WGRAD_STREAM this launch may still be pending on the side stream when the
             #  block launches size theirs -- a shared name could reallocate, i.e. free, the buffer under it)
             hws = self.buf("wgrad_group_ws_head", (nws,), torch.float32) if hs > 1 else None
@@ -1279,9 +1290,9 @@ class Engine:
             if side is not None:        # beside the LM head's dgrad, ln_f and the last block's chain (reads dlogits / hf only)
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
-                    hip.wgrad_group([(dlogits, a["hf"], self.Gp("wte"), Vp, D, Vp, D, D)], M, hs, hws, hcnt, accumulate=not self.wgrad_overwrite)
+                    hip.wgrad_group([(dlogits, a["hf"], self.Gp("wte"), Vp, D, Vp, D, D)], M, hs, hws, hcnt, accumulate=not self.wgrad_overwrite, config=hcfg)
             else:
-                hip.wgrad_group([(dlogits, a["hf"], self.Gp("wte"), Vp, D, Vp, D, D)], M, hs, hws, hcnt, accumulate=not self.wgrad_overwrite)
+                hip.wgrad_group([(dlogits, a["hf"], self.Gp("wte"), Vp, D, Vp, D, D)], M, hs, hws, hcnt, accumulate=not self.wgrad_overwrite, config=hcfg)
             if self.wgrad_overwrite and self._ow_rec is not None:
                 self._ow_rec[1].append((self.layout.pack_range["wte"][0], Vp * D))
         else:
@@ -1309,7 +1320,7 @@ class Engine:
         dmask_b = (self.buf("d_masked_b", (M, D)) if group else dmask) if (pr > 0 and not x3) else None
         if group:
             gshapes = ((D, 4 * D), (4 * D, D), (D, D), (D, 3 * D))
-            gcfg = 1 if (_WGRAD_GROUP_CFG and D >= 256 and not x3) else 0
+            gcfg = _group_cfg(D, x3)
             gtiles = hip.wgrad_group_sizes(gshapes, 1, gcfg)[0]
             gsplits = _group_splits_x3(gtiles, M) if x3 else _group_splits(gtiles, M, 256 if gcfg else 1024)
             _, nws, ncnt = hip.wgrad_group_sizes(gshapes, gsplits, gcfg)

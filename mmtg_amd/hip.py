@@ -749,9 +749,12 @@ class WgradProblem(C.Structure):
                 ("planeA", C.c_long), ("planeB", C.c_long)]
 
 
+WGRAD_RING = 8      # mmtg_wgrad_group config: 256x256 tiles, one 16-wave workgroup per CU over a 3-deep ring of 32-k stages
+
+
 def wgrad_group_sizes(shapes, splits, config=0):
     """(tiles, workspace floats, counters) of a grouped launch over problems of the given (M, N) shapes."""
-    tb, nw = (256, 8) if config else (128, 4)
+    tb, nw = (256, 16) if config == WGRAD_RING else (256, 8) if config else (128, 4)
     tiles = sum(((M + tb - 1) // tb) * ((N + tb - 1) // tb) for (M, N) in shapes)
     return tiles, tiles * splits * tb * tb, tiles * nw
 
@@ -759,7 +762,7 @@ def wgrad_group_sizes(shapes, splits, config=0):
 def wgrad_group(problems, K, splits, ws, counters, accumulate=False, config=0):
     """Grouped weight gradients C (+)= A^T B (include/mmtg_hip.h, mmtg_wgrad_group).
     problems: list of (A [K, lda] bf16, B [K, ldb] bf16, C [M, ldc] f32, M, N[, lda, ldb, ldc]).
-    config 2 (x3): A and B are Planes (hi | lo plane pairs)."""
+    config 2 (x3): A and B are Planes (hi | lo plane pairs); config WGRAD_RING: the 16-wave ring form of the bf16 product."""
     arr = (WgradProblem * len(problems))()
     for i, pr in enumerate(problems):
         A, B, C_, M, N = pr[:5]

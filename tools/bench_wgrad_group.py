@@ -62,3 +62,7 @@ for cold in (False, True):
             t8 = hip.wgrad_group_sizes([(M, N) for (_, _, M, N) in shapes], S, 1)[0]
             t = timeit(grouped(S, 1), cold)
             print("%-5s grouped eight-phase 256x256, %d K split(s), %4d workgroups %7.1f us  %6.0f TFLOP/s" % ("cold" if cold else "warm", S, t8 * S, t, flops / t / 1e6))
+        for S in [int(x) for x in os.environ.get("SPLITSR", "1,2").split(",")]:
+            tr = hip.wgrad_group_sizes([(M, N) for (_, _, M, N) in shapes], S, hip.WGRAD_RING)[0]
+            t = timeit(grouped(S, hip.WGRAD_RING), cold)
+            print("%-5s grouped 16-wave ring 256x256, %d K split(s), %4d workgroups %7.1f us  %6.0f TFLOP/s" % ("cold" if cold else "warm", S, tr * S, t, flops / t / 1e6))
