@@ -405,6 +405,30 @@ MMTG_API int mmtg_sumsq(const float* x, long n, float* out, float* ws, long ws_f
 MMTG_API int mmtg_adamw(float* p, const float* g, float* m, float* v, void* p_bf16, void* p_lo, long n,
                float lr, float beta1, float beta2, float eps, float wd, int step,
                const float* normsq, float max_norm, float grad_scale, const float* count, void* stream);
+/* ---- parameter groups: frozen tensors, per-group learning rate and decay over the same flat buffers.
+ * A table of nsegs (begin, end, group) triples of int64, sorted, disjoint, non-empty, inside [0, n): elements outside every
+ * segment (alignment gaps, pads) and elements of frozen groups are neither read nor written by the two launch entries.
+ * mmtg_param_groups_check validates a host table (1 <= ngroups <= MMTG_MAX_PARAM_GROUPS, 0 <= nsegs <= MMTG_MAX_PARAM_SEGS)
+ * without any device call; the launch entries run the same checks on segs_host (the host copy of the device table segs_dev,
+ * which is built once and stays in device memory) before they launch.                                                     */
+#define MMTG_MAX_PARAM_GROUPS 16
+#define MMTG_MAX_PARAM_SEGS 1024
+typedef struct { float lr_scale; float weight_decay; int frozen; int pad; } mmtg_param_group;
+MMTG_API int mmtg_param_groups_check(const long* segs, int nsegs, int ngroups, long n);
+/* out[g] = sum x^2 over group g's segments (0 for a group whose bit is set in frozen_mask, or without segments),
+ * out[ngroups] = the non-frozen groups' values added in group order: the clip norm of the trainable tensors.  Written, not
+ * accumulated; one partial per workgroup and group in `ws` (mmtg_sumsq_groups_ws(n, ngroups) floats) + an ordered final sum:
+ * no atomics, equal bits call after call.                                                                                */
+MMTG_API long mmtg_sumsq_groups_ws(long n, int ngroups);
+MMTG_API int mmtg_sumsq_groups(const float* x, long n, const long* segs_dev, const long* segs_host, int nsegs, int ngroups,
+               unsigned frozen_mask, float* out, float* ws, long ws_floats, void* stream);
+/* mmtg_adamw per group: every element of a non-frozen group g gets the bits mmtg_adamw gives it when called with
+ * lr = (float)((double)lr * (double)groups[g].lr_scale) and wd = groups[g].weight_decay (same clip coefficient, count rule
+ * and planes).  `groups` is a host array of ngroups records, handed to the kernel by value.                               */
+MMTG_API int mmtg_adamw_groups(float* p, const float* g, float* m, float* v, void* p_bf16, void* p_lo, long n,
+               const long* segs_dev, const long* segs_host, int nsegs, const mmtg_param_group* groups, int ngroups,
+               float lr, float beta1, float beta2, float eps, int step,
+               const float* normsq, float max_norm, float grad_scale, const float* count, void* stream);
 MMTG_API int mmtg_cast_f32_to(int dtype, const float* src, void* dst, long n, void* stream);
 /* dst[r, 0:cols] = cast(src[r, 0:cols]); dst[r, cols:ldd] = 0 */
 MMTG_API int mmtg_cast_pad_rows(int dtype, const float* src, long lds_, void* dst, long ldd, int rows, int cols, void* stream);

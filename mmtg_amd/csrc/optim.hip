@@ -100,6 +100,200 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     }
 }
 
+// ---------------------------------------------------------------- parameter groups
+// The two kernels above over a table of (begin, end, group) segments of the flat buffer: same geometry (one 16-byte vector per
+// lane and pass, 1024 elements per workgroup and pass, grid-stride over <= 2048 workgroups), but a lane first finds the segment of
+// its vector.  The table (<= 1024 segments) is staged in LDS: ends, begins, group bytes.  A vector that lies inside one segment
+// takes the 16-byte path; one that a boundary cuts, or that reaches into a gap, goes element by element; a vector without any
+// element of a trainable segment issues no load and no store -- pads, gaps and frozen tensors keep every bit and cost no traffic.
+struct SegTable {
+    const long* end;             // LDS: end[s], ascending (the segments are sorted and disjoint)
+    const long* begin;           // LDS
+    const unsigned char* group;  // LDS
+    int n;
+};
+
+__device__ __forceinline__ SegTable stage_segments(unsigned char* lds, const long* __restrict__ segs, int nsegs) {
+    long* se = reinterpret_cast<long*>(lds);
+    long* sb = se + nsegs;
+    unsigned char* sg = reinterpret_cast<unsigned char*>(sb + nsegs);
+    for (int s = threadIdx.x; s < nsegs; s += 256) {
+        sb[s] = segs[3 * s];
+        se[s] = segs[3 * s + 1];
+        sg[s] = (unsigned char)segs[3 * s + 2];
+    }
+    return SegTable{se, sb, sg, nsegs};
+}
+// bytes of LDS stage_segments fills, rounded up so that what follows it is 16-byte aligned
+inline size_t seg_lds_bytes(int nsegs) { return ((size_t)nsegs * 17 + 15) & ~(size_t)15; }
+
+// first segment that ends behind element e (nsegs if there is none): the only one that can hold e
+__device__ __forceinline__ int seg_find(const SegTable& t, long e) {
+    int lo = 0, hi = t.n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (t.end[mid] > e) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// out[g * gridDim.x + blockIdx.x] = this workgroup's sum of x^2 over group g's elements, for every group (0 for frozen ones).
+// A lane adds into one register while its vectors stay in one group and into its own LDS slot acc[g * 256 + lane] when the group
+// changes; the slots are then summed per group in a fixed order (slot t, t + 64, ... per lane; lanes; nothing else).
+__global__ __launch_bounds__(256) void sumsq_groups_kernel(const float* __restrict__ x, long n, const long* __restrict__ segs,
+        int nsegs, int ngroups, unsigned frozen, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const SegTable t = stage_segments(lds, segs, nsegs);
+    float* acc = reinterpret_cast<float*>(lds + (((size_t)nsegs * 17 + 15) & ~(size_t)15));
+    for (int k = threadIdx.x; k < ngroups * 256; k += 256) acc[k] = 0.f;
+    __syncthreads();
+    float a = 0.f;
+    int ag = -1;                // the group `a` belongs to
+    const long nv = (n + 3) >> 2;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
+        const long e0 = i << 2;
+        int s = seg_find(t, e0);
+        if (s >= nsegs || t.begin[s] >= e0 + 4) continue;               // nothing of this vector is in a segment
+        if (t.begin[s] <= e0 && t.end[s] >= e0 + 4) {
+            const int g = t.group[s];
+            if ((frozen >> g) & 1u) continue;
+            if (g != ag) {
+                if (ag >= 0) acc[ag * 256 + threadIdx.x] += a;
+                a = 0.f; ag = g;
+            }
+            const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+            a += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+            continue;
+        }
+        for (long e = e0; e < e0 + 4; ++e) {
+            while (s < nsegs && t.end[s] <= e) ++s;
+            if (s >= nsegs) break;
+            if (t.begin[s] > e) continue;
+            const int g = t.group[s];
+            if ((frozen >> g) & 1u) continue;
+            if (g != ag) {
+                if (ag >= 0) acc[ag * 256 + threadIdx.x] += a;
+                a = 0.f; ag = g;
+            }
+            a += x[e] * x[e];
+        }
+    }
+    if (ag >= 0) acc[ag * 256 + threadIdx.x] += a;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int g = threadIdx.x >> 6; g < ngroups; g += 4) {
+        const float* r = acc + g * 256;
+        float w = ((r[lane] + r[lane + 64]) + r[lane + 128]) + r[lane + 192];
+        w = wave_sum(w);
+        if (lane == 0) out[(long)g * gridDim.x + blockIdx.x] = w;
+    }
+}
+
+// out[g] = ordered sum of group g's np partials (sumsq_final_kernel's order), out[ngroups] = the non-frozen groups' sums added in
+// group order.  One workgroup.
+__global__ __launch_bounds__(256) void sumsq_groups_final_kernel(const float* __restrict__ part, int np, int ngroups, unsigned frozen,
+                                                                 float* __restrict__ out) {
+    __shared__ float sh[4];
+    float total = 0.f;
+    for (int g = 0; g < ngroups; ++g) {
+        float a = 0.f;
+        if (!((frozen >> g) & 1u))
+            for (int i = threadIdx.x; i < np; i += 256) a += part[(long)g * np + i];
+        a = wave_sum(a);
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const float r = sh[0] + sh[1] + sh[2] + sh[3];
+            out[g] = r;
+            if (!((frozen >> g) & 1u)) total += r;
+        }
+    }
+    if (threadIdx.x == 0) out[ngroups] = total;
+}
+
+// what adamw_groups_kernel needs of every group, by value in the kernel arguments (16 groups: 196 bytes)
+struct AdamGroups {
+    float lr[MMTG_MAX_PARAM_GROUPS];            // (float)((double)lr * (double)lr_scale): the lr mmtg_adamw would be called with
+    float wd[MMTG_MAX_PARAM_GROUPS];
+    float step_size[MMTG_MAX_PARAM_GROUPS];     // that lr's bias-corrected step size, from double as in mmtg_adamw
+    unsigned frozen;
+};
+
+// adamw_kernel per segment: the same clip coefficient, the same adamw_update, the same plane expressions; lrwd and step_size
+// are the segment's group's.  The element path is adamw_kernel's scalar fallback, also taken by every vector when a pointer is
+// misaligned.
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
+        float* __restrict__ m, float* __restrict__ v, bf16* __restrict__ pc, bf16* __restrict__ pl, long n,
+        const long* __restrict__ segs, int nsegs, const AdamGroups grp, float b1, float b2, float eps,
+        const float* __restrict__ normsq, float max_norm, float gscale, const float* __restrict__ count) {
+    if (count) {
+        const float c = *count;
+        if (!(c > 0.f)) return;
+        gscale *= 1.0f / c;
+    }
+    float coef = gscale;
+    if (normsq) {
+        // torch.nn.utils.clip_grad_norm_: coef = max_norm / (norm + 1e-6), clamped to 1
+        const float nrm = sqrtf(*normsq) * gscale;
+        coef *= fminf(1.0f, max_norm / (nrm + 1e-6f));
+    }
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const SegTable t = stage_segments(lds, segs, nsegs);
+    float* g_lrwd = reinterpret_cast<float*>(lds + (((size_t)nsegs * 17 + 15) & ~(size_t)15));
+    float* g_step = g_lrwd + MMTG_MAX_PARAM_GROUPS;
+    if (threadIdx.x < MMTG_MAX_PARAM_GROUPS) {
+        const int k = threadIdx.x;
+        const float lr = grp.lr[k], wd = grp.wd[k];
+        g_lrwd[k] = wd > 0.f ? lr * wd : 0.f;      // decoupled decay p -= lr wd p (wd > 0 only)
+        g_step[k] = grp.step_size[k];
+    }
+    __syncthreads();
+    const bool vec_ok = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                          reinterpret_cast<uintptr_t>(v)) & 15) == 0 && ((reinterpret_cast<uintptr_t>(pc) | reinterpret_cast<uintptr_t>(pl)) & 7) == 0;
+    const unsigned frozen = grp.frozen;
+    const long nv = (n + 3) >> 2;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
+        const long e0 = i << 2;
+        int s = seg_find(t, e0);
+        if (s >= nsegs || t.begin[s] >= e0 + 4) continue;               // nothing of this vector is in a segment
+        if (vec_ok && t.begin[s] <= e0 && t.end[s] >= e0 + 4) {
+            const int k = t.group[s];
+            if ((frozen >> k) & 1u) continue;
+            const float lrwd = g_lrwd[k], step_size = g_step[k];
+            const f32x4 g4 = reinterpret_cast<const f32x4*>(g)[i];
+            f32x4 m4 = reinterpret_cast<f32x4*>(m)[i], v4 = reinterpret_cast<f32x4*>(v)[i], p4 = reinterpret_cast<f32x4*>(p)[i];
+            bf16x4 c4, l4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float mi = m4[e], vi = v4[e], pi = p4[e];
+                adamw_update(g4[e], mi, vi, pi, coef, b1, b2, eps, lrwd, step_size);
+                m4[e] = mi; v4[e] = vi; p4[e] = pi;
+                c4[e] = (bf16)pi;
+                l4[e] = (bf16)(pi - (float)c4[e]);
+            }
+            reinterpret_cast<f32x4*>(m)[i] = m4;
+            reinterpret_cast<f32x4*>(v)[i] = v4;
+            reinterpret_cast<f32x4*>(p)[i] = p4;
+            if (pc) reinterpret_cast<bf16x4*>(pc)[i] = c4;
+            if (pl) reinterpret_cast<bf16x4*>(pl)[i] = l4;
+            continue;
+        }
+        for (long e = e0; e < e0 + 4; ++e) {
+            while (s < nsegs && t.end[s] <= e) ++s;
+            if (s >= nsegs) break;
+            if (t.begin[s] > e) continue;
+            const int k = t.group[s];
+            if ((frozen >> k) & 1u) continue;
+            float mi = m[e], vi = v[e], pi = p[e];
+            adamw_update(g[e], mi, vi, pi, coef, b1, b2, eps, g_lrwd[k], g_step[k]);
+            m[e] = mi; v[e] = vi; p[e] = pi;
+            if (pc) pc[e] = (bf16)pi;
+            if (pl) pl[e] = (bf16)(pi - (float)(bf16)pi);
+        }
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void cast_from_f32_kernel(const float* __restrict__ src, T* __restrict__ dst, long n) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = (T)src[i];
@@ -243,6 +437,83 @@ extern "C" int mmtg_adamw(float* p, const float* g, float* m, float* v, void* p_
     hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, p, g, m, v, (bf16*)p_bf16, (bf16*)p_lo, n, lr, beta1, beta2,
                        eps, wd, step_size, normsq, max_norm, grad_scale, count);
     MMTG_LAUNCH_CHECK("adamw");
+    return MMTG_OK;
+}
+
+// the table rules of the header; `trainable` (optional): elements of the groups whose bit is clear in `frozen`
+static int param_groups_check(const char* who, const long* segs, int nsegs, int ngroups, long n, unsigned frozen = 0,
+                              double* trainable = nullptr) {
+    MMTG_REQUIRE(ngroups >= 1 && ngroups <= MMTG_MAX_PARAM_GROUPS, "%s: ngroups = %d (1 .. %d)", who, ngroups, MMTG_MAX_PARAM_GROUPS);
+    MMTG_REQUIRE(nsegs >= 0 && nsegs <= MMTG_MAX_PARAM_SEGS, "%s: nsegs = %d (0 .. %d)", who, nsegs, MMTG_MAX_PARAM_SEGS);
+    MMTG_REQUIRE(n > 0, "%s: n = %ld", who, n);
+    MMTG_REQUIRE(segs || nsegs == 0, "%s: null segment table", who);
+    double live = 0;
+    for (int s = 0; s < nsegs; ++s) {
+        const long b = segs[3 * s], e = segs[3 * s + 1], g = segs[3 * s + 2];
+        MMTG_REQUIRE(e > b, "%s: segment %d [%ld, %ld) is empty", who, s, b, e);
+        MMTG_REQUIRE(b >= 0 && e <= n, "%s: segment %d [%ld, %ld) is outside [0, %ld)", who, s, b, e, n);
+        MMTG_REQUIRE(g >= 0 && g < ngroups, "%s: segment %d has group %ld (0 .. %d)", who, s, g, ngroups - 1);
+        if (s > 0) {
+            MMTG_REQUIRE(b >= segs[3 * s - 3], "%s: segment %d begins at %ld, before segment %d (%ld): not sorted", who, s, b, s - 1, segs[3 * s - 3]);
+            MMTG_REQUIRE(b >= segs[3 * s - 2], "%s: segment %d [%ld, %ld) overlaps segment %d, which ends at %ld", who, s, b, e, s - 1, segs[3 * s - 2]);
+        }
+        if (!((frozen >> g) & 1u)) live += (double)(e - b);
+    }
+    if (trainable) *trainable = live;
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_param_groups_check(const long* segs, int nsegs, int ngroups, long n) {
+    return param_groups_check("param_groups_check", segs, nsegs, ngroups, n);
+}
+
+extern "C" long mmtg_sumsq_groups_ws(long n, int ngroups) { return (long)grid_for(n / 4 + 1) * (ngroups > 0 ? ngroups : 0); }
+
+extern "C" int mmtg_sumsq_groups(const float* x, long n, const long* segs_dev, const long* segs_host, int nsegs, int ngroups,
+                                 unsigned frozen_mask, float* out, float* ws, long ws_floats, void* stream) {
+    double live = 0;
+    if (int rc = param_groups_check("sumsq_groups", segs_host, nsegs, ngroups, n, frozen_mask, &live)) return rc;
+    MMTG_REQUIRE(x && out && MMTG_ALIGNED16(x) && (segs_dev || nsegs == 0), "sumsq_groups: bad args");
+    const int g = grid_for(n / 4 + 1);
+    MMTG_REQUIRE(ws && ws_floats >= (long)g * ngroups, "sumsq_groups: workspace of %ld floats required (mmtg_sumsq_groups_ws)", (long)g * ngroups);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_OPTIM, s, 2.0 * live, 4.0 * live);
+    hipLaunchKernelGGL(sumsq_groups_kernel, dim3(g), dim3(256), seg_lds_bytes(nsegs) + (size_t)ngroups * 1024, s, x, n, segs_dev, nsegs,
+                       ngroups, frozen_mask, ws);
+    hipLaunchKernelGGL(sumsq_groups_final_kernel, dim3(1), dim3(256), 0, s, (const float*)ws, g, ngroups, frozen_mask, out);
+    MMTG_LAUNCH_CHECK("sumsq_groups");
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_adamw_groups(float* p, const float* g, float* m, float* v, void* p_bf16, void* p_lo, long n,
+                                 const long* segs_dev, const long* segs_host, int nsegs, const mmtg_param_group* groups, int ngroups,
+                                 float lr, float beta1, float beta2, float eps, int step,
+                                 const float* normsq, float max_norm, float grad_scale, const float* count, void* stream) {
+    MMTG_REQUIRE(groups, "adamw_groups: null groups");
+    MMTG_REQUIRE(ngroups >= 1 && ngroups <= MMTG_MAX_PARAM_GROUPS, "adamw_groups: ngroups = %d (1 .. %d)", ngroups, MMTG_MAX_PARAM_GROUPS);
+    AdamGroups grp;
+    memset(&grp, 0, sizeof(grp));
+    // transformers.AdamW(correct_bias=True): step_size = lr * sqrt(1-b2^t) / (1-b1^t), per group from the group's fp32 lr
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    for (int k = 0; k < ngroups; ++k) {
+        const float sc = groups[k].lr_scale, wd = groups[k].weight_decay;
+        MMTG_REQUIRE(sc >= 0.f && sc <= 3.0e38f, "adamw_groups: group %d has lr_scale %g (finite, >= 0)", k, (double)sc);
+        MMTG_REQUIRE(wd >= 0.f && wd <= 3.0e38f, "adamw_groups: group %d has weight_decay %g (finite, >= 0)", k, (double)wd);
+        grp.lr[k] = (float)((double)lr * (double)sc);
+        grp.wd[k] = wd;
+        grp.step_size[k] = (float)((double)grp.lr[k] * sqrt(bc2) / bc1);
+        if (groups[k].frozen) grp.frozen |= 1u << k;
+    }
+    double live = 0;
+    if (int rc = param_groups_check("adamw_groups", segs_host, nsegs, ngroups, n, grp.frozen, &live)) return rc;
+    MMTG_REQUIRE(p && g && m && v && step >= 1 && (segs_dev || nsegs == 0), "adamw_groups: bad args");
+    MMTG_REQUIRE(!p_lo || p_bf16, "adamw_groups: the lo plane comes with the hi plane (p_bf16)");
+    if (live == 0) return MMTG_OK;              // nothing trainable: nothing to launch
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_OPTIM, s, 12.0 * live, (28.0 + (p_bf16 ? 2 : 0) + (p_lo ? 2 : 0)) * live);
+    hipLaunchKernelGGL(adamw_groups_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), seg_lds_bytes(nsegs) + 2 * MMTG_MAX_PARAM_GROUPS * sizeof(float), s,
+                       p, g, m, v, (bf16*)p_bf16, (bf16*)p_lo, n, segs_dev, nsegs, grp, beta1, beta2, eps, normsq, max_norm, grad_scale, count);
+    MMTG_LAUNCH_CHECK("adamw_groups");
     return MMTG_OK;
 }
 

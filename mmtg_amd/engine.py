@@ -377,6 +377,7 @@ class Engine:
         self.opt_m = None
         self.opt_v = None
         self.normsq = torch.zeros(1, device=self.dev)
+        self.group_normsq = None   # [ngroups + 1] of a grouped step (group_norm_sq); normsq is then its last element
         self.bucket_hook = None   # callable(pack_index) fired as packs of gradients become final
         self._sums, self._defer = [], False     # deferred column sums of the backward (see _defer_sum)
         self._tail_jobs, self._tail_side = [], None      # grouped weight gradients deferred to the backward's tail (_WGRAD_TAIL)
@@ -1715,18 +1716,36 @@ class Engine:
         hip.sumsq(self.grad, self.layout.total, self.normsq)        # (written, in a fixed order: no memset, no atomics)
         return self.normsq
 
-    def adamw_step(self, lr, max_norm=1.0, betas=(0.9, 0.999), eps=1e-6, wd=0.0, grad_scale=1.0, clip=True, count=None):
+    def group_norm_sq(self, groups):
+        """Per-group sums of squares of the gradient (hip.GroupTable `groups`) into self.group_normsq[:ngroups]; the trainable
+        groups' total lands in self.normsq[0], which is the last element of the same buffer: the norm clip_grad_norm_ sees when
+        frozen parameters have no gradient."""
+        if self.group_normsq is None or self.group_normsq.numel() != groups.ngroups + 1:
+            self.group_normsq = torch.zeros(groups.ngroups + 1, device=self.dev)
+            self.normsq = self.group_normsq[groups.ngroups:]
+        hip.sumsq_groups(self.grad, self.layout.total, groups, self.group_normsq)
+        return self.normsq
+
+    def adamw_step(self, lr, max_norm=1.0, betas=(0.9, 0.999), eps=1e-6, wd=0.0, grad_scale=1.0, clip=True, count=None, groups=None):
         """clip_grad_norm_(1.0) + transformers.AdamW(lr, eps=1e-6, wd=0) over the flat buffers,
         refreshing the bf16 weight copies in the same pass.  count: device scalar, the global row count when the
-        flat buffer holds row SUMS (mmtg_adamw divides by it; zero rows = no update)."""
+        flat buffer holds row SUMS (mmtg_adamw divides by it; zero rows = no update).
+        groups: a hip.GroupTable -- the step then runs per parameter group (lr * lr_scale, the group's weight decay in place of
+        `wd`, frozen groups untouched) through mmtg_sumsq_groups + mmtg_adamw_groups; None is the plain step."""
         if self.opt_m is None:
             self.opt_m = torch.zeros_like(self.master)
             self.opt_v = torch.zeros_like(self.master)
         self.step_count += 1
-        ns = self.grad_norm_sq() if clip else None
-        hip.adamw(self.master, self.grad, self.opt_m, self.opt_v,
-                  self.wc2[0] if self.x3 else None if self.dtype == hip.F32 else self.wc,
-                  self.layout.total, lr, betas[0], betas[1], eps, wd, self.step_count, ns, max_norm, grad_scale, count=count,
-                  p_lo=self.wc2[1] if self.x3 else None)
+        p_hi = self.wc2[0] if self.x3 else None if self.dtype == hip.F32 else self.wc
+        p_lo = self.wc2[1] if self.x3 else None
+        if groups is None:
+            ns = self.grad_norm_sq() if clip else None
+            hip.adamw(self.master, self.grad, self.opt_m, self.opt_v, p_hi,
+                      self.layout.total, lr, betas[0], betas[1], eps, wd, self.step_count, ns, max_norm, grad_scale, count=count,
+                      p_lo=p_lo)
+        else:
+            ns = self.group_norm_sq(groups) if clip else None
+            hip.adamw_groups(self.master, self.grad, self.opt_m, self.opt_v, p_hi, self.layout.total, groups, lr, betas[0], betas[1],
+                             eps, self.step_count, ns, max_norm, grad_scale, count=count, p_lo=p_lo)
         self._refresh_transposed()
         self.copies_fresh = True

@@ -77,6 +77,10 @@ _SIGS = {
     "mmtg_sumsq": ([_vp, _l, _vp, _vp, _l, _vp], _i),
     "mmtg_sumsq_ws": ([_l], _l),
     "mmtg_adamw": ([_vp, _vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _vp, _f, _f, _vp, _vp], _i),
+    "mmtg_param_groups_check": ([_vp, _i, _i, _l], _i),
+    "mmtg_sumsq_groups_ws": ([_l, _i], _l),
+    "mmtg_sumsq_groups": ([_vp, _l, _vp, _vp, _i, _i, _u, _vp, _vp, _l, _vp], _i),
+    "mmtg_adamw_groups": ([_vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _vp, _i, _f, _f, _f, _f, _i, _vp, _f, _f, _vp, _vp], _i),
     "mmtg_gemm_x3": ([_i, _i, _i, _vp, _l, _l, _vp, _l, _l, _vp, _l, _vp, _l, _l, _vp, _i, _vp, _l, _vp, _u, _u, _i, _vp], _i),
     "mmtg_split_planes": ([_vp, _l, _i, _i, _vp, _l, _l, _vp], _i),
     "mmtg_layernorm_fwd_x3": ([_vp, _vp, _l, _l, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp], _i),
@@ -719,6 +723,58 @@ def adamw(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, wd, step, normsq, max_no
     _check(lib().mmtg_adamw(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), _p(p_lo), n, float(lr), float(beta1), float(beta2),
                             float(eps), float(wd), int(step), _p(normsq), float(max_norm), float(grad_scale),
                             _p(count), _stream()), "adamw")
+
+
+class ParamGroup(C.Structure):
+    """mmtg_param_group of include/mmtg_hip.h."""
+    _fields_ = [("lr_scale", C.c_float), ("weight_decay", C.c_float), ("frozen", C.c_int), ("pad", C.c_int)]
+
+
+def param_groups_check(segments, ngroups, n):
+    """Host-only validation of an int64 [S, 3] (begin, end, group) table (no device call); raises RuntimeError with the library's message."""
+    import numpy as np
+    segs = np.ascontiguousarray(segments, dtype=np.int64).reshape(-1, 3)
+    _check(lib().mmtg_param_groups_check(segs.ctypes.data, len(segs), int(ngroups), int(n)), "param_groups_check")
+
+
+class GroupTable:
+    """A parameter-group plan (mmtg_amd.param_groups.build_param_groups) as the grouped optimizer entries take it: the segment
+    table on the host and, uploaded once, on the device; the groups' records; the frozen groups as a bit mask."""
+
+    def __init__(self, plan, device):
+        import numpy as np
+        self.plan = plan
+        self.segs_host = np.ascontiguousarray(plan.segments, dtype=np.int64).reshape(-1, 3)
+        self.nsegs, self.ngroups = len(self.segs_host), len(plan.groups)
+        param_groups_check(self.segs_host, self.ngroups, plan.total)
+        self.segs_dev = torch.from_numpy(self.segs_host.copy()).to(device) if self.nsegs else None
+        self.records = (ParamGroup * self.ngroups)(*[ParamGroup(float(g["lr_scale"]), float(g["weight_decay"]), int(bool(g["frozen"])), 0)
+                                                      for g in plan.groups])
+        self.frozen_mask = sum(1 << i for i, g in enumerate(plan.groups) if g["frozen"])
+
+
+_sumsq_groups_ws = {}
+
+
+def sumsq_groups(x, n, table, out):
+    """out[g] = sum of squares of group g's segments of x[:n] (0 for frozen groups), out[ngroups] = the trainable groups' total:
+    written, not accumulated, in a fixed summation order.  Gaps and frozen segments are not read."""
+    need = int(lib().mmtg_sumsq_groups_ws(n, table.ngroups))
+    key = (x.device, need, _stream())
+    ws = _sumsq_groups_ws.get(key)
+    if ws is None:
+        ws = _sumsq_groups_ws[key] = torch.empty(need, device=x.device, dtype=torch.float32)
+    _check(lib().mmtg_sumsq_groups(_p(x), n, _p(table.segs_dev), table.segs_host.ctypes.data, table.nsegs, table.ngroups,
+                                   table.frozen_mask, _p(out), _p(ws), need, _stream()), "sumsq_groups")
+
+
+def adamw_groups(p, g, m, v, p_bf16, n, table, lr, beta1, beta2, eps, step, normsq, max_norm, grad_scale=1.0, count=None, p_lo=None):
+    """mmtg_adamw per parameter group: group i runs with the fp32 product lr * lr_scale_i and its own weight decay; frozen groups
+    and the elements outside every segment keep every bit of p, m, v and both planes."""
+    _check(lib().mmtg_adamw_groups(_p(p), _p(g), _p(m), _p(v), _p(p_bf16), _p(p_lo), n, _p(table.segs_dev), table.segs_host.ctypes.data,
+                                   table.nsegs, C.addressof(table.records), table.ngroups, float(lr), float(beta1), float(beta2),
+                                   float(eps), int(step), _p(normsq), float(max_norm), float(grad_scale), _p(count), _stream()),
+           "adamw_groups")
 
 
 def cast_f32_to(src, dst, n):

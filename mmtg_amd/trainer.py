@@ -14,6 +14,7 @@ get_linear_schedule_with_warmup (train.py:146-148).
 """
 from __future__ import annotations
 
+import copy
 import os
 
 import torch
@@ -44,9 +45,18 @@ _LOGITS_F32 = bool(os.environ.get("MMTG_LOGITS_F32"))     # A/B switch: fp32 log
 class MMTGTrainer:
     def __init__(self, model, lr=1e-5, alpha=0.0, max_norm=1.0, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.0, warmup_steps=0, total_steps=None, distributed=False, bucket_mb=64.0,
-                 lm_weight=0.0):
+                 lm_weight=0.0, param_groups=None):
+        """param_groups: a list of specs as mmtg_amd.param_groups takes them (fnmatch patterns on the state-dict keys; per group
+        `lr_scale`, `weight_decay`, `frozen`).  `lr` and the schedule stay the base rate, groups scale it; None is the single
+        group of the reference."""
         self.model = model
         self.eng = model.engine()
+        self.group_plan = self.groups = None
+        if param_groups is not None:
+            from . import hip
+            from .param_groups import build_param_groups
+            self.group_plan = build_param_groups(self.eng.layout, param_groups, weight_decay)
+            self.groups = hip.GroupTable(self.group_plan, self.eng.dev)       # the segment table is uploaded once, here
         self.lr, self.alpha, self.max_norm = lr, alpha, max_norm
         self.betas, self.eps, self.wd = betas, eps, weight_decay
         self.warmup, self.total = warmup_steps, total_steps
@@ -89,7 +99,9 @@ class MMTGTrainer:
                 "cu_budget": None if self.budget_report is None else self.budget_report.get("budget_chosen"),
                 "hparams": {"lr": self.lr, "alpha": self.alpha, "max_norm": self.max_norm, "betas": tuple(self.betas),
                             "eps": self.eps, "weight_decay": self.wd, "warmup_steps": self.warmup,
-                            "total_steps": self.total, "lm_weight": self.lm_weight}}
+                            "total_steps": self.total, "lm_weight": self.lm_weight,
+                            # for the record, like the rest: load_state_dict keeps the trainer's own groups as it keeps its own lr
+                            "param_groups": None if self.group_plan is None else copy.deepcopy(self.group_plan.specs)}}
 
     def load_state_dict(self, sd):
         eng = self.eng
@@ -206,7 +218,7 @@ class MMTGTrainer:
                 self.finish_events.append((e0, e1))
             else:
                 red.finish(eng.grad)
-        eng.adamw_step(self.current_lr(), self.max_norm, self.betas, self.eps, self.wd, count=self._count)
+        eng.adamw_step(self.current_lr(), self.max_norm, self.betas, self.eps, self.wd, count=self._count, groups=self.groups)
         self.sched_step += 1
         return out
 
@@ -267,6 +279,22 @@ class MMTGTrainer:
         """Global gradient norm of the last step as clip_grad_norm_ saw it (device scalar): the flat buffer holds row
         sums, so sqrt(sum g^2) / global row count."""
         return torch.sqrt(self.eng.normsq[0]) / self._count[0]
+
+    def group_grad_norms(self):
+        """Per-group gradient norms of the last step (device vector, one entry per group, the implicit group last; 0 for a frozen
+        group): sqrt(sum over the group's tensors of g^2) / global row count.  With frozen groups grad_norm() is the norm of the
+        trainable tensors, as clip_grad_norm_ sees it when frozen parameters have no gradient."""
+        if self.groups is None:
+            raise RuntimeError("group_grad_norms: this trainer has no param_groups")
+        return torch.sqrt(self.eng.group_normsq[:self.groups.ngroups]) / self._count[0]
+
+    def describe_groups(self):
+        """One dict per group, the implicit group of unmatched keys last: the spec as given (None for the implicit group), the
+        resolved lr_scale / weight_decay / frozen, and how many tensors and parameters the group holds."""
+        if self.group_plan is None:
+            return []
+        return [{"spec": copy.deepcopy(g["spec"]), "lr_scale": g["lr_scale"], "weight_decay": g["weight_decay"], "frozen": g["frozen"],
+                 "tensors": len(g["keys"]), "parameters": g["parameters"]} for g in self.group_plan.groups]
 
 
 def save_checkpoint(path, model, trainer=None, args=None, model_cfgs=None, reference_compatible=False):
