@@ -1227,18 +1227,24 @@ class Engine:
         model; parameter gradients are ACCUMULATED into the flat fp32 buffer."""
         a = self.act
         self.ensure_grad()
-        if self._lazy is not None and not self.wgrad_overwrite:
-            # (a backward that accumulates after a zero_grad(shape_key) that relied on overwrites: zero what it skipped)
-            self.grad.zero_()
+        # (nothing of an earlier backward that raised may reach this one: its queued column sums hold raw pointers)
+        self._sums, self._defer, self._tail_jobs = [], False, []
+        try:
+            if self._lazy is not None and not self.wgrad_overwrite:
+                # (a backward that accumulates after a zero_grad(shape_key) that relied on overwrites: zero what it skipped)
+                self.grad.zero_()
+                self._lazy = None
+            if self.hybrid and a.get("x3"):
+                self._backward_hybrid(dlogits, dkl)
+            else:
+                self._backward_encoder(a, self._backward_decoder(a, dlogits), dkl)
+        finally:
+            # (on the way out of an exception too: a window of micro-batches would otherwise accumulate on top of what is left)
+            if self._tail_side is not None:         # the weight gradients that ran beside the tail: final before anything reads the gradient
+                torch.cuda.current_stream().wait_stream(self._tail_side)
+                self._tail_side = None
+            self._sums, self._defer, self._tail_jobs = [], False, []
             self._lazy = None
-        if self.hybrid and a.get("x3"):
-            self._backward_hybrid(dlogits, dkl)
-        else:
-            self._backward_encoder(a, self._backward_decoder(a, dlogits), dkl)
-        if self._tail_side is not None:         # the weight gradients that ran beside the tail: final before anything reads the gradient
-            torch.cuda.current_stream().wait_stream(self._tail_side)
-            self._tail_side = None
-        self._lazy = None
 
     def _backward_decoder(self, a, dlogits):
         """LM head -> GPT-2 blocks -> input embedding -> projector; returns the per-segment sums of d(h1_pre) [B*S, H] that the

@@ -45,10 +45,14 @@ _LOGITS_F32 = bool(os.environ.get("MMTG_LOGITS_F32"))     # A/B switch: fp32 log
 class MMTGTrainer:
     def __init__(self, model, lr=1e-5, alpha=0.0, max_norm=1.0, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.0, warmup_steps=0, total_steps=None, distributed=False, bucket_mb=64.0,
-                 lm_weight=0.0, param_groups=None):
-        """param_groups: a list of specs as mmtg_amd.param_groups takes them (fnmatch patterns on the state-dict keys; per group
+                 lm_weight=0.0, param_groups=None, accumulation_steps=1):
+        """accumulation_steps: calls of step() per optimizer step (a window of micro-batches, see step()).
+        param_groups: a list of specs as mmtg_amd.param_groups takes them (fnmatch patterns on the state-dict keys; per group
         `lr_scale`, `weight_decay`, `frozen`).  `lr` and the schedule stay the base rate, groups scale it; None is the single
         group of the reference."""
+        if type(accumulation_steps) is not int or accumulation_steps < 1:
+            raise ValueError("accumulation_steps must be an int of at least 1, got %r" % (accumulation_steps,))
+        self.accumulation_steps = accumulation_steps
         self.model = model
         self.eng = model.engine()
         self.group_plan = self.groups = None
@@ -65,8 +69,14 @@ class MMTGTrainer:
         self.reducer = GradReducer(self.eng.layout, bucket_mb) if distributed else None
         self._count = None
         self.measure_finish, self.finish_events = False, []
+        # (the exchange belongs to a window's closing backward: only there are the packs it passes final, see _step)
+        self._hook = None if self.reducer is None else (lambda pack: self.reducer.on_pack_ready(self.eng.grad, pack))
         if self.reducer is not None:
-            self.eng.bucket_hook = lambda pack: self.reducer.on_pack_ready(self.eng.grad, pack)
+            self.eng.bucket_hook = self._hook if accumulation_steps == 1 else None
+        self.window = None          # device scalars of the last closed window (see step)
+        self._micro = self._rows = 0            # calls / local rows of the open window
+        self._bwd_ran = False                   # a backward of the open window has run (the buffer is zeroed before the first)
+        self._wacc = self._tune_ev = None
         # Self-tuning CU reservation (round 5): a multi-rank GPU run whose environment does not pin MMTG_DDP_GEMM_CUS spends its
         # first steps under each candidate (ddp.BUDGET_CANDIDATES: 0 / 16 / 32 CUs left to the RCCL kernels; TUNE_STEPS real
         # optimisation steps each, the first of every candidate untimed), then all ranks agree on the fastest through one MAX
@@ -88,7 +98,11 @@ class MMTGTrainer:
     # ---- true resume (the reference saves the model only, train.py:212)
     def state_dict(self):
         """Optimizer moments (flat fp32, the engine's parameter order), AdamW step count, scheduler position
-        and the dropout counter: together with ``model.state_dict()`` everything a bit-continuing run needs."""
+        and the dropout counter: together with ``model.state_dict()`` everything a bit-continuing run needs.  Only at a window
+        boundary: the gradient sums of an open window are not part of it."""
+        if self._micro:
+            raise RuntimeError("state_dict() inside an open accumulation window (micro_step = %d of %d): take the checkpoint at a "
+                               "boundary, or close the window with flush() first" % (self._micro, self.accumulation_steps))
         eng = self.eng
         return {"format": "mmtg-trainer-1", "layout_total": eng.layout.total,
                 "exp_avg": None if eng.opt_m is None else eng.opt_m.detach().cpu().clone(),
@@ -99,11 +113,12 @@ class MMTGTrainer:
                 "cu_budget": None if self.budget_report is None else self.budget_report.get("budget_chosen"),
                 "hparams": {"lr": self.lr, "alpha": self.alpha, "max_norm": self.max_norm, "betas": tuple(self.betas),
                             "eps": self.eps, "weight_decay": self.wd, "warmup_steps": self.warmup,
-                            "total_steps": self.total, "lm_weight": self.lm_weight,
+                            "total_steps": self.total, "lm_weight": self.lm_weight, "accumulation_steps": self.accumulation_steps,
                             # for the record, like the rest: load_state_dict keeps the trainer's own groups as it keeps its own lr
                             "param_groups": None if self.group_plan is None else copy.deepcopy(self.group_plan.specs)}}
 
     def load_state_dict(self, sd):
+        """(accumulation_steps stays the trainer's own, like lr and the groups; an open window is abandoned)"""
         eng = self.eng
         if sd.get("format") != "mmtg-trainer-1" or sd.get("layout_total") != eng.layout.total:
             raise ValueError("trainer state of a different model layout (%s, %s parameters; this model has %d)"
@@ -112,6 +127,7 @@ class MMTGTrainer:
             v = sd[key]
             setattr(eng, name, None if v is None else v.to(eng.dev, torch.float32).clone())
         eng.step_count, self.sched_step, eng.drop_seed = int(sd["step_count"]), int(sd["sched_step"]), int(sd["drop_seed"])
+        self.reset_window()
         if sd.get("cu_budget") is not None and self._tune is not None:
             from . import ddp as _ddp
             _ddp.set_chosen_budget(int(sd["cu_budget"]))
@@ -134,17 +150,64 @@ class MMTGTrainer:
         still advances the Adam step (bias correction) and the LR schedule by one.  A single process `continue`s before
         either counter moves (train.py:184-185).  Shards of a shuffled global batch that are ALL empty after the stage
         filter do not occur with the released data (every rating occurs in every batch of 64+ rows); the price of the
-        exact behaviour would be a host read of the all-reduced count every step."""
-        tune_ev = None
-        if self._tune is not None:
-            tune_ev = torch.cuda.Event(enable_timing=True)
-            tune_ev.record()
-        out = self._step(batch, stage, filter_rows)
+        exact behaviour would be a host read of the all-reduced count every step.
+
+        Gradient accumulation.  With accumulation_steps = k > 1 a call is a MICRO-step and k consecutive calls -- counted in calls,
+        not rows, so every rank of a group closes at the same call -- are a window: the buffer is zeroed once, before the window's
+        first backward (which overwrites, as the single step's does); the later backwards add their row sums; the closing call fills
+        the row count with the window's total, runs the exchange (the bucket hook is installed for its backward alone: a pack the
+        closing backward has passed is final) and ONE clip + AdamW + schedule step.  The same arithmetic as a data-parallel step over
+        k ranks.  A call the stage filter empties runs nothing and still counts; a single-rank window without any row moves no
+        counter.  `window` then holds the closed window's row-weighted means {'loss','lm_loss','kl'} (device scalars; with k = 1 the
+        step's own, valid until the next call) and its local 'rows'.  If a call raises, the window is abandoned (reset_window)."""
+        if self._tune is not None and self._micro == 0:      # the tuning books whole windows
+            self._tune_ev = torch.cuda.Event(enable_timing=True)
+            self._tune_ev.record()
+        try:
+            out, closed = self._step(batch, stage, filter_rows)
+        except BaseException:
+            self.reset_window()
+            raise
         # (only after a step that RETURNED: the book-keeping ends in a blocking all-reduce, which after an exception on one rank
         #  would turn that rank's error into a hang of the group)
-        if tune_ev is not None:
-            self._tune_after_step(tune_ev)
+        if closed:
+            self._tune_after_window()
         return out
+
+    @property
+    def micro_step(self):
+        """Calls of step() in the open window; 0 at a window boundary."""
+        return self._micro
+
+    def reset_window(self):
+        """Abandon the open window: the next call starts a fresh one (zeroing included); collectives in flight are dropped."""
+        self._micro = self._rows = 0
+        self._bwd_ran = False
+        self._tune_ev = None
+        if self.reducer is not None:
+            self.reducer.reset()
+
+    def flush(self):
+        """Close a partial window (the end of an epoch): the exchange and the optimizer step over the rows so far.  True when a
+        window was open, False -- and nothing done -- at a boundary."""
+        if not self._micro:
+            return False
+        red = self.reducer if (self.reducer is not None and self.reducer.active) else None
+        try:
+            if self._close_begin(red, self._rows):
+                self._close_end(red)
+            else:
+                self._end_window()
+        except BaseException:
+            self.reset_window()
+            raise
+        self._tune_after_window()
+        return True
+
+    def _tune_after_window(self):
+        ev, self._tune_ev = self._tune_ev, None
+        if ev is not None and self._tune is not None:
+            self._tune_after_step(ev)
 
     TUNE_STEPS = 3
 
@@ -186,29 +249,72 @@ class MMTGTrainer:
             batch = {k: v for k, v in batch.items() if k != "rating_host"}
         n_local = int(batch["rating"].shape[0]) if "rating" in batch else int(batch["targets"].shape[0])
         red = self.reducer if (self.reducer is not None and self.reducer.active) else None
-        if n_local == 0 and (red is None or red.world == 1):
-            return None             # nothing to exchange with: no counter moves, as train.py:184-185 `continue`s
-        if self._count is None:
-            self._count = torch.zeros(1, device=eng.dev, dtype=torch.float32)
-        self._count.fill_(float(n_local))           # asynchronous fill; the value is known on the host
-        if red is not None:
-            red.start_count(self._count)            # SUM over ranks, in place, asynchronous
-        # (a step without rows runs no backward: everything must be zero for the exchange)
-        eng.zero_grad((n_local, int(batch["targets"].shape[1])) if n_local > 0 and "targets" in batch else None)
+        self._micro += 1
+        closing = self._micro >= self.accumulation_steps
+        rows = self._rows + n_local
+        if closing and not self._close_begin(red, rows):
+            self._end_window()
+            return None, True       # nothing to exchange with: no counter moves, as train.py:184-185 `continue`s
         out = None
         if n_local > 0:
+            first = not self._bwd_ran
+            if first:               # once per window: the later backwards add to what this one writes
+                eng.zero_grad((n_local, int(batch["targets"].shape[1])) if "targets" in batch else None)
             eng.forward(batch, train_flag=True, training=self.model.training, logits_f32=_LOGITS_F32)
             sc = eng.loss(batch["rating"], stage, batch_den=n_local)
             T = eng.act["T"]
             dl = eng.loss_backward(float(n_local), lm_coef=self.lm_weight / (T - 1) if self.lm_weight else 0.0)
-            eng.wgrad_overwrite = True      # gradients were zeroed above and every weight is written once
+            if self.reducer is not None:
+                # (before the closing backward the packs are not final; without a hook those backwards overlap their tail, _WGRAD_TAIL)
+                eng.bucket_hook = self._hook if closing else None
+            eng.wgrad_overwrite = first     # gradients were zeroed above and every weight is written once
             try:
                 eng.backward(dl, dkl=self.alpha * n_local)
-                eng._finish_overwrite_record()
+                if first:
+                    eng._finish_overwrite_record()
             finally:
                 eng.wgrad_overwrite = False
                 eng._ow_rec = None
+            self._bwd_ran = True
             out = {"loss": sc[0], "lm_loss": sc[1], "kl": eng.act["kl"][0]}
+            self._add_to_window(out, sc, n_local)
+        self._rows = rows
+        if closing:
+            self._close_end(red)
+        return out, closing
+
+    def _add_to_window(self, out, sc, n):
+        """The window's loss: sum of n_i * v_i on the device, divided by the window's rows when it closes."""
+        if self.accumulation_steps == 1:
+            self._wacc = out        # the step's own scalars: no launch that today's step does not have
+            return
+        if self._wacc is None:
+            self._wacc = torch.empty(3, device=sc.device, dtype=torch.float32)
+        if self._rows == 0:         # the window's first rows
+            torch.mul(sc[:2], float(n), out=self._wacc[:2])
+            torch.mul(out["kl"].reshape(1), float(n), out=self._wacc[2:])
+        else:
+            self._wacc[:2].add_(sc[:2], alpha=float(n))
+            self._wacc[2:].add_(out["kl"].reshape(1), alpha=float(n))
+
+    def _close_begin(self, red, rows):
+        """The closing call's part BEFORE its backward: the window's row count onto the device and into the exchange.  False when
+        there is nothing to step on (no rows and no other rank)."""
+        if rows == 0 and (red is None or red.world == 1):
+            return False
+        if self._count is None:
+            self._count = torch.zeros(1, device=self.eng.dev, dtype=torch.float32)
+        self._count.fill_(float(rows))              # asynchronous fill; the value is known on the host
+        if red is not None:
+            red.start_count(self._count)            # SUM over ranks, in place, asynchronous
+        if rows == 0:
+            # (a window without rows ran no backward: everything must be zero for the exchange)
+            self.eng.zero_grad(None)
+        return True
+
+    def _close_end(self, red):
+        """Exchange, clip + AdamW, schedule: once per window."""
+        eng = self.eng
         if red is not None:
             if self.measure_finish:     # exposed exchange time: how long the compute stream sits in finish() (bench.py --gpus N)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -220,7 +326,19 @@ class MMTGTrainer:
                 red.finish(eng.grad)
         eng.adamw_step(self.current_lr(), self.max_norm, self.betas, self.eps, self.wd, count=self._count, groups=self.groups)
         self.sched_step += 1
-        return out
+        rows = self._rows
+        if rows == 0:
+            self.window = {"loss": None, "lm_loss": None, "kl": None, "rows": 0}
+        elif self.accumulation_steps == 1:
+            self.window = dict(self._wacc, rows=rows)
+        else:
+            w = self._wacc / float(rows)
+            self.window = {"loss": w[0], "lm_loss": w[1], "kl": w[2], "rows": rows}
+        self._end_window()
+
+    def _end_window(self):
+        self._micro = self._rows = 0
+        self._bwd_ran = False
 
     # ---- evaluation (train.py:241-268)
     @torch.no_grad()
