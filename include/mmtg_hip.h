@@ -429,6 +429,17 @@ MMTG_API int mmtg_adamw_groups(float* p, const float* g, float* m, float* v, voi
                const long* segs_dev, const long* segs_host, int nsegs, const mmtg_param_group* groups, int ngroups,
                float lr, float beta1, float beta2, float eps, int step,
                const float* normsq, float max_norm, float grad_scale, const float* count, void* stream);
+/* ---- weight averaging: an exponential moving average of the flat parameter buffer.
+ * ema[i] = fmaf(w, p[i] - ema[i], ema[i]) with w = 1 - decay in [0, 1]: the difference is rounded once and the multiply-add once,
+ * on the 16-byte path and the scalar path alike (equal bits whatever the alignment), and p[i] == ema[i] gives ema[i] back bit for
+ * bit -- frozen tensors, pads and gaps keep tracking p without a segment table.  (One select on top of the expression: a result
+ * that compares equal to ema[i] is ema[i], so that an ema[i] of -0, which the multiply-add would return as +0, keeps its sign;
+ * w = 0 therefore keeps every bit too.)  count (nullable): mmtg_adamw's device scalar; a
+ * *count that is not greater than 0 (0, negative, NaN) leaves every bit of ema, as it left every bit of p.  The two ranges must
+ * not overlap.                                                                                                             */
+MMTG_API int mmtg_ema_update(float* ema, const float* p, long n, float w, const float* count, void* stream);
+/* a[0:n] <-> b[0:n], moved as 32-bit words (NaN payloads and -0 survive); the two ranges must not overlap */
+MMTG_API int mmtg_swap_f32(float* a, float* b, long n, void* stream);
 MMTG_API int mmtg_cast_f32_to(int dtype, const float* src, void* dst, long n, void* stream);
 /* dst[r, 0:cols] = cast(src[r, 0:cols]); dst[r, cols:ldd] = 0 */
 MMTG_API int mmtg_cast_pad_rows(int dtype, const float* src, long lds_, void* dst, long ldd, int rows, int cols, void* stream);

@@ -294,6 +294,51 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
     }
 }
 
+// ---------------------------------------------------------------- weight averaging
+// One element of the exponential moving average, shared by the 16-byte path and the scalar path so that both round alike (see
+// adamw_update): the difference is rounded once, the multiply-add once.  p == e gives e back (w * 0 + e), so frozen tensors, pads
+// and gaps of the flat buffer follow the master without a segment table -- bit for bit but for one case, which the select below
+// takes care of: e = -0 comes out of the multiply-add as +0 (p - e = +0, and +0 + -0 = +0; likewise w = 0 with p > e), and GPT-2
+// checkpoints do hold a -0 here and there.  A result that compares equal to e IS e, so the select changes nothing but that sign.
+__device__ __forceinline__ float ema_step(float e, float p, float w) {
+#pragma clang fp contract(off)
+    const float d = p - e;
+    const float r = fmaf(w, d, e);
+    return r == e ? e : r;
+}
+
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float w,
+                                                         const float* __restrict__ count) {
+    // the device scalar mmtg_adamw takes: an empty global batch skipped the step and skips the average
+    if (count && !(*count > 0.f)) return;
+    const bool vec_ok = ((reinterpret_cast<uintptr_t>(ema) | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
+    const long n4 = vec_ok ? n >> 2 : 0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const f32x4 p4 = reinterpret_cast<const f32x4*>(p)[i];
+        f32x4 e4 = reinterpret_cast<f32x4*>(ema)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) e4[e] = ema_step(e4[e], p4[e], w);
+        reinterpret_cast<f32x4*>(ema)[i] = e4;
+    }
+    for (long i = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) ema[i] = ema_step(ema[i], p[i], w);
+}
+
+// a <-> b as 32-bit words: NaN payloads and -0 survive (no floating-point instruction touches the data)
+__global__ __launch_bounds__(256) void swap_kernel(unsigned* __restrict__ a, unsigned* __restrict__ b, long n) {
+    const bool vec_ok = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+    const long n4 = vec_ok ? n >> 2 : 0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const u32x4 a4 = reinterpret_cast<u32x4*>(a)[i], b4 = reinterpret_cast<u32x4*>(b)[i];
+        reinterpret_cast<u32x4*>(a)[i] = b4;
+        reinterpret_cast<u32x4*>(b)[i] = a4;
+    }
+    for (long i = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const unsigned x = a[i], y = b[i];
+        a[i] = y;
+        b[i] = x;
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void cast_from_f32_kernel(const float* __restrict__ src, T* __restrict__ dst, long n) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = (T)src[i];
@@ -514,6 +559,35 @@ extern "C" int mmtg_adamw_groups(float* p, const float* g, float* m, float* v, v
     hipLaunchKernelGGL(adamw_groups_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), seg_lds_bytes(nsegs) + 2 * MMTG_MAX_PARAM_GROUPS * sizeof(float), s,
                        p, g, m, v, (bf16*)p_bf16, (bf16*)p_lo, n, segs_dev, nsegs, grp, beta1, beta2, eps, normsq, max_norm, grad_scale, count);
     MMTG_LAUNCH_CHECK("adamw_groups");
+    return MMTG_OK;
+}
+
+// [x, x + n floats) and [y, y + n floats) share a byte
+static bool ranges_overlap(const void* x, const void* y, long n) {
+    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y, bytes = (uintptr_t)n * sizeof(float);
+    return a < b + bytes && b < a + bytes;
+}
+
+extern "C" int mmtg_ema_update(float* ema, const float* p, long n, float w, const float* count, void* stream) {
+    MMTG_REQUIRE(ema && p, "ema_update: null pointer (ema %p, p %p)", (void*)ema, (const void*)p);
+    MMTG_REQUIRE(n > 0, "ema_update: n = %ld", n);
+    MMTG_REQUIRE(w >= 0.f && w <= 1.f, "ema_update: w = %g (0 .. 1)", (double)w);         // (NaN fails both comparisons)
+    MMTG_REQUIRE(!ranges_overlap(ema, p, n), "ema_update: ema and p overlap (%ld floats at %p and %p)", n, (void*)ema, (const void*)p);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_OPTIM, s, 3.0 * n, 12.0 * n);
+    hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, ema, p, n, w, count);
+    MMTG_LAUNCH_CHECK("ema_update");
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_swap_f32(float* a, float* b, long n, void* stream) {
+    MMTG_REQUIRE(a && b, "swap_f32: null pointer (a %p, b %p)", (void*)a, (void*)b);
+    MMTG_REQUIRE(n > 0, "swap_f32: n = %ld", n);
+    MMTG_REQUIRE(!ranges_overlap(a, b, n), "swap_f32: the buffers overlap (%ld floats at %p and %p)", n, (void*)a, (void*)b);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_OPTIM, s, 0, 16.0 * n);
+    hipLaunchKernelGGL(swap_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, s, (unsigned*)a, (unsigned*)b, n);
+    MMTG_LAUNCH_CHECK("swap_f32");
     return MMTG_OK;
 }
 

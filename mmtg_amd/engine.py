@@ -376,6 +376,7 @@ class Engine:
         self.step_count = 0
         self.opt_m = None
         self.opt_v = None
+        self.ema = None            # flat fp32 average of the master (ema_update), None until first use
         self.normsq = torch.zeros(1, device=self.dev)
         self.group_normsq = None   # [ngroups + 1] of a grouped step (group_norm_sq); normsq is then its last element
         self.bucket_hook = None   # callable(pack_index) fired as packs of gradients become final
@@ -1755,3 +1756,26 @@ class Engine:
                              eps, self.step_count, ns, max_norm, grad_scale, count=count, p_lo=p_lo)
         self._refresh_transposed()
         self.copies_fresh = True
+
+    # ---------------------------------------------------------------- weight averaging
+    def ema_update(self, w, count=None):
+        """ema += w (master - ema) over the whole flat buffer (hip.ema_update), w = 1 - decay.  The first call allocates `ema` as a
+        copy of the master -- data movement, no arithmetic -- so a caller that wants the average to start from the weights BEFORE an
+        optimizer step makes that call's copy first (MMTGTrainer._close_end does).  Pads, gaps and frozen tensors are equal in both
+        buffers and stay so bit for bit.  count: adamw_step's device scalar; a step it skipped skips the average."""
+        self.ema_init()
+        hip.ema_update(self.ema, self.master, self.layout.total, w, count=count)
+
+    def ema_init(self):
+        """Allocate `ema` as a copy of the master if there is none yet."""
+        if self.ema is None:
+            self.ema = self.master.detach().clone()
+
+    def swap_ema(self):
+        """Exchange master and average in place, bit for bit (hip.swap_f32); every derived copy -- the bf16 copy, the (hi | lo)
+        planes, the [out,in] transposes, the decoders' folds -- is re-derived by the next forward() or generation through
+        refresh_copies().  All pointers stay valid: captured decode graphs replay over the swapped data."""
+        if self.ema is None:
+            raise RuntimeError("Engine.swap_ema: there is no average yet (ema_update has not run)")
+        hip.swap_f32(self.master, self.ema, self.layout.total)
+        self.invalidate_copies()

@@ -81,6 +81,8 @@ _SIGS = {
     "mmtg_sumsq_groups_ws": ([_l, _i], _l),
     "mmtg_sumsq_groups": ([_vp, _l, _vp, _vp, _i, _i, _u, _vp, _vp, _l, _vp], _i),
     "mmtg_adamw_groups": ([_vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _vp, _i, _f, _f, _f, _f, _i, _vp, _f, _f, _vp, _vp], _i),
+    "mmtg_ema_update": ([_vp, _vp, _l, _f, _vp, _vp], _i),
+    "mmtg_swap_f32": ([_vp, _vp, _l, _vp], _i),
     "mmtg_gemm_x3": ([_i, _i, _i, _vp, _l, _l, _vp, _l, _l, _vp, _l, _vp, _l, _l, _vp, _i, _vp, _l, _vp, _u, _u, _i, _vp], _i),
     "mmtg_split_planes": ([_vp, _l, _i, _i, _vp, _l, _l, _vp], _i),
     "mmtg_layernorm_fwd_x3": ([_vp, _vp, _l, _l, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _vp], _i),
@@ -775,6 +777,17 @@ def adamw_groups(p, g, m, v, p_bf16, n, table, lr, beta1, beta2, eps, step, norm
                                    table.nsegs, C.addressof(table.records), table.ngroups, float(lr), float(beta1), float(beta2),
                                    float(eps), int(step), _p(normsq), float(max_norm), float(grad_scale), _p(count), _stream()),
            "adamw_groups")
+
+
+def ema_update(ema, p, n, w, count=None):
+    """ema[:n] = fmaf(w, p - ema, ema), w = 1 - decay rounded once to fp32; p == ema keeps ema's bits.  count: the optional device
+    scalar of adamw -- a count that is not greater than 0 leaves ema untouched."""
+    _check(lib().mmtg_ema_update(_p(ema), _p(p), n, float(w), _p(count), _stream()), "ema_update")
+
+
+def swap_f32(a, b, n):
+    """a[:n] <-> b[:n], bit for bit."""
+    _check(lib().mmtg_swap_f32(_p(a), _p(b), n, _stream()), "swap_f32")
 
 
 def cast_f32_to(src, dst, n):

@@ -14,6 +14,7 @@ get_linear_schedule_with_warmup (train.py:146-148).
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 import os
 
@@ -45,14 +46,25 @@ _LOGITS_F32 = bool(os.environ.get("MMTG_LOGITS_F32"))     # A/B switch: fp32 log
 class MMTGTrainer:
     def __init__(self, model, lr=1e-5, alpha=0.0, max_norm=1.0, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.0, warmup_steps=0, total_steps=None, distributed=False, bucket_mb=64.0,
-                 lm_weight=0.0, param_groups=None, accumulation_steps=1):
+                 lm_weight=0.0, param_groups=None, accumulation_steps=1, ema_decay=None, ema_warmup=True):
         """accumulation_steps: calls of step() per optimizer step (a window of micro-batches, see step()).
+        ema_decay: None (no average: no buffer, no launch) or a float in (0, 1), the decay of an exponential moving average of
+        the parameters kept next to the masters and updated once per optimizer step (see _close_end); ema_warmup: the decay of
+        update t (from 0) is min(ema_decay, (1 + t) / (10 + t)), so that the first steps do not pin the average to the initial
+        weights.  In a data-parallel group every rank keeps its own average and nothing is exchanged: the parameters are identical
+        across ranks after every step, and so are the averages.  averaged_weights() / evaluate(averaged=True) /
+        ema_state_dict() / save_checkpoint(averaged=True) read it.
         param_groups: a list of specs as mmtg_amd.param_groups takes them (fnmatch patterns on the state-dict keys; per group
         `lr_scale`, `weight_decay`, `frozen`).  `lr` and the schedule stay the base rate, groups scale it; None is the single
         group of the reference."""
         if type(accumulation_steps) is not int or accumulation_steps < 1:
             raise ValueError("accumulation_steps must be an int of at least 1, got %r" % (accumulation_steps,))
+        if ema_decay is not None and not (isinstance(ema_decay, float) and 0.0 < ema_decay < 1.0):
+            raise ValueError("ema_decay must be None or a float in (0, 1), got %r" % (ema_decay,))
         self.accumulation_steps = accumulation_steps
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        self.ema_updates = 0                    # updates of the average made so far
+        self._averaged = False                  # inside averaged_weights(): master and average are exchanged
         self.model = model
         self.eng = model.engine()
         self.group_plan = self.groups = None
@@ -99,7 +111,9 @@ class MMTGTrainer:
     def state_dict(self):
         """Optimizer moments (flat fp32, the engine's parameter order), AdamW step count, scheduler position
         and the dropout counter: together with ``model.state_dict()`` everything a bit-continuing run needs.  Only at a window
-        boundary: the gradient sums of an open window are not part of it."""
+        boundary: the gradient sums of an open window are not part of it.  'ema' is None for a trainer without an average, else
+        {'decay', 'warmup', 'updates', 'average'} with the flat fp32 average (None before the first step)."""
+        self._refuse_averaged("state_dict()")
         if self._micro:
             raise RuntimeError("state_dict() inside an open accumulation window (micro_step = %d of %d): take the checkpoint at a "
                                "boundary, or close the window with flush() first" % (self._micro, self.accumulation_steps))
@@ -111,18 +125,34 @@ class MMTGTrainer:
                 # the CU reservation the ranks agreed on (None: not tuned): a resumed run keeps it instead of spending nine steps
                 # re-tuning under wall-clock timings (MMTG_DDP_GEMM_CUS pins it from the environment)
                 "cu_budget": None if self.budget_report is None else self.budget_report.get("budget_chosen"),
+                "ema": None if self.ema_decay is None else {
+                    "decay": self.ema_decay, "warmup": self.ema_warmup, "updates": self.ema_updates,
+                    "average": None if eng.ema is None else eng.ema.detach().cpu().clone()},
                 "hparams": {"lr": self.lr, "alpha": self.alpha, "max_norm": self.max_norm, "betas": tuple(self.betas),
                             "eps": self.eps, "weight_decay": self.wd, "warmup_steps": self.warmup,
                             "total_steps": self.total, "lm_weight": self.lm_weight, "accumulation_steps": self.accumulation_steps,
+                            "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup,
                             # for the record, like the rest: load_state_dict keeps the trainer's own groups as it keeps its own lr
                             "param_groups": None if self.group_plan is None else copy.deepcopy(self.group_plan.specs)}}
 
     def load_state_dict(self, sd):
-        """(accumulation_steps stays the trainer's own, like lr and the groups; an open window is abandoned)"""
+        """(accumulation_steps stays the trainer's own, like lr and the groups; an open window is abandoned)
+        A trainer with an average takes 'average' and 'updates' from the dict; from a dict without an average (an older
+        checkpoint, a run that kept none) the average is dropped and restarts from the loaded weights at the next step.  The decay
+        and the warm-up rule stay the trainer's own; a trainer without an average ignores the key."""
+        self._refuse_averaged("load_state_dict()")
         eng = self.eng
         if sd.get("format") != "mmtg-trainer-1" or sd.get("layout_total") != eng.layout.total:
             raise ValueError("trainer state of a different model layout (%s, %s parameters; this model has %d)"
                              % (sd.get("format"), sd.get("layout_total"), eng.layout.total))
+        if self.ema_decay is not None:
+            rec = sd.get("ema") or {}
+            avg = rec.get("average")
+            if avg is not None and avg.numel() != eng.layout.total:
+                raise ValueError("trainer state with an average of %d elements; this model's flat buffer has %d"
+                                 % (avg.numel(), eng.layout.total))
+            eng.ema = None if avg is None else avg.to(eng.dev, torch.float32).reshape(-1).clone()
+            self.ema_updates = 0 if avg is None else int(rec.get("updates", 0))
         for name, key in (("opt_m", "exp_avg"), ("opt_v", "exp_avg_sq")):
             v = sd[key]
             setattr(eng, name, None if v is None else v.to(eng.dev, torch.float32).clone())
@@ -150,7 +180,9 @@ class MMTGTrainer:
         still advances the Adam step (bias correction) and the LR schedule by one.  A single process `continue`s before
         either counter moves (train.py:184-185).  Shards of a shuffled global batch that are ALL empty after the stage
         filter do not occur with the released data (every rating occurs in every batch of 64+ rows); the price of the
-        exact behaviour would be a host read of the all-reduced count every step.
+        exact behaviour would be a host read of the all-reduced count every step.  The average (ema_decay) follows the same rule:
+        its kernel reads the count and leaves the average untouched, while the host advances `ema_updates` -- and with it the
+        warm-up of the decay -- by one.
 
         Gradient accumulation.  With accumulation_steps = k > 1 a call is a MICRO-step and k consecutive calls -- counted in calls,
         not rows, so every rank of a group closes at the same call -- are a window: the buffer is zeroed once, before the window's
@@ -160,6 +192,7 @@ class MMTGTrainer:
         k ranks.  A call the stage filter empties runs nothing and still counts; a single-rank window without any row moves no
         counter.  `window` then holds the closed window's row-weighted means {'loss','lm_loss','kl'} (device scalars; with k = 1 the
         step's own, valid until the next call) and its local 'rows'.  If a call raises, the window is abandoned (reset_window)."""
+        self._refuse_averaged("step()")
         if self._tune is not None and self._micro == 0:      # the tuning books whole windows
             self._tune_ev = torch.cuda.Event(enable_timing=True)
             self._tune_ev.record()
@@ -190,6 +223,7 @@ class MMTGTrainer:
     def flush(self):
         """Close a partial window (the end of an epoch): the exchange and the optimizer step over the rows so far.  True when a
         window was open, False -- and nothing done -- at a boundary."""
+        self._refuse_averaged("flush()")
         if not self._micro:
             return False
         red = self.reducer if (self.reducer is not None and self.reducer.active) else None
@@ -313,8 +347,12 @@ class MMTGTrainer:
         return True
 
     def _close_end(self, red):
-        """Exchange, clip + AdamW, schedule: once per window."""
+        """Exchange, clip + AdamW, the average, schedule: once per window.  With ema_decay the order is: the average's lazy first
+        copy of the master (so that it starts from the weights BEFORE the first optimizer step), the AdamW step, then
+        ema += (1 - decay_t) (master - ema) with decay_t computed here in double and the kernel reading the same row count as AdamW."""
         eng = self.eng
+        if self.ema_decay is not None:
+            eng.ema_init()
         if red is not None:
             if self.measure_finish:     # exposed exchange time: how long the compute stream sits in finish() (bench.py --gpus N)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -325,6 +363,11 @@ class MMTGTrainer:
             else:
                 red.finish(eng.grad)
         eng.adamw_step(self.current_lr(), self.max_norm, self.betas, self.eps, self.wd, count=self._count, groups=self.groups)
+        if self.ema_decay is not None:
+            t = self.ema_updates
+            decay = min(self.ema_decay, (1.0 + t) / (10.0 + t)) if self.ema_warmup else self.ema_decay
+            eng.ema_update(1.0 - decay, count=self._count)
+            self.ema_updates = t + 1
         self.sched_step += 1
         rows = self._rows
         if rows == 0:
@@ -361,11 +404,15 @@ class MMTGTrainer:
         return {"loss": loss, "kl": kl, "total": loss + self.alpha * kl}
 
     @torch.no_grad()
-    def evaluate(self, valid_batches, stage=3):
+    def evaluate(self, valid_batches, stage=3, averaged=False):
         """The reference's evaluate() (train.py:241-268) over an iterable of validation batches: per batch
         total = MyLoss.mean() + alpha * kl.mean(), summed -- on the device, one host read at the end -- and divided by the NUMBER OF
         BATCHES (filtered-out ones included, as `valid_loss /= len(valid_dataset)` does).  Returns (valid_loss, kldiv_loss) floats;
-        the model is in eval mode during the pass (train.py:242) and gets its previous mode back afterwards."""
+        the model is in eval mode during the pass (train.py:242) and gets its previous mode back afterwards.
+        averaged=True runs the pass inside averaged_weights()."""
+        if averaged:
+            with self.averaged_weights():
+                return self.evaluate(valid_batches, stage)
         was_training = self.model.training
         self.model.eval()
         acc = torch.zeros(2, device=self.eng.dev, dtype=torch.float32)
@@ -384,6 +431,49 @@ class MMTGTrainer:
             return 0.0, 0.0
         v = (acc / n).tolist()
         return v[0], v[1]
+
+    # ---- the averaged weights
+    def _refuse_averaged(self, what):
+        if self._averaged:
+            raise RuntimeError("%s inside averaged_weights(): the masters hold the average until the context exits" % what)
+
+    def _require_average(self, what):
+        if self.ema_decay is None:
+            raise RuntimeError("%s: this trainer keeps no average (ema_decay=None)" % what)
+        if self.eng.ema is None:
+            raise RuntimeError("%s: there is no average yet (no optimizer step has been taken)" % what)
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Context in which the model computes with the averaged weights: master and average are exchanged in place on entry and
+        exchanged back on exit (also when the body raises), each time invalidating the derived copies, so evaluate*, the model's
+        forward and every decoder or generator built on this model read the average inside and the last iterate after.  step(),
+        flush(), state_dict(), load_state_dict() and a nested entry raise inside; entering inside an open accumulation window is
+        fine, gradients are not touched."""
+        self._refuse_averaged("averaged_weights()")
+        self._require_average("averaged_weights()")
+        self.eng.swap_ema()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self.eng.swap_ema()
+            self._averaged = False
+
+    def ema_state_dict(self):
+        """The averaged model as CPU tensors with the keys, shapes and dtypes of model.state_dict(): every key of the flat buffer
+        (the tied lm_head included) from the average, anything else from the model.  Loads into another MMTG."""
+        self._require_average("ema_state_dict()")
+        eng = self.eng
+        flat = (eng.master if self._averaged else eng.ema).detach().cpu()
+        out = {}
+        for k, v in self.model.state_dict().items():
+            key = "decoder.gpt2.transformer.wte.weight" if k == "decoder.gpt2.lm_head.weight" else k
+            if key in eng.layout.entries:
+                out[k] = eng.layout.view(flat, key).clone()
+            else:
+                out[k] = v.detach().cpu().clone()
+        return out
 
     def finish_wait_ms(self):
         """Mean time per step the compute stream waited in the reducer's finish() -- the part of the gradient exchange the
@@ -415,7 +505,7 @@ class MMTGTrainer:
                  "tensors": len(g["keys"]), "parameters": g["parameters"]} for g in self.group_plan.groups]
 
 
-def save_checkpoint(path, model, trainer=None, args=None, model_cfgs=None, reference_compatible=False):
+def save_checkpoint(path, model, trainer=None, args=None, model_cfgs=None, reference_compatible=False, averaged=False):
     """The reference's checkpoint dict ``{'model', 'args', 'model_cfgs'}`` (train.py:212) plus, when a trainer is
     given, ``'trainer'`` for resuming.
 
@@ -423,11 +513,22 @@ def save_checkpoint(path, model, trainer=None, args=None, model_cfgs=None, refer
     ``module.`` prefix of its nn.DataParallel wrapper (train.py:113,212) and every GPT-2 block has the persistent
     ``attn.bias`` / ``attn.masked_bias`` buffers of transformers 4.12.3, so the reference's strict
     ``load_state_dict`` into its DataParallel-wrapped model (generate.py:191-192) accepts the file.  The default
-    writes ``model.state_dict()`` (what ``load_checkpoint`` and any unwrapped consumer read)."""
+    writes ``model.state_dict()`` (what ``load_checkpoint`` and any unwrapped consumer read).
+
+    averaged=True writes the ``'model'`` entry from the trainer's averaged weights (``trainer.ema_state_dict()``), in either key
+    style: a file for evaluation and generation.  ``'trainer'`` still holds the raw trainer state -- moments, counters, the
+    average -- but the last iterate's parameters are in no entry: resume from a file written without the flag.  It raises when
+    there is no trainer or the trainer has no average."""
+    if averaged:
+        if trainer is None:
+            raise RuntimeError("save_checkpoint(averaged=True) needs the trainer that keeps the average")
+        avg = trainer.ema_state_dict()
     if reference_compatible:
         sd = {"module." + k: v for k, v in model.legacy_state_dict().items()}
+        if averaged:
+            sd.update(("module." + k, v) for k, v in avg.items())
     else:
-        sd = model.state_dict()
+        sd = avg if averaged else model.state_dict()
     ckpt = {"model": {k: v.detach().cpu() for k, v in sd.items()}, "args": args, "model_cfgs": model_cfgs}
     if trainer is not None:
         ckpt["trainer"] = trainer.state_dict()
