@@ -474,7 +474,8 @@ def test_gemm_rejects_bad_arguments():
 @pytest.mark.parametrize("cols,rows", [(512, 333), (768, 333), (768, 5001), (1024, 2100), (512, 2048)])
 def test_layernorm(dtype, cols, rows):
     # 333 rows: the small-launch kernels; >= 2048 rows: the grid-stride bf16 kernels (a full wave per row with
-    # 16-byte + 8-byte vectors per lane, next row prefetched) incl. a ragged last sweep; 1024 columns: GPT-2-medium
+    # 16-byte + 8-byte vectors per lane, next row prefetched), one sweep each: cdiv(5001, 4) = 1251 workgroups stay under the
+    # grid cap of 6 per CU -- the second, ragged sweep is tests/test_row_ops_gpu.py's; 1024 columns: GPT-2-medium
     x = rnd(rows, cols, dtype=dtype, seed=1, scale=2.0)
     g = 1 + 0.1 * rnd(cols, seed=2)
     b = 0.1 * rnd(cols, seed=3)
