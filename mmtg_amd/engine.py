@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import contextlib
 import math
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -179,12 +180,6 @@ def _dist_rank():
 
 
 _NO_OCC4 = bool(_os.environ.get("MMTG_GEMM_NO_OCC4"))     # A/B switch, mirrors the library's
-_WG_NUM = float(_os.environ.get("MMTG_WGRAD_NUM", "760"))     # tuning knobs of the slab weight-gradient split count
-_WG_CAP = int(_os.environ.get("MMTG_WGRAD_CAP", "12"))
-_NO_FEW_ROWS = bool(_os.environ.get("MMTG_NO_FEW_ROWS"))   # A/B switch: plain launches for the encoder-sized products
-_WGRAD_SLAB = not _os.environ.get("MMTG_WGRAD_ATOMIC")     # A/B switch: fp32-atomic weight gradients everywhere
-_NO_GATHER = bool(_os.environ.get("MMTG_NO_GATHER"))       # A/B switch: materialise the conditioned embeddings (round-1 path)
-_PREFETCH = int(_os.environ.get("MMTG_PREFETCH", "0"))      # backward: Infinity-Cache prefetch of saved activations on a side stream (workgroups; 0 = off)
 
 
 def _wgrad_splits(M, N, K, occ4=False, slots=512, t_iter=1.1, t_fixed=6.0):
@@ -199,8 +194,8 @@ def _wgrad_splits(M, N, K, occ4=False, slots=512, t_iter=1.1, t_fixed=6.0):
         # so only the fill of the last round and the atomic volume matter.  Measured optima
         # (profiles/r01_v6_gemm_tn_split_sweep.log): 144 tiles -> 5, 108 -> 6..7, 630 -> 4, 36 -> 8+.
         smax = max(1, K // 256)
-        s = round(_WG_NUM / tiles) if tiles < 512 else round(2520.0 / tiles)
-        return int(max(1, min(smax, s, _WG_CAP)))
+        s = round(760.0 / tiles) if tiles < 512 else round(2520.0 / tiles)
+        return int(max(1, min(smax, s, 12)))
     best, best_t = 1, None
     for s in range(1, 33):
         if s > 1 and K // s < 256:
@@ -213,15 +208,7 @@ def _wgrad_splits(M, N, K, occ4=False, slots=512, t_iter=1.1, t_fixed=6.0):
     return best
 
 
-_LAZY_ZERO = _os.environ.get("MMTG_FULL_ZERO_GRAD") is None   # zero only the accumulated gradients once a step shape is known (A/B switch)
-_WTE_T = _os.environ.get("MMTG_NO_WTE_T") is None      # [D, Vpad] copy of wte for the LM head's dgrad (A/B switch)
-_P8T = _os.environ.get("MMTG_GEMM_P8T", "0") != "0"      # eight-phase K-strided kernel for the slab weight gradients (opt-in: measured slower in situ)
-_WGRAD_GROUP = _os.environ.get("MMTG_WGRAD_GROUP", "1") != "0"   # one grouped launch per GPT-2 block for its four weight gradients (A/B switch)
 _WGRAD_GROUP_SPLITS = int(_os.environ.get("MMTG_WGRAD_GROUP_SPLITS", "0"))    # 0 = the one-round rule below
-# fc1's epilogue saves gelu'(pre-activation) instead of the pre-activation (MMTG_GEMM_GELU_GRAD): OPT-IN.  Same box: 15.11 -> 15.03 ms
-# per step, but the tiny, cancellation-dominated gradient of mm_atten_layer.att_matrices.3.weight moves from 1.05x to 1.18x of the
-# oracle's norm on the 2-layer golden model (every other tensor within 1 %): outside the parity suite's 10 % bound, so not the default
-_GELU_GRAD = _os.environ.get("MMTG_GELU_GRAD", "0") != "0"
 # the bf16 decoder backward's small ordered column sums (LayerNorm second stages, dGELU bands, attention bias rows: 4 per block) summed
 # by ONE batched launch per data-parallel hand-over point -- one per step without a bucket hook -- instead of a launch each (A/B switch)
 _DEFER_SUMS = _os.environ.get("MMTG_DEFER_SUMS", "1") != "0"
@@ -230,25 +217,15 @@ _DEFER_SUMS = _os.environ.get("MMTG_DEFER_SUMS", "1") != "0"
 # the block loop; joined before the gradient norm.  Single-GPU steps with dropout on (their operands are the masked copies, which get
 # buffers of their own: 209 MB per block at GPT-2 base); 0 = off.  Measured (same box, ms per step): 0: 14.91, 1-2: 14.9-15.0 (the
 # co-running launches slow the tail as much as they hide), 4: 14.72, 6: 14.66, 8: 14.64, 12: 14.67; the same launches at the same
-# place on the MAIN stream (MMTG_WGRAD_TAIL_MAIN=1): 14.98 -- the gain is the overlap, not the order.  bf16x3 (plane-pair operands,
-# with or without dropout): 33.57 -> 33.07 at 8 (33.03 at 4, 33.29 at 12)
+# place on the MAIN stream: 14.98 -- the gain is the overlap, not the order.  bf16x3 (plane-pair operands, with or without dropout):
+# 33.57 -> 33.07 at 8 (33.03 at 4, 33.29 at 12)
 _WGRAD_TAIL = int(_os.environ.get("MMTG_WGRAD_TAIL", "8"))
-# where the side stream forks: "loop" = right after the block loop (beside the embedding / projector backward too: 14.28 -> 14.10 ms on
-# top of the above), "proj" = after the projector backward (A/B)
-_TAIL_FORK_EARLY = _os.environ.get("MMTG_WGRAD_TAIL_FORK", "loop") == "loop"
-_LMHEAD_GROUP = _os.environ.get("MMTG_LMHEAD_GROUP", "1") != "0"      # the tied embedding's weight gradient through the grouped kernel (A/B switch)
 _LMHEAD_GROUP_SPLITS = int(_os.environ.get("MMTG_LMHEAD_GROUP_SPLITS", "0"))
-# the grouped weight-gradient launches on a SIDE stream, one block behind the dgrad chain (MMTG_WGRAD_STREAM; see Engine.backward)
+# the grouped weight-gradient launches on a SIDE stream, one block behind the dgrad chain (MMTG_WGRAD_STREAM; see Engine._bwd_blocks)
 _WGRAD_STREAM = _os.environ.get("MMTG_WGRAD_STREAM", "0") != "0"
-# x3 grouped weight gradients: config 6 = combined stages (all four planes of a K tile per 64 KB stage, two workgroups per CU: 512
-# slots), MMTG_WGRAD_X3_COMBINED=0 = config 2, three passes over 32 KB stages at four workgroups per CU (A/B switch)
-# Round 6 (MMTG_ENC_STREAMS=1, opt-in: measured NEUTRAL -- 14.73 / 14.72 ms per step without, 14.71 / 14.72 with, same box, all gradient /
-# reproducibility tests green under it): the two encoder channels (image / text: independent chains of ~20 tiny dependent launches each
-# way) side by side -- the text channel on a second stream with its own workspaces -- forward and backward
-_ENC_STREAMS = _os.environ.get("MMTG_ENC_STREAMS", "0") != "0"
-# bf16x3f: the encoder / fuser backward on the bf16 kernels as well (MMTG_HYBRID_ENC_BF16=0: exact fp32, the round's first version)
-_HYBRID_ENC_BF16 = _os.environ.get("MMTG_HYBRID_ENC_BF16", "1") != "0"
-_X3_WG_CFG = 6 if _os.environ.get("MMTG_WGRAD_X3_COMBINED", "1") != "0" else 2
+# x3 grouped weight gradients: mmtg_wgrad_group's config 6 = combined stages (all four planes of a K tile per 64 KB stage, two
+# workgroups per CU: 512 slots)
+_X3_WG_CFG = 6
 # 0: 128x128 tiles, four workgroups per CU; 1: 256x256 eight-phase; 2: 256x256, one 16-wave workgroup per CU over a 3-deep ring of
 # 32-k stages (mmtg_wgrad_group's config 8 -- its 2 is the split-precision form).  Default 2: 14.71 -> 14.07 ms per step over three
 # alternating pairs, the launch 275 -> 228 us, parameters and gradients bit-equal to config 0's (docs/experiments.md, last section)
@@ -270,34 +247,26 @@ def _group_splits(tiles, K, slots=1024):
     return int(max(1, min(slots // max(1, tiles), K // 1024, 16)))
 
 
+def _group_sizing(shapes, cfg, rule):
+    """(K splits, workspace floats, counters) of a grouped launch over problems of the given (M, N) shapes in the kernel's tile
+    configuration `cfg` (hip.wgrad_group_sizes'); rule(tiles) gives the split count.  No device access."""
+    tiles = hip.wgrad_group_sizes(shapes, 1, cfg)[0]
+    splits = rule(tiles)
+    _, nws, ncnt = hip.wgrad_group_sizes(shapes, splits, cfg)
+    return splits, nws, ncnt
+
+
 def _group_splits_x3(tiles, K):
     """K splits of a split-precision grouped launch.  Combined stages (config 6, two workgroups per CU = 512 slots), measured at
     K = 15104 (tools/bench_wgrad_x3.py): one full round when the tiles fit (projector: 88 tiles x 5 = 122 us against 172 at x 6),
     else about four rounds' worth (tied embedding, 630 tiles: x 3 = 783 us, x 2 = 845, x 1 = 1054); a block's 432 tiles run within
     2 % of their best at any count from 1 to 5."""
-    if _X3_WG_CFG != 6:
-        return _group_splits(tiles, K)
     if _WGRAD_GROUP_SPLITS > 0:
         return _WGRAD_GROUP_SPLITS
     s = 512 // max(1, tiles)
     if s == 0:
         s = 2048 // tiles
     return int(max(1, min(s, K // 1024, 16)))
-
-
-def _wgrad_splits_p8(M, N, K, cus=256):
-    """Split count for the eight-phase weight-gradient kernel (256x256 tiles, ONE workgroup per CU): tiles x splits fills one
-    round of the CUs, every split a whole number of 128-deep K units, no empty trailing split.  None when the product is
-    not eligible (mmtg_gemm's rule: K % 128 == 0, M, N >= 256) or has too many tiles to gain from splitting."""
-    if not _P8T or K % 128 or M < 256 or N < 256:
-        return None
-    tiles = ((M + 255) // 256) * ((N + 255) // 256)
-    if tiles > cus // 2:
-        return None
-    units = K // 128
-    s0 = max(1, min(cus // tiles, units // 4))
-    per = -(-units // s0)
-    return -(-units // per)
 
 
 def _round_capacity(n):
@@ -366,7 +335,6 @@ class Engine:
         self.set_table(table)
         self.prior = torch.from_numpy(gaussian_prior(self.sh.S)).to(self.dev)
         self.ws = {}
-        self._ws_tag = ""
         self.act = None
         self.training = False
         self.drop_seed = initial_drop_seed(_dist_rank())
@@ -382,7 +350,7 @@ class Engine:
         self.bucket_hook = None   # callable(pack_index) fired as packs of gradients become final
         self._sums, self._defer = [], False     # deferred column sums of the backward (see _defer_sum)
         self._tail_jobs, self._tail_side = [], None      # grouped weight gradients deferred to the backward's tail (_WGRAD_TAIL)
-        self._pf_stream = None
+        self._side, self._events = None, {}     # the side stream of the weight-gradient launches and its per-block events
         self._rowmaps = {}
 
     # ---------------------------------------------------------------- buffers / views
@@ -409,7 +377,7 @@ class Engine:
         n = 1
         for d in shape:
             n *= int(d)
-        key = (name + self._ws_tag, dtype)          # (_ws_tag: "" / "~s" while a second stream's chain is being enqueued: its own workspaces)
+        key = (name, dtype)
         t = self.ws.get(key)
         if t is None or t.numel() < n:
             cap = _round_capacity(n)
@@ -450,7 +418,7 @@ class Engine:
         self.ensure_grad()
         self._ow_rec = None
         self._lazy = None
-        if shape_key is not None and _LAZY_ZERO:
+        if shape_key is not None:
             ent = self._ow_desc.get(shape_key)
             if ent is not None:
                 desc, ranges = ent
@@ -517,8 +485,7 @@ class Engine:
         # vocabulary, wte's ROW index -- through the copy it is a K-contiguous x K-contiguous product like every other
         # forward / dgrad product (eight-phase kernel).  Its own launch: a shared grid would be sized by its 13440 rows.
         woff = self.layout.pack_range["wte"][0]
-        self.wte_t = (torch.zeros(*((2,) if self.x3 else ()), self.sh.D, self.layout.Vpad, device=self.dev, dtype=torch.bfloat16)
-                      if (_WTE_T or self.x3) else None)
+        self.wte_t = torch.zeros(*((2,) if self.x3 else ()), self.sh.D, self.layout.Vpad, device=self.dev, dtype=torch.bfloat16)
         self.wte_desc = torch.tensor([(woff, self.layout.Vpad, self.sh.D, 0)], dtype=torch.int64, device=self.dev)
 
     def Wt(self, key):   # [out, in] copy of a Conv1D weight (bf16 mode)
@@ -534,8 +501,7 @@ class Engine:
                 hip.transpose_batch(self.wc2[pl], self.wte_t[pl], self.wte_desc, 1, self.layout.Vpad, self.sh.D)
         elif self.wt is not None:
             hip.transpose_batch(self.wc, self.wt, self.wt_desc, self.wt_desc.shape[0], *self.wt_max)
-            if self.wte_t is not None:
-                hip.transpose_batch(self.wc, self.wte_t, self.wte_desc, 1, self.layout.Vpad, self.sh.D)
+            hip.transpose_batch(self.wc, self.wte_t, self.wte_desc, 1, self.layout.Vpad, self.sh.D)
 
     def refresh_copies(self):
         """bf16 mode: re-derive the GEMM weight copies from the fp32 masters (an
@@ -591,7 +557,7 @@ class Engine:
         """Encoder-sized products (M = B or B*S rows, K >= 1024): a handful of output tiles each walking a long K
         serially leaves most CUs idle, so the bf16 mode splits K into fp32 slabs (deterministic) and lets the
         finish kernel add the bias.  Returns False when the plain launch should be used."""
-        if K < 1024 or K % 8 or N % 8 or out.dtype != self.tdt or _NO_FEW_ROWS:
+        if K < 1024 or K % 8 or N % 8 or out.dtype != self.tdt:
             return False
         if self.dtype == hip.F32 and (K % 32 or (lda or K) % 4):
             return False
@@ -647,12 +613,10 @@ class Engine:
         bf = self.dtype == hip.BF16
         splits = _wgrad_splits(Mg, Ng, Mtok, bf)
         tiles = ((Mg + 127) // 128) * ((Ng + 127) // 128)
-        if bf and _WGRAD_SLAB and Ng % 8 == 0:
-            splits = _wgrad_splits_p8(Mg, Ng, Mtok) or splits
         # (the exact-fp32 cross-check mode, round 6: its split weight gradients as slabs too -- any tile count, speed is not its
-        #  point -- so that the mode's gradient is bit-reproducible like the others'; MMTG_WGRAD_ATOMIC=1 restores the atomics)
+        #  point -- so that the mode's gradient is bit-reproducible like the others')
         exact = self.dtype == hip.F32 and not self.x3
-        use_slab = _WGRAD_SLAB and 1 < splits and Ng % 8 == 0 and ((bf and tiles < 512) or exact)
+        use_slab = 1 < splits and Ng % 8 == 0 and ((bf and tiles < 512) or exact)
         if self._lazy is not None and (self.layout.entries[wkey][0], Mg * Ng) in self._lazy and not (use_slab and self.wgrad_overwrite):
             gw.zero_()          # the lazy zero_grad skipped this tensor expecting an overwrite that is not happening now
         if use_slab:
@@ -761,7 +725,7 @@ class Engine:
             M = B * T
             if T > sh.NP:
                 raise ValueError("sequence length %d exceeds n_positions %d" % (T, sh.NP))
-        a = {"B": B, "L": L, "T": T, "M": M, "seed": seed, "pdrop": (pe, pa, pr), "train_flag": train_flag, "gelu_grad": _GELU_GRAD,
+        a = {"B": B, "L": L, "T": T, "M": M, "seed": seed, "pdrop": (pe, pa, pr), "train_flag": train_flag,
              "targets": targets, "topic_ids": topic_ids}
 
         # ---------------- encoder: topic_fc + 2 GRUs (model.py:63-81) + ln_layer1..3 (:380-382)
@@ -776,14 +740,12 @@ class Engine:
         hip.layernorm_fwd(t_raw, t_ln, self.P("ln_layer1.weight"), self.P("ln_layer1.bias"), *st["ln1"], B, H)
         enc = {}
         for ch, x, lnk, site in (("image", xi, "ln_layer2", 0), ("text", xr, "ln_layer3", 1)):
-            with self._beside(ch == "text"):
-                layers = self._rnn_fwd(ch, x, B, training, seed, site)
-                h_all = layers[-1]["h"]
-                h_ln = self.buf("hln_" + ch, (B * S, H))
-                st[lnk] = (self.buf(lnk + "_mu", (B * S,), torch.float32), self.buf(lnk + "_rs", (B * S,), torch.float32))
-                hip.layernorm_fwd(h_all, h_ln, self.P(lnk + ".weight"), self.P(lnk + ".bias"), *st[lnk], B * S, H)
+            layers = self._rnn_fwd(ch, x, B, training, seed, site)
+            h_all = layers[-1]["h"]
+            h_ln = self.buf("hln_" + ch, (B * S, H))
+            st[lnk] = (self.buf(lnk + "_mu", (B * S,), torch.float32), self.buf(lnk + "_rs", (B * S,), torch.float32))
+            hip.layernorm_fwd(h_all, h_ln, self.P(lnk + ".weight"), self.P(lnk + ".bias"), *st[lnk], B * S, H)
             enc[ch] = (layers, h_ln)
-        self._join_beside()
 
         # ---------------- alpha attention (model.py:133-161) on batch-first rows b*S+i
         kl = self.buf("kl", (1,), torch.float32, zero=True)
@@ -817,10 +779,9 @@ class Engine:
         type_ids = type_ids.contiguous().view(-1)
         keep = (keep != 0).to(torch.int32).contiguous()
         h1 = self.buf("h1", (M, H))
-        px3 = (self.x3 and E % 128 == 0 and H % 128 == 0 and D % 8 == 0 and "decoder.projector_layer2.weight" in self.wt_entries
-               and _os.environ.get("MMTG_X3_PROJECTOR", "1") != "0")
+        px3 = self.x3 and E % 128 == 0 and H % 128 == 0 and D % 8 == 0 and "decoder.projector_layer2.weight" in self.wt_entries
         a["px3"] = px3
-        gather = self.dtype == hip.BF16 and M > 256 and not _NO_GATHER
+        gather = self.dtype == hip.BF16 and M > 256
         if gather:
             # Fused conditioning (model.py:254-281): X[m] = E[id_m] + c[b, seg_m] is never materialised.  By linearity
             # X W1^T = E[id] W1^T + (c W1^T)[b, seg]: the projector product gathers its A rows straight from the WenLan table
@@ -932,10 +893,9 @@ class Engine:
             hip.layernorm_fwd(xmid, m2, self.P(p + "ln_2.weight"), self.P(p + "ln_2.bias"), mu2, rs2, M, D, sh.eps)
             u = self.buf(f"l{l}_u", (M, 4 * D))
             gact = self.buf(f"l{l}_g", (M, 4 * D))
-            # (u: the pre-activation -- or, with MMTG_GELU_GRAD=1, gelu_new'(pre-activation): all the backward ever takes from it;
-            #  saving the derivative moves the backward's exp / rcp into this epilogue, which computes the sigmoid anyway)
+            # (u: the pre-activation, which the dGELU epilogue of the backward reads)
             self._fwd(m2, p + "mlp.c_fc.weight", gact, M, "conv1d", bias=self.P(p + "mlp.c_fc.bias"),
-                      epi=hip.EPI_GELU, aux2=u, flags=hip.GEMM_GELU_GRAD if _GELU_GRAD else 0)
+                      epi=hip.EPI_GELU, aux2=u)
             xout = self.buf(f"resid_{l + 1}", (M, D))
             self._fwd(gact, p + "mlp.c_proj.weight", xout, M, "conv1d", bias=self.P(p + "mlp.c_proj.bias"),
                       epi=hip.EPI_RESID, aux=xmid, ldaux=D, drop_p=pr, drop_seed=s[2])
@@ -1034,49 +994,9 @@ class Engine:
         return dl
 
     # ---------------------------------------------------------------- backward
-    def _prefetch(self, *tensors):
-        """Saved activations are cold by the time the backward reads them (4.5 GB of activations against a 256 MB
-        Infinity Cache).  Called right before kernel k is enqueued: a side stream waits for that point and pulls the
-        operands of the kernels after k into the cache while k runs (mmtg_prefetch).  MEASURED NEGATIVE (round 2, same box):
-        16.41 ms per step without, 17.2-17.7 with 64 / 256 / 1024 prefetch workgroups -- the side-stream kernels take
-        workgroup slots and L2 bandwidth from the product they run beside -- so it is off unless MMTG_PREFETCH=<workgroups>."""
-        if not _PREFETCH:
-            return
-        if self._pf_stream is None:
-            self._pf_stream = torch.cuda.Stream(device=self.dev, priority=-1)
-            self._pf_sink = torch.zeros(1, device=self.dev, dtype=torch.int32)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._pf_stream.wait_event(ev)
-        for t in tensors:
-            hip.prefetch(t, self._pf_sink, _PREFETCH, stream=self._pf_stream)
-
-    @contextlib.contextmanager
-    def _beside(self, on):
-        """MMTG_ENC_STREAMS=1: enqueue the body on the second stream (forked from the current one) with workspaces of its own --
-        every buffer it names through buf() carries a tag -- so that it runs beside what the current stream enqueues next;
-        `_join_beside` makes the current stream wait for it.  Off (default) / on=False: a no-op."""
-        if not (on and _ENC_STREAMS):
-            yield
-            return
-        side = self._side_stream()
-        side.wait_stream(torch.cuda.current_stream())
-        self._ws_tag, self._beside_live = "~s", True
-        try:
-            with torch.cuda.stream(side):
-                yield
-        finally:
-            self._ws_tag = ""
-
-    def _join_beside(self):
-        if getattr(self, "_beside_live", False):
-            torch.cuda.current_stream().wait_stream(self._side)
-            self._beside_live = False
-
     def _side_stream(self):
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(device=self.dev)
-            self._events = {}
         return self._side
 
     def _event(self, i):
@@ -1158,8 +1078,7 @@ class Engine:
         """compute_dtype "bf16x3f": d(logits) through the decoder as ONE bf16 pass per product -- the bf16 mode's kernels over the hi
         planes the split-precision forward stored (LayerNorm outputs, qkv, attention context, GELU output, projector activations),
         the bf16 copies of the LayerNorm inputs and of the c_fc pre-activation it wrote beside them, and the hi planes of the
-        weights -- then the encoder / fuser backward, on the bf16 kernels as well (MMTG_HYBRID_ENC_BF16=0: in exact fp32 as in the x3
-        mode).  Gradients land in the same flat fp32 buffer."""
+        weights -- then the encoder / fuser backward, on the bf16 kernels as well.  Gradients land in the same flat fp32 buffer."""
         a, sh = self.act, self.sh
         M, Vp = a["M"], self.layout.Vpad
         if isinstance(dlogits, hip.Planes):
@@ -1181,24 +1100,19 @@ class Engine:
             hip.cast_f32_to(a["h1"], h1b, a["h1"].numel())
             xb = self.buf("x_cond_b", tuple(a["x"].shape), torch.bfloat16)
             hip.cast_f32_to(a["x"], xb, a["x"].numel())
-        ab.update(x3=False, px3=False, gelu_grad=False, elem_mask=True, layers=layers, x_last=a["x_last_b"], hf=hi(a["hf"]), h1=h1b, x=xb, ids32=None)
+        ab.update(x3=False, px3=False, elem_mask=True, layers=layers, x_last=a["x_last_b"], hf=hi(a["hf"]), h1=h1b, x=xb, ids32=None)
         try:
             with self._as_bf16():
                 self.act = ab
                 seg = self._backward_decoder(ab, dlogits)
         finally:
             self.act = a
-        if _HYBRID_ENC_BF16:
-            # the encoder / fuser backward on the bf16 kernels too (the mode's gradients are bf16-accurate by contract): bf16 copies of
-            # the ~14 small activations it reads (320 x 512 ... 320 x 2048), then the same code path under the bf16 presentation --
-            # 0.8 ms of exact-fp32 products (14 TFLOP/s on 34 few-row launches) become ~0.2
-            ae = self._encoder_record_bf16(a)
-            with self._as_bf16():
-                self._backward_encoder(ae, seg, dkl)
-            return
-        seg32 = self.buf("d_seg32", tuple(seg.shape), torch.float32)
-        hip.cast_to_f32(seg, seg32, seg.numel())
-        self._backward_encoder(a, seg32, dkl)
+        # the encoder / fuser backward on the bf16 kernels too (the mode's gradients are bf16-accurate by contract): bf16 copies of
+        # the ~14 small activations it reads (320 x 512 ... 320 x 2048), then the same code path under the bf16 presentation --
+        # 0.8 ms of exact-fp32 products (14 TFLOP/s on 34 few-row launches) become ~0.2
+        ae = self._encoder_record_bf16(a)
+        with self._as_bf16():
+            self._backward_encoder(ae, seg, dkl)
 
     def _encoder_record_bf16(self, a):
         """The activation record `_backward_encoder` reads, with every fp32 tensor it takes as a kernel operand replaced by a bf16
@@ -1250,62 +1164,80 @@ class Engine:
     def _backward_decoder(self, a, dlogits):
         """LM head -> GPT-2 blocks -> input embedding -> projector; returns the per-segment sums of d(h1_pre) [B*S, H] that the
         experience vectors' gradient is made of."""
-        sh = self.sh
-        B, T, M, L = a["B"], a["T"], a["M"], a["L"]
-        S, E, H, D, P = sh.S, sh.E, sh.H, sh.D, sh.P
-        pe, pa, pr = a["pdrop"]
-        Vp = self.layout.Vpad
-        pre = "decoder.gpt2.transformer."
-        # ---- LM head (tied wte)
+        dhf = self._bwd_lm_head(a, dlogits)
+        dx = self._bwd_blocks(a, dhf)
+        # (deferred column sums: everything the blocks queued since the last hand-over point -- the whole decoder's without a bucket hook --
+        #  in one launch, here, with the embedding / projector / encoder backward still to come behind it)
+        self._flush_sums()
+        self._defer = False
+        # (the side stream forks here, beside the embedding / projector backward too: 14.28 -> 14.10 ms against a fork after the projector)
+        self._launch_tail_jobs()
+        return self._bwd_embed_projector(a, dx)
+
+    # ---- grouped weight-gradient launches (mmtg_wgrad_group): sizing and launch
+    def _group_bufs(self, shapes, cfg, rule, ws_name, cnt_name="wgrad_group_cnt"):
+        """(splits, workspace, counters) of a grouped launch: _group_sizing's numbers, the named workspace (none for one split)
+        and the named counter tensor."""
+        splits, nws, ncnt = _group_sizing(shapes, cfg, rule)
+        ws = self.buf(ws_name, (nws,), torch.float32) if splits > 1 else None
+        cnt = self.ws.get((cnt_name, torch.int32))
+        if cnt is None or cnt.numel() < ncnt:      # zero once: every launch leaves the counters zeroed
+            cnt = self.ws[(cnt_name, torch.int32)] = torch.zeros(ncnt, device=self.dev, dtype=torch.int32)
+        return splits, ws, cnt
+
+    def _launch_group(self, probs, M, bufs, cfg, written, side=None, event=None, tail=False):
+        """One grouped launch over `bufs` (_group_bufs): on the current stream, on `side` behind everything enqueued so far (`event`
+        recorded after it), or queued for the backward's tail.  `written`: the (offset, count) gradient ranges it writes, for the
+        record the lazy zero_grad is built from."""
+        splits, ws, cnt = bufs
+        if tail:
+            self._tail_jobs.append((probs, M, splits, ws, cnt, not self.wgrad_overwrite, cfg))       # launched at the tail
+        elif side is not None:
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                hip.wgrad_group(probs, M, splits, ws, cnt, accumulate=not self.wgrad_overwrite, config=cfg)
+                if event is not None:
+                    event.record(side)
+        else:
+            hip.wgrad_group(probs, M, splits, ws, cnt, accumulate=not self.wgrad_overwrite, config=cfg)
+        if self.wgrad_overwrite and self._ow_rec is not None:
+            self._ow_rec[1].extend(written)
+
+    # ---- stage 1: LM head (tied wte)
+    def _bwd_lm_head(self, a, dlogits):
+        """d(ln_f output) = dlogits wte into d_hf (returned), and the tied embedding's weight gradient dlogits^T hf."""
+        M, D, Vp = a["M"], self.sh.D, self.layout.Vpad
+        pr = a["pdrop"][2]
         dhf = self.buf("d_hf", (M, D))
         x3 = bool(a.get("x3"))
         if x3:
             # split-precision backward: d(logits) as a plane pair feeds both the LM head's dgrad (through the [D, Vpad] copy of the
-            # tied embedding) and its weight gradient (grouped kernel, config 2: written, not accumulated with atomics)
+            # tied embedding) and its weight gradient (grouped kernel: written, not accumulated with atomics)
             dlp = dlogits if isinstance(dlogits, hip.Planes) else hip.split_planes(dlogits, M, Vp, self.pbuf("dlogits_p", M, Vp))
             hip.gemm_x3(dlp, hip.Planes(self.wte_t, D, Vp), dhf, M, D, Vp)
-            tiles = hip.wgrad_group_sizes(((Vp, D),), 1, 0)[0]
-            hs = _LMHEAD_GROUP_SPLITS or _group_splits_x3(tiles, M)
-            _, nws, ncnt = hip.wgrad_group_sizes(((Vp, D),), hs, 0)
-            hws = self.buf("wgrad_group_ws_head", (nws,), torch.float32) if hs > 1 else None
-            hcnt = self.ws.get(("wgrad_group_cnt", torch.int32))
-            if hcnt is None or hcnt.numel() < ncnt:
-                hcnt = self.ws[("wgrad_group_cnt", torch.int32)] = torch.zeros(ncnt, device=self.dev, dtype=torch.int32)
-            hip.wgrad_group([(dlp, a["hf"], self.Gp("wte"), Vp, D, Vp, D, D)], M, hs, hws, hcnt, accumulate=not self.wgrad_overwrite, config=_X3_WG_CFG)
-            if self.wgrad_overwrite and self._ow_rec is not None:
-                self._ow_rec[1].append((self.layout.pack_range["wte"][0], Vp * D))
-        elif getattr(self, "wte_t", None) is not None and Vp % 128 == 0 and not self.x3:      # (x3: wte_t is a plane pair)
+        elif self.wte_t is not None and Vp % 128 == 0 and not self.x3:      # (x3: wte_t is a plane pair)
             hip.gemm(dlogits, self.wte_t, dhf, M, D, Vp, transB=True, ldb=Vp)
         else:
             hip.gemm(dlogits, self.Wp("wte"), dhf, M, D, Vp, transB=False, ldb=D)
         # (Vpad rows: the pad columns of dlogits are zero, so the pad rows of the pack receive +0)
+        wte = [(self.layout.pack_range["wte"][0], Vp * D)]
         if x3:
-            pass
-        elif _WGRAD_GROUP and _LMHEAD_GROUP and self.dtype == hip.BF16 and M >= 256 and D % 8 == 0 and Vp % 8 == 0:
+            bufs = self._group_bufs(((Vp, D),), 0, lambda tiles: _LMHEAD_GROUP_SPLITS or _group_splits_x3(tiles, M), "wgrad_group_ws_head")
+            self._launch_group([(dlp, a["hf"], self.Gp("wte"), Vp, D, Vp, D, D)], M, bufs, _X3_WG_CFG, wte)
+        elif self.dtype == hip.BF16 and M >= 256 and D % 8 == 0 and Vp % 8 == 0:
             # the tied embedding's gradient through the grouped kernel too: no fp32 atomics (bit-reproducible), and the
             # gradient is WRITTEN, so the lazy zero_grad can skip its 41 MB (the type-embedding rows are added later)
             hcfg = hip.WGRAD_RING if _group_cfg(D) == hip.WGRAD_RING else 0      # (the ring form: the same rule on its 256 slots)
-            tiles = hip.wgrad_group_sizes(((Vp, D),), 1, hcfg)[0]
-            hs = _LMHEAD_GROUP_SPLITS or _group_splits(tiles, M, 256 if hcfg else 1024)
-            _, nws, ncnt = hip.wgrad_group_sizes(((Vp, D),), hs, hcfg)
             # (a workspace of its own: under MMTG_WGRAD_STREAM this launch may still be pending on the side stream when the
             #  block launches size theirs -- a shared name could reallocate, i.e. free, the buffer under it)
-            hws = self.buf("wgrad_group_ws_head", (nws,), torch.float32) if hs > 1 else None
-            hcnt = self.ws.get(("wgrad_group_cnt", torch.int32))
-            if hcnt is None or hcnt.numel() < ncnt:
-                hcnt = self.ws[("wgrad_group_cnt", torch.int32)] = torch.zeros(ncnt, device=self.dev, dtype=torch.int32)
-            side = self._side_stream() if (_WGRAD_STREAM and pr > 0) else None
-            if side is not None:        # beside the LM head's dgrad, ln_f and the last block's chain (reads dlogits / hf only)
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    hip.wgrad_group([(dlogits, a["hf"], self.Gp("wte"), Vp, D, Vp, D, D)], M, hs, hws, hcnt, accumulate=not self.wgrad_overwrite, config=hcfg)
-            else:
-                hip.wgrad_group([(dlogits, a["hf"], self.Gp("wte"), Vp, D, Vp, D, D)], M, hs, hws, hcnt, accumulate=not self.wgrad_overwrite, config=hcfg)
-            if self.wgrad_overwrite and self._ow_rec is not None:
-                self._ow_rec[1].append((self.layout.pack_range["wte"][0], Vp * D))
+            bufs = self._group_bufs(((Vp, D),), hcfg, lambda tiles: _LMHEAD_GROUP_SPLITS or _group_splits(tiles, M, 256 if hcfg else 1024),
+                                    "wgrad_group_ws_head")
+            # (MMTG_WGRAD_STREAM: beside the LM head's dgrad, ln_f and the last block's chain -- reads dlogits / hf only)
+            self._launch_group([(dlogits, a["hf"], self.Gp("wte"), Vp, D, Vp, D, D)], M, bufs, hcfg, wte,
+                               side=self._side_stream() if (_WGRAD_STREAM and pr > 0) else None)
         else:
             splits = _wgrad_splits(Vp, D, M, self.dtype == hip.BF16)
-            if self.dtype == hip.F32 and not self.x3 and _WGRAD_SLAB and splits > 1:
+            if self.dtype == hip.F32 and not self.x3 and splits > 1:
                 # exact-fp32 mode: K-split slabs summed in order ON TOP of what the gradient already holds (no fp32 atomics)
                 part = self.buf("wgrad_slabs", (splits * Vp * D,), torch.float32)
                 hip.gemm(dlogits, a["hf"], part, Vp, D, M, transA=True, transB=False, lda=Vp, ldb=D, ldc=D,
@@ -1314,229 +1246,240 @@ class Engine:
             else:
                 hip.gemm(dlogits, a["hf"], self.Gp("wte"), Vp, D, M, transA=True, transB=False, lda=Vp, ldb=D, ldc=D,
                          epi=hip.EPI_ATOMIC, splits=splits)
-        # Every LayerNorm backward on the residual stream also emits, in the same pass, the
-        # dropout-masked gradient entering the previous residual branch and that branch's bias
-        # gradient (column sum) -- see mmtg_layernorm_bwd.
+        return dhf
+
+    # ---- stage 2: ln_f and the GPT-2 blocks
+    def _bwd_blocks(self, a, dhf):
+        """ln_f and the blocks, top to bottom; owns the gradient buffers the chain runs through -- one shared set, a set per block
+        parity under MMTG_WGRAD_STREAM, a set per deferred block under MMTG_WGRAD_TAIL.  Returns d(resid_0), the input embedding's
+        gradient.  Every LayerNorm backward on the residual stream also emits, in the same pass, the dropout-masked gradient
+        entering the previous residual branch and that branch's bias gradient (column sum) -- see mmtg_layernorm_bwd."""
+        sh = self.sh
+        B, T, M, D = a["B"], a["T"], a["M"], sh.D
+        pr = a["pdrop"][2]
+        pre = "decoder.gpt2.transformer."
+        x3 = bool(a.get("x3"))
         self._defer = _DEFER_SUMS and (self.dtype == hip.BF16 or x3)
-        dx = self.buf("d_resid_a", (M, D))
-        dx2 = self.buf("d_resid_b", (M, D))
+        s = SimpleNamespace(dx=self.buf("d_resid_a", (M, D)), dx2=self.buf("d_resid_b", (M, D)))
         # One grouped launch per block for its four weight gradients (mmtg_wgrad_group): the mlp.c_proj product's dy must then
         # outlive the LayerNorm backward that produces the attention c_proj's dy, so the masked gradients alternate
         # between two buffers.
-        group = (_WGRAD_GROUP and self.dtype == hip.BF16 and M >= 256 and D % 8 == 0) or x3
-        dmask = self.buf("d_masked", (M, D)) if (pr > 0 and not x3) else None
-        dmask_b = (self.buf("d_masked_b", (M, D)) if group else dmask) if (pr > 0 and not x3) else None
+        group = s.group = (self.dtype == hip.BF16 and M >= 256 and D % 8 == 0) or x3
+        s.dmask = self.buf("d_masked", (M, D)) if (pr > 0 and not x3) else None
+        s.dmask_b = (self.buf("d_masked_b", (M, D)) if group else s.dmask) if (pr > 0 and not x3) else None
         if group:
-            gshapes = ((D, 4 * D), (4 * D, D), (D, D), (D, 3 * D))
             gcfg = _group_cfg(D, x3)
-            gtiles = hip.wgrad_group_sizes(gshapes, 1, gcfg)[0]
-            gsplits = _group_splits_x3(gtiles, M) if x3 else _group_splits(gtiles, M, 256 if gcfg else 1024)
-            _, nws, ncnt = hip.wgrad_group_sizes(gshapes, gsplits, gcfg)
-            gws = self.buf("wgrad_group_ws", (nws,), torch.float32) if gsplits > 1 else None
-            gcnt = self.ws.get(("wgrad_group_cnt", torch.int32))
-            if gcnt is None or gcnt.numel() < ncnt:      # zero once: every launch leaves the counters zeroed
-                gcnt = self.ws[("wgrad_group_cnt", torch.int32)] = torch.zeros(ncnt, device=self.dev, dtype=torch.int32)
+            rule = (lambda tiles: _group_splits_x3(tiles, M)) if x3 else (lambda tiles: _group_splits(tiles, M, 256 if gcfg else 1024))
+            s.gbufs = self._group_bufs(((D, 4 * D), (4 * D, D), (D, D), (D, 3 * D)), gcfg, rule, "wgrad_group_ws")
+            s.gcfg = _X3_WG_CFG if x3 else gcfg
         lastp = f"{pre}h.{sh.L - 1}."
         # (MMTG_WGRAD_STREAM: the top block's masked gradient goes into the buffer set of that block's parity, see below)
-        dmask_top = self.buf("d_masked_1", (M, D)) if (group and not x3 and _WGRAD_STREAM and pr > 0 and (sh.L - 1) & 1) else dmask
+        dmask_top = self.buf("d_masked_1", (M, D)) if (group and not x3 and _WGRAD_STREAM and pr > 0 and (sh.L - 1) & 1) else s.dmask
         # MMTG_WGRAD_TAIL: the last blocks' operand buffers are their own (nothing rewrites them before their launch at the tail)
         # (the split-precision blocks' operands are plane pairs the LayerNorm backward writes with or without dropout: name suffix per block)
-        ntail = min(_WGRAD_TAIL, sh.L) if (group and not _WGRAD_STREAM and (pr > 0 or x3) and self.bucket_hook is None) else 0
-        tsets = {} if x3 else {t: (self.buf("d_u_t%d" % t, (M, 4 * D)), self.buf("d_masked_t%d" % t, (M, D)),
-                                   self.buf("d_masked_b_t%d" % t, (M, D)), self.buf("d_qkv_t%d" % t, (M, 3 * D))) for t in range(ntail)}
-        xsfx = (lambda t: "_t%d" % t if t < ntail else "") if x3 else (lambda t: "")
+        ntail = s.ntail = min(_WGRAD_TAIL, sh.L) if (group and not _WGRAD_STREAM and (pr > 0 or x3) and self.bucket_hook is None) else 0
+        s.tsets = {} if x3 else {t: (self.buf("d_u_t%d" % t, (M, 4 * D)), self.buf("d_masked_t%d" % t, (M, D)),
+                                     self.buf("d_masked_b_t%d" % t, (M, D)), self.buf("d_qkv_t%d" % t, (M, 3 * D))) for t in range(ntail)}
+        s.xsfx = (lambda t: "_t%d" % t if t < ntail else "") if x3 else (lambda t: "")
         if ntail == sh.L and not x3:
-            dmask_top = tsets[sh.L - 1][1]
+            dmask_top = s.tsets[sh.L - 1][1]
         self._tail_jobs = []
         if x3:
             # (x3: every LayerNorm backward writes the masked gradient entering the previous residual branch as the plane pair
             #  that branch's split-precision products read -- no fp32 copy, no separate split pass)
-            dyp = self.pbuf("d_masked_p" + xsfx(sh.L - 1), M, D)
-            self._ln_bwd_x3("f", dhf, a["x_last"], pre + "ln_f.weight", a["muf"], a["rsf"], None, dx, M, D, dyp,
+            s.dyp = self.pbuf("d_masked_p" + s.xsfx(sh.L - 1), M, D)
+            self._ln_bwd_x3("f", dhf, a["x_last"], pre + "ln_f.weight", a["muf"], a["rsf"], None, s.dx, M, D, s.dyp,
                             drop_p=pr, drop_seed=a["layers"][sh.L - 1][13][2], colsum_key=lastp + "mlp.c_proj.bias")
         else:
-            self._ln_bwd("f", dhf, a["x_last"], pre + "ln_f.weight", a["muf"], a["rsf"], None, dx, M, D,
+            self._ln_bwd("f", dhf, a["x_last"], pre + "ln_f.weight", a["muf"], a["rsf"], None, s.dx, M, D,
                          dx_masked=dmask_top, drop_p=pr, drop_seed=a["layers"][sh.L - 1][13][2], colsum_key=lastp + "mlp.c_proj.bias")
         self._ready("ln_f.b")
-        du = None if x3 else self.buf("d_u", (M, 4 * D))
-        dm = self.buf("d_m", (M, D))
-        dctx = self.buf("d_ctx", (M, D))
-        dqkv = self.buf("d_qkv", (M, 3 * D))
+        s.du = None if x3 else self.buf("d_u", (M, 4 * D))
+        s.dm = self.buf("d_m", (M, D))
+        s.dctx = self.buf("d_ctx", (M, D))
+        s.dqkv = self.buf("d_qkv", (M, 3 * D))
         # MMTG_WGRAD_STREAM: block l's grouped weight gradients run on a side stream while the main stream already walks block
         # l - 1 -- the operands the chain produces (du, the two masked residual gradients, dqkv) then live in two buffer sets that
         # alternate block by block, and the main stream waits for block l + 1's launch before it rewrites that block's set.
-        stream_mode = group and _WGRAD_STREAM and pr > 0 and not x3
-        if stream_mode:
-            side = self._side_stream()
+        s.stream_mode = group and _WGRAD_STREAM and pr > 0 and not x3
+        if s.stream_mode:
+            s.side = self._side_stream()
             odd = (self.buf("d_u_1", (M, 4 * D)), self.buf("d_masked_1", (M, D)), self.buf("d_masked_b_1", (M, D)),
                    self.buf("d_qkv_1", (M, 3 * D)))
-            sets = ((du, dmask, dmask_b, dqkv), odd)
-            wdone = {}
-        da = self.buf("d_a", (M, D))
-        delta = self.buf("attn_delta", (M, sh.nH), torch.float32)
+            s.sets = ((s.du, s.dmask, s.dmask_b, s.dqkv), odd)
+            s.wdone = {}
+        s.da = self.buf("d_a", (M, D))
+        s.delta = self.buf("attn_delta", (M, sh.nH), torch.float32)
         # (x3: one [M, D] buffer per block of 128 keys -- plain stores summed in block order, no atomics)
-        dq32 = self.buf("attn_dq32", (hip.attn_bwd_x3_dq_floats(B, T, D),) if x3 else (M, D), torch.float32)
+        s.dq32 = self.buf("attn_dq32", (hip.attn_bwd_x3_dq_floats(B, T, D),) if x3 else (M, D), torch.float32)
+        block = self._bwd_block_x3 if x3 else self._bwd_block
         for l in range(sh.L - 1, -1, -1):
-            p = f"{pre}h.{l}."
-            (xin, mu1, rs1, a1, qkv, ctx, lse, xmid, mu2, rs2, m2, u, gact, s, ctxp) = a["layers"][l]
-            if stream_mode:
-                du, dmask, dmask_b, dqkv = sets[l & 1]
-            if l in tsets:
-                du, dmask, dmask_b, dqkv = tsets[l]
-            if x3:
-                # ---- split-precision block backward: every gradient that feeds a product travels as a plane pair
-                bands = self.buf("d_u_bands_%d" % l if self._defer else "d_u_bands", ((M + 63) // 64, 4 * D), torch.float32)
-                dup = self.pbuf("d_u_p" + xsfx(l), M, 4 * D)
-                self._dgrad_x3(dyp, p + "mlp.c_proj.weight", None, M, planes=dup, ldc=4 * D, epi=hip.EPI_DGELU, aux=u, ldaux=4 * D, aux2=bands)
-                if self._defer and bands.shape[0] <= 2048:
-                    self._defer_sum(bands, 4 * D, bands.shape[0], 4 * D, self.G(p + "mlp.c_fc.bias"))
-                else:
-                    hip.colsum(bands, bands.shape[0], 4 * D, self.G(p + "mlp.c_fc.bias"))
-                self._dgrad_x3(dup, p + "mlp.c_fc.weight", dm, M)
-                dy2p = self.pbuf("d_masked_b_p" + xsfx(l), M, D)
-                self._ln_bwd_x3("%d_2" % l, dm, xmid, p + "ln_2.weight", mu2, rs2, dx, dx2, M, D, dy2p,
-                                drop_p=pr, drop_seed=s[1], colsum_key=p + "attn.c_proj.bias")
-                dqkvp = self.pbuf("d_qkv_p" + xsfx(l), M, 3 * D)
-                # d(ctx) as a plane pair only (the attention backward is its one reader); the dgrad's epilogue also emits delta =
-                # rowsum(d ctx * ctx) per head: no separate pass over ctx / d ctx
-                dctxp = self.pbuf("d_ctx_p", M, D)
-                self._dgrad_x3(dy2p, p + "attn.c_proj.weight", None, M, planes=dctxp, ldc=D, epi=hip.EPI_ROWDOT, aux=ctx, ldaux=D, aux2=delta)
-                # (deferred sums: the partial bias rows -- k / v parts per key block, q part per 16-row band -- stay in this block's own scratch)
-                nkv, nq = B * (-(-T // 128)), -(-M // 16)
-                brows = self._defer and nkv <= 2048 and nq <= 2048
-                bws = self.buf("attn_dbias_x3_%d" % l if brows else "attn_dbias_x3", (hip.attn_bwd_x3_ws(B, T, D),), torch.float32)
-                hip.attn_bwd_x3(qkv, a["keep"], ctx, dctxp, lse, delta, dq32, dqkvp, B, T, sh.nH, D // sh.nH, drop_p=pa, drop_seed=s[0],
-                                dbias=None if brows else self.G(p + "attn.c_attn.bias"), delta_ready=True, dbias_ws=bws)
-                if brows:
-                    # (two items must not share output columns -- they run in one launch: the key-block rows carry the k and v parts,
-                    #  their q columns are zero; the band rows carry the q part)
-                    self._defer_sum(bws, 3 * D, nkv, 2 * D, self.G(p + "attn.c_attn.bias")[D:], offset=D)
-                    self._defer_sum(bws, D, nq, D, self.G(p + "attn.c_attn.bias"), offset=nkv * 3 * D)
-                self._dgrad_x3(dqkvp, p + "attn.c_attn.weight", da, M)
-                keys = (p + "mlp.c_fc.weight", p + "mlp.c_proj.weight", p + "attn.c_proj.weight", p + "attn.c_attn.weight")
-                probs = [(m2, dup, self.G(keys[0]), D, 4 * D), (gact, dyp, self.G(keys[1]), 4 * D, D),
-                         (ctxp, dy2p, self.G(keys[2]), D, D), (a1, dqkvp, self.G(keys[3]), D, 3 * D)]
-                if l < ntail:
-                    self._tail_jobs.append((probs, M, gsplits, gws, gcnt, not self.wgrad_overwrite, _X3_WG_CFG))       # launched at the tail
-                else:
-                    hip.wgrad_group(probs, M, gsplits, gws, gcnt, accumulate=not self.wgrad_overwrite, config=_X3_WG_CFG)
-                if self.wgrad_overwrite and self._ow_rec is not None:
-                    self._ow_rec[1].extend((self.layout.entries[k][0], self.layout.entries[k][2]) for k in keys)
-                if l > 0:
-                    dyp = self.pbuf("d_masked_p" + xsfx(l - 1), M, D)          # the planes block l - 1 reads (its own when it is deferred)
-                    self._ln_bwd_x3("%d_1" % l, da, xin, p + "ln_1.weight", mu1, rs1, dx2, dx, M, D, dyp,
-                                    drop_p=pr, drop_seed=a["layers"][l - 1][13][2], colsum_key=f"{pre}h.{l - 1}.mlp.c_proj.bias")
-                else:
-                    self._ln_bwd("0_1", da, xin, p + "ln_1.weight", mu1, rs1, dx2, dx, M, D)
-                self._ready(p + "ln_1.bias")
-                continue
-            # x_out = x_mid + drop(gact W2 + b2): dy = dx * mask (already produced, with its bias gradient)
-            dy = dmask if pr > 0 else dx
-            # (the dGELU epilogue also emits the column sums of du per 64-row band: a [M/64, 4D] reduction
-            #  gives the c_fc bias gradient instead of a pass over du)
-            bands = self.buf("d_u_bands_%d" % l if self._defer else "d_u_bands", ((M + 63) // 64, 4 * D), torch.float32)
-            self._prefetch(m2, gact)            # while dGELU runs: the operands of the two weight gradients after it
-            self._dgrad(dy, p + "mlp.c_proj.weight", du, M, "conv1d", epi=hip.EPI_DGELU, aux=u, ldaux=4 * D, aux2=bands,
-                        flags=hip.GEMM_GELU_GRAD if a["gelu_grad"] else 0)
-            if self._defer and bands.shape[0] <= 2048:
-                self._defer_sum(bands, 4 * D, bands.shape[0], 4 * D, self.G(p + "mlp.c_fc.bias"))
-            else:
-                hip.colsum(bands, bands.shape[0], 4 * D, self.G(p + "mlp.c_fc.bias"))
-            # (both consumers of du run while it is still in the Infinity Cache; the c_proj weight gradient, whose
-            #  operands come from HBM either way, goes last -- it must precede the LayerNorm backward, which reuses dmask)
-            self._dgrad(du, p + "mlp.c_fc.weight", dm, M, "conv1d")
-            dy_fc2 = dy
-            if not group:
-                self._wgrad(m2, du, p + "mlp.c_fc.weight", None, M, "conv1d")
-                self._prefetch(xmid, ctx)           # while the c_proj weight gradient runs: LayerNorm input, attention context
-                self._wgrad(gact, dy, p + "mlp.c_proj.weight", None, M, "conv1d")
-            self._ln_bwd("%d_2" % l, dm, xmid, p + "ln_2.weight", mu2, rs2, dx, dx2, M, D,
-                         dx_masked=dmask_b, drop_p=pr, drop_seed=s[1], colsum_key=p + "attn.c_proj.bias")
-            # x_mid = x_in + drop(ctx Wp + bp)
-            dy = dmask_b if pr > 0 else dx2
-            # bf16: the dgrad GEMM's epilogue also emits delta = rowsum(d ctx * ctx) per head
-            fuse_delta = self.dtype == hip.BF16 and M > 256
-            if fuse_delta:
-                self._dgrad(dy, p + "attn.c_proj.weight", dctx, M, "conv1d", epi=hip.EPI_ROWDOT, aux=ctx, ldaux=D, aux2=delta)
-            else:
-                self._dgrad(dy, p + "attn.c_proj.weight", dctx, M, "conv1d")
-            self._prefetch(qkv)                 # while the c_proj weight gradient runs: the attention backward's rows
-            if not group:
-                self._wgrad(ctx, dy, p + "attn.c_proj.weight", None, M, "conv1d")
-            # (hybrid: the split-precision forward drew the attention-dropout mask element by element; the whole-head backward
-            #  kernels regenerate THAT mask instead of their own word masks)
-            # (exact-fp32 mode: the tiled kernel combines its waves' bias sums with LDS atomics -- arrival order -- so the c_attn bias
-            #  gradient is an ordered column sum over d(qkv) there instead: one more pass in the cross-check mode, reproducible bits)
-            exact = self.dtype == hip.F32 and not self.x3 and _WGRAD_SLAB
-            # (deferred sums: the whole-head kernels leave their B partial bias rows in this block's own scratch for the batched sum)
-            brows = hip.attn_bwd_dbias_rows(self.dtype, B, T) if self._defer else 0
-            brows = brows if 0 < brows <= 2048 else 0
-            bws = None if exact else self.buf("attn_dbias_rows_%d" % l if brows else "attn_dbias_rows",
-                                               (hip.attn_bwd_bias_rows(B, T, self.dtype), 3 * D), torch.float32)
-            hip.attn_bwd(qkv, a["keep"], ctx, dctx, lse, delta, dq32, dqkv, B, T, sh.nH, D // sh.nH,
-                         drop_p=pa, drop_seed=s[0], delta_ready=fuse_delta, dbias=None if exact else self.G(p + "attn.c_attn.bias"),
-                         flags=(hip.ATTN_ELEM_MASK if a.get("elem_mask") else 0) | (hip.ATTN_DBIAS_ROWS if brows else 0), dbias_ws=bws)
-            if brows:
-                self._defer_sum(bws, 3 * D, brows, 3 * D, self.G(p + "attn.c_attn.bias"))
-            if exact:
-                hip.colsum(dqkv, M, 3 * D, self.G(p + "attn.c_attn.bias"))
-            self._prefetch(a1, xin)             # while the c_attn dgrad runs: its weight gradient's operand, LayerNorm input
-            self._dgrad(dqkv, p + "attn.c_attn.weight", da, M, "conv1d")
-            if l > 0:
-                self._prefetch(a["layers"][l - 1][11])      # the next layer's saved pre-activation (dGELU)
-            if group:
-                # gw[in, out] (+)= x^T dy for the block's four Conv1D layers: 432 tiles x 2 K halves at GPT-2 base, reduced in
-                # the kernel (must run before the LayerNorm backward below, which rewrites dmask / dx for the next block)
-                keys = (p + "mlp.c_fc.weight", p + "mlp.c_proj.weight", p + "attn.c_proj.weight", p + "attn.c_attn.weight")
-                probs = [(m2, du, self.G(keys[0]), D, 4 * D), (gact, dy_fc2, self.G(keys[1]), 4 * D, D),
-                         (ctx, dy, self.G(keys[2]), D, D), (a1, dqkv, self.G(keys[3]), D, 3 * D)]
-                if stream_mode:
-                    side.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(side):
-                        hip.wgrad_group(probs, M, gsplits, gws, gcnt, accumulate=not self.wgrad_overwrite, config=gcfg)
-                        wdone[l] = self._event(l)
-                        wdone[l].record(side)
-                elif l in tsets:
-                    self._tail_jobs.append((probs, M, gsplits, gws, gcnt, not self.wgrad_overwrite, gcfg))       # launched at the tail
-                else:
-                    hip.wgrad_group(probs, M, gsplits, gws, gcnt, accumulate=not self.wgrad_overwrite, config=gcfg)
-                if self.wgrad_overwrite and self._ow_rec is not None:
-                    self._ow_rec[1].extend((self.layout.entries[k][0], self.layout.entries[k][2]) for k in keys)
-            else:
-                self._wgrad(a1, dqkv, p + "attn.c_attn.weight", None, M, "conv1d")
-            if stream_mode and (l + 1) in wdone:
-                # block l + 1's weight gradients have read the set this LayerNorm backward starts to rewrite; its gradients are
-                # final only now (the data-parallel bucket hook must not see them earlier)
-                torch.cuda.current_stream().wait_event(wdone.pop(l + 1))
-                self._ready(f"{pre}h.{l + 1}.ln_1.bias")
-            if l > 0:
-                self._ln_bwd("%d_1" % l, da, xin, p + "ln_1.weight", mu1, rs1, dx2, dx, M, D,
-                             dx_masked=(sets[(l - 1) & 1][1] if stream_mode else tsets[l - 1][1] if (l - 1) in tsets else dmask),
-                             drop_p=pr, drop_seed=a["layers"][l - 1][13][2],
-                             colsum_key=f"{pre}h.{l - 1}.mlp.c_proj.bias")
-            else:
-                self._ln_bwd("0_1", da, xin, p + "ln_1.weight", mu1, rs1, dx2, dx, M, D)
-            if not stream_mode:
-                self._ready(p + "ln_1.bias")
-        if stream_mode:
-            torch.cuda.current_stream().wait_stream(side)        # block 0's launch (and the tied embedding's, long done)
-            for l_ in sorted(wdone, reverse=True):
+            if s.stream_mode:
+                s.du, s.dmask, s.dmask_b, s.dqkv = s.sets[l & 1]
+            if l in s.tsets:
+                s.du, s.dmask, s.dmask_b, s.dqkv = s.tsets[l]
+            block(a, l, s)
+        if s.stream_mode:
+            torch.cuda.current_stream().wait_stream(s.side)        # block 0's launch (and the tied embedding's, long done)
+            for l_ in sorted(s.wdone, reverse=True):
                 self._ready(f"{pre}h.{l_}.ln_1.bias")
-        elif _WGRAD_STREAM and pr > 0 and getattr(self, "_side", None) is not None:
+        elif _WGRAD_STREAM and pr > 0 and self._side is not None:
             torch.cuda.current_stream().wait_stream(self._side)  # (only the tied embedding's gradient ran on the side stream)
-        # (deferred column sums: everything the blocks queued since the last hand-over point -- the whole decoder's without a bucket hook --
-        #  in one launch, here, with the embedding / projector / encoder backward still to come behind it)
-        self._flush_sums()
-        self._defer = False
-        if _TAIL_FORK_EARLY:            # (fork here: beside the embedding / projector backward too; MMTG_WGRAD_TAIL_FORK=proj: after the projector)
-            self._launch_tail_jobs()
-        # ---- GPT-2 input embedding: h0 = drop(g + wpe + wte[type])
+        return s.dx
+
+    def _bwd_block_x3(self, a, l, s):
+        """Split-precision backward of block l: every gradient that feeds a product travels as a plane pair.  In: s.dx = d(block
+        output), s.dyp = its masked planes; out: s.dx = d(block input), s.dyp = the planes block l - 1 reads."""
+        sh = self.sh
+        B, T, M, D = a["B"], a["T"], a["M"], sh.D
+        _, pa, pr = a["pdrop"]
+        pre = "decoder.gpt2.transformer."
+        p = f"{pre}h.{l}."
+        dx, dx2, dm, da, delta, dq32, dyp = s.dx, s.dx2, s.dm, s.da, s.delta, s.dq32, s.dyp
+        (xin, mu1, rs1, a1, qkv, ctx, lse, xmid, mu2, rs2, m2, u, gact, seeds, ctxp) = a["layers"][l]
+        bands = self.buf("d_u_bands_%d" % l if self._defer else "d_u_bands", ((M + 63) // 64, 4 * D), torch.float32)
+        dup = self.pbuf("d_u_p" + s.xsfx(l), M, 4 * D)
+        self._dgrad_x3(dyp, p + "mlp.c_proj.weight", None, M, planes=dup, ldc=4 * D, epi=hip.EPI_DGELU, aux=u, ldaux=4 * D, aux2=bands)
+        if self._defer and bands.shape[0] <= 2048:
+            self._defer_sum(bands, 4 * D, bands.shape[0], 4 * D, self.G(p + "mlp.c_fc.bias"))
+        else:
+            hip.colsum(bands, bands.shape[0], 4 * D, self.G(p + "mlp.c_fc.bias"))
+        self._dgrad_x3(dup, p + "mlp.c_fc.weight", dm, M)
+        dy2p = self.pbuf("d_masked_b_p" + s.xsfx(l), M, D)
+        self._ln_bwd_x3("%d_2" % l, dm, xmid, p + "ln_2.weight", mu2, rs2, dx, dx2, M, D, dy2p,
+                        drop_p=pr, drop_seed=seeds[1], colsum_key=p + "attn.c_proj.bias")
+        dqkvp = self.pbuf("d_qkv_p" + s.xsfx(l), M, 3 * D)
+        # d(ctx) as a plane pair only (the attention backward is its one reader); the dgrad's epilogue also emits delta =
+        # rowsum(d ctx * ctx) per head: no separate pass over ctx / d ctx
+        dctxp = self.pbuf("d_ctx_p", M, D)
+        self._dgrad_x3(dy2p, p + "attn.c_proj.weight", None, M, planes=dctxp, ldc=D, epi=hip.EPI_ROWDOT, aux=ctx, ldaux=D, aux2=delta)
+        # (deferred sums: the partial bias rows -- k / v parts per key block, q part per 16-row band -- stay in this block's own scratch)
+        nkv, nq = B * (-(-T // 128)), -(-M // 16)
+        brows = self._defer and nkv <= 2048 and nq <= 2048
+        bws = self.buf("attn_dbias_x3_%d" % l if brows else "attn_dbias_x3", (hip.attn_bwd_x3_ws(B, T, D),), torch.float32)
+        hip.attn_bwd_x3(qkv, a["keep"], ctx, dctxp, lse, delta, dq32, dqkvp, B, T, sh.nH, D // sh.nH, drop_p=pa, drop_seed=seeds[0],
+                        dbias=None if brows else self.G(p + "attn.c_attn.bias"), delta_ready=True, dbias_ws=bws)
+        if brows:
+            # (two items must not share output columns -- they run in one launch: the key-block rows carry the k and v parts,
+            #  their q columns are zero; the band rows carry the q part)
+            self._defer_sum(bws, 3 * D, nkv, 2 * D, self.G(p + "attn.c_attn.bias")[D:], offset=D)
+            self._defer_sum(bws, D, nq, D, self.G(p + "attn.c_attn.bias"), offset=nkv * 3 * D)
+        self._dgrad_x3(dqkvp, p + "attn.c_attn.weight", da, M)
+        keys = (p + "mlp.c_fc.weight", p + "mlp.c_proj.weight", p + "attn.c_proj.weight", p + "attn.c_attn.weight")
+        probs = [(m2, dup, self.G(keys[0]), D, 4 * D), (gact, dyp, self.G(keys[1]), 4 * D, D),
+                 (ctxp, dy2p, self.G(keys[2]), D, D), (a1, dqkvp, self.G(keys[3]), D, 3 * D)]
+        written = ((self.layout.entries[k][0], self.layout.entries[k][2]) for k in keys)
+        self._launch_group(probs, M, s.gbufs, s.gcfg, written, tail=l < s.ntail)
+        if l > 0:
+            s.dyp = self.pbuf("d_masked_p" + s.xsfx(l - 1), M, D)          # the planes block l - 1 reads (its own when it is deferred)
+            self._ln_bwd_x3("%d_1" % l, da, xin, p + "ln_1.weight", mu1, rs1, dx2, dx, M, D, s.dyp,
+                            drop_p=pr, drop_seed=a["layers"][l - 1][13][2], colsum_key=f"{pre}h.{l - 1}.mlp.c_proj.bias")
+        else:
+            self._ln_bwd("0_1", da, xin, p + "ln_1.weight", mu1, rs1, dx2, dx, M, D)
+        self._ready(p + "ln_1.bias")
+
+    def _bwd_block(self, a, l, s):
+        """bf16 / exact-fp32 backward of block l.  In: s.dx = d(block output), s.dmask = its dropout-masked copy; out: s.dx =
+        d(block input), the masked copy in the set block l - 1 reads."""
+        sh = self.sh
+        B, T, M, D = a["B"], a["T"], a["M"], sh.D
+        _, pa, pr = a["pdrop"]
+        pre = "decoder.gpt2.transformer."
+        p = f"{pre}h.{l}."
+        dx, dx2, dm, dctx, da, delta, dq32 = s.dx, s.dx2, s.dm, s.dctx, s.da, s.delta, s.dq32
+        du, dmask, dmask_b, dqkv = s.du, s.dmask, s.dmask_b, s.dqkv
+        group, stream_mode = s.group, s.stream_mode
+        (xin, mu1, rs1, a1, qkv, ctx, lse, xmid, mu2, rs2, m2, u, gact, seeds, ctxp) = a["layers"][l]
+        # x_out = x_mid + drop(gact W2 + b2): dy = dx * mask (already produced, with its bias gradient)
+        dy = dmask if pr > 0 else dx
+        # (the dGELU epilogue also emits the column sums of du per 64-row band: a [M/64, 4D] reduction
+        #  gives the c_fc bias gradient instead of a pass over du)
+        bands = self.buf("d_u_bands_%d" % l if self._defer else "d_u_bands", ((M + 63) // 64, 4 * D), torch.float32)
+        self._dgrad(dy, p + "mlp.c_proj.weight", du, M, "conv1d", epi=hip.EPI_DGELU, aux=u, ldaux=4 * D, aux2=bands)
+        if self._defer and bands.shape[0] <= 2048:
+            self._defer_sum(bands, 4 * D, bands.shape[0], 4 * D, self.G(p + "mlp.c_fc.bias"))
+        else:
+            hip.colsum(bands, bands.shape[0], 4 * D, self.G(p + "mlp.c_fc.bias"))
+        # (both consumers of du run while it is still in the Infinity Cache; the c_proj weight gradient, whose
+        #  operands come from HBM either way, goes last -- it must precede the LayerNorm backward, which reuses dmask)
+        self._dgrad(du, p + "mlp.c_fc.weight", dm, M, "conv1d")
+        dy_fc2 = dy
+        if not group:
+            self._wgrad(m2, du, p + "mlp.c_fc.weight", None, M, "conv1d")
+            self._wgrad(gact, dy, p + "mlp.c_proj.weight", None, M, "conv1d")
+        self._ln_bwd("%d_2" % l, dm, xmid, p + "ln_2.weight", mu2, rs2, dx, dx2, M, D,
+                     dx_masked=dmask_b, drop_p=pr, drop_seed=seeds[1], colsum_key=p + "attn.c_proj.bias")
+        # x_mid = x_in + drop(ctx Wp + bp)
+        dy = dmask_b if pr > 0 else dx2
+        # bf16: the dgrad GEMM's epilogue also emits delta = rowsum(d ctx * ctx) per head
+        fuse_delta = self.dtype == hip.BF16 and M > 256
+        if fuse_delta:
+            self._dgrad(dy, p + "attn.c_proj.weight", dctx, M, "conv1d", epi=hip.EPI_ROWDOT, aux=ctx, ldaux=D, aux2=delta)
+        else:
+            self._dgrad(dy, p + "attn.c_proj.weight", dctx, M, "conv1d")
+        if not group:
+            self._wgrad(ctx, dy, p + "attn.c_proj.weight", None, M, "conv1d")
+        # (hybrid: the split-precision forward drew the attention-dropout mask element by element; the whole-head backward
+        #  kernels regenerate THAT mask instead of their own word masks)
+        # (exact-fp32 mode: the tiled kernel combines its waves' bias sums with LDS atomics -- arrival order -- so the c_attn bias
+        #  gradient is an ordered column sum over d(qkv) there instead: one more pass in the cross-check mode, reproducible bits)
+        exact = self.dtype == hip.F32 and not self.x3
+        # (deferred sums: the whole-head kernels leave their B partial bias rows in this block's own scratch for the batched sum)
+        brows = hip.attn_bwd_dbias_rows(self.dtype, B, T) if self._defer else 0
+        brows = brows if 0 < brows <= 2048 else 0
+        bws = None if exact else self.buf("attn_dbias_rows_%d" % l if brows else "attn_dbias_rows",
+                                           (hip.attn_bwd_bias_rows(B, T, self.dtype), 3 * D), torch.float32)
+        hip.attn_bwd(qkv, a["keep"], ctx, dctx, lse, delta, dq32, dqkv, B, T, sh.nH, D // sh.nH,
+                     drop_p=pa, drop_seed=seeds[0], delta_ready=fuse_delta, dbias=None if exact else self.G(p + "attn.c_attn.bias"),
+                     flags=(hip.ATTN_ELEM_MASK if a.get("elem_mask") else 0) | (hip.ATTN_DBIAS_ROWS if brows else 0), dbias_ws=bws)
+        if brows:
+            self._defer_sum(bws, 3 * D, brows, 3 * D, self.G(p + "attn.c_attn.bias"))
+        if exact:
+            hip.colsum(dqkv, M, 3 * D, self.G(p + "attn.c_attn.bias"))
+        self._dgrad(dqkv, p + "attn.c_attn.weight", da, M, "conv1d")
+        if group:
+            # gw[in, out] (+)= x^T dy for the block's four Conv1D layers: 432 tiles x 2 K halves at GPT-2 base, reduced in
+            # the kernel (must run before the LayerNorm backward below, which rewrites dmask / dx for the next block)
+            keys = (p + "mlp.c_fc.weight", p + "mlp.c_proj.weight", p + "attn.c_proj.weight", p + "attn.c_attn.weight")
+            probs = [(m2, du, self.G(keys[0]), D, 4 * D), (gact, dy_fc2, self.G(keys[1]), 4 * D, D),
+                     (ctx, dy, self.G(keys[2]), D, D), (a1, dqkv, self.G(keys[3]), D, 3 * D)]
+            written = ((self.layout.entries[k][0], self.layout.entries[k][2]) for k in keys)
+            if stream_mode:
+                s.wdone[l] = self._event(l)
+                self._launch_group(probs, M, s.gbufs, s.gcfg, written, side=s.side, event=s.wdone[l])
+            else:
+                self._launch_group(probs, M, s.gbufs, s.gcfg, written, tail=l in s.tsets)
+        else:
+            self._wgrad(a1, dqkv, p + "attn.c_attn.weight", None, M, "conv1d")
+        if stream_mode and (l + 1) in s.wdone:
+            # block l + 1's weight gradients have read the set this LayerNorm backward starts to rewrite; its gradients are
+            # final only now (the data-parallel bucket hook must not see them earlier)
+            torch.cuda.current_stream().wait_event(s.wdone.pop(l + 1))
+            self._ready(f"{pre}h.{l + 1}.ln_1.bias")
+        if l > 0:
+            self._ln_bwd("%d_1" % l, da, xin, p + "ln_1.weight", mu1, rs1, dx2, dx, M, D,
+                         dx_masked=(s.sets[(l - 1) & 1][1] if stream_mode else s.tsets[l - 1][1] if (l - 1) in s.tsets else dmask),
+                         drop_p=pr, drop_seed=a["layers"][l - 1][13][2],
+                         colsum_key=f"{pre}h.{l - 1}.mlp.c_proj.bias")
+        else:
+            self._ln_bwd("0_1", da, xin, p + "ln_1.weight", mu1, rs1, dx2, dx, M, D)
+        if not stream_mode:
+            self._ready(p + "ln_1.bias")
+
+    # ---- stage 3: input embedding and projector
+    def _bwd_embed_projector(self, a, dx):
+        """GPT-2 input embedding h0 = drop(g + wpe + wte[type]) and the projector (model.py:279-281); returns the per-segment
+        sums of d(h1_pre)."""
+        sh = self.sh
+        B, T, M, L = a["B"], a["T"], a["M"], a["L"]
+        S, E, H, D, P = sh.S, sh.E, sh.H, sh.D, sh.P
+        pe = a["pdrop"][0]
+        pre = "decoder.gpt2.transformer."
         nty = min(32, sh.V)
         hip.embed_add_bwd(dx, a["type_ids"], self.G(pre + "wpe.weight"), self.G(pre + "wte.weight"), M, T, D,
                           nty, drop_p=pe, drop_seed=a["seed"],
                           ws=self.buf("embed_bwd_ws", (int(hip.lib().mmtg_embed_add_bwd_ws(M, D, nty)),), torch.float32))
         self._ready("wpe")
-        # ---- projector (model.py:279-281)
         dh1 = self.buf("d_h1", (M, H))
         px3 = bool(a.get("px3"))
         if px3:
@@ -1545,23 +1488,14 @@ class Engine:
             dxp = hip.split_planes(dx, M, D, self.pbuf("d_resid0_p", M, D))
             dh1p = self.pbuf("d_h1_p", M, H)
             hip.gemm_x3(dxp, self.Wtx("decoder.projector_layer2.weight"), dh1, M, H, D, planes=dh1p, epi=hip.EPI_DTANH, aux=a["h1"], ldaux=H)
-            pshapes = ((D, H), (H, E))
-            ptiles = hip.wgrad_group_sizes(pshapes, 1, 0)[0]
-            psplits = _group_splits_x3(ptiles, M)
-            _, pnws, pncnt = hip.wgrad_group_sizes(pshapes, psplits, 0)
-            pws = self.buf("wgrad_group_ws_proj", (pnws,), torch.float32) if psplits > 1 else None
             # (counters of its own: the blocks' deferred launches may be running on the side stream by now -- _WGRAD_TAIL)
-            pcnt = self.ws.get(("wgrad_group_cnt_proj", torch.int32))
-            if pcnt is None or pcnt.numel() < pncnt:
-                pcnt = self.ws[("wgrad_group_cnt_proj", torch.int32)] = torch.zeros(pncnt, device=self.dev, dtype=torch.int32)
+            bufs = self._group_bufs(((D, H), (H, E)), 0, lambda tiles: _group_splits_x3(tiles, M), "wgrad_group_ws_proj", "wgrad_group_cnt_proj")
             pkeys = ("decoder.projector_layer2.weight", "decoder.projector_layer1.weight")
             for k in pkeys:      # (tensors the lazy zero_grad skipped are overwritten below; otherwise accumulate as ever)
                 if self._lazy is not None and (self.layout.entries[k][0], self.layout.entries[k][2]) in self._lazy and not self.wgrad_overwrite:
                     self.G(k).zero_()
-            hip.wgrad_group([(dxp, a["h1p"], self.G(pkeys[0]), D, H), (dh1p, a["xp"], self.G(pkeys[1]), H, E)], M, psplits, pws, pcnt,
-                            accumulate=not self.wgrad_overwrite, config=_X3_WG_CFG)
-            if self.wgrad_overwrite and self._ow_rec is not None:
-                self._ow_rec[1].extend((self.layout.entries[k][0], self.layout.entries[k][2]) for k in pkeys)
+            self._launch_group([(dxp, a["h1p"], self.G(pkeys[0]), D, H), (dh1p, a["xp"], self.G(pkeys[1]), H, E)], M, bufs, _X3_WG_CFG,
+                               ((self.layout.entries[k][0], self.layout.entries[k][2]) for k in pkeys))
             hip.colsum(dx, M, D, self.G("decoder.projector_layer2.bias"))
         else:
             self._dgrad(dx, "decoder.projector_layer2.weight", dh1, M, "linear", epi=hip.EPI_DTANH, aux=a["h1"], ldaux=H)
@@ -1584,19 +1518,12 @@ class Engine:
             hip.colsum(dh1, M, H, self.G("decoder.projector_layer1.bias"))      # (the weight gradient went with W2's above)
         else:
             self._wgrad(a["x"], dh1, "decoder.projector_layer1.weight", "decoder.projector_layer1.bias", M, "linear")
-        if not _TAIL_FORK_EARLY:
-            self._launch_tail_jobs()
         return seg
 
     def _launch_tail_jobs(self):
         """The deferred blocks' grouped weight gradients, in block order on ONE side stream (they share a workspace and counters; the
         in-loop launches are complete by now): behind everything enqueued so far, beside what the main stream enqueues next."""
         if not self._tail_jobs:
-            return
-        if _os.environ.get("MMTG_WGRAD_TAIL_MAIN"):          # (A/B: the same launches on the main stream, no overlap with the tail)
-            for probs, m_, gs_, gws_, gcnt_, acc_, cfg_ in self._tail_jobs:
-                hip.wgrad_group(probs, m_, gs_, gws_, gcnt_, accumulate=acc_, config=cfg_)
-            self._tail_jobs = []
             return
         side = self._side_stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -1624,27 +1551,26 @@ class Engine:
         hip.beta_fuse_bwd(a["t_ln"], a["alpha"]["img"][1], a["alpha"]["text"][1], self.Pp("att_w"), a["ba"], do,
                           dtopic, dci, dct, self.Gp("att_w"), self.Gp("att_b"), B, S, H)
         self._ready("att_b")
-        # ---- alpha attention + LayerNorm + GRU per modality (MMTG_ENC_STREAMS=1: the text channel's chain on the second stream)
+        # ---- alpha attention + LayerNorm + GRU per modality
         for mod, ch, lnk, dctx_a in (("text", "text", "ln_layer3", dct), ("img", "image", "ln_layer2", dci)):
-            with self._beside(mod == "text"):
-                dhp32 = self.buf("d_hp32", (B, H), torch.float32)
-                tmp32 = self.buf("d_tmp32", (B, H), torch.float32)
-                lnws_m = self.buf("ln_bwd_ws", (hip.lib().mmtg_layernorm_bwd_ws(M, max(D, H)),), torch.float32)
-                qkv_a, _, probs = a["alpha"][mod]
-                layers, h_ln = a["enc"][ch]
-                h_all = layers[-1]["h"]
-                dqkv_a = self.buf("d_aqkv", (B * S, 3 * H))
-                hip.alpha_attn_bwd(qkv_a, self.prior, probs, dctx_a, dkl, dqkv_a, B, S, H, sh.heads)
-                dhln = self.buf("d_hln", (B * S, H))
-                if not self._gemm_few_rows(dqkv_a, self.Wp(mod + "_qkv_w"), dhln, B * S, H, 3 * H, False, H):
-                    hip.gemm(dqkv_a, self.Wp(mod + "_qkv_w"), dhln, B * S, H, 3 * H, transB=False, ldb=H)
-                hip.gemm(dqkv_a, h_ln, self.Gp(mod + "_qkv_w"), 3 * H, H, B * S, transA=True, transB=False, lda=3 * H,
-                         ldb=H, ldc=H, epi=hip.EPI_ATOMIC, splits=1)
-                hip.colsum(dqkv_a, B * S, 3 * H, self.Gp(mod + "_qkv_b"))
-                dh_all = self.buf("d_hall", (B * S, H))
-                hip.layernorm_bwd(dhln, h_all, self.P(lnk + ".weight"), *a["st"][lnk], None, dh_all,
-                                  self.G(lnk + ".weight"), self.G(lnk + ".bias"), B * S, H, ws=lnws_m)
-                self._rnn_bwd(ch, layers, dh_all, B, dhp32, tmp32)
+            dhp32 = self.buf("d_hp32", (B, H), torch.float32)
+            tmp32 = self.buf("d_tmp32", (B, H), torch.float32)
+            lnws_m = self.buf("ln_bwd_ws", (hip.lib().mmtg_layernorm_bwd_ws(M, max(D, H)),), torch.float32)
+            qkv_a, _, probs = a["alpha"][mod]
+            layers, h_ln = a["enc"][ch]
+            h_all = layers[-1]["h"]
+            dqkv_a = self.buf("d_aqkv", (B * S, 3 * H))
+            hip.alpha_attn_bwd(qkv_a, self.prior, probs, dctx_a, dkl, dqkv_a, B, S, H, sh.heads)
+            dhln = self.buf("d_hln", (B * S, H))
+            if not self._gemm_few_rows(dqkv_a, self.Wp(mod + "_qkv_w"), dhln, B * S, H, 3 * H, False, H):
+                hip.gemm(dqkv_a, self.Wp(mod + "_qkv_w"), dhln, B * S, H, 3 * H, transB=False, ldb=H)
+            hip.gemm(dqkv_a, h_ln, self.Gp(mod + "_qkv_w"), 3 * H, H, B * S, transA=True, transB=False, lda=3 * H,
+                     ldb=H, ldc=H, epi=hip.EPI_ATOMIC, splits=1)
+            hip.colsum(dqkv_a, B * S, 3 * H, self.Gp(mod + "_qkv_b"))
+            dh_all = self.buf("d_hall", (B * S, H))
+            hip.layernorm_bwd(dhln, h_all, self.P(lnk + ".weight"), *a["st"][lnk], None, dh_all,
+                              self.G(lnk + ".weight"), self.G(lnk + ".bias"), B * S, H, ws=lnws_m)
+            self._rnn_bwd(ch, layers, dh_all, B, dhp32, tmp32)
         # ---- topic channel
         dt_ln = self.buf("d_tln", (B, H))
         hip.cast_f32_to(dtopic, dt_ln, B * H)
@@ -1652,7 +1578,6 @@ class Engine:
         hip.layernorm_bwd(dt_ln, a["t_raw"], self.P("ln_layer1.weight"), *a["st"]["ln1"], None, dt_raw,
                           self.G("ln_layer1.weight"), self.G("ln_layer1.bias"), B, H, ws=lnws)
         self._wgrad(a["xt"], dt_raw, "encoder.topic_fc.weight", "encoder.topic_fc.bias", B, "linear")
-        self._join_beside()
         self._ready("encoder.topic_fc.bias")
 
     def _rnn_bwd(self, ch, layers, dh_all, B, dhp32, tmp32):

@@ -453,6 +453,40 @@ def test_grouped_weight_gradient_split_rule_and_workspace_sizes():
     assert _group_splits(t8, 15104, 256) == 2
 
 
+def test_grouped_launch_sizing_helper_equals_the_inline_rules(monkeypatch):
+    """engine._group_sizing -- tile count, split rule, workspace floats and counter count of a grouped weight-gradient launch, no
+    device access -- for the four launch families (split-precision LM head, bf16 LM head, a block's four products in both
+    precisions, split-precision projector) at GPT-2 base and at the golden 2-layer model's sizes, K = 15104 and K = 512 tokens.
+    The literals are what the engine computed inline, per site, before the helper existed (default switches)."""
+    from mmtg_amd import engine as E
+    monkeypatch.setattr(E, "_WGRAD_GROUP_SPLITS", 0)
+    monkeypatch.setattr(E, "_LMHEAD_GROUP_SPLITS", 0)
+    monkeypatch.setattr(E, "_WGRAD_GROUP_CFG", 2)
+    mc = make_model_cfgs(seq_len=5)
+    H, Ein = mc["topic"]["hidden_dim"], mc["topic"]["input_dim"]
+    assert (H, Ein) == (512, 2048)
+    want = {
+        ("base", 15104): [(3, 30965760, 2520), (1, 10420224, 2544), (2, 14155776, 1728), (1, 7077888, 1728), (5, 7208960, 352)],
+        ("base", 512): [(1, 10321920, 2520), (1, 10420224, 2544), (1, 7077888, 1728), (1, 7077888, 1728), (1, 1441792, 352)],
+        ("golden", 15104): [(14, 2752512, 48), (14, 2752512, 48), (2, 14155776, 1728), (1, 7077888, 1728), (5, 7208960, 352)],
+        ("golden", 512): [(1, 196608, 48), (1, 196608, 48), (1, 7077888, 1728), (1, 7077888, 1728), (1, 1441792, 352)],
+    }
+    for name, g in (("base", gpt2_config()), ("golden", gpt2_config(n_layer=2, vocab_size=160, n_positions=256))):
+        D = g["n_embd"]
+        Vp = (g["vocab_size"] + 127) // 128 * 128
+        assert (D, Vp) == ((768, 13440) if name == "base" else (768, 256))
+        head, blocks, proj = ((Vp, D),), ((D, 4 * D), (4 * D, D), (D, D), (D, 3 * D)), ((D, H), (H, Ein))
+        hcfg, gcfg = hip.WGRAD_RING, E._group_cfg(D)
+        assert gcfg == hip.WGRAD_RING and E._group_cfg(D, x3=True) == 0
+        for K in (15104, 512):
+            got = [E._group_sizing(head, 0, lambda t: E._LMHEAD_GROUP_SPLITS or E._group_splits_x3(t, K)),
+                   E._group_sizing(head, hcfg, lambda t: E._LMHEAD_GROUP_SPLITS or E._group_splits(t, K, 256)),
+                   E._group_sizing(blocks, gcfg, lambda t: E._group_splits(t, K, 256)),
+                   E._group_sizing(blocks, 0, lambda t: E._group_splits_x3(t, K)),
+                   E._group_sizing(proj, 0, lambda t: E._group_splits_x3(t, K))]
+            assert got == want[(name, K)], (name, K, got)
+
+
 def test_split_precision_mode_host_contract():
     """bf16x3 = fp32 storage + split-precision products: the mode string maps to the fp32 storage code with the x3 flag, plane pairs
     address (hi | lo) views of one allocation, and the engine refuses the flag on bf16 storage (no GPU needed)."""
@@ -485,7 +519,7 @@ def test_split_precision_mode_host_contract():
     assert hip.attn_bwd_x3_dq_floats(1, 128, 768) == 128 * 768 and hip.attn_bwd_x3_dq_floats(2, 129, 64) == 2 * 2 * 129 * 64
     assert hip.attn_bwd_x3_ws(64, 236, 768) == (64 * 2 + (64 * 236 + 15) // 16) * 3 * 768
     from mmtg_amd import engine as E
-    if E._X3_WG_CFG == 6 and E._WGRAD_GROUP_SPLITS <= 0:
+    if E._WGRAD_GROUP_SPLITS <= 0:
         assert E._group_splits_x3(432, 15104) == 1          # a GPT-2 block: one round of 432 workgroups
         assert E._group_splits_x3(88, 15104) == 5           # the projector: 440 workgroups
         assert E._group_splits_x3(630, 15104) == 3          # the tied embedding: ~4 rounds' worth

@@ -125,10 +125,25 @@ case("dgrad qkv (NT)", M, D, 3 * D, False, True)
 case("dgrad lm head (NN)", M, D, V, False, False)
 if os.environ.get("TNSET"):
     # weight gradients as the trainer launches them: K-split slabs (+ the ordered slab sum), split count per kernel family
-    from mmtg_amd.engine import _wgrad_splits_p8 as ws8
+    _P8T = os.environ.get("MMTG_GEMM_P8T", "0") != "0"      # the library's eight-phase K-strided kernel for these products
+
+    def _wgrad_splits_p8(M, N, K, cus=256):
+        """Split count for the eight-phase weight-gradient kernel (256x256 tiles, ONE workgroup per CU): tiles x splits fills one
+        round of the CUs, every split a whole number of 128-deep K units, no empty trailing split.  None when the product is
+        not eligible (mmtg_gemm's rule: K % 128 == 0, M, N >= 256) or has too many tiles to gain from splitting."""
+        if not _P8T or K % 128 or M < 256 or N < 256:
+            return None
+        tiles = ((M + 255) // 256) * ((N + 255) // 256)
+        if tiles > cus // 2:
+            return None
+        units = K // 128
+        s0 = max(1, min(cus // tiles, units // 4))
+        per = -(-units // s0)
+        return -(-units // per)
+
     SLAB = int(os.environ.get("SLAB", "1"))
     for nm, a, b in (("wgrad fc2", 4 * D, D), ("wgrad fc1", D, 4 * D), ("wgrad proj", D, D), ("wgrad qkv", D, 3 * D)):
-        sp = (ws8(a, b, M) if os.environ.get("MMTG_GEMM_P8T", "0") != "0" else None) or ws(a, b, M, True)
+        sp = _wgrad_splits_p8(a, b, M) or ws(a, b, M, True)
         case(nm + " (TN s=%d)" % sp, a, b, M, True, False, hip.EPI_ATOMIC, sp)
     sys.exit(0)
 for nm, a, b in (("wgrad fc2", 4 * D, D), ("wgrad fc1", D, 4 * D), ("wgrad proj", D, D), ("wgrad qkv", D, 3 * D), ("wgrad lm head", V, D), ("wgrad proj1", 512, 2048)):
