@@ -330,6 +330,48 @@ MMTG_API int mmtg_loss_bwd_x3(const float* logits, long ldl, int V, const long l
                      const float* coef, float gscale, float lm_coef, int B, int P, int L, void* planes, long ldd, long plane,
                      int Vpad, void* stream);
 
+/* ---------------------------------------------------------------- token-level unlikelihood on repeated lyric tokens
+ * The training-time counterpart of the decoders' repetition controls: the unlikelihood term of Welleck et al., 2019 (fairseq's
+ * unlikelihood_loss) next to the reference's per-sequence objective (loss.py:45-74; the term is added where train.py:191-192 form
+ * the total loss).  Opt-in: MMTGTrainer(ul_weight=...).
+ *
+ * Notation as above: P topic columns, L lyric columns, Tt = P + L, row m = b * Tt + t.  The loss rows of a sample are
+ * P <= t <= Tt - 2 (ntok = Tt - 1 - P of them); row t predicts targets[b, j], j = t + 1 - P; p_t(v) = exp(x[m, v] - lse[m]).
+ *
+ *   candidates  C(b, t) = the DISTINCT ids among targets[b, 0 .. j-1] that lie in [0, V), are not targets[b, j] (the label) and
+ *               are not in the exclude list (a device array of at most 32 ids; the trainer's default is PAD and the ids the
+ *               decoders ban, (0, 1, 2, 100, 102): they repeat by the slot format, not by the model's choice).  The topic prompt
+ *               is not context; an id that occurs several times counts once.
+ *   row term    ul_row[m] = sum over c in C of -log(q_c),  q_c = max(1 - p_t(c), MMTG_UL_FLOOR)
+ *   weight      g_c = p_t(c) / (1 - p_t(c)) where 1 - p_t(c) >= MMTG_UL_FLOOR, else 0 (a clamped candidate carries no gradient);
+ *               S[m] = sum over c of g_c
+ *   sample      ul_sample[b] = (1 / ntok) * sum over the loss rows of ul_row;   ul = sum_b ul_sample[b] / batch_den
+ *               (every sample takes part whatever its rating; rows t < P and each sample's last row carry none: 0)
+ *   objective   MyLoss + alpha * KL (+ lm_weight * LM) + ul_weight * ul
+ *   gradient    on a loss row, with u = ul_weight * gscale / (ntok * batch_den) and cf the row factor of mmtg_loss_bwd:
+ *               d[m, v] = cf * (p_v - [v == label]) - (u * S[m]) * p_v + u * [v in C] * g_v
+ *               (the first term is mmtg_loss_bwd's expression in its order: with u = 0 the same bits are written)
+ * All sums run in a fixed order and nothing is accumulated with atomics: equal inputs give equal bits.                       */
+#define MMTG_UL_FLOOR 1e-5f
+#define MMTG_UL_MAX_EXCLUDE 32
+#define MMTG_UL_MAX_L 1024     /* lyric columns the candidate search stages per row; a larger L is refused */
+/* Forward of the term on the logits and the row lse of mmtg_loss_fwd (logits of `logits_dtype`, row stride ldl).
+ * Outputs (f32): ul_row[M], ul_S[M] (both 0 outside the loss rows), ul_sample[B], ul[1].                                    */
+MMTG_API int mmtg_loss_ul_fwd(int logits_dtype, const void* logits, long ldl, int V, const long long* targets, const float* lse,
+                     const long long* exclude, int n_exclude, int B, int P, int L, float batch_den,
+                     float* ul_row, float* ul_S, float* ul_sample, float* ul, void* stream);
+/* mmtg_loss_bwd with the term's gradient folded in (ul_S from mmtg_loss_ul_fwd on the same logits, ul_coef = u above, finite
+ * and >= 0): the same storage forms, zeros and in-place rule; the candidates' logits are read before the row is rewritten.   */
+MMTG_API int mmtg_loss_bwd_ul(int dtype, int logits_dtype, const void* logits, long ldl, int V, const long long* topic_ids,
+                     const long long* targets, const float* lse, const float* coef, float gscale, float lm_coef,
+                     const float* ul_S, float ul_coef, const long long* exclude, int n_exclude,
+                     int B, int P, int L, void* dlogits, long ldd, int Vpad, void* stream);
+/* ... and mmtg_loss_bwd_x3 with it: the candidate columns are fixed up in the hi and the lo plane.                            */
+MMTG_API int mmtg_loss_bwd_ul_x3(const float* logits, long ldl, int V, const long long* topic_ids, const long long* targets,
+                        const float* lse, const float* coef, float gscale, float lm_coef, const float* ul_S, float ul_coef,
+                        const long long* exclude, int n_exclude, int B, int P, int L, void* planes, long ldd, long plane,
+                        int Vpad, void* stream);
+
 /* ---------------------------------------------------------------- encoder / fuser pieces
  * GRU cell (nn.GRU math, model.py:78-79): gi (row stride ld_gi), gh (row stride ld_gh >= 3H, or 0 = one
  * [3H] row for every b: at step 0, h_prev = 0, the recurrent product is just b_hh)

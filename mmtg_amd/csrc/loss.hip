@@ -233,6 +233,218 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const LT* logits, long ld
     }
 }
 
+// ---------------------------------------------------------------- token-level unlikelihood (the rule: include/mmtg_hip.h)
+constexpr int UL_L = MMTG_UL_MAX_L;           // context ids a workgroup stages: four per thread
+constexpr int UL_SLOTS = UL_L / 256;
+
+// the context of loss row (b, t), targets[b, 0 .. j-1], into LDS (ids outside [0, V) become -1) with the exclude list
+__device__ __forceinline__ void ul_stage(const long long* __restrict__ trow, int j, int V, const long long* __restrict__ exclude,
+                                         int n_exclude, int* ids, long long* ex) {
+    for (int i = threadIdx.x; i < j; i += 256) {
+        const long long v = trow[i];
+        ids[i] = (v >= 0 && v < V) ? (int)v : -1;
+    }
+    if ((int)threadIdx.x < n_exclude) ex[threadIdx.x] = exclude[threadIdx.x];
+    __syncthreads();
+}
+
+// is context slot i a candidate: in range, not the label, not excluded, and the first occurrence of its id
+__device__ __forceinline__ bool ul_candidate(const int* ids, int i, long long label, const long long* ex, int n_exclude) {
+    const int id = ids[i];
+    if (id < 0 || (long long)id == label) return false;
+    for (int e = 0; e < n_exclude; ++e)
+        if (ex[e] == (long long)id) return false;
+    bool dup = false;
+    int k = 0;
+    for (; k + 4 <= i; k += 4) {            // (every lane reads the same four ids: one broadcast 16-byte LDS read)
+        const int4 v = *reinterpret_cast<const int4*>(ids + k);
+        dup |= (v.x == id) | (v.y == id) | (v.z == id) | (v.w == id);
+    }
+    for (; k < i; ++k) dup |= ids[k] == id;
+    return !dup;
+}
+
+// -log q and g of one candidate from its logit
+__device__ __forceinline__ void ul_terms(float x, float l, float& p, float& nlq, float& g) {
+    p = expf(x - l);
+    const float q = 1.f - p;
+    if (q >= MMTG_UL_FLOOR) { nlq = -logf(q); g = p / q; }
+    else { nlq = -logf(MMTG_UL_FLOOR); g = 0.f; }
+}
+
+// one workgroup per row: ul_row[m] and S[m].  A thread sums its (at most four) candidates in context order, the workgroup
+// combines the 256 partial sums by the butterfly of block_sum: a fixed order.
+template <typename LT>
+__global__ __launch_bounds__(256) void ul_row_kernel(const LT* __restrict__ logits, long ldl, int V,
+        const long long* __restrict__ targets, const float* __restrict__ lse, const long long* __restrict__ exclude, int n_exclude,
+        int P, int L, float* __restrict__ ul_row, float* __restrict__ ul_S) {
+    __shared__ __attribute__((aligned(16))) int ids[UL_L];
+    __shared__ long long ex[MMTG_UL_MAX_EXCLUDE];
+    __shared__ float sh[4];
+    const int Tt = P + L;
+    const long m = blockIdx.x;
+    const int b = (int)(m / Tt), t = (int)(m % Tt);
+    if (t < P || t + 1 >= Tt) {
+        if (threadIdx.x == 0) { ul_row[m] = 0.f; ul_S[m] = 0.f; }
+        return;
+    }
+    const int j = t + 1 - P;                    // 1 .. L - 1
+    const long long* trow = targets + (long)b * L;
+    const long long label = trow[j];
+    ul_stage(trow, j, V, exclude, n_exclude, ids, ex);
+    const LT* row = logits + m * ldl;
+    const float l = lse[m];
+    float term = 0.f, gs = 0.f;
+    for (int i = threadIdx.x; i < j; i += 256) {
+        if (!ul_candidate(ids, i, label, ex, n_exclude)) continue;
+        float p, nlq, g;
+        ul_terms((float)row[ids[i]], l, p, nlq, g);
+        term += nlq;
+        gs += g;
+    }
+    term = block_sum(term, sh);
+    gs = block_sum(gs, sh);
+    if (threadIdx.x == 0) { ul_row[m] = term; ul_S[m] = gs; }
+}
+
+// single workgroup: ul_sample[b] and ul, in sample_loss_kernel's order (one wave per sample, the sixteen waves' sums in wave order)
+__global__ __launch_bounds__(1024) void ul_sample_kernel(const float* __restrict__ ul_row, int B, int P, int L, float batch_den,
+        float* __restrict__ ul_sample, float* __restrict__ ul) {
+    __shared__ float sh[16];
+    const int Tt = P + L;
+    const int ntok = Tt - 1 - P;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float my = 0.f;
+    for (int b = wave; b < B; b += 16) {
+        float s = 0.f;
+        for (int t = P + lane; t < Tt - 1; t += 64) s += ul_row[(long)b * Tt + t];
+        s = wave_sum(s);
+        if (lane != 0) continue;
+        s = ntok > 0 ? s / ntok : 0.f;
+        ul_sample[b] = s;
+        my += s;
+    }
+    if (lane == 0) sh[wave] = my;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        my = 0.f;
+        for (int w = 0; w < 16; ++w) my += sh[w];       // fixed order
+        ul[0] = my / batch_den;
+    }
+}
+
+// loss_bwd_kernel with the term: the dense pass carries -(u S[m]) p_v next to today's expression, and the row's candidate columns
+// are then rewritten whole.  The candidates' logits go to LDS before the first store (the row may be rewritten in place), the
+// columns are written after a barrier behind the dense pass, each by the thread that fetched it: no read-modify-write.
+template <typename T, typename LT>
+__global__ __launch_bounds__(256) void loss_bwd_ul_kernel(const LT* logits, long ldl, int V,
+        const long long* __restrict__ topic_ids, const long long* __restrict__ targets,
+        const float* __restrict__ lse, const float* __restrict__ coef, float gscale, float lm_coef,
+        const float* __restrict__ ul_S, float ucoef, const long long* __restrict__ exclude, int n_exclude, int P, int L,
+        T* dlogits, long ldd, int Vpad, long plane = 0) {
+    __shared__ __attribute__((aligned(16))) int ids[UL_L];
+    __shared__ float cx[UL_L];
+    __shared__ long long ex[MMTG_UL_MAX_EXCLUDE];
+    const int Tt = P + L;
+    const long m = blockIdx.x;
+    const int b = (int)(m / Tt), t = (int)(m % Tt);
+    T* drow = dlogits + m * ldd;
+    const bool active = t + 1 < Tt && (t >= P || lm_coef != 0.f);
+    if (!active) {
+        if ((Vpad & 7) == 0 && (ldd & 7) == 0) {
+            typedef typename Vec16<T>::type V16;
+            V16 z;
+#pragma unroll
+            for (int e = 0; e < Vec16<T>::N; ++e) z[e] = (T)0.f;
+            for (int v = threadIdx.x * Vec16<T>::N; v < Vpad; v += 256 * Vec16<T>::N) {
+                *reinterpret_cast<V16*>(drow + v) = z;
+                if (plane) *reinterpret_cast<V16*>(drow + plane + v) = z;
+            }
+        } else {
+            for (int v = threadIdx.x; v < Vpad; v += 256) drow[v] = (T)0.f;
+        }
+        return;
+    }
+    const LT* row = logits + m * ldl;
+    const float l = lse[m], cf = (t >= P ? coef[b] * gscale : 0.f) + lm_coef;
+    long long lab = label_of(topic_ids, targets, b, t + 1, P, L, 0);
+    if (lab < 0) lab = 0;
+    if (lab >= V) lab = V - 1;
+    // (uniform over the workgroup) a loss row with the term switched on: its context is targets[b, 0 .. j-1]
+    const bool ulrow = t >= P && ucoef != 0.f;
+    const int j = ulrow ? t + 1 - P : 0;
+    const float us = ulrow ? ucoef * ul_S[m] : 0.f;
+    bool cand[UL_SLOTS];
+#pragma unroll
+    for (int r = 0; r < UL_SLOTS; ++r) cand[r] = false;
+    if (ulrow) {
+        const long long* trow = targets + (long)b * L;
+        const long long label = trow[j];        // (the label as given: an id outside [0, V) is no candidate anyway)
+        ul_stage(trow, j, V, exclude, n_exclude, ids, ex);
+#pragma unroll
+        for (int r = 0; r < UL_SLOTS; ++r) {
+            const int i = threadIdx.x + 256 * r;
+            if (i < j && ul_candidate(ids, i, label, ex, n_exclude)) {
+                cand[r] = true;
+                cx[i] = (float)row[ids[i]];
+            }
+        }
+        __syncthreads();        // every candidate's logit is in LDS before the first store of the row
+    }
+    const bool vec = (Vpad & 7) == 0 && (ldl & (sizeof(LT) == 4 ? 3 : 7)) == 0 && ldl >= Vpad && (ldd & 7) == 0;
+    if (vec) {
+        for (int v = threadIdx.x * 8; v < Vpad; v += 2048) {
+            float d[8], x[8];
+            load8(row + v, x);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int vv = v + e;
+                const float pv = expf(x[e] - l);
+                d[e] = vv < V ? cf * (pv - (vv == (int)lab ? 1.f : 0.f)) - us * pv : 0.f;
+            }
+            if constexpr (sizeof(T) == 2) {
+                bf16x8 o = {(bf16)d[0], (bf16)d[1], (bf16)d[2], (bf16)d[3], (bf16)d[4], (bf16)d[5], (bf16)d[6], (bf16)d[7]};
+                *reinterpret_cast<bf16x8*>(drow + v) = o;
+                if (plane) {
+                    bf16x8 lo;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) lo[e] = (bf16)(d[e] - (float)o[e]);
+                    *reinterpret_cast<bf16x8*>(drow + plane + v) = lo;
+                }
+            } else {
+                *reinterpret_cast<f32x4*>(drow + v) = f32x4{d[0], d[1], d[2], d[3]};
+                *reinterpret_cast<f32x4*>(drow + v + 4) = f32x4{d[4], d[5], d[6], d[7]};
+            }
+        }
+    } else {
+        for (int v = threadIdx.x; v < Vpad; v += 256) {
+            float d = 0.f;
+            if (v < V) {
+                const float pv = expf((float)row[v] - l);
+                d = cf * (pv - (v == (int)lab ? 1.f : 0.f)) - us * pv;
+            }
+            drow[v] = (T)d;
+        }
+    }
+    if (!ulrow) return;
+    __syncthreads();            // the dense pass of every thread lies behind: the candidate columns are written last
+#pragma unroll
+    for (int r = 0; r < UL_SLOTS; ++r) {
+        if (!cand[r]) continue;
+        const int i = threadIdx.x + 256 * r;
+        const int c = ids[i];
+        float pc, nlq, g;
+        ul_terms(cx[i], l, pc, nlq, g);
+        // (a candidate is never the label as given, but a label outside [0, V) is clamped INTO the row and may land on one)
+        const float d = cf * (pc - (c == (int)lab ? 1.f : 0.f)) - us * pc + ucoef * g;
+        const T hi = (T)d;
+        drow[c] = hi;
+        if constexpr (sizeof(T) == 2) {
+            if (plane) drow[plane + c] = (bf16)(d - (float)hi);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int mmtg_loss_fwd(int logits_dtype, const void* logits, long ldl, int V, const long long* topic_ids,
@@ -292,5 +504,82 @@ extern "C" int mmtg_loss_bwd_x3(const float* logits, long ldl, int V, const long
     hipLaunchKernelGGL((loss_bwd_kernel<bf16, float>), dim3((unsigned)M), dim3(256), 0, s, logits, ldl, V, topic_ids, targets, lse, coef, gscale, lm_coef,
                        P, L, (bf16*)planes, ldd, Vpad, plane);
     MMTG_LAUNCH_CHECK("loss_bwd_x3");
+    return MMTG_OK;
+}
+
+/* ---- token-level unlikelihood: the rule is stated at the declarations in include/mmtg_hip.h */
+static bool ul_coef_ok(float u) { return u >= 0.f && u <= 3.0e38f; }       // finite and not negative (NaN fails both comparisons)
+
+extern "C" int mmtg_loss_ul_fwd(int logits_dtype, const void* logits, long ldl, int V, const long long* targets, const float* lse,
+                                const long long* exclude, int n_exclude, int B, int P, int L, float batch_den,
+                                float* ul_row, float* ul_S, float* ul_sample, float* ul, void* stream) {
+    MMTG_REQUIRE(logits_dtype == MMTG_F32 || logits_dtype == MMTG_BF16, "loss_ul_fwd: bad logits dtype %d", logits_dtype);
+    MMTG_REQUIRE(B > 0 && L >= 1 && P >= 0 && P + L >= 2 && V > 0 && ldl >= V, "loss_ul_fwd: bad sizes (B=%d P=%d L=%d V=%d ldl=%ld)", B, P, L, V, ldl);
+    MMTG_REQUIRE(L <= MMTG_UL_MAX_L, "loss_ul_fwd: L = %d lyric columns; the candidate search holds at most %d", L, MMTG_UL_MAX_L);
+    MMTG_REQUIRE(logits && targets && lse && ul_row && ul_S && ul_sample && ul, "loss_ul_fwd: null pointer");
+    MMTG_REQUIRE(n_exclude >= 0 && n_exclude <= MMTG_UL_MAX_EXCLUDE, "loss_ul_fwd: n_exclude = %d (0 .. %d)", n_exclude, MMTG_UL_MAX_EXCLUDE);
+    MMTG_REQUIRE(n_exclude == 0 || exclude, "loss_ul_fwd: null exclude list of %d ids", n_exclude);
+    MMTG_REQUIRE(batch_den > 0.f && batch_den <= 3.0e38f, "loss_ul_fwd: batch_den = %g", (double)batch_den);
+    hipStream_t s = (hipStream_t)stream;
+    const long M = (long)B * (P + L);
+    ProfScope prof(MMTG_PROF_LOSS, s, 8.0 * B * L * L, 16.0 * B * L * L);
+    if (logits_dtype == MMTG_F32)
+        hipLaunchKernelGGL(ul_row_kernel<float>, dim3((unsigned)M), dim3(256), 0, s, (const float*)logits, ldl, V, targets, lse, exclude, n_exclude, P, L, ul_row, ul_S);
+    else
+        hipLaunchKernelGGL(ul_row_kernel<bf16>, dim3((unsigned)M), dim3(256), 0, s, (const bf16*)logits, ldl, V, targets, lse, exclude, n_exclude, P, L, ul_row, ul_S);
+    hipLaunchKernelGGL(ul_sample_kernel, dim3(1), dim3(1024), 0, s, ul_row, B, P, L, batch_den, ul_sample, ul);
+    MMTG_LAUNCH_CHECK("loss_ul_fwd");
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_loss_bwd_ul(int dtype, int logits_dtype, const void* logits, long ldl, int V, const long long* topic_ids,
+                                const long long* targets, const float* lse, const float* coef, float gscale, float lm_coef,
+                                const float* ul_S, float ul_coef, const long long* exclude, int n_exclude,
+                                int B, int P, int L, void* dlogits, long ldd, int Vpad, void* stream) {
+    MMTG_REQUIRE(B > 0 && L >= 1 && P >= 0 && P + L >= 2 && V > 0 && ldl >= V && Vpad >= V && ldd >= Vpad, "loss_bwd_ul: bad sizes");
+    MMTG_REQUIRE(L <= MMTG_UL_MAX_L, "loss_bwd_ul: L = %d lyric columns; the candidate search holds at most %d", L, MMTG_UL_MAX_L);
+    MMTG_REQUIRE(logits && targets && lse && coef && ul_S && dlogits, "loss_bwd_ul: null pointer");
+    MMTG_REQUIRE(P == 0 || lm_coef == 0.f || topic_ids, "loss_bwd_ul: topic_ids required (the LM-loss rows t < P read them)");
+    MMTG_REQUIRE(dtype == MMTG_F32 || dtype == MMTG_BF16, "loss_bwd_ul: bad dtype");
+    MMTG_REQUIRE(logits_dtype == MMTG_F32 || (logits_dtype == MMTG_BF16 && dtype == MMTG_BF16), "loss_bwd_ul: bf16 logits go with bf16 dlogits");
+    MMTG_REQUIRE(logits != dlogits || (logits_dtype == dtype && ldl == ldd), "loss_bwd_ul: in-place needs one storage type and one row stride");
+    MMTG_REQUIRE(n_exclude >= 0 && n_exclude <= MMTG_UL_MAX_EXCLUDE, "loss_bwd_ul: n_exclude = %d (0 .. %d)", n_exclude, MMTG_UL_MAX_EXCLUDE);
+    MMTG_REQUIRE(n_exclude == 0 || exclude, "loss_bwd_ul: null exclude list of %d ids", n_exclude);
+    MMTG_REQUIRE(ul_coef_ok(ul_coef), "loss_bwd_ul: ul_coef = %g (finite, >= 0)", (double)ul_coef);
+    // the 16-byte path of the dense pass (the condition the kernel tests) needs aligned rows
+    const bool vec = Vpad % 8 == 0 && ldl % (logits_dtype == MMTG_F32 ? 4 : 8) == 0 && ldl >= Vpad && ldd % 8 == 0;
+    MMTG_REQUIRE(!vec || (MMTG_ALIGNED16(logits) && MMTG_ALIGNED16(dlogits)), "loss_bwd_ul: logits and dlogits must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const long M = (long)B * (P + L);
+    ProfScope prof(MMTG_PROF_LOSS, s, 4.0 * M * V, ((logits_dtype == MMTG_F32 ? 4.0 : 2.0) + (dtype == MMTG_F32 ? 4 : 2)) * M * V);
+#define LB(T, LT) hipLaunchKernelGGL((loss_bwd_ul_kernel<T, LT>), dim3((unsigned)M), dim3(256), 0, s, (const LT*)logits, ldl, V, topic_ids, targets, \
+                                     lse, coef, gscale, lm_coef, ul_S, ul_coef, exclude, n_exclude, P, L, (T*)dlogits, ldd, Vpad)
+    if (dtype == MMTG_F32) LB(float, float);
+    else if (logits_dtype == MMTG_F32) LB(bf16, float);
+    else LB(bf16, bf16);
+#undef LB
+    MMTG_LAUNCH_CHECK("loss_bwd_ul");
+    return MMTG_OK;
+}
+
+extern "C" int mmtg_loss_bwd_ul_x3(const float* logits, long ldl, int V, const long long* topic_ids, const long long* targets,
+                                   const float* lse, const float* coef, float gscale, float lm_coef, const float* ul_S, float ul_coef,
+                                   const long long* exclude, int n_exclude, int B, int P, int L, void* planes, long ldd, long plane,
+                                   int Vpad, void* stream) {
+    MMTG_REQUIRE(B > 0 && L >= 1 && P >= 0 && P + L >= 2 && V > 0 && Vpad >= V && ldd >= Vpad && Vpad % 8 == 0 && ldd % 8 == 0 && ldl % 4 == 0 && ldl >= Vpad,
+                 "loss_bwd_ul_x3: bad sizes (Vpad, ldd multiples of 8, ldl >= Vpad)");
+    MMTG_REQUIRE(L <= MMTG_UL_MAX_L, "loss_bwd_ul_x3: L = %d lyric columns; the candidate search holds at most %d", L, MMTG_UL_MAX_L);
+    MMTG_REQUIRE(logits && targets && lse && coef && ul_S && planes && MMTG_ALIGNED16(planes) && MMTG_ALIGNED16(logits), "loss_bwd_ul_x3: null / misaligned pointer");
+    MMTG_REQUIRE(P == 0 || lm_coef == 0.f || topic_ids, "loss_bwd_ul_x3: topic_ids required (the LM-loss rows t < P read them)");
+    const long M = (long)B * (P + L);
+    MMTG_REQUIRE(plane % 8 == 0 && plane >= (M - 1) * ldd + Vpad, "loss_bwd_ul_x3: the lo plane must lie behind the hi plane");
+    MMTG_REQUIRE(n_exclude >= 0 && n_exclude <= MMTG_UL_MAX_EXCLUDE, "loss_bwd_ul_x3: n_exclude = %d (0 .. %d)", n_exclude, MMTG_UL_MAX_EXCLUDE);
+    MMTG_REQUIRE(n_exclude == 0 || exclude, "loss_bwd_ul_x3: null exclude list of %d ids", n_exclude);
+    MMTG_REQUIRE(ul_coef_ok(ul_coef), "loss_bwd_ul_x3: ul_coef = %g (finite, >= 0)", (double)ul_coef);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_LOSS, s, 4.0 * M * V, 8.0 * M * V);
+    hipLaunchKernelGGL((loss_bwd_ul_kernel<bf16, float>), dim3((unsigned)M), dim3(256), 0, s, logits, ldl, V, topic_ids, targets, lse, coef, gscale, lm_coef,
+                       ul_S, ul_coef, exclude, n_exclude, P, L, (bf16*)planes, ldd, Vpad, plane);
+    MMTG_LAUNCH_CHECK("loss_bwd_ul_x3");
     return MMTG_OK;
 }

@@ -345,6 +345,7 @@ class Engine:
         self.opt_m = None
         self.opt_v = None
         self.ema = None            # flat fp32 average of the master (ema_update), None until first use
+        self.ul_exclude = None     # int64 device ids the unlikelihood term never takes as candidates (set_ul_exclude)
         self.normsq = torch.zeros(1, device=self.dev)
         self.group_normsq = None   # [ngroups + 1] of a grouped step (group_norm_sq); normsq is then its last element
         self.bucket_hook = None   # callable(pack_index) fired as packs of gradients become final
@@ -983,6 +984,45 @@ class Engine:
         dl = a["logits"] if a["logits"].dtype == self.tdt and self.dtype != hip.F32 else self.buf("dlogits", (a["M"], self.layout.Vpad))
         hip.loss_bwd(a["logits"], self.layout.Vpad, sh.V, a["topic_ids"], a["targets"], a["lse_rows"], a["coef"],
                      gscale, a["B"], sh.P, a["L"], dl, self.layout.Vpad, self.layout.Vpad, lm_coef=lm_coef)
+        return dl
+
+    # ---- token-level unlikelihood on repeated lyric tokens (the rule: include/mmtg_hip.h; MMTGTrainer(ul_weight=...))
+    def set_ul_exclude(self, ids):
+        """The ids that are never candidates (at most 32), uploaded once."""
+        ids = [int(i) for i in ids]
+        self.ul_exclude = torch.tensor(ids, device=self.dev, dtype=torch.long) if ids else None
+
+    def ul_loss(self, batch_den=None):
+        """The term on the forward's logits, after loss() (it reads the row lse): the device scalar ul [1]; also fills the row sums
+        S for loss_backward_ul()."""
+        a, sh = self.act, self.sh
+        B, L, M = a["B"], a["L"], a["M"]
+        row = self.buf("ul_row", (M,), torch.float32)
+        S = self.buf("ul_S", (M,), torch.float32)
+        smp = self.buf("ul_sample", (B,), torch.float32)
+        ul = self.buf("ul_scalar", (1,), torch.float32)
+        hip.loss_ul_fwd(a["logits"], self.layout.Vpad, sh.V, a["targets"], a["lse_rows"], self.ul_exclude,
+                        B, sh.P, L, float(B if batch_den is None else batch_den), row, S, smp, ul)
+        a.update(ul_row=row, ul_S=S, ul_sample=smp, ul=ul)
+        return ul
+
+    def loss_backward_ul(self, gscale=1.0, lm_coef=0.0, ul_coef=0.0):
+        """loss_backward() with ul_coef * d(sum of the row terms)/d logits added, ul_coef = ul_weight * gscale / (ntok * batch_den);
+        the same buffers and storage forms."""
+        a, sh = self.act, self.sh
+        Vp, ex = self.layout.Vpad, self.ul_exclude
+        args = (a["logits"], Vp, sh.V, a["topic_ids"], a["targets"], a["lse_rows"], a["coef"], gscale, a["ul_S"], ul_coef, ex,
+                a["B"], sh.P, a["L"])
+        if a.get("x3") and self.hybrid:
+            dl = self.buf("dlogits_b", (a["M"], Vp), torch.bfloat16)
+            hip.loss_bwd_ul(*args, dl, Vp, Vp, lm_coef=lm_coef)
+            return dl
+        if a.get("x3"):
+            dlp = self.pbuf("dlogits_p", a["M"], Vp)
+            hip.loss_bwd_ul_x3(*args, dlp, Vp, lm_coef=lm_coef)
+            return dlp
+        dl = a["logits"] if a["logits"].dtype == self.tdt and self.dtype != hip.F32 else self.buf("dlogits", (a["M"], Vp))
+        hip.loss_bwd_ul(*args, dl, Vp, Vp, lm_coef=lm_coef)
         return dl
 
     def dlogits_from(self, g32):

@@ -62,6 +62,9 @@ _SIGS = {
     "mmtg_loss_fwd": ([_i, _vp, _l, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "mmtg_loss_bwd": ([_i, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _vp, _l, _i, _vp], _i),
     "mmtg_loss_bwd_x3": ([_vp, _l, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _i, _vp, _l, _l, _i, _vp], _i),
+    "mmtg_loss_ul_fwd": ([_i, _vp, _l, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp], _i),
+    "mmtg_loss_bwd_ul": ([_i, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _f, _vp, _i, _i, _i, _i, _vp, _l, _i, _vp], _i),
+    "mmtg_loss_bwd_ul_x3": ([_vp, _l, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _f, _vp, _i, _i, _i, _i, _vp, _l, _l, _i, _vp], _i),
     "mmtg_gru_cell_fwd": ([_i, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _vp], _i),
     "mmtg_gru_cell_bwd_fused": ([_i, _vp, _l, _vp, _vp, _i, _vp, _vp, _l, _vp, _l, _vp, _vp, _i, _i, _vp], _i),
     "mmtg_rnn_cell_fwd": ([_i, _i, _vp, _l, _vp, _l, _vp, _vp, _l, _vp, _vp, _i, _i, _vp], _i),
@@ -630,6 +633,35 @@ def loss_bwd_x3(logits, ldl, V, topic_ids, targets, lse, coef, gscale, B, P, L, 
     """d(logits) of fp32 logits as a Planes pair (x3 mode)."""
     _check(lib().mmtg_loss_bwd_x3(_p(logits), ldl, V, _p(topic_ids), _p(targets), _p(lse), _p(coef), float(gscale), float(lm_coef), B, P, L,
                                   _p(planes.t), planes.ld, planes.plane, Vpad, _stream()), "loss_bwd_x3")
+
+
+# token-level unlikelihood on repeated lyric tokens (the rule: include/mmtg_hip.h)
+UL_FLOOR, UL_MAX_EXCLUDE, UL_MAX_L = 1e-5, 32, 1024
+
+
+def _n_ex(exclude):
+    return 0 if exclude is None else int(exclude.numel())
+
+
+def loss_ul_fwd(logits, ldl, V, targets, lse, exclude, B, P, L, batch_den, ul_row, ul_S, ul_sample, ul):
+    """ul_row [M], ul_S [M], ul_sample [B] and the scalar ul [1] from the logits and the row lse of loss_fwd; exclude: an int64
+    device tensor of at most 32 ids, or None."""
+    _check(lib().mmtg_loss_ul_fwd(dt(logits), _p(logits), ldl, V, _p(targets), _p(lse), _p(exclude), _n_ex(exclude), B, P, L,
+                                  float(batch_den), _p(ul_row), _p(ul_S), _p(ul_sample), _p(ul), _stream()), "loss_ul_fwd")
+
+
+def loss_bwd_ul(logits, ldl, V, topic_ids, targets, lse, coef, gscale, ul_S, ul_coef, exclude, B, P, L, dlogits, ldd, Vpad, lm_coef=0.0):
+    """loss_bwd with the term's gradient: ul_S from loss_ul_fwd, ul_coef = ul_weight * gscale / (ntok * batch_den)."""
+    _check(lib().mmtg_loss_bwd_ul(dt(dlogits), dt(logits), _p(logits), ldl, V, _p(topic_ids), _p(targets), _p(lse), _p(coef),
+                                  float(gscale), float(lm_coef), _p(ul_S), float(ul_coef), _p(exclude), _n_ex(exclude), B, P, L,
+                                  _p(dlogits), ldd, Vpad, _stream()), "loss_bwd_ul")
+
+
+def loss_bwd_ul_x3(logits, ldl, V, topic_ids, targets, lse, coef, gscale, ul_S, ul_coef, exclude, B, P, L, planes, Vpad, lm_coef=0.0):
+    """... into a Planes pair (x3 mode): hi and lo of the candidate columns are both rewritten."""
+    _check(lib().mmtg_loss_bwd_ul_x3(_p(logits), ldl, V, _p(topic_ids), _p(targets), _p(lse), _p(coef), float(gscale), float(lm_coef),
+                                     _p(ul_S), float(ul_coef), _p(exclude), _n_ex(exclude), B, P, L,
+                                     _p(planes.t), planes.ld, planes.plane, Vpad, _stream()), "loss_bwd_ul_x3")
 
 
 # ------------------------------------------------------------------ encoder pieces

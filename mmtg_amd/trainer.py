@@ -46,8 +46,17 @@ _LOGITS_F32 = bool(os.environ.get("MMTG_LOGITS_F32"))     # A/B switch: fp32 log
 class MMTGTrainer:
     def __init__(self, model, lr=1e-5, alpha=0.0, max_norm=1.0, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.0, warmup_steps=0, total_steps=None, distributed=False, bucket_mb=64.0,
-                 lm_weight=0.0, param_groups=None, accumulation_steps=1, ema_decay=None, ema_warmup=True):
-        """accumulation_steps: calls of step() per optimizer step (a window of micro-batches, see step()).
+                 lm_weight=0.0, param_groups=None, accumulation_steps=1, ema_decay=None, ema_warmup=True,
+                 ul_weight=0.0, ul_exclude_ids=None):
+        """ul_weight: weight of the token-level unlikelihood term on repeated lyric tokens (Welleck et al., 2019; the rule is stated
+        in include/mmtg_hip.h): at every lyric position the characters the lyric has already used are pushed down, so the objective
+        becomes MyLoss + alpha * KL (+ lm_weight * LM) + ul_weight * ul.  0.0 (the default) is the reference's objective and runs
+        exactly the launches it always did; > 0 adds two small launches and replaces the d(logits) kernel by the one that carries the
+        term.  ul_exclude_ids: at most 32 ids that are never pushed down, None = PAD and the ids the decoders ban
+        (0,) + constraints.BANNED -- they repeat by the slot format, not by the model's choice; with another tokenizer pass
+        tokenizer.convert_tokens_to_ids of its own format tokens.  Only the fused step takes the term; the drop-in autograd path
+        (mmtg_amd.loss.MyLoss) is the reference's loss.
+        accumulation_steps: calls of step() per optimizer step (a window of micro-batches, see step()).
         ema_decay: None (no average: no buffer, no launch) or a float in (0, 1), the decay of an exponential moving average of
         the parameters kept next to the masters and updated once per optimizer step (see _close_end); ema_warmup: the decay of
         update t (from 0) is min(ema_decay, (1 + t) / (10 + t)), so that the first steps do not pin the average to the initial
@@ -61,12 +70,26 @@ class MMTGTrainer:
             raise ValueError("accumulation_steps must be an int of at least 1, got %r" % (accumulation_steps,))
         if ema_decay is not None and not (isinstance(ema_decay, float) and 0.0 < ema_decay < 1.0):
             raise ValueError("ema_decay must be None or a float in (0, 1), got %r" % (ema_decay,))
+        if isinstance(ul_weight, bool) or not isinstance(ul_weight, (int, float)) or not (0.0 <= ul_weight < float("inf")):
+            raise ValueError("ul_weight must be a finite float >= 0, got %r" % (ul_weight,))
+        if ul_exclude_ids is None:
+            from .constraints import BANNED
+            ul_exclude_ids = (0,) + tuple(BANNED)
+        try:
+            ul_exclude_ids = tuple(ul_exclude_ids)
+        except TypeError:
+            raise ValueError("ul_exclude_ids must be None or a sequence of at most 32 non-negative ints, got %r" % (ul_exclude_ids,)) from None
+        if len(ul_exclude_ids) > 32 or any(type(i) is not int or i < 0 for i in ul_exclude_ids):
+            raise ValueError("ul_exclude_ids must be None or a sequence of at most 32 non-negative ints, got %r" % (ul_exclude_ids,))
+        self.ul_weight, self.ul_exclude_ids = float(ul_weight), ul_exclude_ids
         self.accumulation_steps = accumulation_steps
         self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
         self.ema_updates = 0                    # updates of the average made so far
         self._averaged = False                  # inside averaged_weights(): master and average are exchanged
         self.model = model
         self.eng = model.engine()
+        if self.ul_weight > 0.0:
+            self.eng.set_ul_exclude(self.ul_exclude_ids)         # uploaded once, here
         self.group_plan = self.groups = None
         if param_groups is not None:
             from . import hip
@@ -132,11 +155,12 @@ class MMTGTrainer:
                             "eps": self.eps, "weight_decay": self.wd, "warmup_steps": self.warmup,
                             "total_steps": self.total, "lm_weight": self.lm_weight, "accumulation_steps": self.accumulation_steps,
                             "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup,
+                            "ul_weight": self.ul_weight, "ul_exclude_ids": tuple(self.ul_exclude_ids),
                             # for the record, like the rest: load_state_dict keeps the trainer's own groups as it keeps its own lr
                             "param_groups": None if self.group_plan is None else copy.deepcopy(self.group_plan.specs)}}
 
     def load_state_dict(self, sd):
-        """(accumulation_steps stays the trainer's own, like lr and the groups; an open window is abandoned)
+        """(accumulation_steps, ul_weight and ul_exclude_ids stay the trainer's own, like lr and the groups; an open window is abandoned)
         A trainer with an average takes 'average' and 'updates' from the dict; from a dict without an average (an older
         checkpoint, a run that kept none) the average is dropped and restarts from the loaded weights at the next step.  The decay
         and the warm-up rule stay the trainer's own; a trainer without an average ignores the key."""
@@ -165,7 +189,8 @@ class MMTGTrainer:
             self._tune = None
 
     def step(self, batch, stage=3, filter_rows=True):
-        """One optimisation step; returns device scalars (no host sync) {'loss','lm_loss','kl'} of the LOCAL rows.
+        """One optimisation step; returns device scalars (no host sync) {'loss','lm_loss','kl'} of the LOCAL rows (with ul_weight > 0
+        also 'ul', the unweighted unlikelihood term).
         Returns None when the stage filter leaves no rows on a single rank (train.py:184-185); in a data-parallel
         group a rank without rows still takes part in the exchange and in the (identical) optimizer step.
 
@@ -297,7 +322,14 @@ class MMTGTrainer:
             eng.forward(batch, train_flag=True, training=self.model.training, logits_f32=_LOGITS_F32)
             sc = eng.loss(batch["rating"], stage, batch_den=n_local)
             T = eng.act["T"]
-            dl = eng.loss_backward(float(n_local), lm_coef=self.lm_weight / (T - 1) if self.lm_weight else 0.0)
+            lm_coef = self.lm_weight / (T - 1) if self.lm_weight else 0.0
+            if self.ul_weight > 0.0:
+                # (every row of the batch takes part whatever its rating; ntok = the lyric columns but the first, as in the loss)
+                ul = eng.ul_loss(batch_den=n_local)
+                ntok = max(1, int(batch["targets"].shape[1]) - 1)
+                dl = eng.loss_backward_ul(float(n_local), lm_coef, self.ul_weight / (ntok * n_local) * float(n_local))
+            else:
+                dl = eng.loss_backward(float(n_local), lm_coef=lm_coef)
             if self.reducer is not None:
                 # (before the closing backward the packs are not final; without a hook those backwards overlap their tail, _WGRAD_TAIL)
                 eng.bucket_hook = self._hook if closing else None
@@ -311,6 +343,8 @@ class MMTGTrainer:
                 eng._ow_rec = None
             self._bwd_ran = True
             out = {"loss": sc[0], "lm_loss": sc[1], "kl": eng.act["kl"][0]}
+            if self.ul_weight > 0.0:
+                out["ul"] = ul[0]
             self._add_to_window(out, sc, n_local)
         self._rows = rows
         if closing:
@@ -323,13 +357,17 @@ class MMTGTrainer:
             self._wacc = out        # the step's own scalars: no launch that today's step does not have
             return
         if self._wacc is None:
-            self._wacc = torch.empty(3, device=sc.device, dtype=torch.float32)
+            self._wacc = torch.empty(4 if self.ul_weight > 0.0 else 3, device=sc.device, dtype=torch.float32)
         if self._rows == 0:         # the window's first rows
             torch.mul(sc[:2], float(n), out=self._wacc[:2])
-            torch.mul(out["kl"].reshape(1), float(n), out=self._wacc[2:])
+            torch.mul(out["kl"].reshape(1), float(n), out=self._wacc[2:3])
+            if "ul" in out:
+                torch.mul(out["ul"].reshape(1), float(n), out=self._wacc[3:])
         else:
             self._wacc[:2].add_(sc[:2], alpha=float(n))
-            self._wacc[2:].add_(out["kl"].reshape(1), alpha=float(n))
+            self._wacc[2:3].add_(out["kl"].reshape(1), alpha=float(n))
+            if "ul" in out:
+                self._wacc[3:].add_(out["ul"].reshape(1), alpha=float(n))
 
     def _close_begin(self, red, rows):
         """The closing call's part BEFORE its backward: the window's row count onto the device and into the exchange.  False when
@@ -372,11 +410,15 @@ class MMTGTrainer:
         rows = self._rows
         if rows == 0:
             self.window = {"loss": None, "lm_loss": None, "kl": None, "rows": 0}
+            if self.ul_weight > 0.0:
+                self.window["ul"] = None
         elif self.accumulation_steps == 1:
             self.window = dict(self._wacc, rows=rows)
         else:
             w = self._wacc / float(rows)
             self.window = {"loss": w[0], "lm_loss": w[1], "kl": w[2], "rows": rows}
+            if self.ul_weight > 0.0:
+                self.window["ul"] = w[3]
         self._end_window()
 
     def _end_window(self):
@@ -389,7 +431,8 @@ class MMTGTrainer:
         """Forward + MyLoss (+ KL) of one validation batch, no update: the stage's row filter, the engine's forward in eval mode (no
         dropout) with compute-dtype logits -- no fp32 [B, T, V] tensor, no autograd boundary -- and the loss kernels.  Returns the
         DEVICE scalars {'loss': MyLoss mean, 'kl': kl, 'total': loss + alpha * kl} (no host sync), or None when the filter leaves
-        no rows (train.py:252-253 `continue`s)."""
+        no rows (train.py:252-253 `continue`s).  With ul_weight > 0 also 'ul', the unweighted unlikelihood term of the batch; 'total'
+        stays the reference's validation loss."""
         eng = self.eng
         if filter_rows and stage in (1, 2):
             idx = curriculum_filter(batch["rating_host"] if "rating_host" in batch else batch["rating"], stage)
@@ -401,7 +444,10 @@ class MMTGTrainer:
         eng.forward(batch, train_flag=True, training=False, logits_f32=_LOGITS_F32)
         sc = eng.loss(batch["rating"], stage)
         loss, kl = sc[0], eng.act["kl"][0]
-        return {"loss": loss, "kl": kl, "total": loss + self.alpha * kl}
+        out = {"loss": loss, "kl": kl, "total": loss + self.alpha * kl}
+        if self.ul_weight > 0.0:
+            out["ul"] = eng.ul_loss()[0]
+        return out
 
     @torch.no_grad()
     def evaluate(self, valid_batches, stage=3, averaged=False):
