@@ -372,6 +372,43 @@ MMTG_API int mmtg_loss_bwd_ul_x3(const float* logits, long ldl, int V, const lon
                         const long long* exclude, int n_exclude, int B, int P, int L, void* planes, long ldd, long plane,
                         int Vpad, void* stream);
 
+/* ---------------------------------------------------------------- contrastive token loss on the last-layer states
+ * The training-time counterpart of contrastive search (mmtg_decode_contrastive_sim reads the cosines between last-layer states;
+ * this term shapes them): the margin loss of SimCTG (Su et al., 2022) on the output of ln_f, the operand of the LM head.
+ * Opt-in: MMTGTrainer(cl_weight=..., cl_margin=...).
+ *
+ * Notation as above: P topic columns, L lyric columns, Tt = P + L, row m = b * Tt + t.  hf [M, D] is the output of ln_f (storage
+ * type `dtype`, row stride ldh), keep the forward's int32 [B, Tt] attention mask (row stride ldkeep), rho the margin in (0, 1].
+ *
+ *   positions   I_b = { t in [P, Tt) : keep[b, t] != 0 },  n_b = |I_b|: the context mmtg_decode_contrastive_sim compares against --
+ *               lyric columns, [#START#] / [#EOS#] included, PAD excluded, topic columns never.
+ *   unit vector r_i = ||hf[b, i, :]||_2 in fp32 over the values as stored (widened exactly), rinv_i = 1 / r_i;
+ *               u_i = h_i * rinv_i, the zero vector (rinv_i = 0) when r_i = 0.
+ *   cosine      s_ij = (h_i . h_j) * (rinv_i * rinv_j): the dot accumulated in fp32 in one fixed k order, the two reciprocals
+ *               multiplied first, so s_ij and s_ji are the same bits; s_ii is taken as exactly 1 and never computed.
+ *   pair term   l_ij = max(0, rho - 1 + s_ij) for i != j in I_b;  activity a_ij = [rho - 1 + s_ij > 0] (strict).
+ *   row         cl_row[m] = sum over j != i of l_ij  (0 on rows outside I_b)
+ *   sample      cl_sample[b] = sum over i of cl_row / (n_b (n_b - 1))  (0 when n_b < 2)
+ *   batch       cl = sum_b cl_sample[b] / batch_den   (every sample takes part whatever its rating, as in the unlikelihood term)
+ *               The normalisation is PER SAMPLE, not SimCTG's batch-global pair count: a window of micro-batches, and a
+ *               data-parallel shard, then equal the big batch.
+ *   objective   MyLoss + alpha * KL (+ lm_weight * LM) (+ ul_weight * ul) + cl_weight * cl
+ *   gradient    with c = cl_weight * gscale / batch_den (the `coef` argument):
+ *               g_i = (2 / (n_b (n_b - 1))) * sum over j != i of a_ij u_j      (the 2: a_ij == a_ji, by the cosine's definition)
+ *               d(hf)[m, :] += c * (g_i - (g_i . u_i) u_i) * rinv_i
+ *               Rows outside I_b and rows with r_i = 0 keep their d(hf) bits.  The increment is formed at fp32 accuracy (u_j in
+ *               fp32, the a x U product on the fp32 matrix cores in every storage form) and rounded once, when it is added.
+ * All sums run in a fixed order and nothing is accumulated with atomics: equal inputs give equal bits.                       */
+#define MMTG_CL_MAX_L 1024     /* lyric columns; a larger L is refused */
+#define MMTG_CL_MAX_D 1024     /* D must be a multiple of 32 up to this (GPT-2-medium) */
+/* Forward.  Outputs (f32): rinv[M] (0 outside I_b and on zero rows), cl_row[M], cl_sample[B], cl[1].  hf rows 16-byte aligned. */
+MMTG_API int mmtg_cl_fwd(int dtype, const void* hf, long ldh, const int* keep, long ldkeep, float margin, int B, int P, int L, int D,
+                     float batch_den, float* rinv, float* cl_row, float* cl_sample, float* cl, void* stream);
+/* Backward: adds the increment into dhf IN PLACE (storage type out_dtype, row stride ldd; f32 -> f32, bf16 -> bf16 and
+ * f32 -> bf16).  rinv from mmtg_cl_fwd on the same hf and keep; coef finite and >= 0 (0: no launch, the bits stay).          */
+MMTG_API int mmtg_cl_bwd(int dtype, int out_dtype, const void* hf, long ldh, const int* keep, long ldkeep, const float* rinv,
+                     float margin, float coef, int B, int P, int L, int D, void* dhf, long ldd, void* stream);
+
 /* ---------------------------------------------------------------- encoder / fuser pieces
  * GRU cell (nn.GRU math, model.py:78-79): gi (row stride ld_gi), gh (row stride ld_gh >= 3H, or 0 = one
  * [3H] row for every b: at step 0, h_prev = 0, the recurrent product is just b_hh)

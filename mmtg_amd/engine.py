@@ -1025,6 +1025,35 @@ class Engine:
         hip.loss_bwd_ul(*args, dl, Vp, Vp, lm_coef=lm_coef)
         return dl
 
+    # ---- contrastive token loss on the last-layer states (the rule: include/mmtg_hip.h; MMTGTrainer(cl_weight=...))
+    def cl_loss(self, margin, batch_den=None):
+        """The term on the forward's ln_f output and keep mask: the device scalar cl [1]; also fills the row reciprocals that
+        backward(cl_coef=...) reads.  The bf16 and f32 modes pass hf as it is; the x3 modes join its (hi | lo) planes into an fp32
+        [M, D] buffer first (hi + lo is exact in fp32: two casts and one axpy_f32) and run the f32 form."""
+        a, sh = self.act, self.sh
+        B, L, M, D = a["B"], a["L"], a["M"], sh.D
+        hf = a["hf"]
+        if isinstance(hf, hip.Planes):
+            h32 = self.buf("cl_hf32", (M, D), torch.float32)
+            lo = self.buf("cl_lo32", (M, D), torch.float32)
+            hip.cast_to_f32(hf.t[0], h32, M * D)
+            hip.cast_to_f32(hf.t[1], lo, M * D)
+            hip.axpy_f32(h32, lo, 1.0, M * D)
+            hf = h32
+        rinv = self.buf("cl_rinv", (M,), torch.float32)
+        row = self.buf("cl_row", (M,), torch.float32)
+        smp = self.buf("cl_sample", (B,), torch.float32)
+        cl = self.buf("cl_scalar", (1,), torch.float32)
+        hip.cl_fwd(hf, D, a["keep"], sh.P + L, margin, B, sh.P, L, D, float(B if batch_den is None else batch_den), rinv, row, smp, cl)
+        a.update(cl_hf=hf, cl_rinv=rinv, cl_row=row, cl_sample=smp, cl=cl, cl_margin=float(margin))
+        return cl
+
+    def _cl_record(self, a, cl_coef, cl_margin):
+        """What _backward_decoder hands to hip.cl_bwd: (hf as cl_loss read it, rinv, margin, coef)."""
+        if "cl_rinv" not in a:
+            raise RuntimeError("backward(cl_coef > 0) needs cl_loss() on this forward")
+        return (a["cl_hf"], a["cl_rinv"], a["cl_margin"] if cl_margin is None else float(cl_margin), float(cl_coef))
+
     def dlogits_from(self, g32):
         """External d(logits) [B,T,V] fp32 (drop-in autograd path) -> padded compute-dtype buffer."""
         a = self.act
@@ -1114,7 +1143,7 @@ class Engine:
         finally:
             self.dtype, self.tdt, self.x3, self.wc, self.wt, self.wte_t = saved
 
-    def _backward_hybrid(self, dlogits, dkl):
+    def _backward_hybrid(self, dlogits, dkl, cl=None):
         """compute_dtype "bf16x3f": d(logits) through the decoder as ONE bf16 pass per product -- the bf16 mode's kernels over the hi
         planes the split-precision forward stored (LayerNorm outputs, qkv, attention context, GELU output, projector activations),
         the bf16 copies of the LayerNorm inputs and of the c_fc pre-activation it wrote beside them, and the hi planes of the
@@ -1144,7 +1173,7 @@ class Engine:
         try:
             with self._as_bf16():
                 self.act = ab
-                seg = self._backward_decoder(ab, dlogits)
+                seg = self._backward_decoder(ab, dlogits, cl)
         finally:
             self.act = a
         # the encoder / fuser backward on the bf16 kernels too (the mode's gradients are bf16-accurate by contract): bf16 copies of
@@ -1177,10 +1206,13 @@ class Engine:
         ae["enc"] = enc
         return ae
 
-    def backward(self, dlogits, dkl=0.0):
+    def backward(self, dlogits, dkl=0.0, cl_coef=0.0, cl_margin=None):
         """Back-propagate d(logits) [M,Vpad] (compute dtype) and d(kl) through the whole
-        model; parameter gradients are ACCUMULATED into the flat fp32 buffer."""
+        model; parameter gradients are ACCUMULATED into the flat fp32 buffer.
+        cl_coef > 0 (after cl_loss() on this forward): cl_coef * d(sum_b cl_sample)/d(hf) is added to d(ln_f output) between the LM
+        head and ln_f's backward, cl_coef = cl_weight * gscale / batch_den; cl_margin: None = the margin cl_loss() used."""
         a = self.act
+        cl = self._cl_record(a, cl_coef, cl_margin) if cl_coef > 0.0 else None
         self.ensure_grad()
         # (nothing of an earlier backward that raised may reach this one: its queued column sums hold raw pointers)
         self._sums, self._defer, self._tail_jobs = [], False, []
@@ -1190,9 +1222,9 @@ class Engine:
                 self.grad.zero_()
                 self._lazy = None
             if self.hybrid and a.get("x3"):
-                self._backward_hybrid(dlogits, dkl)
+                self._backward_hybrid(dlogits, dkl, cl)
             else:
-                self._backward_encoder(a, self._backward_decoder(a, dlogits), dkl)
+                self._backward_encoder(a, self._backward_decoder(a, dlogits, cl), dkl)
         finally:
             # (on the way out of an exception too: a window of micro-batches would otherwise accumulate on top of what is left)
             if self._tail_side is not None:         # the weight gradients that ran beside the tail: final before anything reads the gradient
@@ -1201,10 +1233,14 @@ class Engine:
             self._sums, self._defer, self._tail_jobs = [], False, []
             self._lazy = None
 
-    def _backward_decoder(self, a, dlogits):
+    def _backward_decoder(self, a, dlogits, cl=None):
         """LM head -> GPT-2 blocks -> input embedding -> projector; returns the per-segment sums of d(h1_pre) [B*S, H] that the
-        experience vectors' gradient is made of."""
+        experience vectors' gradient is made of.  cl: backward()'s record of the contrastive term, or None."""
         dhf = self._bwd_lm_head(a, dlogits)
+        if cl is not None:
+            # (the LM head's side-stream weight gradient reads dlogits and hf only: d_hf is this stream's own)
+            hf, rinv, margin, coef = cl
+            hip.cl_bwd(hf, self.sh.D, a["keep"], self.sh.P + a["L"], rinv, margin, coef, a["B"], self.sh.P, a["L"], self.sh.D, dhf, self.sh.D)
         dx = self._bwd_blocks(a, dhf)
         # (deferred column sums: everything the blocks queued since the last hand-over point -- the whole decoder's without a bucket hook --
         #  in one launch, here, with the embedding / projector / encoder backward still to come behind it)

@@ -65,6 +65,8 @@ _SIGS = {
     "mmtg_loss_ul_fwd": ([_i, _vp, _l, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp], _i),
     "mmtg_loss_bwd_ul": ([_i, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _f, _vp, _i, _i, _i, _i, _vp, _l, _i, _vp], _i),
     "mmtg_loss_bwd_ul_x3": ([_vp, _l, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _f, _vp, _i, _i, _i, _i, _vp, _l, _l, _i, _vp], _i),
+    "mmtg_cl_fwd": ([_i, _vp, _l, _vp, _l, _f, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp], _i),
+    "mmtg_cl_bwd": ([_i, _i, _vp, _l, _vp, _l, _vp, _f, _f, _i, _i, _i, _i, _vp, _l, _vp], _i),
     "mmtg_gru_cell_fwd": ([_i, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _vp], _i),
     "mmtg_gru_cell_bwd_fused": ([_i, _vp, _l, _vp, _vp, _i, _vp, _vp, _l, _vp, _l, _vp, _vp, _i, _i, _vp], _i),
     "mmtg_rnn_cell_fwd": ([_i, _i, _vp, _l, _vp, _l, _vp, _vp, _l, _vp, _vp, _i, _i, _vp], _i),
@@ -662,6 +664,23 @@ def loss_bwd_ul_x3(logits, ldl, V, topic_ids, targets, lse, coef, gscale, ul_S, 
     _check(lib().mmtg_loss_bwd_ul_x3(_p(logits), ldl, V, _p(topic_ids), _p(targets), _p(lse), _p(coef), float(gscale), float(lm_coef),
                                      _p(ul_S), float(ul_coef), _p(exclude), _n_ex(exclude), B, P, L,
                                      _p(planes.t), planes.ld, planes.plane, Vpad, _stream()), "loss_bwd_ul_x3")
+
+
+# contrastive token loss on the last-layer states (the rule: include/mmtg_hip.h)
+CL_MAX_L, CL_MAX_D = 1024, 1024
+
+
+def cl_fwd(hf, ldh, keep, ldkeep, margin, B, P, L, D, batch_den, rinv, cl_row, cl_sample, cl):
+    """rinv [M], cl_row [M], cl_sample [B] and the scalar cl [1] from hf [M, D] (fp32 or bf16, row stride ldh) and the int32 keep
+    mask [B, P + L]."""
+    _check(lib().mmtg_cl_fwd(dt(hf), _p(hf), ldh, _p(keep), ldkeep, float(margin), B, P, L, D, float(batch_den),
+                             _p(rinv), _p(cl_row), _p(cl_sample), _p(cl), _stream()), "cl_fwd")
+
+
+def cl_bwd(hf, ldh, keep, ldkeep, rinv, margin, coef, B, P, L, D, dhf, ldd):
+    """dhf += coef * d(sum_b cl_sample)/d hf in place (rinv from cl_fwd); dhf fp32 or bf16, bf16 hf goes with bf16 dhf."""
+    _check(lib().mmtg_cl_bwd(dt(hf), dt(dhf), _p(hf), ldh, _p(keep), ldkeep, _p(rinv), float(margin), float(coef), B, P, L, D,
+                             _p(dhf), ldd, _stream()), "cl_bwd")
 
 
 # ------------------------------------------------------------------ encoder pieces

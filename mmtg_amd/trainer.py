@@ -47,8 +47,15 @@ class MMTGTrainer:
     def __init__(self, model, lr=1e-5, alpha=0.0, max_norm=1.0, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.0, warmup_steps=0, total_steps=None, distributed=False, bucket_mb=64.0,
                  lm_weight=0.0, param_groups=None, accumulation_steps=1, ema_decay=None, ema_warmup=True,
-                 ul_weight=0.0, ul_exclude_ids=None):
-        """ul_weight: weight of the token-level unlikelihood term on repeated lyric tokens (Welleck et al., 2019; the rule is stated
+                 ul_weight=0.0, ul_exclude_ids=None, cl_weight=0.0, cl_margin=0.5):
+        """cl_weight: weight of the contrastive token loss on the last-layer states (SimCTG, Su et al., 2022; the rule is stated in
+        include/mmtg_hip.h): within one sample the ln_f outputs of different kept lyric positions are pushed apart until their cosine
+        is below 1 - cl_margin, which is what generate_contrastive's degeneration penalty reads.  The objective becomes
+        ... + cl_weight * cl, normalised per sample (not by SimCTG's batch-global pair count), so a window of micro-batches and a
+        data-parallel shard equal the big batch.  0.0 (the default) runs exactly the launches it always did; > 0 adds two entries
+        (mmtg_cl_fwd after the loss, mmtg_cl_bwd between the LM head's backward and ln_f's).  cl_margin: a float in (0, 1], the paper's
+        rho.  Only the fused step takes the term.
+        ul_weight: weight of the token-level unlikelihood term on repeated lyric tokens (Welleck et al., 2019; the rule is stated
         in include/mmtg_hip.h): at every lyric position the characters the lyric has already used are pushed down, so the objective
         becomes MyLoss + alpha * KL (+ lm_weight * LM) + ul_weight * ul.  0.0 (the default) is the reference's objective and runs
         exactly the launches it always did; > 0 adds two small launches and replaces the d(logits) kernel by the one that carries the
@@ -82,6 +89,11 @@ class MMTGTrainer:
         if len(ul_exclude_ids) > 32 or any(type(i) is not int or i < 0 for i in ul_exclude_ids):
             raise ValueError("ul_exclude_ids must be None or a sequence of at most 32 non-negative ints, got %r" % (ul_exclude_ids,))
         self.ul_weight, self.ul_exclude_ids = float(ul_weight), ul_exclude_ids
+        if isinstance(cl_weight, bool) or not isinstance(cl_weight, (int, float)) or not (0.0 <= cl_weight < float("inf")):
+            raise ValueError("cl_weight must be a finite float >= 0, got %r" % (cl_weight,))
+        if isinstance(cl_margin, bool) or not isinstance(cl_margin, (int, float)) or not (0.0 < cl_margin <= 1.0):
+            raise ValueError("cl_margin must be a float in (0, 1], got %r" % (cl_margin,))
+        self.cl_weight, self.cl_margin = float(cl_weight), float(cl_margin)
         self.accumulation_steps = accumulation_steps
         self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
         self.ema_updates = 0                    # updates of the average made so far
@@ -156,11 +168,12 @@ class MMTGTrainer:
                             "total_steps": self.total, "lm_weight": self.lm_weight, "accumulation_steps": self.accumulation_steps,
                             "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup,
                             "ul_weight": self.ul_weight, "ul_exclude_ids": tuple(self.ul_exclude_ids),
+                            "cl_weight": self.cl_weight, "cl_margin": self.cl_margin,
                             # for the record, like the rest: load_state_dict keeps the trainer's own groups as it keeps its own lr
                             "param_groups": None if self.group_plan is None else copy.deepcopy(self.group_plan.specs)}}
 
     def load_state_dict(self, sd):
-        """(accumulation_steps, ul_weight and ul_exclude_ids stay the trainer's own, like lr and the groups; an open window is abandoned)
+        """(accumulation_steps, ul_weight, ul_exclude_ids, cl_weight and cl_margin stay the trainer's own, like lr and the groups; an open window is abandoned)
         A trainer with an average takes 'average' and 'updates' from the dict; from a dict without an average (an older
         checkpoint, a run that kept none) the average is dropped and restarts from the loaded weights at the next step.  The decay
         and the warm-up rule stay the trainer's own; a trainer without an average ignores the key."""
@@ -190,7 +203,7 @@ class MMTGTrainer:
 
     def step(self, batch, stage=3, filter_rows=True):
         """One optimisation step; returns device scalars (no host sync) {'loss','lm_loss','kl'} of the LOCAL rows (with ul_weight > 0
-        also 'ul', the unweighted unlikelihood term).
+        also 'ul', the unweighted unlikelihood term; with cl_weight > 0 also 'cl', the unweighted contrastive term).
         Returns None when the stage filter leaves no rows on a single rank (train.py:184-185); in a data-parallel
         group a rank without rows still takes part in the exchange and in the (identical) optimizer step.
 
@@ -334,8 +347,14 @@ class MMTGTrainer:
                 # (before the closing backward the packs are not final; without a hook those backwards overlap their tail, _WGRAD_TAIL)
                 eng.bucket_hook = self._hook if closing else None
             eng.wgrad_overwrite = first     # gradients were zeroed above and every weight is written once
+            if self.cl_weight > 0.0:
+                # (every row of the batch takes part; the coefficient cl_weight * gscale / batch_den with gscale = batch_den = n_local)
+                cl = eng.cl_loss(self.cl_margin, batch_den=n_local)
             try:
-                eng.backward(dl, dkl=self.alpha * n_local)
+                if self.cl_weight > 0.0:
+                    eng.backward(dl, dkl=self.alpha * n_local, cl_coef=self.cl_weight)
+                else:
+                    eng.backward(dl, dkl=self.alpha * n_local)
                 if first:
                     eng._finish_overwrite_record()
             finally:
@@ -345,6 +364,8 @@ class MMTGTrainer:
             out = {"loss": sc[0], "lm_loss": sc[1], "kl": eng.act["kl"][0]}
             if self.ul_weight > 0.0:
                 out["ul"] = ul[0]
+            if self.cl_weight > 0.0:
+                out["cl"] = cl[0]
             self._add_to_window(out, sc, n_local)
         self._rows = rows
         if closing:
@@ -357,17 +378,22 @@ class MMTGTrainer:
             self._wacc = out        # the step's own scalars: no launch that today's step does not have
             return
         if self._wacc is None:
-            self._wacc = torch.empty(4 if self.ul_weight > 0.0 else 3, device=sc.device, dtype=torch.float32)
+            # (slot 3 is 'ul', slot 4 'cl'; a slot whose term is off is neither written nor read)
+            self._wacc = torch.empty(5 if self.cl_weight > 0.0 else 4 if self.ul_weight > 0.0 else 3, device=sc.device, dtype=torch.float32)
         if self._rows == 0:         # the window's first rows
             torch.mul(sc[:2], float(n), out=self._wacc[:2])
             torch.mul(out["kl"].reshape(1), float(n), out=self._wacc[2:3])
             if "ul" in out:
-                torch.mul(out["ul"].reshape(1), float(n), out=self._wacc[3:])
+                torch.mul(out["ul"].reshape(1), float(n), out=self._wacc[3:4])
+            if "cl" in out:
+                torch.mul(out["cl"].reshape(1), float(n), out=self._wacc[4:5])
         else:
             self._wacc[:2].add_(sc[:2], alpha=float(n))
             self._wacc[2:3].add_(out["kl"].reshape(1), alpha=float(n))
             if "ul" in out:
-                self._wacc[3:].add_(out["ul"].reshape(1), alpha=float(n))
+                self._wacc[3:4].add_(out["ul"].reshape(1), alpha=float(n))
+            if "cl" in out:
+                self._wacc[4:5].add_(out["cl"].reshape(1), alpha=float(n))
 
     def _close_begin(self, red, rows):
         """The closing call's part BEFORE its backward: the window's row count onto the device and into the exchange.  False when
@@ -412,6 +438,8 @@ class MMTGTrainer:
             self.window = {"loss": None, "lm_loss": None, "kl": None, "rows": 0}
             if self.ul_weight > 0.0:
                 self.window["ul"] = None
+            if self.cl_weight > 0.0:
+                self.window["cl"] = None
         elif self.accumulation_steps == 1:
             self.window = dict(self._wacc, rows=rows)
         else:
@@ -419,6 +447,8 @@ class MMTGTrainer:
             self.window = {"loss": w[0], "lm_loss": w[1], "kl": w[2], "rows": rows}
             if self.ul_weight > 0.0:
                 self.window["ul"] = w[3]
+            if self.cl_weight > 0.0:
+                self.window["cl"] = w[4]
         self._end_window()
 
     def _end_window(self):
@@ -431,7 +461,7 @@ class MMTGTrainer:
         """Forward + MyLoss (+ KL) of one validation batch, no update: the stage's row filter, the engine's forward in eval mode (no
         dropout) with compute-dtype logits -- no fp32 [B, T, V] tensor, no autograd boundary -- and the loss kernels.  Returns the
         DEVICE scalars {'loss': MyLoss mean, 'kl': kl, 'total': loss + alpha * kl} (no host sync), or None when the filter leaves
-        no rows (train.py:252-253 `continue`s).  With ul_weight > 0 also 'ul', the unweighted unlikelihood term of the batch; 'total'
+        no rows (train.py:252-253 `continue`s).  With ul_weight > 0 also 'ul', the unweighted unlikelihood term of the batch, with cl_weight > 0 also 'cl'; 'total'
         stays the reference's validation loss."""
         eng = self.eng
         if filter_rows and stage in (1, 2):
@@ -447,6 +477,8 @@ class MMTGTrainer:
         out = {"loss": loss, "kl": kl, "total": loss + self.alpha * kl}
         if self.ul_weight > 0.0:
             out["ul"] = eng.ul_loss()[0]
+        if self.cl_weight > 0.0:
+            out["cl"] = eng.cl_loss(self.cl_margin)[0]
         return out
 
     @torch.no_grad()
