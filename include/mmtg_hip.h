@@ -1182,6 +1182,46 @@ MMTG_API int mmtg_decode_guidance(const float* cond, const float* uncond, long l
                          void* stream);
 MMTG_API int mmtg_decode_mirror(long long* seq, long ldseq, const int* pos_ptr, int N, void* stream);
 
+/* ---- the training side of guidance (MMTGTrainer(experience_drop=...), evaluate_guided; csrc/guidance_train.hip).  Classifier-free
+ * guidance assumes a model that was also trained with the condition removed (Ho & Salimans, 2022); the two entries give the fused
+ * step that input and measure the guided distribution on held-out lyrics.  Additive to ABI 12.
+ * mmtg_experience_drop: one launch for both channels.  img, txt: fp32 [B, n] (n = S * E), never written; img_out, txt_out: [B, n] of
+ *   `dtype` (MMTG_F32 or MMTG_BF16); code: int32 [B].  Per sample b, with h = hash_u32(seed, b) (the counter hash of csrc/common.h:
+ *   h = b * 0x9E3779B1 + seed; h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16) compared as 64-bit values:
+ *     h < c_both -> code 3;  else h < c_img -> code 1;  else h < c_txt -> code 2;  else code 0.
+ *   Bit 0 of the code: the images are dropped; bit 1: the texts are dropped.  A dropped channel's row is +0.0 in every element; a kept
+ *   row holds the bits mmtg_cast_f32_to would write (f32 -> f32 is a copy).  No rescaling: a condition switch, not a dropout of
+ *   activations.  One hash per sample decides both channels, so the three events are disjoint; equal inputs give equal bits.  The
+ *   thresholds are cumulative, c_both <= c_img <= c_txt <= 2^32; the host computes each probability's share in float64 as
+ *   min(int(p * 2^32), 2^32) and accumulates: p = 1 drops every row, p = 0 none.  Rows with n % 4 == 0 on 16-byte aligned bases
+ *   move as 16-byte loads, all others one element at a time.
+ *   Fails before any device call: a null pointer, B < 1, n < 1, thresholds negative, not monotone or above 2^32, an unknown dtype,
+ *   an output overlapping an input.
+ * mmtg_guided_loss: the cross-entropy of the lyric under softmax(lu + s_k (lc - lu)) for K scales in one sweep.  cond, uncond: the
+ *   logits [M, ldl] of `logits_dtype` (fp32, or bf16 widened to fp32 first: exact), M = B (P + L), columns >= V ignored; lse_c, lse_u:
+ *   each matrix's fp32 row log-sum-exp [M] as mmtg_loss_fwd produced it; scales: a HOST array of K floats, 1 <= K <=
+ *   MMTG_GUIDED_MAX_SCALES, each finite and >= 0, read before the launch and passed by value.  Rows and labels are those of
+ *   mmtg_loss_fwd's sample_ce: the loss rows P <= t <= T - 2 of each sample (T = P + L, ntok = T - 1 - P), the label
+ *   cat(topic_ids, targets)[b, t + 1] clamped into [0, V) -- always an element of targets, so topic_ids is never read and may be
+ *   null; PAD rows are included, as the reference's loss includes them.  In fp32 and in mmtg_decode_guidance's order:
+ *     lc = c[v] - lse_c[m]      lu = u[v] - lse_u[m]      g_k[v] = lu + s_k * (lc - lu)
+ *     nll_k[m] = L(g_k) - g_k[label],   L(x) = max x + log(sum_v exp(x[v] - max x))
+ *   (the exponentials are v_exp_f32 in both storage forms, the one log per row and scale is logf).  Outputs, all fp32:
+ *   nll [K, M] (0 outside the loss rows), sample_ce [K, B] = (1 / ntok) * the sum of the sample's loss rows, ce [K] = sum_b
+ *   sample_ce[k, b] / batch_den.  One workgroup of 256 threads per row; every logit is fetched once (16-byte aligned rows in slices
+ *   of eight, the tail and unaligned fp32 rows one logit at a time: an fp32 ldl may be odd) and feeds the K running (max, sum)
+ *   pairs; nothing is staged, so V and L have no limit.  Wave shuffles and static LDS words reduce in a fixed order, one wave sums
+ *   a sample's rows and one thread a scale's samples in sample order: no atomics, equal inputs give equal bits.  Where c == u bit
+ *   for bit and lse_c == lse_u, g_k = lu for every k and all K results of the row are the same bits.
+ *   Fails before any device call: a null pointer (topic_ids excepted), K outside 1 .. 8, a scale that is not finite or is negative,
+ *   V < 1, ldl < V, bf16 rows that are not 16-byte aligned (ldl % 8, the bases), B < 1, P < 0, L < 2, batch_den not finite or <= 0. */
+#define MMTG_GUIDED_MAX_SCALES 8
+MMTG_API int mmtg_experience_drop(int dtype, const float* img, const float* txt, void* img_out, void* txt_out, int* code, int B, long n,
+                         unsigned seed, long long c_both, long long c_img, long long c_txt, void* stream);
+MMTG_API int mmtg_guided_loss(int logits_dtype, const void* cond, const void* uncond, long ldl, int V, const float* lse_c,
+                     const float* lse_u, const long long* topic_ids, const long long* targets, const float* scales, int K,
+                     int B, int P, int L, float batch_den, float* nll, float* sample_ce, float* ce, void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

@@ -290,6 +290,9 @@ def mix_seed(seed, site):
     return (x ^ (x >> 16)) & 0xFFFFFFFF
 
 
+EXP_DROP_SITE = 0x2000     # the experience dropout's site: the RNN layers use 0x1000 + 64 site + l (< 0x1100), the blocks 3 l + 1 .. 3
+
+
 def initial_drop_seed(rank=0):
     """Start of the dropout counter: a hash of torch's seed (train.py:88-94 seeds torch) and the data-parallel rank,
     so replicas draw independent masks (the reference's DataParallel replicas do) and torch.manual_seed controls
@@ -698,10 +701,13 @@ class Engine:
         return layers
 
     def forward(self, batch, train_flag=True, training=False, per_row_infer=True, need_logits=True, logits_f32=True,
-                encode_only=False):
+                encode_only=False, exp_drop=None):
         """MMTG.forward (model.py:356-400).  Returns dict(logits_pad [M,Vpad] f32, B, T, ...);
         lm_loss / kl are device scalars in self.scalars after loss().  need_logits=False stops after the last block's c_attn (no ln_f, no
-        LM head: the decoder's prompt prefill reads the blocks' K / V rows only); encode_only=True stops after the fuser."""
+        LM head: the decoder's prompt prefill reads the blocks' K / V rows only); encode_only=True stops after the fuser.
+        exp_drop: None or (p_both, p_img, p_txt), the probabilities with which a sample's images and texts, its images alone or its
+        texts alone are replaced by zeros (mmtg_experience_drop: what generate.without_experience feeds the decoders); it acts
+        whenever it is given and not all zero, whatever `training` says, and leaves the int32 codes in act["exp_drop"]."""
         sh = self.sh
         if self.table is None:
             raise RuntimeError("no WenLan token table set (vocab/token_id2emb_dict.pkl or set_token_table())")
@@ -731,8 +737,17 @@ class Engine:
 
         # ---------------- encoder: topic_fc + 2 GRUs (model.py:63-81) + ln_layer1..3 (:380-382)
         xt = self._cast_in(batch["topic_emb"], "xt")
-        xi = self._cast_in(img, "xi").view(B * S, E)
-        xr = self._cast_in(batch["r_embs"], "xr").view(B * S, E)
+        if exp_drop is not None and any(p > 0.0 for p in exp_drop):
+            # one launch casts both channels and zeroes the dropped samples' rows; always into the engine's own buffers (the f32
+            # modes pass the caller's tensors on otherwise).  The backward needs nothing: the layer records keep these as `inp`.
+            src_i = img.to(self.dev, torch.float32).contiguous()
+            src_r = batch["r_embs"].to(self.dev, torch.float32).contiguous()
+            xi, xr = self.buf("xi", (B * S, E)), self.buf("xr", (B * S, E))
+            a["exp_drop"] = self.buf("exp_drop_code", (B,), torch.int32)
+            hip.experience_drop(src_i, src_r, xi, xr, a["exp_drop"], B, S * E, mix_seed(seed, EXP_DROP_SITE), hip.drop_thresholds(exp_drop))
+        else:
+            xi = self._cast_in(img, "xi").view(B * S, E)
+            xr = self._cast_in(batch["r_embs"], "xr").view(B * S, E)
         t_raw = self.buf("t_raw", (B, H))
         self._fwd(xt, "encoder.topic_fc.weight", t_raw, B, "linear", bias=self.P("encoder.topic_fc.bias"))
         t_ln = self.buf("t_ln", (B, H))
@@ -962,7 +977,7 @@ class Engine:
         r = None if ratings is None else ratings.to(self.dev, torch.long).contiguous()
         hip.loss_fwd(a["logits"], self.layout.Vpad, sh.V, a["topic_ids"], a["targets"], r, stage, label_zero,
                      B, sh.P, L, float(B if batch_den is None else batch_den), nll, lse, ce, coef, sc)
-        a.update(nll=nll, lse_rows=lse, coef=coef, scalars=sc)
+        a.update(nll=nll, lse_rows=lse, sample_ce=ce, coef=coef, scalars=sc)
         return sc
 
     def loss_backward(self, gscale=1.0, lm_coef=0.0):
@@ -1053,6 +1068,27 @@ class Engine:
         if "cl_rinv" not in a:
             raise RuntimeError("backward(cl_coef > 0) needs cl_loss() on this forward")
         return (a["cl_hf"], a["cl_rinv"], a["cl_margin"] if cl_margin is None else float(cl_margin), float(cl_coef))
+
+    # ---- the guided validation loss (the rule: include/mmtg_hip.h; MMTGTrainer.evaluate_guided)
+    def guided_loss(self, scales, uncond_logits, uncond_lse, batch_den=None):
+        """After forward() and loss() on the conditional batch: the cross-entropy of the lyric under softmax(lu + s (lc - lu)) for the
+        K <= 8 scales, with the unconditional branch's logits [M, Vpad] (the storage type of this forward's, a buffer of the caller's
+        own: the engine's were overwritten by this forward) and their row lse [M].  Returns the device tensor ce [K]; nll [K, M] and
+        sample_ce [K, B] are recorded in act."""
+        a, sh = self.act, self.sh
+        B, L, M, K = a["B"], a["L"], a["M"], len(scales)
+        if "lse_rows" not in a:
+            raise RuntimeError("guided_loss() needs loss() on this forward (it reads the row lse)")
+        lg = a["logits"]
+        if uncond_logits.dtype != lg.dtype or uncond_logits.numel() != lg.numel() or uncond_lse.numel() != M:
+            raise ValueError("guided_loss: the unconditional logits and lse must have the conditional forward's type and shape")
+        nll = self.buf("guided_nll", (K, M), torch.float32)
+        smp = self.buf("guided_sample_ce", (K, B), torch.float32)
+        ce = self.buf("guided_ce", (K,), torch.float32)
+        hip.guided_loss(lg, uncond_logits, self.layout.Vpad, sh.V, a["lse_rows"], uncond_lse, a["topic_ids"], a["targets"], scales,
+                        B, sh.P, L, float(B if batch_den is None else batch_den), nll, smp, ce)
+        a.update(guided_nll=nll, guided_sample_ce=smp, guided_ce=ce)
+        return ce
 
     def dlogits_from(self, g32):
         """External d(logits) [B,T,V] fp32 (drop-in autograd path) -> padded compute-dtype buffer."""

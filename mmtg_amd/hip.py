@@ -168,6 +168,8 @@ _SIGS = {
                                       _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "mmtg_decode_gumbel_merge": ([_vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp], _i),
     "mmtg_decode_guidance": ([_vp, _vp, _l, _i, _f, _vp, _l, _i, _vp], _i),
+    "mmtg_experience_drop": ([_i, _vp, _vp, _vp, _vp, _vp, _i, _l, _u, C.c_longlong, C.c_longlong, C.c_longlong, _vp], _i),
+    "mmtg_guided_loss": ([_i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp], _i),
     "mmtg_decode_mirror": ([_vp, _l, _vp, _i, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
     "mmtg_decode_mlp_sync_words": ([], _i),
@@ -1459,6 +1461,42 @@ def decode_mirror(seq, pos, N):
     if seq.dtype != torch.long or seq.dim() != 2 or seq.stride(1) != 1 or seq.shape[0] < 2 * N:
         raise ValueError("seq must be int64 [>= 2 N, ld] with unit column stride")
     _check(lib().mmtg_decode_mirror(_p(seq), seq.stride(0), _p(pos), int(N), _stream()), "decode_mirror")
+
+
+# the training side of guidance (the rules: include/mmtg_hip.h; csrc/guidance_train.hip)
+GUIDED_MAX_SCALES = 8
+
+
+def drop_thresholds(probs):
+    """(p_both, p_img, p_txt) -> the cumulative 64-bit thresholds (c_both, c_img, c_txt) of mmtg_experience_drop: each share is
+    min(int(p * 2**32), 2**32) in float64, accumulated."""
+    out, acc = [], 0
+    for p in probs:
+        acc += min(int(float(p) * 4294967296.0), 4294967296)
+        out.append(acc)
+    return tuple(out)
+
+
+def experience_drop(img, txt, img_out, txt_out, code, B, n, seed, thresholds):
+    """img_out / txt_out [B, n] (fp32 or bf16) = img / txt (fp32, never written) with the rows of dropped samples +0.0; code int32 [B]
+    (bit 0: images dropped, bit 1: texts dropped).  thresholds: (c_both, c_img, c_txt) as drop_thresholds gives them."""
+    if img.dtype != torch.float32 or txt.dtype != torch.float32 or code.dtype != torch.int32 or img_out.dtype != txt_out.dtype:
+        raise ValueError("img and txt must be fp32, code int32, img_out and txt_out of one dtype")
+    c_both, c_img, c_txt = (int(c) for c in thresholds)
+    _check(lib().mmtg_experience_drop(dt(img_out), _p(img), _p(txt), _p(img_out), _p(txt_out), _p(code), int(B), int(n),
+                                      int(seed) & 0xFFFFFFFF, c_both, c_img, c_txt, _stream()), "experience_drop")
+
+
+def guided_loss(cond, uncond, ldl, V, lse_c, lse_u, topic_ids, targets, scales, B, P, L, batch_den, nll, sample_ce, ce):
+    """nll [K, M], sample_ce [K, B] and ce [K] (fp32): the cross-entropy of the lyric under softmax(lu + s_k (lc - lu)) for the K <= 8
+    host floats `scales`, from the two logits matrices (one storage type, row stride ldl) and their row lse of loss_fwd."""
+    if cond.dtype != uncond.dtype:
+        raise ValueError("cond and uncond must have one storage type")
+    K = len(scales)
+    arr = (C.c_float * max(K, 1))(*[float(s) for s in scales])
+    _check(lib().mmtg_guided_loss(dt(cond), _p(cond), _p(uncond), int(ldl), int(V), _p(lse_c), _p(lse_u), _p(topic_ids), _p(targets),
+                                  C.addressof(arr), K, int(B), int(P), int(L), float(batch_den), _p(nll), _p(sample_ce), _p(ce),
+                                  _stream()), "guided_loss")
 
 
 def decode_advance(pos):

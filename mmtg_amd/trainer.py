@@ -42,13 +42,57 @@ def linear_schedule(step, warmup, total):
 
 _LOGITS_F32 = bool(os.environ.get("MMTG_LOGITS_F32"))     # A/B switch: fp32 logits in the bf16 trainer too
 
+NO_EXPERIENCE = (1.0, 0.0, 0.0)         # exp_drop of a forward on generate.without_experience of its batch
+
+
+def _check_scales(scales):
+    """The scales of the guided validation loss as a list of floats: 1 .. 8 of them, each as constraints.check_guidance takes it."""
+    from .constraints import check_guidance
+    from .hip import GUIDED_MAX_SCALES
+    if isinstance(scales, (str, bytes)):
+        raise ValueError("scales must be a sequence of 1 .. %d guidance scales, got %r" % (GUIDED_MAX_SCALES, scales))
+    try:
+        scales = list(scales)
+    except TypeError:
+        raise ValueError("scales must be a sequence of 1 .. %d guidance scales, got %r" % (GUIDED_MAX_SCALES, scales)) from None
+    if not 1 <= len(scales) <= GUIDED_MAX_SCALES:
+        raise ValueError("scales must hold 1 .. %d guidance scales, got %d" % (GUIDED_MAX_SCALES, len(scales)))
+    return [check_guidance(s) for s in scales]
+
+
+def _check_experience_drop(value):
+    """MMTGTrainer's experience_drop as the triple (p_both, p_img, p_txt): a float p in [0, 1] is (p, 0, 0); a sequence of three
+    floats, each in [0, 1] with a sum of at most 1, is itself.  Anything else raises a ValueError that names the argument."""
+    msg = "experience_drop must be a float in [0, 1] or three floats (p_both, p_img, p_txt) in [0, 1] with a sum <= 1, got %r" % (value,)
+    real = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and 0.0 <= v <= 1.0       # (NaN fails the comparison)
+    if real(value):
+        return (float(value), 0.0, 0.0)
+    if isinstance(value, (str, bytes, bool, int, float)) or value is None:
+        raise ValueError(msg)
+    try:
+        triple = tuple(value)
+    except TypeError:
+        raise ValueError(msg) from None
+    if len(triple) != 3 or not all(real(v) for v in triple) or sum(float(v) for v in triple) > 1.0:
+        raise ValueError(msg)
+    return tuple(float(v) for v in triple)
+
 
 class MMTGTrainer:
     def __init__(self, model, lr=1e-5, alpha=0.0, max_norm=1.0, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.0, warmup_steps=0, total_steps=None, distributed=False, bucket_mb=64.0,
                  lm_weight=0.0, param_groups=None, accumulation_steps=1, ema_decay=None, ema_warmup=True,
-                 ul_weight=0.0, ul_exclude_ids=None, cl_weight=0.0, cl_margin=0.5):
-        """cl_weight: weight of the contrastive token loss on the last-layer states (SimCTG, Su et al., 2022; the rule is stated in
+                 ul_weight=0.0, ul_exclude_ids=None, cl_weight=0.0, cl_margin=0.5, experience_drop=0.0):
+        """experience_drop: the training side of classifier-free guidance (generate_samples(guidance_scale=...), GuidedDecoder).  A
+        float p in [0, 1] replaces, per sample and with probability p, the images and texts of the experience by zeros -- exactly what
+        generate.without_experience feeds the decoders as the default negative -- so that the branch guidance subtracts is a
+        distribution the model was trained on.  A sequence (p_both, p_img, p_txt), each in [0, 1] and summing to at most 1, also drops
+        the images alone or the texts alone; the three events are disjoint (one hash per sample, mmtg_experience_drop in
+        include/mmtg_hip.h).  Applied in step() while the model is in training mode, the gate of the dropout sites; a dropped row takes
+        part in every term of the objective unchanged.  step() then also returns 'experience_drop', the int32 codes of the local rows
+        (bit 0: images dropped, bit 1: texts dropped).  0.0 (the default) launches nothing new and keeps no buffer.  Only the fused
+        step takes it.
+        cl_weight: weight of the contrastive token loss on the last-layer states (SimCTG, Su et al., 2022; the rule is stated in
         include/mmtg_hip.h): within one sample the ln_f outputs of different kept lyric positions are pushed apart until their cosine
         is below 1 - cl_margin, which is what generate_contrastive's degeneration penalty reads.  The objective becomes
         ... + cl_weight * cl, normalised per sample (not by SimCTG's batch-global pair count), so a window of micro-batches and a
@@ -94,6 +138,8 @@ class MMTGTrainer:
         if isinstance(cl_margin, bool) or not isinstance(cl_margin, (int, float)) or not (0.0 < cl_margin <= 1.0):
             raise ValueError("cl_margin must be a float in (0, 1], got %r" % (cl_margin,))
         self.cl_weight, self.cl_margin = float(cl_weight), float(cl_margin)
+        self.experience_drop = _check_experience_drop(experience_drop)
+        self._exp_drop_on = any(p > 0.0 for p in self.experience_drop)
         self.accumulation_steps = accumulation_steps
         self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
         self.ema_updates = 0                    # updates of the average made so far
@@ -168,12 +214,12 @@ class MMTGTrainer:
                             "total_steps": self.total, "lm_weight": self.lm_weight, "accumulation_steps": self.accumulation_steps,
                             "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup,
                             "ul_weight": self.ul_weight, "ul_exclude_ids": tuple(self.ul_exclude_ids),
-                            "cl_weight": self.cl_weight, "cl_margin": self.cl_margin,
+                            "cl_weight": self.cl_weight, "cl_margin": self.cl_margin, "experience_drop": self.experience_drop,
                             # for the record, like the rest: load_state_dict keeps the trainer's own groups as it keeps its own lr
                             "param_groups": None if self.group_plan is None else copy.deepcopy(self.group_plan.specs)}}
 
     def load_state_dict(self, sd):
-        """(accumulation_steps, ul_weight, ul_exclude_ids, cl_weight and cl_margin stay the trainer's own, like lr and the groups; an open window is abandoned)
+        """(accumulation_steps, ul_weight, ul_exclude_ids, cl_weight, cl_margin and experience_drop stay the trainer's own, like lr and the groups; an open window is abandoned)
         A trainer with an average takes 'average' and 'updates' from the dict; from a dict without an average (an older
         checkpoint, a run that kept none) the average is dropped and restarts from the loaded weights at the next step.  The decay
         and the warm-up rule stay the trainer's own; a trainer without an average ignores the key."""
@@ -203,7 +249,8 @@ class MMTGTrainer:
 
     def step(self, batch, stage=3, filter_rows=True):
         """One optimisation step; returns device scalars (no host sync) {'loss','lm_loss','kl'} of the LOCAL rows (with ul_weight > 0
-        also 'ul', the unweighted unlikelihood term; with cl_weight > 0 also 'cl', the unweighted contrastive term).
+        also 'ul', the unweighted unlikelihood term; with cl_weight > 0 also 'cl', the unweighted contrastive term; with
+        experience_drop on and the model in training mode also 'experience_drop', the device int32 codes of the local rows).
         Returns None when the stage filter leaves no rows on a single rank (train.py:184-185); in a data-parallel
         group a rank without rows still takes part in the exchange and in the (identical) optimizer step.
 
@@ -332,7 +379,11 @@ class MMTGTrainer:
             first = not self._bwd_ran
             if first:               # once per window: the later backwards add to what this one writes
                 eng.zero_grad((n_local, int(batch["targets"].shape[1])) if "targets" in batch else None)
-            eng.forward(batch, train_flag=True, training=self.model.training, logits_f32=_LOGITS_F32)
+            if self._exp_drop_on and self.model.training:
+                # (every micro-step draws its own codes: the step seed advances per forward)
+                eng.forward(batch, train_flag=True, training=True, logits_f32=_LOGITS_F32, exp_drop=self.experience_drop)
+            else:
+                eng.forward(batch, train_flag=True, training=self.model.training, logits_f32=_LOGITS_F32)
             sc = eng.loss(batch["rating"], stage, batch_den=n_local)
             T = eng.act["T"]
             lm_coef = self.lm_weight / (T - 1) if self.lm_weight else 0.0
@@ -367,6 +418,8 @@ class MMTGTrainer:
             if self.cl_weight > 0.0:
                 out["cl"] = cl[0]
             self._add_to_window(out, sc, n_local)
+            if "exp_drop" in eng.act:       # (not a scalar of the window: the step's own rows, valid until the next forward)
+                out = dict(out, experience_drop=eng.act["exp_drop"])
         self._rows = rows
         if closing:
             self._close_end(red)
@@ -457,21 +510,103 @@ class MMTGTrainer:
 
     # ---- evaluation (train.py:241-268)
     @torch.no_grad()
-    def evaluate_batch(self, batch, stage=3, filter_rows=True):
-        """Forward + MyLoss (+ KL) of one validation batch, no update: the stage's row filter, the engine's forward in eval mode (no
-        dropout) with compute-dtype logits -- no fp32 [B, T, V] tensor, no autograd boundary -- and the loss kernels.  Returns the
-        DEVICE scalars {'loss': MyLoss mean, 'kl': kl, 'total': loss + alpha * kl} (no host sync), or None when the filter leaves
-        no rows (train.py:252-253 `continue`s).  With ul_weight > 0 also 'ul', the unweighted unlikelihood term of the batch, with cl_weight > 0 also 'cl'; 'total'
-        stays the reference's validation loss."""
-        eng = self.eng
+    def _eval_rows(self, batch, stage, filter_rows):
+        """The stage's row filter of the evaluation passes; None when it leaves no row."""
         if filter_rows and stage in (1, 2):
             idx = curriculum_filter(batch["rating_host"] if "rating_host" in batch else batch["rating"], stage)
             batch = {k: v[idx.to(v.device, non_blocking=True)] for k, v in batch.items() if k != "rating_host"}
         elif "rating_host" in batch:
             batch = {k: v for k, v in batch.items() if k != "rating_host"}
-        if int(batch["rating"].shape[0]) == 0:
+        return None if int(batch["rating"].shape[0]) == 0 else batch
+
+    @torch.no_grad()
+    def evaluate_guided_batch(self, batch, scales, negative_batch=None, stage=3, filter_rows=True):
+        """The guided validation loss of one batch: the cross-entropy of the held-out lyric under softmax(lu + s (lc - lu)), the
+        distribution generate_samples(guidance_scale=s) and GuidedDecoder draw from, for up to eight scales at once (each goes
+        through constraints.check_guidance).  The stage's row filter as in evaluate_batch; the negative forward -- negative_batch
+        (rows as the batch's; an input it does not name is the batch's own, as in GuidedDecoder.begin), or by default the batch
+        itself without its images and texts -- and its loss, whose logits and row lse are copied into buffers of their own (one more
+        [M, Vpad] matrix in the logits' storage type); the conditional forward and its loss; mmtg_guided_loss over both.  Returns
+        device values, no host sync: {'ce': [K], 'ce_cond': the plain mean of the conditional sample_ce, 'ce_uncond': the negative's,
+        'rows': the row count}, or None when the filter leaves no row."""
+        scales = _check_scales(scales)
+        eng = self.eng
+        if negative_batch is not None:
+            negative_batch = dict(batch, **negative_batch)
+            if int(negative_batch["targets"].shape[0]) != int(batch["targets"].shape[0]):
+                raise ValueError("negative_batch: one row per row of the batch")
+            if filter_rows and stage in (1, 2):         # the batch's selection, applied to both
+                for k in ("rating", "rating_host"):
+                    if k in batch:
+                        negative_batch[k] = batch[k]
+            negative_batch = self._eval_rows(negative_batch, stage, filter_rows)
+        batch = self._eval_rows(batch, stage, filter_rows)
+        if batch is None:
             return None
+        n = int(batch["rating"].shape[0])
+        if negative_batch is None:
+            eng.forward(batch, train_flag=True, training=False, logits_f32=_LOGITS_F32, exp_drop=NO_EXPERIENCE)
+        else:
+            eng.forward(negative_batch, train_flag=True, training=False, logits_f32=_LOGITS_F32)
+        eng.loss(batch["rating"], stage)
+        a = eng.act
+        # (buffers of their own: the second forward overwrites the engine's logits, row lse and sample_ce)
+        ulog = eng.buf("guided_uncond_logits", tuple(a["logits"].shape), a["logits"].dtype)
+        ulse = eng.buf("guided_uncond_lse", (a["M"],), torch.float32)
+        ulog.copy_(a["logits"])
+        ulse.copy_(a["lse_rows"])
+        ce_uncond = a["sample_ce"].mean()
         eng.forward(batch, train_flag=True, training=False, logits_f32=_LOGITS_F32)
+        eng.loss(batch["rating"], stage)
+        ce_cond = eng.act["sample_ce"].mean()
+        ce = eng.guided_loss(scales, ulog, ulse).clone()        # (the engine's buffer is the next call's as well)
+        return {"ce": ce, "ce_cond": ce_cond, "ce_uncond": ce_uncond, "rows": n}
+
+    def evaluate_guided(self, valid_batches, scales, stage=3, negative_batches=None, averaged=False):
+        """evaluate_guided_batch over an iterable of validation batches (negative_batches: None or an iterable alongside it): the
+        ROW-weighted means over all batches, summed on the device with one host read at the end, so that a scale can be chosen on
+        validation data.  Returns {'scales': [...], 'ce': [...], 'ce_cond': x, 'ce_uncond': y, 'rows': n}; the model is in eval mode
+        during the pass and gets its previous mode back afterwards.  averaged=True runs the pass inside averaged_weights()."""
+        if averaged:
+            with self.averaged_weights():
+                return self.evaluate_guided(valid_batches, scales, stage, negative_batches)
+        scales = _check_scales(scales)
+        was_training = self.model.training
+        self.model.eval()
+        acc, rows = None, 0
+        negs = iter(negative_batches) if negative_batches is not None else None
+        try:
+            for batch in valid_batches:
+                out = self.evaluate_guided_batch(batch, scales, None if negs is None else next(negs), stage)
+                if out is None:
+                    continue
+                v = torch.cat([out["ce"], out["ce_cond"].reshape(1), out["ce_uncond"].reshape(1)]) * float(out["rows"])
+                acc = v if acc is None else acc + v
+                rows += out["rows"]
+        finally:
+            self.model.train(was_training)
+        K = len(scales)
+        if rows == 0:
+            return {"scales": [float(s) for s in scales], "ce": [0.0] * K, "ce_cond": 0.0, "ce_uncond": 0.0, "rows": 0}
+        v = (acc / float(rows)).tolist()
+        return {"scales": [float(s) for s in scales], "ce": v[:K], "ce_cond": v[K], "ce_uncond": v[K + 1], "rows": rows}
+
+    @torch.no_grad()
+    def evaluate_batch(self, batch, stage=3, filter_rows=True, without_experience=False):
+        """Forward + MyLoss (+ KL) of one validation batch, no update: the stage's row filter, the engine's forward in eval mode (no
+        dropout) with compute-dtype logits -- no fp32 [B, T, V] tensor, no autograd boundary -- and the loss kernels.  Returns the
+        DEVICE scalars {'loss': MyLoss mean, 'kl': kl, 'total': loss + alpha * kl} (no host sync), or None when the filter leaves
+        no rows (train.py:252-253 `continue`s).  With ul_weight > 0 also 'ul', the unweighted unlikelihood term of the batch, with cl_weight > 0 also 'cl'; 'total'
+        stays the reference's validation loss.  without_experience=True runs the forward on the batch without its images and
+        texts (generate.without_experience): the validation loss of the branch guidance subtracts."""
+        eng = self.eng
+        batch = self._eval_rows(batch, stage, filter_rows)
+        if batch is None:
+            return None
+        if without_experience:
+            eng.forward(batch, train_flag=True, training=False, logits_f32=_LOGITS_F32, exp_drop=NO_EXPERIENCE)
+        else:
+            eng.forward(batch, train_flag=True, training=False, logits_f32=_LOGITS_F32)
         sc = eng.loss(batch["rating"], stage)
         loss, kl = sc[0], eng.act["kl"][0]
         out = {"loss": loss, "kl": kl, "total": loss + self.alpha * kl}
@@ -482,15 +617,15 @@ class MMTGTrainer:
         return out
 
     @torch.no_grad()
-    def evaluate(self, valid_batches, stage=3, averaged=False):
+    def evaluate(self, valid_batches, stage=3, averaged=False, without_experience=False):
         """The reference's evaluate() (train.py:241-268) over an iterable of validation batches: per batch
         total = MyLoss.mean() + alpha * kl.mean(), summed -- on the device, one host read at the end -- and divided by the NUMBER OF
         BATCHES (filtered-out ones included, as `valid_loss /= len(valid_dataset)` does).  Returns (valid_loss, kldiv_loss) floats;
         the model is in eval mode during the pass (train.py:242) and gets its previous mode back afterwards.
-        averaged=True runs the pass inside averaged_weights()."""
+        averaged=True runs the pass inside averaged_weights(); without_experience=True as in evaluate_batch."""
         if averaged:
             with self.averaged_weights():
-                return self.evaluate(valid_batches, stage)
+                return self.evaluate(valid_batches, stage, without_experience=without_experience)
         was_training = self.model.training
         self.model.eval()
         acc = torch.zeros(2, device=self.eng.dev, dtype=torch.float32)
@@ -498,7 +633,7 @@ class MMTGTrainer:
         try:
             for batch in valid_batches:
                 n += 1
-                out = self.evaluate_batch(batch, stage)
+                out = self.evaluate_batch(batch, stage, without_experience=True) if without_experience else self.evaluate_batch(batch, stage)
                 if out is None:
                     continue
                 acc[0] += out["total"]
