@@ -1182,6 +1182,39 @@ MMTG_API int mmtg_decode_guidance(const float* cond, const float* uncond, long l
                          void* stream);
 MMTG_API int mmtg_decode_mirror(long long* seq, long ldseq, const int* pos_ptr, int N, void* stream);
 
+/* ---- per-modality guidance (ModalityGuidedDecoder, mmtg_amd/decode.py; generate_samples / sample_sequence with image_guidance_scale=
+ * / text_guidance_scale=; csrc/decode_guidance_multi.hip): a prompt beside up to three negatives -- without its experience, without
+ * its images, without its texts -- each with a scale of its own.  The decoder runs K N rows, K - 1 the number of running negatives:
+ * block 0 (rows 0 .. N - 1) holds the prompts, block k (rows k N .. k N + N - 1) the k-th running negative of the same prompts.
+ * Additive to ABI 12.
+ * mmtg_decode_guidance_multi: one workgroup per prompt b < N; branch k of prompt b is row k N + b of `logits`.  With x_k = logits[(k N
+ *   + b) * ldl + 0 .. V - 1] (RAW logits; c = x_0), L(x) = max x + log(sum_v exp(x[v] - max x)), w_k = scales[k - 1] - 1 (an fp32
+ *   subtraction), fp32 throughout and in this order of operations:
+ *     lc = c[v] - L(c)     l_k = x_k[v] - L(x_k)     g = lc;  g = g + w_k * (lc - l_k)  for k = 1 .. K - 1 in turn     out[b * ldo + v] = g
+ *   for v < V.  So every scale at 1 gives lc; x_k == c makes branch k vanish bit for bit at any scale (both rows go through the same
+ *   reduction); K = 2 is mmtg_decode_guidance's lu + s (lc - lu) up to rounding.  An id that is -inf in any of the K rows gets -inf,
+ *   never NaN; a row whose V entries are all -inf (any of the K) gives all -inf.  The weight the rule puts on lc, 1 + sum_k w_k, may
+ *   be negative (three scales at 0 give -2): allowed, the result is still a finite score per id, not a log-probability.
+ *   `scales` is a HOST array of K - 1 floats, read at call time and handed to the kernel by value: a captured launch holds the
+ *   numbers, not a pointer.  Columns V .. ldo - 1 of `out`, rows >= N of `out` and the input columns >= V are not touched.
+ *   Two forms.  Register-resident (V <= 14336): 512 threads; all loads of a prompt's K rows are issued before the first is used (up
+ *   to seven float4 per thread and row when `logits`, `out` and both strides are 16-byte aligned, else up to 28 single logits:
+ *   ldl may be odd), the rows stay in registers over the max, the sum and the combine, and each is read once.  Re-read (any V): 256
+ *   threads, one streaming pass per row for a running (max, sum), a second pass for the combine.  Either way wave shuffles and static
+ *   LDS words reduce in a fixed order, without atomics: equal inputs give equal bits (per form).
+ *   Fails before any device call: a null pointer (logits, scales, out), N < 1, V < 1, K outside 2 .. 4, ldl < V, ldo < V, a scale not
+ *   finite or < 0, `out` overlapping the K N input rows.
+ * mmtg_decode_guidance_multi_form: the same with the form named -- 0: what mmtg_decode_guidance_multi chooses (register-resident up to
+ *   V = 14336, re-read beyond), 1: register-resident (fails where V > 14336), 2: re-read.  For tools/bench_mguidance.py and the tests.
+ * mmtg_decode_mirror_multi: with pos = *pos_ptr, seq[(k N + b) * ldseq + pos + 1] = seq[b * ldseq + pos + 1] for k = 1 .. K - 1 and
+ *   b < N when 0 <= pos + 1 < ldseq; nothing otherwise.  Nothing else is written.
+ *   Fails before any device call: a null pointer, N < 1, K outside 2 .. 4, ldseq < 1.                                               */
+MMTG_API int mmtg_decode_guidance_multi(const float* logits, long ldl, int V, int K, const float* scales, float* out, long ldo, int N,
+                               void* stream);
+MMTG_API int mmtg_decode_guidance_multi_form(const float* logits, long ldl, int V, int K, const float* scales, float* out, long ldo,
+                                    int N, int form, void* stream);
+MMTG_API int mmtg_decode_mirror_multi(long long* seq, long ldseq, const int* pos_ptr, int N, int K, void* stream);
+
 /* ---- the training side of guidance (MMTGTrainer(experience_drop=...), evaluate_guided; csrc/guidance_train.hip).  Classifier-free
  * guidance assumes a model that was also trained with the condition removed (Ho & Salimans, 2022); the two entries give the fused
  * step that input and measure the guided distribution on held-out lyrics.  Additive to ABI 12.

@@ -419,6 +419,51 @@ def guidance_scores(cond, uncond, scale):
     return np.where(out_, -np.inf, g)
 
 
+GUIDANCE_BRANCHES = ("u", "i", "t")     # the fixed branch order: without the experience, without the images, without the texts
+
+
+def check_modality_guidance(guidance_scale=GUIDANCE_OFF, image_guidance_scale=GUIDANCE_OFF, text_guidance_scale=GUIDANCE_OFF):
+    """The three scales of per-modality guidance, each as ``check_guidance`` takes it (a ValueError names the argument).  Returns
+    (branches, scales): the running branches -- those whose scale differs from 1 -- as a tuple of "u" / "i" / "t" in that order, and
+    their scales, a tuple of floats.  A prompt then runs beside len(branches) negatives; () is the unguided call.  The weight the rule
+    puts on the prompt's own distribution, 1 + sum(s - 1), may come out negative (three scales at 0 give -2): that is allowed."""
+    branches, scales = [], []
+    for name, arg, value in (("u", "guidance_scale", guidance_scale), ("i", "image_guidance_scale", image_guidance_scale),
+                             ("t", "text_guidance_scale", text_guidance_scale)):
+        try:
+            s = check_guidance(value)
+        except ValueError as e:
+            raise ValueError(str(e).replace("guidance_scale", arg, 1)) from None
+        if s != GUIDANCE_OFF:
+            branches.append(name)
+            scales.append(s)
+    return tuple(branches), tuple(scales)
+
+
+def modality_guidance_scores(branches, scales):
+    """The rule of mmtg_decode_guidance_multi (include/mmtg_hip.h) in float64 numpy.  branches: [K, ..., V] (or a sequence of K
+    arrays), the raw logits of the prompts (branches[0]) and of their K - 1 running negatives in branch order, already cut to the
+    columns the selection reads; scales: the K - 1 scales.  Returns g = lc;  g = g + (s_k - 1) * (lc - l_k) for k = 1 .. K - 1 in turn,
+    with lc / l_k the log-softmax over the last axis: every scale at 1 (or K = 1) gives lc, one branch is ``guidance_scores``'s
+    lu + s (lc - lu) up to rounding, a branch equal to the prompt vanishes exactly.  An id that is -inf in any branch gets -inf (never
+    NaN), and so does every id of a prompt one of whose K rows is all -inf."""
+    x = [np.asarray(b, dtype=np.float64) for b in branches]
+    if len(x) != len(scales) + 1:
+        raise ValueError("modality_guidance_scores: %d branches take %d scales, got %d" % (len(x), len(x) - 1, len(scales)))
+    if any(b.shape != x[0].shape for b in x):
+        raise ValueError("modality_guidance_scores: the branches differ in shape: %r" % ([b.shape for b in x],))
+    s = [check_guidance(v) for v in scales]
+    ls = [_log_softmax64(b) for b in x]
+    dead = np.zeros(x[0].shape, bool)
+    for l in ls:
+        dead |= np.isneginf(l)
+    g = ls[0].copy()
+    with np.errstate(invalid="ignore"):
+        for l, sk in zip(ls[1:], s):
+            g = g + (sk - 1.0) * (ls[0] - l)
+    return np.where(dead, -np.inf, g)
+
+
 def chosen_mask(ids, sent=22, prefix_lens=None):
     """Which columns of generated lyric ids count towards a row's score: bool [B, 1 + length], host only.  Column j >= 1 of row b
     counts iff it is not a cadence column (j % sent not in {0, sent - 1}: the forced [#START#] / [#EOS#]), it lies past the row's

@@ -1623,3 +1623,96 @@ class GuidedDecoder(GreedyDecoder):
             return super().generate(batch, length, **kw)
         finally:
             self._negative_and_scale = None
+
+
+class ModalityGuidedDecoder(GuidedDecoder):
+    """Per-modality guidance on the KV-cached, graph-replayed token step: a scale for the experience as a whole, one for the images and
+    one for the texts.  Built for `max_prompts` = N prompts and `blocks` = K (3 or 4; 2 works and is GuidedDecoder's case through the
+    K-row kernels), the decoder runs K N rows: block 0 (rows 0 .. N - 1) holds the prompts, block k the k-th running negative of the
+    same prompts, in the fixed branch order u (generate.without_experience), i (without_images), t (without_texts) -- a branch runs
+    only if its scale differs from 1.  Rows never interact, so the prefill and the token step see K N ordinary rows; a step that calls
+    the head then ends in
+
+        mmtg_decode_guidance_multi   glogits[b] = lc + sum_k (s_k - 1) (lc - l_k) over the log-softmax of the raw logits rows k N + b
+        the selection entry a plain decoder would pick, over N rows, reading glogits
+        mmtg_decode_logprob          (with return_logprobs) over the N raw prompt rows
+        mmtg_decode_mirror_multi     seq[k N + b, pos + 1] = seq[b, pos + 1], k = 1 .. K - 1: every block stays on the prompts' text
+
+    and a step without the head in its selection over N rows and the mirror.  The scales are host numbers handed to the kernel by
+    value at capture, so the graph key carries the branch set and the scales: other scales capture other graphs.  Everything else is
+    GuidedDecoder's: the constraint tables, the uniforms, ``mirostat_mu`` and ``tok_lp`` are touched for the first N rows only, the
+    log-probabilities stay the model's own, one lane."""
+
+    def __init__(self, model, max_prompts, blocks, max_len=None, use_graph=True, lanes=1):
+        if lanes != 1:
+            raise ValueError("guided decoding runs on one lane (got lanes=%r)" % (lanes,))
+        n, k = int(max_prompts), int(blocks)
+        if n < 1:
+            raise ValueError("max_prompts %r must be at least 1" % (max_prompts,))
+        if not 2 <= k <= 4:
+            raise ValueError("blocks %r must be 2, 3 or 4: a prompt beside one to three negatives" % (blocks,))
+        GreedyDecoder.__init__(self, model, k * n, max_len=max_len, use_graph=use_graph, lanes=1)
+        self.n_prompts, self.blocks = n, k
+        self.guidance_scale = GUIDANCE_OFF      # (GuidedDecoder's attribute; the u branch's scale when it runs)
+        self.branches, self.scales = (), ()
+        self.glogits = torch.zeros(n, self.eng.layout.Vpad, dtype=torch.float32, device=self.eng.dev)
+        self.select_rows, self.select_logits = n, self.glogits
+
+    def _select(self, with_head):
+        if with_head:
+            hip.decode_guidance_multi(self.logits, self.eng.layout.Vpad, min(self.eng.sh.V, 13317), self.scales, self.glogits,
+                                      self.n_prompts)
+        GreedyDecoder._select(self, with_head)
+
+    def _end_step(self, with_head):
+        hip.decode_mirror_multi(self.seq, self.pos, self.n_prompts, self.blocks)
+
+    def _graph_key(self, with_head, parity):
+        return GreedyDecoder._graph_key(self, with_head, parity) + (("modality_guidance", self.branches, self.scales),)
+
+    def describe(self):
+        return GreedyDecoder.describe(self) + ", %d prompts beside %d negatives each (%s)" % (
+            self.n_prompts, self.blocks - 1, ", ".join("%s %g" % bs for bs in zip(self.branches, self.scales)))
+
+    @torch.no_grad()
+    def begin(self, batch, negative_batches, length, branches=(), scales=(), temperature=1.0, repitition_penalty=1.0, top_k=1, top_p=0.0,
+              generator=None, prefix=None, no_repeat_ngram_size=0, line_lengths=None, line_end_ids=None, templates=None,
+              rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False, return_logprobs=False, keywords=None, refrain_scheme=None,
+              **sampler_kw):
+        """GreedyDecoder.begin for N prompts (batch) and their K - 1 negatives (negative_batches: a list of K - 1 batches with the same
+        keys, in branch order): the K are concatenated, the constraints and prefixes -- one per prompt -- are repeated K times, and
+        the branch names (for the graph key and ``describe``) and their scales (each as check_guidance takes it) are kept for the steps."""
+        _keywords_need_beams(keywords)
+        scales = tuple(check_guidance(s) for s in scales)
+        branches = tuple(str(b) for b in branches)
+        n, k, sh = self.n_prompts, self.blocks, self.eng.sh
+        if len(negative_batches) != k - 1 or len(scales) != k - 1 or len(branches) != k - 1:
+            raise ValueError("decoder was built for %d negatives per prompt, got %d batches, %d branches and %d scales"
+                             % (k - 1, len(negative_batches), len(branches), len(scales)))
+        for name, b in [("batch", batch)] + [("negative_batches[%d]" % i, nb) for i, nb in enumerate(negative_batches)]:
+            if b["img_embs"].shape[0] != n:
+                raise ValueError("decoder was built for %d prompts, %s has %d" % (n, name, b["img_embs"].shape[0]))
+        dev = self.eng.dev
+        every = {key: torch.cat([torch.as_tensor(batch[key]).to(dev)] + [torch.as_tensor(nb.get(key, batch[key])).to(dev)
+                                                                         for nb in negative_batches])
+                 for key in batch if key not in ("targets", "rating")}
+        cons = _check_constraints(prefix, no_repeat_ngram_size, line_lengths, line_end_ids, n, length, sh, "%d prompts" % n, templates,
+                                  rhyme_scheme, rhyme_classes, rhyme_distinct, refrain_scheme).take(list(range(n)) * k)
+        self.branches, self.scales = branches, scales
+        self.guidance_scale = dict(zip(branches, scales)).get("u", GUIDANCE_OFF)
+        return GreedyDecoder.begin(self, every, length, temperature, repitition_penalty, top_k, top_p, generator, prefix=cons.prefix,
+                                   no_repeat_ngram_size=cons.ngram, line_lengths=cons.lines, return_logprobs=return_logprobs, **sampler_kw)
+
+    @torch.no_grad()
+    def generate(self, batch, negative_batches, length, branches=(), scales=(), **kw):
+        """batch: N prompts; negative_batches: their K - 1 negatives in branch order; branches / scales: the K - 1 branch names and
+        scales (constraints.check_modality_guidance returns both).  Returns what GuidedDecoder.generate returns, for the prompts.
+        kw: as GuidedDecoder.generate; `tap(j, with_head, picked [K N], logits [K N, Vpad] or None)` receives the raw logits of all K
+        blocks."""
+        if kw.get("teacher") is not None:
+            raise ValueError("guided decoding takes no teacher: every block of the batch follows one text, the prompts' own")
+        self._negative_and_scale = (list(negative_batches), tuple(branches), tuple(scales))
+        try:
+            return GreedyDecoder.generate(self, batch, length, **kw)
+        finally:
+            self._negative_and_scale = None

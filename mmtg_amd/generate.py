@@ -17,9 +17,9 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
-from .constraints import (BANNED, GUIDANCE_OFF, WARP_OFF, Constraints, _check_constraints, check_guidance, check_mirostat, check_warp, check_contrastive, check_groups, check_keywords, check_prefix, check_stochastic, refrain_without_keywords,
+from .constraints import (BANNED, GUIDANCE_OFF, WARP_OFF, Constraints, _check_constraints, check_mirostat, check_modality_guidance, check_warp, check_contrastive, check_groups, check_keywords, check_prefix, check_stochastic, refrain_without_keywords,
                           sequence_scores)
-from .decode import BeamDecoder, ContrastiveDecoder, GreedyDecoder, GuidedDecoder, StochasticBeamDecoder, _keywords_need_beams
+from .decode import BeamDecoder, ContrastiveDecoder, GreedyDecoder, GuidedDecoder, ModalityGuidedDecoder, StochasticBeamDecoder, _keywords_need_beams
 from .data import encode_line_end, encode_prefix, encode_rhyme_classes, encode_template  # noqa: F401  (public: the opening lines / the line-end sets / the line templates / the rhyme classes of generate_samples / generate_beams)
 
 SENT_SLOT = 22  # generate.py:118-121
@@ -50,11 +50,11 @@ def _check_tokenizer(tokenizer):
         raise ValueError("tokenizer special ids %s differ from the reference vocabulary's %s" % (got, BANNED))
 
 
-def _cached_decoder(model, start_input, length, guided=False):
+def _cached_decoder(model, start_input, length, guided=False, blocks=2):
     """The KV-cached, graph-replayed decoder for this call, or None when the call is not the one the reference's
     generate.py makes (an MMTG in inference mode on the GPU -- possibly inside the nn.DataParallel wrapper of generate.py:191 --
     started from the single [#START#] token, generate.py:207-209).  MMTG_SAMPLE_RERUN=1 forces the prefix re-run loop.
-    guided: a GuidedDecoder of one prompt (two rows) instead."""
+    guided: a GuidedDecoder of one prompt (two rows) instead; with blocks > 2 a ModalityGuidedDecoder of one prompt (blocks rows)."""
     from .model import MMTG
     m = getattr(model, "module", model)
     if not isinstance(m, MMTG) or m.train_flag or not m._flat.is_cuda or os.environ.get("MMTG_SAMPLE_RERUN"):
@@ -68,17 +68,19 @@ def _cached_decoder(model, start_input, length, guided=False):
     if t.shape[0] != 1 or int(t[0]) != 1 or length < 1 or sh.P + length + 1 > sh.NP:
         return None
     cache = m.__dict__.setdefault("_sample_decoders", {})
-    key = (m._flat.data_ptr(), int(length)) + (("guided",) if guided else ())
+    key = (m._flat.data_ptr(), int(length)) + (("guided",) if guided else ()) + (("blocks", blocks) if guided and blocks > 2 else ())
     dec = cache.get(key)
     if dec is None:
         cache.clear()                       # one decoder (KV caches + graphs) at a time
-        dec = cache[key] = (GuidedDecoder(m, 1, max_len=int(length)) if guided else GreedyDecoder(m, max_batch=1, max_len=int(length)))
+        dec = cache[key] = (ModalityGuidedDecoder(m, 1, blocks, max_len=int(length)) if guided and blocks > 2
+                            else GuidedDecoder(m, 1, max_len=int(length)) if guided else GreedyDecoder(m, max_batch=1, max_len=int(length)))
     return dec
 
 
 def sample_sequence(model, start_input, length, tokenizer, temperature=1.0, top_k=30, top_p=0.0,
                     repitition_penalty=1.0, device="cuda", *, min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0,
-                    mirostat_tau=0.0, mirostat_eta=0.1, guidance_scale=1.0, negative_input=None):
+                    mirostat_tau=0.0, mirostat_eta=0.1, guidance_scale=1.0, negative_input=None, image_guidance_scale=1.0,
+                    text_guidance_scale=1.0):
     """generate.py:97-145.  When the call is the reference's own (see _cached_decoder) the loop runs on the KV-cached decoder:
     one captured token step replayed per position instead of a full forward over the growing prefix per token; the returned
     list is what the reference loop returns (the sequence before the last model call's append).  Greedy ids are the same as
@@ -91,22 +93,38 @@ def sample_sequence(model, start_input, length, tokenizer, temperature=1.0, top_
     transformers' argument of that name.  Any scale but 1 runs the model on start_input and on negative_input (the same keys; default:
     start_input with img_embs and r_embs zeroed) and selects from lu + guidance_scale * (lc - lu) of their log-softmaxed logits: on
     the cached path a GuidedDecoder of one prompt, in the re-run loop a second forward and mmtg_decode_guidance on the two last rows.
-    guidance_scale=1 (the default) is the call without the arguments; negative_input beside it is a ValueError."""
+    guidance_scale=1 (the default) is the call without the arguments; negative_input beside it is a ValueError.
+    image_guidance_scale / text_guidance_scale (keyword only; constraints.check_modality_guidance, include/mmtg_hip.h): per-modality
+    guidance, as generate_samples takes it.  One scale other than 1 among the three is the guided call above with that branch's
+    negative (start_input without its images, or without its texts); two or three run a ModalityGuidedDecoder of one prompt on the
+    cached path.  The prefix re-run loop does not take them: there two or three scales other than 1 are a ValueError that says so.
+    negative_input replaces the negative of guidance_scale only."""
     _check_tokenizer(tokenizer)
-    scale = check_guidance(guidance_scale)
-    guided = scale != GUIDANCE_OFF
-    if not guided and negative_input is not None:
+    branches, scales = check_modality_guidance(guidance_scale, image_guidance_scale, text_guidance_scale)
+    if "u" not in branches and negative_input is not None:
         raise ValueError("negative_input needs a guidance_scale other than 1 (1 is the unguided call)")
-    if guided and negative_input is None:
-        negative_input = {k: (np.zeros_like(np.asarray(v)) if k in ("img_embs", "r_embs") else v) for k, v in start_input.items()}
+    guided = len(branches) > 0
+    zero = {"u": ("img_embs", "r_embs"), "i": ("img_embs",), "t": ("r_embs",)}
+    negatives = [negative_input if b == "u" and negative_input is not None else
+                 {k: (np.zeros_like(np.asarray(v)) if k in zero[b] else v) for k, v in start_input.items()} for b in branches]
+    scale = scales[0] if guided else GUIDANCE_OFF       # (one running branch: GuidedDecoder's case, whichever branch it is)
+    negative_input = negatives[0] if guided else None
     warp = check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)
     warp_kw = {} if warp == WARP_OFF else dict(zip(("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"), warp))
     tau, eta = check_mirostat(mirostat_tau, mirostat_eta)
     miro_kw = {"mirostat_tau": tau, "mirostat_eta": eta} if tau > 0.0 else {}
-    dec = _cached_decoder(model, start_input, length, guided=guided)
+    dec = _cached_decoder(model, start_input, length, guided=guided, blocks=1 + len(branches))
+    if dec is None and len(branches) > 1:
+        raise ValueError("%d guidance scales other than 1 need the cached decoder: the prefix re-run loop runs one negative (an eval() "
+                         "MMTG on the GPU, started from [#START#], without MMTG_SAMPLE_RERUN)" % len(branches))
     if dec is not None:
         m = getattr(model, "module", model)
         batch = {k: torch.as_tensor(np.asarray(v)).unsqueeze(0) for k, v in start_input.items() if k not in ("targets", "rating")}
+        if len(branches) > 1:
+            negs = [{k: torch.as_tensor(np.asarray(neg[k])).unsqueeze(0) for k in batch} for neg in negatives]
+            ids = dec.generate(batch, negs, int(length), branches, scales, temperature=temperature, repitition_penalty=repitition_penalty,
+                               top_k=int(top_k), top_p=float(top_p), **warp_kw, **miro_kw)
+            return dec.reference_return(ids[0].tolist(), int(length), sent=m.shapes.msl + 2)
         if guided:
             neg = {k: torch.as_tensor(np.asarray(negative_input[k])).unsqueeze(0) for k in batch}
             ids = dec.generate(batch, neg, int(length), scale, temperature=temperature, repitition_penalty=repitition_penalty,
@@ -228,6 +246,20 @@ def without_experience(rows):
     return out
 
 
+def without_images(rows):
+    """The negative prompt of image_guidance_scale: `rows` stacked, with the images (img_embs) zeroed and the texts and the topic kept."""
+    out = _stack_rows(rows)
+    out["img_embs"] = torch.zeros_like(out["img_embs"])
+    return out
+
+
+def without_texts(rows):
+    """The negative prompt of text_guidance_scale: `rows` stacked, with the texts (r_embs) zeroed and the images and the topic kept."""
+    out = _stack_rows(rows)
+    out["r_embs"] = torch.zeros_like(out["r_embs"])
+    return out
+
+
 def _chunks(stacked, cons, size, dev, copies=1):
     """The prompts of `stacked`, each `copies` times in a row, cut into decoder batches of exactly `size` rows on `dev`: yields
     (batch, the rows' Constraints, the number of real rows).  The decoder's batch is fixed, so the last chunk is padded by repeating
@@ -237,6 +269,12 @@ def _chunks(stacked, cons, size, dev, copies=1):
         n = min(total, lo + size) - lo
         idx = [r // copies for r in range(lo, lo + n)] + [lo // copies] * (size - n)
         yield {k: v[idx].to(dev) for k, v in stacked.items()}, cons.take(idx), n
+
+
+def guided_chunk_size(max_batch, blocks, rows):
+    """How many prompts' rows a guided chunk of generate_samples holds: max_batch // blocks (blocks = 1 + the running negatives), at
+    least 1, at most the `rows` there are."""
+    return max(1, min(int(max_batch) // int(blocks), int(rows)))
 
 
 def rank_scored(scored, rank_by):
@@ -252,7 +290,8 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
                      repetition_penalty=1.5, max_batch=256, generator=None, decoder=None, prefixes=None, no_repeat_ngram_size=0,
                      line_lengths=None, line_end_ids=None, templates=None, rhyme_scheme=None, rhyme_classes=None, rhyme_distinct=False,
                      return_scores=False, rank_by=None, keywords=None, refrain_scheme=None, *, min_p=0.0, typical_p=1.0,
-                     epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1, guidance_scale=1.0, negative_rows=None):
+                     epsilon_cutoff=0.0, eta_cutoff=0.0, mirostat_tau=0.0, mirostat_eta=0.1, guidance_scale=1.0, negative_rows=None,
+                     image_guidance_scale=1.0, text_guidance_scale=1.0):
     """n_samples texts per prompt (generate.sh's loop, generate.py:205-235) on the batched, graph-replayed decoder:
     every prompt is replicated over n_samples rows, rows are decoded max_batch at a time with the device-side
     top-k / top-p sampler (one uniform per row and position from `generator`), each row is cut back to what
@@ -294,12 +333,19 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
     as above, one per prompt or one for all; default without_experience(rows): the topic alone).  Every other argument works as
     before, on the guided scores; the scores of return_scores stay the model's own log-probabilities under the real prompt.  A
     guided chunk holds max_batch // 2 rows beside their negatives.  guidance_scale=1 (the default) is the call without the
-    arguments; negative_rows beside it is a ValueError."""
+    arguments; negative_rows beside it is a ValueError.
+    image_guidance_scale / text_guidance_scale (keyword only; constraints.check_modality_guidance, include/mmtg_hip.h,
+    decode.ModalityGuidedDecoder): a scale per modality, e.g. image_guidance_scale=3.0, text_guidance_scale=1.5 -- follow the photos
+    more, the captions a little more.  Each scale other than 1 runs a negative of its own beside the prompt, in the order
+    guidance_scale (without_experience, or negative_rows), image_guidance_scale (without_images), text_guidance_scale (without_texts),
+    and each step selects from lc + sum_k (s_k - 1) (lc - l_k) of the log-softmaxed logits.  One scale other than 1 is the guided
+    call above with that negative: image_guidance_scale=s alone is guidance_scale=s, negative_rows=without_images(rows), bit for bit.
+    With K - 1 running negatives a chunk holds max_batch // K rows.  Both at 1 (the default) is the call without them."""
     _keywords_need_beams(keywords)
-    scale = check_guidance(guidance_scale)
-    guided = scale != GUIDANCE_OFF
-    if not guided and negative_rows is not None:
+    branches, scales = check_modality_guidance(guidance_scale, image_guidance_scale, text_guidance_scale)
+    if "u" not in branches and negative_rows is not None:
         raise ValueError("negative_rows needs a guidance_scale other than 1 (1 is the unguided call)")
+    guided, K = len(branches) > 0, 1 + len(branches)
     warp_kw = dict(zip(("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"), check_warp(min_p, typical_p, epsilon_cutoff, eta_cutoff)))
     warp_kw["mirostat_tau"], warp_kw["mirostat_eta"] = check_mirostat(mirostat_tau, mirostat_eta)
     if rank_by is not None and rank_by not in ("sum", "mean"):
@@ -313,22 +359,32 @@ def generate_samples(model, rows, tokenizer, n_samples=10, length=None, temperat
                               templates, rhyme_scheme, rhyme_classes, rhyme_distinct, refrain_scheme)
     stacked = _stack_rows(rows)
     if guided:
-        neg = without_experience(rows) if negative_rows is None else _stack_rows(negative_rows)
-        n_neg = neg["topic_ids"].shape[0]
-        if n_neg == 1 and n_prompts > 1:
-            neg = {k: v.expand(n_prompts, *v.shape[1:]) for k, v in neg.items()}
-        elif n_neg != n_prompts:
-            raise ValueError("negative_rows: one row per prompt (%d) or one for all, got %d" % (n_prompts, n_neg))
-        bsz = max(1, min(max_batch // 2, n_prompts * n_samples))
-        dec = (decoder if isinstance(decoder, GuidedDecoder) and decoder.n_prompts == bsz
-               else GuidedDecoder(model, bsz, max_len=length))
-        negs = _chunks(neg, cons, bsz, eng.dev, copies=n_samples)       # (the prompts' chunks, row for row)
+        make = {"u": without_experience, "i": without_images, "t": without_texts}
+        neg_list = []
+        for b in branches:
+            neg = _stack_rows(negative_rows) if b == "u" and negative_rows is not None else make[b](rows)
+            n_neg = neg["topic_ids"].shape[0]
+            if n_neg == 1 and n_prompts > 1:
+                neg = {k: v.expand(n_prompts, *v.shape[1:]) for k, v in neg.items()}
+            elif n_neg != n_prompts:
+                raise ValueError("negative_rows: one row per prompt (%d) or one for all, got %d" % (n_prompts, n_neg))
+            neg_list.append(neg)
+        bsz = guided_chunk_size(max_batch, K, n_prompts * n_samples)
+        if K == 2:      # one running branch, whichever: the two-row decoder and its kernels
+            dec = (decoder if isinstance(decoder, GuidedDecoder) and not isinstance(decoder, ModalityGuidedDecoder)
+                   and decoder.n_prompts == bsz else GuidedDecoder(model, bsz, max_len=length))
+        else:
+            dec = (decoder if isinstance(decoder, ModalityGuidedDecoder) and (decoder.n_prompts, decoder.blocks) == (bsz, K)
+                   else ModalityGuidedDecoder(model, bsz, K, max_len=length))
+        negs = [_chunks(neg, cons, bsz, eng.dev, copies=n_samples) for neg in neg_list]     # (the prompts' chunks, row for row)
     else:
         bsz = min(max_batch, n_prompts * n_samples)
         dec = decoder if decoder is not None and decoder.B == bsz else GreedyDecoder(model, max_batch=bsz, max_len=length)
     texts = []
     for chunk, c, n in _chunks(stacked, cons, bsz, eng.dev, copies=n_samples):
-        ids = dec.generate(chunk, *((next(negs)[0], length, scale) if guided else (length,)), temperature=temperature,
+        lead = ((length,) if not guided else (next(negs[0])[0], length, scales[0]) if K == 2 else
+                ([next(g)[0] for g in negs], length, branches, scales))
+        ids = dec.generate(chunk, *lead, temperature=temperature,
                            repitition_penalty=repetition_penalty,
                            top_k=top_k, top_p=top_p, generator=generator, prefix=c.prefix, no_repeat_ngram_size=c.ngram,
                            line_lengths=c.lines, return_logprobs=scoring, **warp_kw)

@@ -171,6 +171,9 @@ _SIGS = {
     "mmtg_experience_drop": ([_i, _vp, _vp, _vp, _vp, _vp, _i, _l, _u, C.c_longlong, C.c_longlong, C.c_longlong, _vp], _i),
     "mmtg_guided_loss": ([_i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp], _i),
     "mmtg_decode_mirror": ([_vp, _l, _vp, _i, _vp], _i),
+    "mmtg_decode_guidance_multi": ([_vp, _l, _i, _i, _vp, _vp, _l, _i, _vp], _i),
+    "mmtg_decode_guidance_multi_form": ([_vp, _l, _i, _i, _vp, _vp, _l, _i, _i, _vp], _i),
+    "mmtg_decode_mirror_multi": ([_vp, _l, _vp, _i, _i, _vp], _i),
     "mmtg_decode_mlp_ws_floats": ([_i], _l),
     "mmtg_decode_mlp_sync_words": ([], _i),
     "mmtg_decode_mlp_census": ([_vp, _vp], _i),
@@ -1461,6 +1464,40 @@ def decode_mirror(seq, pos, N):
     if seq.dtype != torch.long or seq.dim() != 2 or seq.stride(1) != 1 or seq.shape[0] < 2 * N:
         raise ValueError("seq must be int64 [>= 2 N, ld] with unit column stride")
     _check(lib().mmtg_decode_mirror(_p(seq), seq.stride(0), _p(pos), int(N), _stream()), "decode_mirror")
+
+
+GUIDANCE_FORMS = {"auto": 0, "resident": 1, "reread": 2}
+
+
+def decode_guidance_multi(logits, ldl, V, scales, out, N, form="auto"):
+    """out[b, :V] = lc + sum_k (scales[k - 1] - 1) * (lc - l_k), k = 1 .. K - 1 = len(scales), lc / l_k the log-softmax of
+    logits[b, :V] / logits[k N + b, :V], for b < N (include/mmtg_hip.h, mmtg_decode_guidance_multi).  logits is fp32 [>= K N, >= V]
+    with rows ldl apart; scales are host numbers, handed to the kernel by value; out is fp32 [>= N, >= V]; columns V .. stay as
+    they are.  form: "auto" (the entry's own choice), "resident" or "reread" (mmtg_decode_guidance_multi_form)."""
+    K = len(scales) + 1
+    if logits.dtype != torch.float32 or out.dtype != torch.float32:
+        raise ValueError("logits and out must be fp32")
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.stride(0) != ldl or logits.shape[0] < K * N:
+        raise ValueError("logits must be fp32 [>= K N, >= V] with unit column stride and rows ldl apart")
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < N:
+        raise ValueError("out must be fp32 [>= N, >= V] with unit column stride")
+    if form not in GUIDANCE_FORMS:
+        raise ValueError("form must be one of %s, got %r" % (sorted(GUIDANCE_FORMS), form))
+    host = (C.c_float * max(K - 1, 1))(*[float(s) for s in scales])
+    if form == "auto":
+        rc = lib().mmtg_decode_guidance_multi(_p(logits), int(ldl), int(V), K, host, _p(out), out.stride(0), int(N), _stream())
+    else:
+        rc = lib().mmtg_decode_guidance_multi_form(_p(logits), int(ldl), int(V), K, host, _p(out), out.stride(0), int(N),
+                                                   GUIDANCE_FORMS[form], _stream())
+    _check(rc, "decode_guidance_multi")
+
+
+def decode_mirror_multi(seq, pos, N, K):
+    """seq[k N + b, pos + 1] = seq[b, pos + 1] for k = 1 .. K - 1 and b < N, where the column exists (include/mmtg_hip.h,
+    mmtg_decode_mirror_multi).  seq is int64 [>= K N, ld]; pos is the position slot the selection left alone."""
+    if seq.dtype != torch.long or seq.dim() != 2 or seq.stride(1) != 1 or seq.shape[0] < K * N:
+        raise ValueError("seq must be int64 [>= K N, ld] with unit column stride")
+    _check(lib().mmtg_decode_mirror_multi(_p(seq), seq.stride(0), _p(pos), int(N), int(K), _stream()), "decode_mirror_multi")
 
 
 # the training side of guidance (the rules: include/mmtg_hip.h; csrc/guidance_train.hip)
