@@ -70,7 +70,10 @@ __global__ __launch_bounds__(256) void embed_add_kernel(const T* __restrict__ g,
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float v = (float)g[m * D + d + e] + (float)wpe[(long)t * D + d + e] + (float)wte[ty * D + d + e];
-            if (thresh) v *= dropout_scale(seed, (uint32_t)(m * D + d + e), thresh, inv_keep);
+            if (thresh) {       // a dropped element is +0 whatever the sign of the sum (v * 0.f keeps the sign)
+                const float sc = dropout_scale(seed, (uint32_t)(m * D + d + e), thresh, inv_keep);
+                v = sc != 0.f ? v * sc : 0.f;
+            }
             h[m * D + d + e] = (T)v;
         }
     }
@@ -198,6 +201,9 @@ extern "C" int mmtg_embed_add_bwd(int dtype, void* dh, const long long* type_ids
                                   void* stream) {
     MMTG_REQUIRE(M > 0 && T > 0 && M % T == 0 && D > 0 && ntypes > 0 && ntypes <= 32 && dh && type_ids && dwpe && dwte,
                  "embed_add_bwd: bad args");
+    // (every refusal comes before the in-place mask: a refused call leaves dh as it was)
+    MMTG_REQUIRE(!ws || (ws_floats >= mmtg_embed_add_bwd_ws(M, D, ntypes) && D % 4 == 0), "embed_add_bwd: workspace of %ld floats required",
+                 mmtg_embed_add_bwd_ws(M, D, ntypes));
     hipStream_t s = (hipStream_t)stream;
     if (drop_thresh) {
         int rc = mmtg_dropout_apply(dtype, dh, dh, (long)M * D, D, drop_thresh, drop_seed, stream);
@@ -212,8 +218,6 @@ extern "C" int mmtg_embed_add_bwd(int dtype, void* dh, const long long* type_ids
     const size_t shm = (size_t)ntypes * 256 * sizeof(float);
     // token-type rows of wte: per-row-block bins -> workspace -> ordered sum over the row blocks (round 4: no fp32 atomics, the
     // gradient is reproducible bit for bit); without a workspace the round-1 atomics remain
-    MMTG_REQUIRE(!ws || (ws_floats >= mmtg_embed_add_bwd_ws(M, D, ntypes) && D % 4 == 0), "embed_add_bwd: workspace of %ld floats required",
-                 mmtg_embed_add_bwd_ws(M, D, ntypes));
 #define K_(T_, ...)                                                                                                   \
     hipLaunchKernelGGL(embed_dwpe_kernel<T_>, g1, block, 0, s, (const T_*)dh, dwpe, M / T, T, D);                      \
     hipLaunchKernelGGL(embed_dwte_kernel<T_>, g2, block, shm, s, (const T_*)dh, type_ids, dwte, M, D, ntypes, rpb, ws)
