@@ -1255,6 +1255,58 @@ MMTG_API int mmtg_guided_loss(int logits_dtype, const void* cond, const void* un
                      const float* lse_u, const long long* topic_ids, const long long* targets, const float* scales, int K,
                      int B, int P, int L, float batch_den, float* nll, float* sample_ce, float* ce, void* stream);
 
+/* ---------------------------------------------------------------- distillation of a teacher's (guided) distribution
+ * The training-time end of the guidance arc (csrc/distill.hip; MMTGTrainer(distill_weight=..., distill_teacher=...,
+ * distill_scale=...)): the model is pulled towards q = softmax(lu + s (lc - lu)) of a teacher's conditional and negative logits,
+ * after which plain decoding at full batch gives what guided decoding gave at half of it (guidance distillation, Meng et al.,
+ * 2023).  With no negative the same term is ordinary knowledge distillation (Hinton et al., 2015).  Additive to ABI 12.
+ *
+ * Notation as in the unlikelihood section: P topic columns, L lyric columns, Tt = P + L, row m = b * Tt + t.  The loss rows of a
+ * sample are P <= t <= Tt - 2 (ntok = Tt - 1 - P of them; PAD rows included, as in mmtg_guided_loss); every sample takes part
+ * whatever its rating.
+ *   student     x: the step's own logits, lse[m] from mmtg_loss_fwd;  logp_v = x_v - lse[m],  p_v = exp(logp_v)
+ *   teacher     c: its logits for the batch, u: its logits for the negative (u may be null); lse_c, lse_u: each matrix's fp32 row
+ *               log-sum-exp; s: a host float, finite and >= 0, passed by value.  In fp32, in mmtg_decode_guidance's order:
+ *                 lc = c_v - lse_c[m]      lu = u_v - lse_u[m]      g_v = lu + s * (lc - lu)      (u null: g_v = lc, s is ignored)
+ *                 Lg[m] = max g + log(sum_v exp(g_v - max g))       q_v = exp(g_v - Lg[m])
+ *   row term    kd_row[m] = sum_v q_v (g_v - Lg[m] - logp_v) = KL(q || p) >= 0
+ *   sample      kd_sample[b] = (1 / ntok) * sum over the loss rows of kd_row;   kd = sum_b kd_sample[b] / batch_den
+ *               (rows t < P and each sample's last row carry none: kd_row = kd_lg = 0)
+ *   objective   MyLoss + alpha * KL (+ lm_weight * LM) (+ cl_weight * cl) + distill_weight * kd
+ *   gradient    on a loss row, with w = distill_weight * gscale / (ntok * batch_den) and cf the row factor of mmtg_loss_bwd:
+ *               d[m, v] = cf * (p_v - [v == label]) + w * (p_v - q_v)
+ *               (the first term is mmtg_loss_bwd's expression in its order; a row without the term -- w = 0, or t < P -- is written
+ *               by that expression alone: the same bits.  Rows outside the loss rows and pad columns hold what mmtg_loss_bwd writes.)
+ * There is no temperature.  All sums run in a fixed order and nothing is accumulated with atomics: equal inputs give equal bits.
+ *
+ * mmtg_distill_fwd: one sweep, one workgroup of 256 threads per row; every element of the two or three matrices is fetched once
+ *   (rows whose bases are all 16-byte aligned in slices of eight, the tail and unaligned fp32 rows one element at a time: an fp32
+ *   ldl or ldt may be odd).  Student (`logits_dtype`, stride ldl) and teacher (`teacher_dtype`, stride ldt; cond and uncond share
+ *   both) are each fp32 or bf16, independently; bf16 widens to fp32 exactly.  Nothing is staged, so V has no limit.  A lane carries
+ *   (max g, S = sum e^(g - max), A = sum e^(g - max) (g - logp)), rescales S and A together when the max moves; lanes combine by
+ *   the wave's butterfly, waves in wave order.  Lg = max + log S, kd_row = A / S - Lg.  The exponentials are v_exp_f32, the log logf.
+ *   Outputs (fp32): kd_row [M], kd_lg [M] (Lg, which the backward reads), kd_sample [B], kd [1].
+ * mmtg_loss_bwd_kd: mmtg_loss_bwd with the term folded in (kd_lg from mmtg_distill_fwd on the same inputs, kd_coef = w above): the
+ *   same storage forms (dtype of dlogits x logits_dtype), zeros, Vpad and in-place rule -- bf16 dlogits may alias the student's
+ *   logits, no output may overlap a teacher matrix.  p_v is expf as in mmtg_loss_bwd, q_v is v_exp_f32.
+ * mmtg_loss_bwd_kd_x3: the (hi | lo) plane-pair form, beside mmtg_loss_bwd_x3.
+ * All three fail before any device call on: a null pointer (uncond and lse_u excepted, which are null together or not at all;
+ *   topic_ids where no row reads it), a scale that is not finite or is negative, V < 1, a leading dimension below V, bf16 rows that
+ *   are not 16-byte aligned, B < 1, P < 0, L < 2, batch_den not finite or <= 0, kd_coef not finite or negative, an output that
+ *   overlaps a teacher input.                                                                                                    */
+MMTG_API int mmtg_distill_fwd(int logits_dtype, const void* logits, long ldl, int teacher_dtype, const void* cond, const void* uncond,
+                     long ldt, int V, const float* lse, const float* lse_c, const float* lse_u, float scale, int B, int P, int L,
+                     float batch_den, float* kd_row, float* kd_lg, float* kd_sample, float* kd, void* stream);
+MMTG_API int mmtg_loss_bwd_kd(int dtype, int logits_dtype, const void* logits, long ldl, int V, const long long* topic_ids,
+                     const long long* targets, const float* lse, const float* coef, float gscale, float lm_coef,
+                     int teacher_dtype, const void* cond, const void* uncond, long ldt, const float* lse_c, const float* lse_u,
+                     float scale, const float* kd_lg, float kd_coef, int B, int P, int L, void* dlogits, long ldd, int Vpad,
+                     void* stream);
+MMTG_API int mmtg_loss_bwd_kd_x3(const float* logits, long ldl, int V, const long long* topic_ids, const long long* targets,
+                        const float* lse, const float* coef, float gscale, float lm_coef, int teacher_dtype, const void* cond,
+                        const void* uncond, long ldt, const float* lse_c, const float* lse_u, float scale, const float* kd_lg,
+                        float kd_coef, int B, int P, int L, void* planes, long ldd, long plane, int Vpad, void* stream);
+
 /* ---- Round 6: the MLP of a GPT-2 block of the decode token step as ONE launch (bf16, n_embd = 768, M <= 256 rows) -- the
  * c_fc -> gelu_new -> mlp.c_proj -> + residual half of the transformers GPT-2 block the reference runs per token through
  * model.py:320-326 / generate.py:124; replaces the mode-0 + mode-2 mmtg_decode_gemm pair of the fused step.

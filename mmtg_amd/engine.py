@@ -1090,6 +1090,56 @@ class Engine:
         a.update(guided_nll=nll, guided_sample_ce=smp, guided_ce=ce)
         return ce
 
+    # ---- distillation of a teacher's (guided) distribution (the rule: include/mmtg_hip.h; MMTGTrainer(distill_weight=...))
+    def distill_loss(self, teacher_logits, teacher_lse, uncond_logits=None, uncond_lse=None, scale=1.0, batch_den=None):
+        """After forward() and loss(): KL(q || p) of this forward's logits against q = softmax(lu + scale (lc - lu)) of a teacher's
+        conditional logits [M, ld] (fp32 or bf16, ld >= V; a teacher engine's own buffer or a copy) with their row lse [M], and the
+        negative's logits and lse (buffers of the caller's own, both None: q = softmax(lc)).  Returns the device scalar kd [1];
+        kd_row, kd_lg, kd_sample are recorded in act with the teacher's tensors, which loss_backward_kd() reads again."""
+        a, sh = self.act, self.sh
+        B, L, M = a["B"], a["L"], a["M"]
+        if "lse_rows" not in a:
+            raise RuntimeError("distill_loss() needs loss() on this forward (it reads the row lse)")
+        if teacher_logits.dim() != 2 or teacher_logits.shape[0] != M or teacher_logits.shape[1] < sh.V or teacher_lse.numel() != M:
+            raise ValueError("distill_loss: the teacher's logits must be [M = %d, >= V = %d] with M row lse" % (M, sh.V))
+        if (uncond_logits is None) != (uncond_lse is None):
+            raise ValueError("distill_loss: uncond_logits and uncond_lse are given together or not at all")
+        if uncond_logits is not None and (uncond_logits.dtype != teacher_logits.dtype or uncond_logits.shape != teacher_logits.shape
+                                          or uncond_lse.numel() != M):
+            raise ValueError("distill_loss: the negative's logits and lse must have the teacher's type and shape")
+        row = self.buf("kd_row", (M,), torch.float32)
+        lg = self.buf("kd_lg", (M,), torch.float32)
+        smp = self.buf("kd_sample", (B,), torch.float32)
+        kd = self.buf("kd_scalar", (1,), torch.float32)
+        ldt = teacher_logits.stride(0)
+        hip.distill_fwd(a["logits"], self.layout.Vpad, teacher_logits, uncond_logits, ldt, sh.V, a["lse_rows"], teacher_lse, uncond_lse,
+                        scale, B, sh.P, L, float(B if batch_den is None else batch_den), row, lg, smp, kd)
+        a.update(kd_row=row, kd_lg=lg, kd_sample=smp, kd=kd,
+                 kd_teacher=(teacher_logits, uncond_logits, ldt, teacher_lse, uncond_lse, float(scale)))
+        return kd
+
+    def loss_backward_kd(self, gscale=1.0, lm_coef=0.0, kd_coef=0.0):
+        """loss_backward() with kd_coef * d(sum of the row terms)/d logits added, kd_coef = distill_weight * gscale / (ntok *
+        batch_den); the same buffers and storage forms.  Reads the teacher tensors distill_loss() was given."""
+        a, sh = self.act, self.sh
+        if "kd_lg" not in a:
+            raise RuntimeError("loss_backward_kd() needs distill_loss() on this forward")
+        Vp = self.layout.Vpad
+        cond, uncond, ldt, lse_c, lse_u, scale = a["kd_teacher"]
+        args = (a["logits"], Vp, sh.V, a["topic_ids"], a["targets"], a["lse_rows"], a["coef"], gscale, cond, uncond, ldt, lse_c, lse_u,
+                scale, a["kd_lg"], kd_coef, a["B"], sh.P, a["L"])
+        if a.get("x3") and self.hybrid:
+            dl = self.buf("dlogits_b", (a["M"], Vp), torch.bfloat16)
+            hip.loss_bwd_kd(*args, dl, Vp, Vp, lm_coef=lm_coef)
+            return dl
+        if a.get("x3"):
+            dlp = self.pbuf("dlogits_p", a["M"], Vp)
+            hip.loss_bwd_kd_x3(*args, dlp, Vp, lm_coef=lm_coef)
+            return dlp
+        dl = a["logits"] if a["logits"].dtype == self.tdt and self.dtype != hip.F32 else self.buf("dlogits", (a["M"], Vp))
+        hip.loss_bwd_kd(*args, dl, Vp, Vp, lm_coef=lm_coef)
+        return dl
+
     def dlogits_from(self, g32):
         """External d(logits) [B,T,V] fp32 (drop-in autograd path) -> padded compute-dtype buffer."""
         a = self.act

@@ -170,6 +170,11 @@ _SIGS = {
     "mmtg_decode_guidance": ([_vp, _vp, _l, _i, _f, _vp, _l, _i, _vp], _i),
     "mmtg_experience_drop": ([_i, _vp, _vp, _vp, _vp, _vp, _i, _l, _u, C.c_longlong, C.c_longlong, C.c_longlong, _vp], _i),
     "mmtg_guided_loss": ([_i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp], _i),
+    "mmtg_distill_fwd": ([_i, _vp, _l, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp], _i),
+    "mmtg_loss_bwd_kd": ([_i, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _l, _vp, _vp, _f, _vp, _f, _i, _i, _i,
+                         _vp, _l, _i, _vp], _i),
+    "mmtg_loss_bwd_kd_x3": ([_vp, _l, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _l, _vp, _vp, _f, _vp, _f, _i, _i, _i,
+                            _vp, _l, _l, _i, _vp], _i),
     "mmtg_decode_mirror": ([_vp, _l, _vp, _i, _vp], _i),
     "mmtg_decode_guidance_multi": ([_vp, _l, _i, _i, _vp, _vp, _l, _i, _vp], _i),
     "mmtg_decode_guidance_multi_form": ([_vp, _l, _i, _i, _vp, _vp, _l, _i, _i, _vp], _i),
@@ -1534,6 +1539,44 @@ def guided_loss(cond, uncond, ldl, V, lse_c, lse_u, topic_ids, targets, scales, 
     _check(lib().mmtg_guided_loss(dt(cond), _p(cond), _p(uncond), int(ldl), int(V), _p(lse_c), _p(lse_u), _p(topic_ids), _p(targets),
                                   C.addressof(arr), K, int(B), int(P), int(L), float(batch_den), _p(nll), _p(sample_ce), _p(ce),
                                   _stream()), "guided_loss")
+
+
+# distillation of a teacher's (guided) distribution (the rule: include/mmtg_hip.h; csrc/distill.hip)
+def _teacher(cond, uncond, lse_u):
+    if (uncond is None) != (lse_u is None):
+        raise ValueError("uncond and lse_u are given together or not at all")
+    if uncond is not None and (uncond.dtype != cond.dtype or uncond.shape != cond.shape):
+        raise ValueError("cond and uncond must have one storage type and shape")
+
+
+def distill_fwd(logits, ldl, cond, uncond, ldt, V, lse, lse_c, lse_u, scale, B, P, L, batch_den, kd_row, kd_lg, kd_sample, kd):
+    """kd_row [M], kd_lg [M], kd_sample [B] and the scalar kd [1] (fp32): KL(q || p) of the student's logits (row lse of loss_fwd)
+    against q = softmax(lu + scale (lc - lu)) of the teacher's cond / uncond logits and their row lse; uncond = lse_u = None:
+    q = softmax(lc).  Student and teacher are each fp32 or bf16."""
+    _teacher(cond, uncond, lse_u)
+    _check(lib().mmtg_distill_fwd(dt(logits), _p(logits), int(ldl), dt(cond), _p(cond), _p(uncond), int(ldt), int(V), _p(lse), _p(lse_c),
+                                  _p(lse_u), float(scale), int(B), int(P), int(L), float(batch_den), _p(kd_row), _p(kd_lg),
+                                  _p(kd_sample), _p(kd), _stream()), "distill_fwd")
+
+
+def loss_bwd_kd(logits, ldl, V, topic_ids, targets, lse, coef, gscale, cond, uncond, ldt, lse_c, lse_u, scale, kd_lg, kd_coef,
+                B, P, L, dlogits, ldd, Vpad, lm_coef=0.0):
+    """loss_bwd with the term's gradient: kd_lg from distill_fwd, kd_coef = distill_weight * gscale / (ntok * batch_den)."""
+    _teacher(cond, uncond, lse_u)
+    _check(lib().mmtg_loss_bwd_kd(dt(dlogits), dt(logits), _p(logits), int(ldl), int(V), _p(topic_ids), _p(targets), _p(lse), _p(coef),
+                                  float(gscale), float(lm_coef), dt(cond), _p(cond), _p(uncond), int(ldt), _p(lse_c), _p(lse_u),
+                                  float(scale), _p(kd_lg), float(kd_coef), int(B), int(P), int(L), _p(dlogits), int(ldd), int(Vpad),
+                                  _stream()), "loss_bwd_kd")
+
+
+def loss_bwd_kd_x3(logits, ldl, V, topic_ids, targets, lse, coef, gscale, cond, uncond, ldt, lse_c, lse_u, scale, kd_lg, kd_coef,
+                   B, P, L, planes, Vpad, lm_coef=0.0):
+    """... into a Planes pair (x3 mode)."""
+    _teacher(cond, uncond, lse_u)
+    _check(lib().mmtg_loss_bwd_kd_x3(_p(logits), int(ldl), int(V), _p(topic_ids), _p(targets), _p(lse), _p(coef), float(gscale),
+                                     float(lm_coef), dt(cond), _p(cond), _p(uncond), int(ldt), _p(lse_c), _p(lse_u), float(scale),
+                                     _p(kd_lg), float(kd_coef), int(B), int(P), int(L), _p(planes.t), planes.ld, planes.plane, int(Vpad),
+                                     _stream()), "loss_bwd_kd_x3")
 
 
 def decode_advance(pos):

@@ -82,8 +82,22 @@ class MMTGTrainer:
     def __init__(self, model, lr=1e-5, alpha=0.0, max_norm=1.0, betas=(0.9, 0.999), eps=1e-6,
                  weight_decay=0.0, warmup_steps=0, total_steps=None, distributed=False, bucket_mb=64.0,
                  lm_weight=0.0, param_groups=None, accumulation_steps=1, ema_decay=None, ema_warmup=True,
-                 ul_weight=0.0, ul_exclude_ids=None, cl_weight=0.0, cl_margin=0.5, experience_drop=0.0):
-        """experience_drop: the training side of classifier-free guidance (generate_samples(guidance_scale=...), GuidedDecoder).  A
+                 ul_weight=0.0, ul_exclude_ids=None, cl_weight=0.0, cl_margin=0.5, experience_drop=0.0,
+                 distill_weight=0.0, distill_teacher=None, distill_scale=1.0):
+        """distill_weight: weight of the distillation term (the rule is stated in include/mmtg_hip.h): per lyric row the Kullback-
+        Leibler divergence KL(q || p) of the model's distribution p from the teacher's q, so the objective becomes
+        ... + distill_weight * kd, normalised per sample.  distill_teacher: a second MMTG model on the same device, of any compute
+        mode, with the student's vocabulary and topic length; it runs in eval mode, is never updated and is no part of state_dict()
+        or of a checkpoint.  The trained model itself is refused (its forward would overwrite the step's activations): pass
+        copy.deepcopy(model).  distill_scale: q = softmax(lu + s (lc - lu)) of the teacher's logits for the batch (lc) and for the
+        batch without its images and texts (lu) -- the distribution generate_samples(guidance_scale=s) draws from, so that a model
+        trained towards it decodes plainly, at full batch and in every decoder, what guidance gave (choose s with evaluate_guided).
+        At the default 1.0 the teacher runs one forward per micro-step and q = softmax(lc): ordinary knowledge distillation, for
+        example of a 12-layer teacher into a 6-layer student; at any other scale it runs two.  step() and evaluate_batch() then also
+        return 'kd', the unweighted term.  0.0 (the default) launches nothing new and keeps no buffer.  Not together with ul_weight
+        (both replace the d(logits) kernel) or experience_drop (a row whose experience was dropped must not be pulled towards the
+        guided distribution of the full prompt).  Only the fused step takes the term.
+        experience_drop: the training side of classifier-free guidance (generate_samples(guidance_scale=...), GuidedDecoder).  A
         float p in [0, 1] replaces, per sample and with probability p, the images and texts of the experience by zeros -- exactly what
         generate.without_experience feeds the decoders as the default negative -- so that the branch guidance subtracts is a
         distribution the model was trained on.  A sequence (p_both, p_img, p_txt), each in [0, 1] and summing to at most 1, also drops
@@ -140,6 +154,27 @@ class MMTGTrainer:
         self.cl_weight, self.cl_margin = float(cl_weight), float(cl_margin)
         self.experience_drop = _check_experience_drop(experience_drop)
         self._exp_drop_on = any(p > 0.0 for p in self.experience_drop)
+        if isinstance(distill_weight, bool) or not isinstance(distill_weight, (int, float)) or not (0.0 <= distill_weight < float("inf")):
+            raise ValueError("distill_weight must be a finite float >= 0, got %r" % (distill_weight,))
+        from .constraints import check_guidance
+        try:
+            self.distill_scale = check_guidance(distill_scale)
+        except ValueError as e:
+            raise ValueError("distill_scale: %s" % e) from None
+        self.distill_weight = float(distill_weight)
+        if self.distill_weight > 0.0 and distill_teacher is None:
+            raise ValueError("distill_weight = %g needs distill_teacher: the term is measured against a teacher's logits" % self.distill_weight)
+        if self.distill_weight == 0.0 and distill_teacher is not None:
+            raise ValueError("distill_teacher with distill_weight = 0: the teacher would run for nothing; pass a weight > 0 or no teacher")
+        if self.distill_weight > 0.0 and self.ul_weight > 0.0:
+            raise ValueError("distill_weight > 0 with ul_weight > 0: both terms replace the d(logits) kernel and no kernel carries both")
+        if self.distill_weight > 0.0 and self._exp_drop_on:
+            raise ValueError("distill_weight > 0 with experience_drop: a row whose experience was dropped would be pulled towards the "
+                             "teacher's distribution for the full prompt")
+        if distill_teacher is not None and distill_teacher is model:
+            raise ValueError("distill_teacher is the trained model itself: its forward would overwrite the step's activations; "
+                             "pass a copy (copy.deepcopy(model))")
+        self.distill_teacher = distill_teacher
         self.accumulation_steps = accumulation_steps
         self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
         self.ema_updates = 0                    # updates of the average made so far
@@ -148,6 +183,16 @@ class MMTGTrainer:
         self.eng = model.engine()
         if self.ul_weight > 0.0:
             self.eng.set_ul_exclude(self.ul_exclude_ids)         # uploaded once, here
+        self.teng = None
+        if distill_teacher is not None:
+            self.teng = distill_teacher.engine()
+            if self.teng is self.eng:
+                raise ValueError("distill_teacher shares the trained model's engine: pass a copy (copy.deepcopy(model))")
+            if self.teng.dev != self.eng.dev:
+                raise ValueError("distill_teacher is on %s, the model on %s" % (self.teng.dev, self.eng.dev))
+            if (self.teng.sh.V, self.teng.sh.P) != (self.eng.sh.V, self.eng.sh.P):
+                raise ValueError("distill_teacher has V = %d, P = %d; the model has V = %d, P = %d: the two distributions must be over "
+                                 "one vocabulary on the same rows" % (self.teng.sh.V, self.teng.sh.P, self.eng.sh.V, self.eng.sh.P))
         self.group_plan = self.groups = None
         if param_groups is not None:
             from . import hip
@@ -215,11 +260,12 @@ class MMTGTrainer:
                             "ema_decay": self.ema_decay, "ema_warmup": self.ema_warmup,
                             "ul_weight": self.ul_weight, "ul_exclude_ids": tuple(self.ul_exclude_ids),
                             "cl_weight": self.cl_weight, "cl_margin": self.cl_margin, "experience_drop": self.experience_drop,
+                            "distill_weight": self.distill_weight, "distill_scale": self.distill_scale,
                             # for the record, like the rest: load_state_dict keeps the trainer's own groups as it keeps its own lr
                             "param_groups": None if self.group_plan is None else copy.deepcopy(self.group_plan.specs)}}
 
     def load_state_dict(self, sd):
-        """(accumulation_steps, ul_weight, ul_exclude_ids, cl_weight, cl_margin and experience_drop stay the trainer's own, like lr and the groups; an open window is abandoned)
+        """(accumulation_steps, ul_weight, ul_exclude_ids, cl_weight, cl_margin, experience_drop and the distill_* arguments stay the trainer's own, like lr and the groups; an open window is abandoned)
         A trainer with an average takes 'average' and 'updates' from the dict; from a dict without an average (an older
         checkpoint, a run that kept none) the average is dropped and restarts from the loaded weights at the next step.  The decay
         and the warm-up rule stay the trainer's own; a trainer without an average ignores the key."""
@@ -250,7 +296,7 @@ class MMTGTrainer:
     def step(self, batch, stage=3, filter_rows=True):
         """One optimisation step; returns device scalars (no host sync) {'loss','lm_loss','kl'} of the LOCAL rows (with ul_weight > 0
         also 'ul', the unweighted unlikelihood term; with cl_weight > 0 also 'cl', the unweighted contrastive term; with
-        experience_drop on and the model in training mode also 'experience_drop', the device int32 codes of the local rows).
+        distill_weight > 0 also 'kd', the unweighted distillation term; with experience_drop on and the model in training mode also 'experience_drop', the device int32 codes of the local rows).
         Returns None when the stage filter leaves no rows on a single rank (train.py:184-185); in a data-parallel
         group a rank without rows still takes part in the exchange and in the (identical) optimizer step.
 
@@ -379,6 +425,8 @@ class MMTGTrainer:
             first = not self._bwd_ran
             if first:               # once per window: the later backwards add to what this one writes
                 eng.zero_grad((n_local, int(batch["targets"].shape[1])) if "targets" in batch else None)
+            if self.distill_weight > 0.0:
+                teacher = self._teacher_pass(batch, stage)      # (first: the student's activations are the step's last)
             if self._exp_drop_on and self.model.training:
                 # (every micro-step draws its own codes: the step seed advances per forward)
                 eng.forward(batch, train_flag=True, training=True, logits_f32=_LOGITS_F32, exp_drop=self.experience_drop)
@@ -392,6 +440,11 @@ class MMTGTrainer:
                 ul = eng.ul_loss(batch_den=n_local)
                 ntok = max(1, int(batch["targets"].shape[1]) - 1)
                 dl = eng.loss_backward_ul(float(n_local), lm_coef, self.ul_weight / (ntok * n_local) * float(n_local))
+            elif self.distill_weight > 0.0:
+                # (every row takes part whatever its rating; the coefficient distill_weight * gscale / (ntok * batch_den))
+                kd = eng.distill_loss(*teacher, scale=self.distill_scale, batch_den=n_local)
+                ntok = max(1, int(batch["targets"].shape[1]) - 1)
+                dl = eng.loss_backward_kd(float(n_local), lm_coef, self.distill_weight / (ntok * n_local) * float(n_local))
             else:
                 dl = eng.loss_backward(float(n_local), lm_coef=lm_coef)
             if self.reducer is not None:
@@ -417,6 +470,8 @@ class MMTGTrainer:
                 out["ul"] = ul[0]
             if self.cl_weight > 0.0:
                 out["cl"] = cl[0]
+            if self.distill_weight > 0.0:
+                out["kd"] = kd[0]
             self._add_to_window(out, sc, n_local)
             if "exp_drop" in eng.act:       # (not a scalar of the window: the step's own rows, valid until the next forward)
                 out = dict(out, experience_drop=eng.act["exp_drop"])
@@ -431,8 +486,8 @@ class MMTGTrainer:
             self._wacc = out        # the step's own scalars: no launch that today's step does not have
             return
         if self._wacc is None:
-            # (slot 3 is 'ul', slot 4 'cl'; a slot whose term is off is neither written nor read)
-            self._wacc = torch.empty(5 if self.cl_weight > 0.0 else 4 if self.ul_weight > 0.0 else 3, device=sc.device, dtype=torch.float32)
+            # (slot 3 is 'ul', slot 4 'cl', slot 5 'kd'; a slot whose term is off is neither written nor read)
+            self._wacc = torch.empty(6 if self.distill_weight > 0.0 else 5 if self.cl_weight > 0.0 else 4 if self.ul_weight > 0.0 else 3, device=sc.device, dtype=torch.float32)
         if self._rows == 0:         # the window's first rows
             torch.mul(sc[:2], float(n), out=self._wacc[:2])
             torch.mul(out["kl"].reshape(1), float(n), out=self._wacc[2:3])
@@ -440,6 +495,8 @@ class MMTGTrainer:
                 torch.mul(out["ul"].reshape(1), float(n), out=self._wacc[3:4])
             if "cl" in out:
                 torch.mul(out["cl"].reshape(1), float(n), out=self._wacc[4:5])
+            if "kd" in out:
+                torch.mul(out["kd"].reshape(1), float(n), out=self._wacc[5:6])
         else:
             self._wacc[:2].add_(sc[:2], alpha=float(n))
             self._wacc[2:3].add_(out["kl"].reshape(1), alpha=float(n))
@@ -447,6 +504,8 @@ class MMTGTrainer:
                 self._wacc[3:4].add_(out["ul"].reshape(1), alpha=float(n))
             if "cl" in out:
                 self._wacc[4:5].add_(out["cl"].reshape(1), alpha=float(n))
+            if "kd" in out:
+                self._wacc[5:6].add_(out["kd"].reshape(1), alpha=float(n))
 
     def _close_begin(self, red, rows):
         """The closing call's part BEFORE its backward: the window's row count onto the device and into the exchange.  False when
@@ -493,6 +552,8 @@ class MMTGTrainer:
                 self.window["ul"] = None
             if self.cl_weight > 0.0:
                 self.window["cl"] = None
+            if self.distill_weight > 0.0:
+                self.window["kd"] = None
         elif self.accumulation_steps == 1:
             self.window = dict(self._wacc, rows=rows)
         else:
@@ -502,11 +563,34 @@ class MMTGTrainer:
                 self.window["ul"] = w[3]
             if self.cl_weight > 0.0:
                 self.window["cl"] = w[4]
+            if self.distill_weight > 0.0:
+                self.window["kd"] = w[5]
         self._end_window()
 
     def _end_window(self):
         self._micro = self._rows = 0
         self._bwd_ran = False
+
+    # ---- the distillation teacher
+    @torch.no_grad()
+    def _teacher_pass(self, batch, stage):
+        """The teacher's side of a micro-step, on the rows the student sees: at distill_scale != 1 its forward on the batch without
+        images and texts (eval mode) and the loss, whose logits and row lse go into buffers of the teacher engine's own (as in
+        evaluate_guided_batch); then its conditional forward and loss, whose logits and lse stay where they are -- the teacher runs
+        nothing else until the next call.  Returns (cond, lse_c, uncond or None, lse_u or None) for Engine.distill_loss."""
+        teng = self.teng
+        ulog = ulse = None
+        if self.distill_scale != 1.0:
+            teng.forward(batch, train_flag=True, training=False, logits_f32=_LOGITS_F32, exp_drop=NO_EXPERIENCE)
+            teng.loss(batch["rating"], stage)
+            a = teng.act
+            ulog = teng.buf("distill_uncond_logits", tuple(a["logits"].shape), a["logits"].dtype)
+            ulse = teng.buf("distill_uncond_lse", (a["M"],), torch.float32)
+            ulog.copy_(a["logits"])
+            ulse.copy_(a["lse_rows"])
+        teng.forward(batch, train_flag=True, training=False, logits_f32=_LOGITS_F32)
+        teng.loss(batch["rating"], stage)
+        return teng.act["logits"], teng.act["lse_rows"], ulog, ulse
 
     # ---- evaluation (train.py:241-268)
     @torch.no_grad()
@@ -596,13 +680,16 @@ class MMTGTrainer:
         """Forward + MyLoss (+ KL) of one validation batch, no update: the stage's row filter, the engine's forward in eval mode (no
         dropout) with compute-dtype logits -- no fp32 [B, T, V] tensor, no autograd boundary -- and the loss kernels.  Returns the
         DEVICE scalars {'loss': MyLoss mean, 'kl': kl, 'total': loss + alpha * kl} (no host sync), or None when the filter leaves
-        no rows (train.py:252-253 `continue`s).  With ul_weight > 0 also 'ul', the unweighted unlikelihood term of the batch, with cl_weight > 0 also 'cl'; 'total'
+        no rows (train.py:252-253 `continue`s).  With ul_weight > 0 also 'ul', the unweighted unlikelihood term of the batch, with cl_weight > 0 also 'cl', with
+        distill_weight > 0 also 'kd' (against the teacher's distribution for the batch as given, also under without_experience); 'total'
         stays the reference's validation loss.  without_experience=True runs the forward on the batch without its images and
         texts (generate.without_experience): the validation loss of the branch guidance subtracts."""
         eng = self.eng
         batch = self._eval_rows(batch, stage, filter_rows)
         if batch is None:
             return None
+        if self.distill_weight > 0.0:
+            teacher = self._teacher_pass(batch, stage)
         if without_experience:
             eng.forward(batch, train_flag=True, training=False, logits_f32=_LOGITS_F32, exp_drop=NO_EXPERIENCE)
         else:
@@ -614,6 +701,8 @@ class MMTGTrainer:
             out["ul"] = eng.ul_loss()[0]
         if self.cl_weight > 0.0:
             out["cl"] = eng.cl_loss(self.cl_margin)[0]
+        if self.distill_weight > 0.0:
+            out["kd"] = eng.distill_loss(*teacher, scale=self.distill_scale)[0]
         return out
 
     @torch.no_grad()
