@@ -552,7 +552,8 @@ MMTG_API int mmtg_slab_sum(const float* part, int splits, long stride, float* ds
  * config 8: 256x256 tiles, ONE 1024-thread workgroup per CU (sixteen waves, a 64x64 quadrant each) over a ring of three 32-k
  *           stages (96 KB of LDS), two stages in flight while one is read (65536 floats and 16 counters per tile and split; K
  *           slices are multiples of 64).  Same summation order per element as config 0: bit-equal to it at an equal split
- *           count.  (bf16 operands only: not combined with 2 / 4.)                                                          */
+ *           count.  (bf16 operands only: not combined with 2 / 4.)
+ * Every other value of config is refused, 4 without 2 (alone or beside 1 / 8) included.                                      */
 typedef struct mmtg_wgrad_problem {
     const void* A; long lda;
     const void* B; long ldb;

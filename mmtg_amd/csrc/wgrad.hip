@@ -577,8 +577,9 @@ extern "C" int mmtg_wgrad_group(int config, int n, const mmtg_wgrad_problem* pro
                                 unsigned* counters, long n_counters, int accumulate, void* stream) {
     const bool x3 = (config & 2) != 0;             // split-precision operands (plane pairs), 128x128 tiles only
     const bool x3c = x3 && (config & 4) != 0;      // ... on combined stages (all four planes of a K tile per stage, two workgroups per CU)
+    const bool stray4 = !x3 && (config & 4) != 0;  // 4 alone (or beside 1 / 8) is no configuration: it must not run as 0, 1 or 8
     config &= ~6;
-    MMTG_REQUIRE(config == 0 || ((config == 1 || config == 8) && !x3),
+    MMTG_REQUIRE(!stray4 && (config == 0 || ((config == 1 || config == 8) && !x3)),
                  "wgrad_group: config 0 (128x128 tiles), 1 (256x256 eight-phase tiles), 8 (256x256 tiles, 16-wave ring), 2 (128x128 tiles, x3 operands) or 6 (x3, combined stages)");
     const int TB = config ? 256 : 128, NWV = config == 8 ? 16 : config ? 8 : 4, KQ = config == 1 ? 128 : 64;
     MMTG_REQUIRE(n >= 1 && n <= WG_MAXP && probs, "wgrad_group: 1..%d problems", WG_MAXP);

@@ -883,7 +883,9 @@ WGRAD_RING = 8      # mmtg_wgrad_group config: 256x256 tiles, one 16-wave workgr
 
 
 def wgrad_group_sizes(shapes, splits, config=0):
-    """(tiles, workspace floats, counters) of a grouped launch over problems of the given (M, N) shapes."""
+    """(tiles, workspace floats, counters) of a grouped launch over problems of the given (M, N) shapes.  The split-precision
+    bits of config (2, 6) do not change the tiles: configs 2 and 6 size as config 0."""
+    config &= ~6
     tb, nw = (256, 16) if config == WGRAD_RING else (256, 8) if config else (128, 4)
     tiles = sum(((M + tb - 1) // tb) * ((N + tb - 1) // tb) for (M, N) in shapes)
     return tiles, tiles * splits * tb * tb, tiles * nw
