@@ -1248,13 +1248,41 @@ MMTG_API int mmtg_decode_mirror_multi(long long* seq, long ldseq, const int* pos
  *   a sample's rows and one thread a scale's samples in sample order: no atomics, equal inputs give equal bits.  Where c == u bit
  *   for bit and lse_c == lse_u, g_k = lu for every k and all K results of the row are the same bits.
  *   Fails before any device call: a null pointer (topic_ids excepted), K outside 1 .. 8, a scale that is not finite or is negative,
- *   V < 1, ldl < V, bf16 rows that are not 16-byte aligned (ldl % 8, the bases), B < 1, P < 0, L < 2, batch_den not finite or <= 0. */
+ *   V < 1, ldl < V, bf16 rows that are not 16-byte aligned (ldl % 8, the bases), B < 1, P < 0, L < 2, batch_den not finite or <= 0.
+ * mmtg_guided_loss_multi: the cross-entropy of the lyric under the distribution mmtg_decode_guidance_multi selects from
+ *   (evaluate_modality_guided), for G scale tuples in one sweep over K logits matrices.  logits: a HOST array of K device pointers,
+ *   2 <= K <= MMTG_GUIDED_MAX_BRANCHES, pointer 0 the conditional matrix and pointers 1 .. K - 1 the running negatives, each [M, ldl] of
+ *   `logits_dtype` with the one stride ldl; lse: a HOST array of K device pointers to the fp32 row log-sum-exps [M] as mmtg_loss_fwd
+ *   produced them; both arrays are read at call time and their entries handed to the kernel by value.  scales: a HOST array of
+ *   G (K - 1) floats, tuple-major (scales[g (K - 1) + k - 1] is tuple g's scale for branch k), 1 <= G <= MMTG_GUIDED_MAX_SCALES, each
+ *   finite and >= 0, passed by value.  targets, B, P, L, batch_den, the loss rows, the clamped labels and the PAD rows are
+ *   mmtg_guided_loss's; there is no topic_ids.  In fp32 and in mmtg_decode_guidance_multi's order of operations, so that the
+ *   training-side and the decode-side numbers describe one distribution:
+ *     l_k[v] = x_k[v] - lse_k[m]   (lc = l_0)      w_k = scales[g][k - 1] - 1   (an fp32 subtraction, on the host)
+ *     g = lc;   g = g + w_k * (lc - l_k)   for k = 1 .. K - 1 in turn   (one fused multiply-add per branch, in every instantiation)
+ *     nll_g[m] = L(g) - g[label],   L(x) = max x + log(sum_v exp(x[v] - max x))
+ *   Outputs, all fp32: nll [G, M] (0 outside the loss rows), sample_ce [G, B], ce [G] = sum_b sample_ce[g, b] / batch_den in sample
+ *   order.  One workgroup of 256 threads per row, with mmtg_guided_loss's trip structure: every logit of each of the K rows is
+ *   fetched once and feeds all G running (max, sum) pairs; 16-byte loads (slices of eight logits, the K rows' loads of a slice issued
+ *   before the first is used) only where ALL K row pointers are 16-byte aligned, otherwise and for the tail V % 8 one logit at a
+ *   time (an fp32 ldl may be odd); nothing is staged, so V and L have no limit.  Wave shuffles and static LDS words reduce in a fixed
+ *   order: no atomics, equal inputs give equal bits, equal tuples give equal bits.  One expression serves every K, so a branch whose
+ *   w_k is 0 (scale 1) adds +-0 and the row's nll is the bits of the launch without that matrix, at K - 1; x_k equal to x_0 bit for
+ *   bit with equal lse makes branch k vanish bit for bit at any scale; all scales at 1 give L(lc) - lc[label] for every tuple.  The
+ *   weight on lc, 1 + sum_k w_k, may be negative (three scales at 0 give -2): allowed.
+ *   Fails before any device call: a null pointer (any of the K entries of either array included), K outside 2 .. 4, G outside 1 .. 8,
+ *   a scale that is not finite or is negative, V < 1, ldl < V, bf16 rows that are not 16-byte aligned (ldl % 8, any base), an fp32
+ *   base that is not 4-byte aligned, B < 1, P < 0, L < 2, batch_den not finite or <= 0, nll overlapping any of the K matrices.       */
 #define MMTG_GUIDED_MAX_SCALES 8
+#define MMTG_GUIDED_MAX_BRANCHES 4
 MMTG_API int mmtg_experience_drop(int dtype, const float* img, const float* txt, void* img_out, void* txt_out, int* code, int B, long n,
                          unsigned seed, long long c_both, long long c_img, long long c_txt, void* stream);
 MMTG_API int mmtg_guided_loss(int logits_dtype, const void* cond, const void* uncond, long ldl, int V, const float* lse_c,
                      const float* lse_u, const long long* topic_ids, const long long* targets, const float* scales, int K,
                      int B, int P, int L, float batch_den, float* nll, float* sample_ce, float* ce, void* stream);
+MMTG_API int mmtg_guided_loss_multi(int logits_dtype, const void* const* logits, const float* const* lse, int K, long ldl, int V,
+                           const long long* targets, const float* scales, int G, int B, int P, int L, float batch_den,
+                           float* nll, float* sample_ce, float* ce, void* stream);
 
 /* ---------------------------------------------------------------- distillation of a teacher's (guided) distribution
  * The training-time end of the guidance arc (csrc/distill.hip; MMTGTrainer(distill_weight=..., distill_teacher=...,

@@ -195,6 +195,139 @@ __global__ __launch_bounds__(1024) void guided_sample_kernel(const float* __rest
     }
 }
 
+// ---------------------------------------------------------------- guided cross-entropy, K logits matrices and G scale tuples
+constexpr int MB = MMTG_GUIDED_MAX_BRANCHES;
+template <typename LT> struct Mats { const LT* x[MB]; const float* lse[MB]; };
+struct Weights { float w[GK][MB - 1]; };           // w[g][k - 1] = scale of tuple g for branch k, minus 1 (the host's fp32 subtraction)
+
+// the rule, in mmtg_decode_guidance_multi's order: d[k - 1] = lc - l_k.  One expression for every K: a branch with w = 0 (or d = 0)
+// adds +-0 and leaves the bits of the K - 1 form.  The step is an EXPLICIT fused multiply-add, and the functions below switch the
+// compiler's own contraction off: left to it, the K = 2 instantiation fused the step (v_fmac_f32) where K = 3 multiplied and added
+// in packed halves (v_pk_mul_f32, v_pk_add_f32), and the two forms round differently.
+template <int K>
+__device__ __forceinline__ float guide_multi(float lc, const float (&d)[MB - 1], const float (&w)[MB - 1]) {
+    float g = lc;
+#pragma unroll
+    for (int k = 1; k < K; ++k) g = __builtin_fmaf(w[k - 1], d[k - 1], g);
+    return g;
+}
+
+// eight logits of each of the K rows into the G running (max, sum)s of a thread: fold8's steps per tuple
+template <int K, int G>
+__device__ __forceinline__ void fold8_multi(const float (&x)[MB][8], const float (&Ls)[MB], const Weights& wt, float (&mx)[GK],
+                                            float (&sm)[GK]) {
+#pragma clang fp contract(off)
+    float lc[8], d[8][MB - 1];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        lc[e] = x[0][e] - Ls[0];
+#pragma unroll
+        for (int k = 1; k < K; ++k) d[e][k - 1] = lc[e] - (x[k][e] - Ls[k]);
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = guide_multi<K>(lc[e], d[e], wt.w[g]);
+        const float m8 = fmaxf(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), fmaxf(fmaxf(v[4], v[5]), fmaxf(v[6], v[7])));
+        if (m8 > mx[g]) { sm[g] *= exp_fast(mx[g] - m8); mx[g] = m8; }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sm[g] += exp_fast(v[e] - mx[g]);
+    }
+}
+
+// one workgroup per row m: nll[g * M + m] for g < G, from the K rows x[k] + m * ldl.  guided_row_kernel's trip structure: slices of
+// 2048 logits (eight per thread), two in flight, then the odd trailing slice, then the tail V % 8 -- or, where one of the K rows is
+// not 16-byte aligned, every logit on its own.  The 2 K (or K) loads of a trip are issued before the first is used.
+template <typename LT, int K, int G>
+__global__ __launch_bounds__(256) void guided_multi_row_kernel(Mats<LT> mt, long ldl, int V, const long long* __restrict__ targets,
+        Weights wt, int P, int L, long M, float* __restrict__ nll) {
+#pragma clang fp contract(off)
+    __shared__ float shm[GK][4];
+    __shared__ float shs[GK][4];
+    const int Tt = P + L;
+    const long m = blockIdx.x;
+    const int b = (int)(m / Tt), t = (int)(m % Tt), tid = threadIdx.x;
+    if (t < P || t + 1 >= Tt) {
+        if (tid < G) nll[(long)tid * M + m] = 0.f;
+        return;
+    }
+    const LT* r[MB];
+    float Ls[MB];
+    uintptr_t bits = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        r[k] = mt.x[k] + m * ldl;
+        Ls[k] = mt.lse[k][m];
+        bits |= reinterpret_cast<uintptr_t>(r[k]);
+    }
+    float mx[GK], sm[GK];
+#pragma unroll
+    for (int g = 0; g < GK; ++g) { mx[g] = -INFINITY; sm[g] = 0.f; }
+    int done = 0;
+    if ((bits & 15) == 0) {
+        const int V8 = V & ~7;
+        int v = tid * 8;
+        for (; v + 2048 < V8; v += 4096) {
+            float x0[MB][8], x1[MB][8];
+#pragma unroll
+            for (int k = 0; k < K; ++k) load8(r[k] + v, x0[k]);
+#pragma unroll
+            for (int k = 0; k < K; ++k) load8(r[k] + v + 2048, x1[k]);
+            fold8_multi<K, G>(x0, Ls, wt, mx, sm);
+            fold8_multi<K, G>(x1, Ls, wt, mx, sm);
+        }
+        if (v < V8) {
+            float x0[MB][8];
+#pragma unroll
+            for (int k = 0; k < K; ++k) load8(r[k] + v, x0[k]);
+            fold8_multi<K, G>(x0, Ls, wt, mx, sm);
+        }
+        done = V8;
+    }
+    for (int v = done + tid; v < V; v += 256) {
+        float x[MB], d[MB - 1];
+#pragma unroll
+        for (int k = 0; k < K; ++k) x[k] = (float)r[k][v];
+        const float lc = x[0] - Ls[0];
+#pragma unroll
+        for (int k = 1; k < K; ++k) d[k - 1] = lc - (x[k] - Ls[k]);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float gv = guide_multi<K>(lc, d, wt.w[g]);
+            if (gv > mx[g]) { sm[g] *= exp_fast(mx[g] - gv); mx[g] = gv; }
+            sm[g] += exp_fast(gv - mx[g]);
+        }
+    }
+    // fixed order: the wave's butterfly, then the four waves' pairs in wave order
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float om = __shfl_xor(mx[g], off, 64);
+            const float os = __shfl_xor(sm[g], off, 64);
+            ms_merge(mx[g], sm[g], om, os);
+        }
+        if ((tid & 63) == 0) { shm[g][tid >> 6] = mx[g]; shs[g][tid >> 6] = sm[g]; }
+    }
+    __syncthreads();
+    if (tid < G) {
+        float mm = shm[tid][0], sv = shs[tid][0];
+        for (int w = 1; w < 4; ++w) ms_merge(mm, sv, shm[tid][w], shs[tid][w]);
+        long long lab = targets[(long)b * L + (t + 1 - P)];
+        if (lab < 0) lab = 0;
+        if (lab >= V) lab = V - 1;
+        float d[MB - 1], w[MB - 1];
+        const float lc = (float)r[0][lab] - Ls[0];
+#pragma unroll
+        for (int k = 1; k < K; ++k) {
+            d[k - 1] = lc - ((float)r[k][lab] - Ls[k]);
+            w[k - 1] = wt.w[tid][k - 1];
+        }
+        nll[(long)tid * M + m] = (mm + logf(sv)) - guide_multi<K>(lc, d, w);
+    }
+}
+
 // whether the byte ranges [a, a + na) and [b, b + nb) share a byte
 bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
@@ -289,5 +422,88 @@ extern "C" int mmtg_guided_loss(int logits_dtype, const void* cond, const void* 
         launch_guided_rows<bf16>(K, M, s, (const bf16*)cond, (const bf16*)uncond, ldl, V, lse_c, lse_u, targets, sc, P, L, nll);
     hipLaunchKernelGGL(guided_sample_kernel, dim3(1), dim3(1024), 0, s, (const float*)nll, K, B, P, L, M, batch_den, sample_ce, ce);
     MMTG_LAUNCH_CHECK("guided_loss");
+    return MMTG_OK;
+}
+
+template <typename LT, int K>
+static void launch_guided_multi_rows(int G, long M, hipStream_t s, const Mats<LT>& mt, long ldl, int V, const long long* targets,
+                                     const Weights& wt, int P, int L, float* nll) {
+#define GM(GG) hipLaunchKernelGGL((guided_multi_row_kernel<LT, K, GG>), dim3((unsigned)M), dim3(256), 0, s, mt, ldl, V, targets, wt, P, L, M, nll)
+    switch (G) {
+        case 1: GM(1); break;
+        case 2: GM(2); break;
+        case 3: GM(3); break;
+        case 4: GM(4); break;
+        case 5: GM(5); break;
+        case 6: GM(6); break;
+        case 7: GM(7); break;
+        default: GM(8); break;
+    }
+#undef GM
+}
+
+template <typename LT>
+static void launch_guided_multi(int K, int G, long M, hipStream_t s, const void* const* logits, const float* const* lse, long ldl, int V,
+                                const long long* targets, const Weights& wt, int P, int L, float* nll) {
+    Mats<LT> mt;
+    for (int k = 0; k < MB; ++k) {          // (the slots behind K repeat matrix 0: never read)
+        mt.x[k] = (const LT*)logits[k < K ? k : 0];
+        mt.lse[k] = lse[k < K ? k : 0];
+    }
+    if (K == 2) launch_guided_multi_rows<LT, 2>(G, M, s, mt, ldl, V, targets, wt, P, L, nll);
+    else if (K == 3) launch_guided_multi_rows<LT, 3>(G, M, s, mt, ldl, V, targets, wt, P, L, nll);
+    else launch_guided_multi_rows<LT, 4>(G, M, s, mt, ldl, V, targets, wt, P, L, nll);
+}
+
+extern "C" int mmtg_guided_loss_multi(int logits_dtype, const void* const* logits, const float* const* lse, int K, long ldl, int V,
+                                      const long long* targets, const float* scales, int G, int B, int P, int L, float batch_den,
+                                      float* nll, float* sample_ce, float* ce, void* stream) {
+    const char* what = "guided_loss_multi";
+    MMTG_REQUIRE(logits_dtype == MMTG_F32 || logits_dtype == MMTG_BF16, "%s: bad logits dtype %d", what, logits_dtype);
+    MMTG_REQUIRE(logits, "%s: logits is a null pointer", what);
+    MMTG_REQUIRE(lse, "%s: lse is a null pointer", what);
+    MMTG_REQUIRE(targets, "%s: targets is a null pointer", what);
+    MMTG_REQUIRE(scales, "%s: scales is a null pointer", what);
+    MMTG_REQUIRE(nll, "%s: nll is a null pointer", what);
+    MMTG_REQUIRE(sample_ce, "%s: sample_ce is a null pointer", what);
+    MMTG_REQUIRE(ce, "%s: ce is a null pointer", what);
+    MMTG_REQUIRE(K >= 2 && K <= MMTG_GUIDED_MAX_BRANCHES, "%s: K = %d logits matrices (2 .. %d)", what, K, MMTG_GUIDED_MAX_BRANCHES);
+    MMTG_REQUIRE(G >= 1 && G <= MMTG_GUIDED_MAX_SCALES, "%s: G = %d scale tuples (1 .. %d)", what, G, MMTG_GUIDED_MAX_SCALES);
+    for (int k = 0; k < K; ++k) {
+        MMTG_REQUIRE(logits[k], "%s: logits[%d] is a null pointer", what, k);
+        MMTG_REQUIRE(lse[k], "%s: lse[%d] is a null pointer", what, k);
+    }
+    Weights wt;
+    for (int g = 0; g < GK; ++g)
+        for (int k = 1; k < MB; ++k) {
+            float sv = 1.f;
+            if (g < G && k < K) {
+                sv = scales[g * (K - 1) + (k - 1)];
+                MMTG_REQUIRE(sv >= 0.f && sv <= 3.0e38f, "%s: scale %d of tuple %d = %g must be finite and >= 0", what, k - 1, g, (double)sv);
+            }
+            wt.w[g][k - 1] = sv - 1.f;
+        }
+    MMTG_REQUIRE(V >= 1, "%s: V = %d must be positive", what, V);
+    MMTG_REQUIRE(ldl >= V, "%s: ldl %ld is below V %d", what, ldl, V);
+    for (int k = 0; k < K; ++k) {
+        MMTG_REQUIRE(logits_dtype == MMTG_F32 || (ldl % 8 == 0 && MMTG_ALIGNED16(logits[k])),
+                     "%s: bf16 rows must be 16-byte aligned (ldl %ld a multiple of 8, aligned bases; matrix %d)", what, ldl, k);
+        MMTG_REQUIRE(logits_dtype == MMTG_BF16 || (((uintptr_t)logits[k]) & 3) == 0, "%s: fp32 rows must be 4-byte aligned (matrix %d)", what, k);
+    }
+    MMTG_REQUIRE(B >= 1, "%s: B = %d must be positive", what, B);
+    MMTG_REQUIRE(P >= 0, "%s: P = %d must not be negative", what, P);
+    MMTG_REQUIRE(L >= 2, "%s: L = %d lyric columns; a loss row needs 2", what, L);
+    MMTG_REQUIRE(batch_den > 0.f && batch_den <= 3.0e38f, "%s: batch_den = %g must be finite and > 0", what, (double)batch_den);
+    const long M = (long)B * (P + L);
+    MMTG_REQUIRE(M <= 0x7fffffffL, "%s: %ld rows", what, M);
+    const size_t es = logits_dtype == MMTG_F32 ? 4 : 2;
+    for (int k = 0; k < K; ++k)
+        MMTG_REQUIRE(!overlaps(nll, (size_t)G * M * 4, logits[k], ((size_t)(M - 1) * ldl + V) * es), "%s: nll overlaps logits matrix %d", what, k);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(MMTG_PROF_LOSS, s, (3.0 * (K - 1) + 1.0 + (2.0 * (K - 1) + 3.0) * G) * B * (L - 1) * V, (double)es * K * B * (L - 1) * V);
+    if (logits_dtype == MMTG_F32) launch_guided_multi<float>(K, G, M, s, logits, (const float* const*)lse, ldl, V, targets, wt, P, L, nll);
+    else launch_guided_multi<bf16>(K, G, M, s, logits, (const float* const*)lse, ldl, V, targets, wt, P, L, nll);
+    hipLaunchKernelGGL(guided_sample_kernel, dim3(1), dim3(1024), 0, s, (const float*)nll, G, B, P, L, M, batch_den, sample_ce, ce);
+    MMTG_LAUNCH_CHECK("guided_loss_multi");
     return MMTG_OK;
 }

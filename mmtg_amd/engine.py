@@ -1090,6 +1090,27 @@ class Engine:
         a.update(guided_nll=nll, guided_sample_ce=smp, guided_ce=ce)
         return ce
 
+    def guided_loss_multi(self, scale_tuples, neg_logits, neg_lses, batch_den=None):
+        """After forward() and loss() on the conditional batch: the cross-entropy of the lyric under lc + sum_k (s_k - 1) (lc - l_k),
+        what ModalityGuidedDecoder selects from, for the G <= 8 tuples of len(neg_logits) scales each, with the 1 .. 3 running
+        negatives' logits [M, Vpad] (the storage type of this forward's, buffers of the caller's own) and their row lse [M] in branch
+        order.  Returns the device tensor ce [G]; nll [G, M] and sample_ce [G, B] are recorded in act."""
+        a, sh = self.act, self.sh
+        B, L, M, G = a["B"], a["L"], a["M"], len(scale_tuples)
+        if "lse_rows" not in a:
+            raise RuntimeError("guided_loss_multi() needs loss() on this forward (it reads the row lse)")
+        lg = a["logits"]
+        if len(neg_logits) != len(neg_lses) or any(x.dtype != lg.dtype or x.numel() != lg.numel() for x in neg_logits) or any(
+                v.numel() != M for v in neg_lses):
+            raise ValueError("guided_loss_multi: the negatives' logits and lse must have the conditional forward's type and shape")
+        nll = self.buf("guided_nll", (G, M), torch.float32)
+        smp = self.buf("guided_sample_ce", (G, B), torch.float32)
+        ce = self.buf("guided_ce", (G,), torch.float32)
+        hip.guided_loss_multi([lg] + list(neg_logits), [a["lse_rows"]] + list(neg_lses), self.layout.Vpad, sh.V, a["targets"],
+                              scale_tuples, B, sh.P, L, float(B if batch_den is None else batch_den), nll, smp, ce)
+        a.update(guided_nll=nll, guided_sample_ce=smp, guided_ce=ce)
+        return ce
+
     # ---- distillation of a teacher's (guided) distribution (the rule: include/mmtg_hip.h; MMTGTrainer(distill_weight=...))
     def distill_loss(self, teacher_logits, teacher_lse, uncond_logits=None, uncond_lse=None, scale=1.0, batch_den=None):
         """After forward() and loss(): KL(q || p) of this forward's logits against q = softmax(lu + scale (lc - lu)) of a teacher's

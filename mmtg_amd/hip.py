@@ -170,6 +170,7 @@ _SIGS = {
     "mmtg_decode_guidance": ([_vp, _vp, _l, _i, _f, _vp, _l, _i, _vp], _i),
     "mmtg_experience_drop": ([_i, _vp, _vp, _vp, _vp, _vp, _i, _l, _u, C.c_longlong, C.c_longlong, C.c_longlong, _vp], _i),
     "mmtg_guided_loss": ([_i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp], _i),
+    "mmtg_guided_loss_multi": ([_i, _vp, _vp, _i, _l, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp], _i),
     "mmtg_distill_fwd": ([_i, _vp, _l, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _f, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp], _i),
     "mmtg_loss_bwd_kd": ([_i, _i, _vp, _l, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _l, _vp, _vp, _f, _vp, _f, _i, _i, _i,
                          _vp, _l, _i, _vp], _i),
@@ -1541,6 +1542,28 @@ def guided_loss(cond, uncond, ldl, V, lse_c, lse_u, topic_ids, targets, scales, 
     _check(lib().mmtg_guided_loss(dt(cond), _p(cond), _p(uncond), int(ldl), int(V), _p(lse_c), _p(lse_u), _p(topic_ids), _p(targets),
                                   C.addressof(arr), K, int(B), int(P), int(L), float(batch_den), _p(nll), _p(sample_ce), _p(ce),
                                   _stream()), "guided_loss")
+
+
+GUIDED_MAX_BRANCHES = 4
+
+
+def guided_loss_multi(mats, lses, ldl, V, targets, scale_tuples, B, P, L, batch_den, nll, sample_ce, ce):
+    """nll [G, M], sample_ce [G, B] and ce [G] (fp32): the cross-entropy of the lyric under lc + sum_k (s_k - 1) (lc - l_k), the rule of
+    decode_guidance_multi, for the G <= 8 tuples of K - 1 host floats `scale_tuples`, from the K = 2 .. 4 logits matrices `mats`
+    (mats[0] the conditional one; one storage type, row stride ldl) and their row lse of loss_fwd `lses`."""
+    K, G = len(mats), len(scale_tuples)
+    if len(lses) != K:
+        raise ValueError("guided_loss_multi: %d logits matrices beside %d lse vectors" % (K, len(lses)))
+    if any(m.dtype != mats[0].dtype for m in mats[1:]):
+        raise ValueError("guided_loss_multi: the logits matrices must have one storage type")
+    if any(len(t) != K - 1 for t in scale_tuples):
+        raise ValueError("guided_loss_multi: every scale tuple holds K - 1 = %d scales" % (K - 1))
+    xs = (C.c_void_p * max(K, 1))(*[_p(m) for m in mats])
+    ls = (C.c_void_p * max(K, 1))(*[_p(v) for v in lses])
+    arr = (C.c_float * max(G * (K - 1), 1))(*[float(s) for t in scale_tuples for s in t])
+    _check(lib().mmtg_guided_loss_multi(dt(mats[0]) if K else F32, C.addressof(xs), C.addressof(ls), K, int(ldl), int(V), _p(targets),
+                                        C.addressof(arr), G, int(B), int(P), int(L), float(batch_den), _p(nll), _p(sample_ce), _p(ce),
+                                        _stream()), "guided_loss_multi")
 
 
 # distillation of a teacher's (guided) distribution (the rule: include/mmtg_hip.h; csrc/distill.hip)

@@ -60,6 +60,51 @@ def _check_scales(scales):
     return [check_guidance(s) for s in scales]
 
 
+def _check_scale_triples(scales):
+    """The scales of the per-modality guided validation loss as a list of float triples (guidance_scale, image_guidance_scale,
+    text_guidance_scale): 1 .. 8 of them, each through constraints.check_modality_guidance, whose messages name the decoder's arguments."""
+    from .constraints import check_guidance, check_modality_guidance
+    from .hip import GUIDED_MAX_SCALES
+    msg = "scales must be a sequence of 1 .. %d (guidance_scale, image_guidance_scale, text_guidance_scale) triples, got %r" % (
+        GUIDED_MAX_SCALES, scales)
+    if isinstance(scales, (str, bytes)):
+        raise ValueError(msg)
+    try:
+        scales = list(scales)
+    except TypeError:
+        raise ValueError(msg) from None
+    if not 1 <= len(scales) <= GUIDED_MAX_SCALES:
+        raise ValueError("scales must hold 1 .. %d triples of guidance scales, got %d" % (GUIDED_MAX_SCALES, len(scales)))
+    out = []
+    for t in scales:
+        if isinstance(t, (str, bytes)):
+            raise ValueError(msg)
+        try:
+            t = tuple(t)
+        except TypeError:
+            raise ValueError(msg) from None
+        if len(t) != 3:
+            raise ValueError(msg)
+        check_modality_guidance(*t)
+        out.append(tuple(check_guidance(s) for s in t))
+    return out
+
+
+def best_scale(result):
+    """The entry of result['scales'] with the lowest result['ce'] (the first of equal minima), for the result of
+    MMTGTrainer.evaluate_guided (a float) or evaluate_modality_guided (a triple).  A result over no rows, or one with a ce that is
+    not finite, raises a ValueError: there is nothing to choose by."""
+    import math
+    scales, ce = list(result["scales"]), [float(v) for v in result["ce"]]
+    if int(result["rows"]) == 0:
+        raise ValueError("best_scale: the result covers no rows (rows == 0)")
+    if len(scales) != len(ce) or not ce:
+        raise ValueError("best_scale: %d scales beside %d ce values" % (len(scales), len(ce)))
+    if not all(math.isfinite(v) for v in ce):
+        raise ValueError("best_scale: ce must be finite, got %r" % (ce,))
+    return scales[min(range(len(ce)), key=ce.__getitem__)]
+
+
 def _check_experience_drop(value):
     """MMTGTrainer's experience_drop as the triple (p_both, p_img, p_txt): a float p in [0, 1] is (p, 0, 0); a sequence of three
     floats, each in [0, 1] with a sum of at most 1, is itself.  Anything else raises a ValueError that names the argument."""
@@ -674,6 +719,83 @@ class MMTGTrainer:
             return {"scales": [float(s) for s in scales], "ce": [0.0] * K, "ce_cond": 0.0, "ce_uncond": 0.0, "rows": 0}
         v = (acc / float(rows)).tolist()
         return {"scales": [float(s) for s in scales], "ce": v[:K], "ce_cond": v[K], "ce_uncond": v[K + 1], "rows": rows}
+
+    @torch.no_grad()
+    def evaluate_modality_guided_batch(self, batch, scales, stage=3, filter_rows=True):
+        """The per-modality guided validation loss of one batch: the cross-entropy of the held-out lyric under
+        lc + sum_k (s_k - 1) (lc - l_k), the distribution generate_samples(guidance_scale=, image_guidance_scale=,
+        text_guidance_scale=) and ModalityGuidedDecoder draw from, for up to eight triples (guidance_scale, image_guidance_scale,
+        text_guidance_scale) at once (each goes through constraints.check_modality_guidance).  A branch runs if any triple's scale
+        for it differs from 1, in the decoder's order u, i, t; its negative is the batch itself without its images and texts, without
+        its images or without its texts (exp_drop (1, 0, 0), (0, 1, 0), (0, 0, 1): what generate.without_experience / without_images
+        / without_texts feed the decoders).  Each negative's forward and loss run first, and its logits and row lse are copied
+        into engine buffers of its own, guided_neg{k}_logits and guided_neg{k}_lse: up to three more [M, Vpad] matrices in the
+        logits' storage type, 402 MB each at 64 x 236 in bf16.  The conditional forward and its loss run last, so its logits stay in
+        place; then one mmtg_guided_loss_multi launch covers all triples (a triple's scale for a running branch may be 1).  When no
+        branch runs -- every triple is (1, 1, 1) -- nothing is launched and every ce is ce_cond.  Returns device values, no host
+        sync: {'ce': [G], 'ce_cond': the plain mean of the conditional sample_ce, 'ce_negatives': {'u' / 'i' / 't': the running
+        branches' own}, 'rows': the row count}, or None when the filter leaves no row."""
+        from .constraints import GUIDANCE_BRANCHES
+        scales = _check_scale_triples(scales)
+        eng = self.eng
+        batch = self._eval_rows(batch, stage, filter_rows)
+        if batch is None:
+            return None
+        n = int(batch["rating"].shape[0])
+        running = [j for j in range(3) if any(t[j] != 1.0 for t in scales)]
+        neg_logits, neg_lses, ce_neg = [], [], {}
+        for k, j in enumerate(running, 1):
+            eng.forward(batch, train_flag=True, training=False, logits_f32=_LOGITS_F32, exp_drop=tuple(float(i == j) for i in range(3)))
+            eng.loss(batch["rating"], stage)
+            a = eng.act
+            # (buffers of their own: the next forward overwrites the engine's logits, row lse and sample_ce)
+            nlog = eng.buf("guided_neg%d_logits" % k, tuple(a["logits"].shape), a["logits"].dtype)
+            nlse = eng.buf("guided_neg%d_lse" % k, (a["M"],), torch.float32)
+            nlog.copy_(a["logits"])
+            nlse.copy_(a["lse_rows"])
+            neg_logits.append(nlog)
+            neg_lses.append(nlse)
+            ce_neg[GUIDANCE_BRANCHES[j]] = a["sample_ce"].mean()
+        eng.forward(batch, train_flag=True, training=False, logits_f32=_LOGITS_F32)
+        eng.loss(batch["rating"], stage)
+        ce_cond = eng.act["sample_ce"].mean()
+        if running:
+            ce = eng.guided_loss_multi([tuple(t[j] for j in running) for t in scales], neg_logits, neg_lses).clone()
+        else:
+            ce = ce_cond.reshape(1).repeat(len(scales))
+        return {"ce": ce, "ce_cond": ce_cond, "ce_negatives": ce_neg, "rows": n}
+
+    def evaluate_modality_guided(self, valid_batches, scales, stage=3, averaged=False):
+        """evaluate_modality_guided_batch over an iterable of validation batches: the ROW-weighted means over all batches, summed on
+        the device with one host read at the end, so that the image and the text scale can be chosen on validation data
+        (best_scale).  Returns {'scales': [(s, s_img, s_txt), ...], 'ce': [...], 'ce_cond': x, 'ce_negatives': {'u' / 'i' / 't': y},
+        'rows': n}; the model is in eval mode during the pass and gets its previous mode back afterwards.  averaged=True runs the
+        pass inside averaged_weights()."""
+        if averaged:
+            with self.averaged_weights():
+                return self.evaluate_modality_guided(valid_batches, scales, stage)
+        scales = _check_scale_triples(scales)
+        was_training = self.model.training
+        self.model.eval()
+        acc, rows, names = None, 0, []
+        try:
+            for batch in valid_batches:
+                out = self.evaluate_modality_guided_batch(batch, scales, stage)
+                if out is None:
+                    continue
+                names = list(out["ce_negatives"])
+                v = torch.cat([out["ce"], out["ce_cond"].reshape(1)] + [out["ce_negatives"][k].reshape(1) for k in names]) * float(out["rows"])
+                acc = v if acc is None else acc + v
+                rows += out["rows"]
+        finally:
+            self.model.train(was_training)
+        G = len(scales)
+        if rows == 0:
+            from .constraints import GUIDANCE_BRANCHES
+            names = [GUIDANCE_BRANCHES[j] for j in range(3) if any(t[j] != 1.0 for t in scales)]
+            return {"scales": scales, "ce": [0.0] * G, "ce_cond": 0.0, "ce_negatives": {k: 0.0 for k in names}, "rows": 0}
+        v = (acc / float(rows)).tolist()
+        return {"scales": scales, "ce": v[:G], "ce_cond": v[G], "ce_negatives": dict(zip(names, v[G + 1:])), "rows": rows}
 
     @torch.no_grad()
     def evaluate_batch(self, batch, stage=3, filter_rows=True, without_experience=False):
